@@ -37,6 +37,8 @@ from sbsim_amd.environment import BatchedEnvironment, MixedBatchedEnvironment, S
 from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
+DUMP_LIMIT_BYTES = 60 * 2**20   # --dump-outputs: array data in all (with the .npy headers: under 64 MB)
+DUMP_GRID_BUILDINGS = 16        # --dump-outputs: whole temperature grids of this many buildings per floor plan
 
 
 # what decides the sweep kernel's memory behaviour: its sources, the planner (LDS layout, tables) and the build flags
@@ -57,6 +59,39 @@ def kernel_source_sha256() -> str:
 
 def r9_plan() -> FloorPlan:
   return FloorPlan.from_file_input(rectangular_floor_plan((3, 3), (20, 30)), Materials.sb1(), 10.0, 300.0)
+
+
+def _sample_buildings(n: int, k: int) -> np.ndarray:
+  """A fixed, seeded choice of k of n building indices in ascending order (all n when k >= n)."""
+  if k >= n:
+    return np.arange(n)
+  return np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir: str, per_building: dict, grids: dict) -> None:
+  """--dump-outputs: what the timed path computed in its last step, one `out_dir/<name>.npy` (float32 / float64) per
+  array, so that two builds run with the same arguments (hence the same seeded inputs) can be compared output for
+  output.  `per_building`: name -> [B, ...] device tensor, what a caller of the timed path receives; `grids`: name ->
+  callable returning a floor plan's [b, H, W] temperature grids, of which a fixed sample of DUMP_GRID_BUILDINGS
+  buildings is written (`<name>_buildings`: their indices).  Should everything exceed DUMP_LIMIT_BYTES, the
+  per-building arrays keep one fixed sample of buildings; `buildings` holds the indices written."""
+  out = {}
+  for name, get in grids.items():
+    g = get()
+    rows = _sample_buildings(g.shape[0], DUMP_GRID_BUILDINGS)
+    out[name] = g[torch.as_tensor(rows, device=g.device)].cpu().numpy()
+    out[name + "_buildings"] = rows
+    del g
+  B = next(iter(per_building.values())).shape[0]
+  row_bytes = sum(t[0].numel() * t.element_size() for t in per_building.values()) + 8   # (+ the row's index)
+  rows = _sample_buildings(B, (DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values())) // row_bytes)
+  idx = torch.as_tensor(rows, device=next(iter(per_building.values())).device)
+  for name, t in per_building.items():
+    out[name] = t[idx].cpu().numpy()
+  out["buildings"] = rows
+  os.makedirs(out_dir, exist_ok=True)
+  for name, a in out.items():
+    np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
 
 
 def cpu_baseline(env: BatchedEnvironment, plan: FloorPlan, init: np.ndarray, acts: np.ndarray,
@@ -394,6 +429,9 @@ def mixed_config(args, ctx=None, emit=True):
     torch.cuda.synchronize(dev)
     gather_ms = (time.perf_counter() - g0) * 1e3
     assert n_gathered == sum(menv.class_totals)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, {"observation": menv._obs, "reward": menv._reward, "returns": returns},
+                 {f"temps_{name}": env.sim.temps for (name, _, _), env in zip(MIXED_CLASSES, menv.envs)})
   for t in range(W + K, W + K + N_ALONE):   # after the timed rounds, in the same regime
     alone(t)
   per_class, alg_bytes, kern_s = {}, 0.0, 0.0
@@ -529,6 +567,11 @@ def policy_config(args, ctx=None, emit=True):
   mine = time.perf_counter() - t0
   per_rank = sd.all_ranks(mine / K * 1e3, dev)
   elapsed = sd.max_over_ranks(mine, dev)
+  if args.dump_outputs and rank == 0:
+    outs = {"observation": ts.observation, "reward": ts.reward, "zone_temps": env.sim.zone_temps(), "returns": returns}
+    if env._info is not None:
+      outs["info"] = env._info
+    dump_outputs(args.dump_outputs, outs, {"temps": env.sim.temps})
   # after the timed region: eight more steps with HIP events around the sweep kernel (BatchedSimulator.sweep_events) --
   # the kernel's own time in this regime (a smooth policy: ~2 sweeps per step) and the HBM rate it sustains there
   env.sim.sweep_events = []
@@ -640,6 +683,7 @@ def also_legs(args, dev, pf) -> dict:
   for name, fn, twins in (("mixed", mixed_config, 8), ("policy", policy_config, 32)):
     a = copy.copy(args)
     a.steps, a.warmup, a.check_buildings, a.config = 24, 12, twins, name
+    a.dump_outputs = None   # the outputs written are the headline's
     t0 = time.perf_counter()
     try:
       r = fn(a, ctx=(0, dev, False, pf), emit=False)
@@ -694,7 +738,13 @@ def main() -> None:
                        "reported under \"also\")")
   ap.add_argument("--stub-step", action="store_true",
                   help="developer / CPU test: launcher, barrier and return-gather plumbing with a stub step (gloo)")
+  ap.add_argument("--dump-outputs", metavar="DIR",
+                  help="after the timed steps, write what the timed path computed in its last step (observations, rewards, "
+                       "returns, zone temperatures, the temperature grids of a fixed sample of buildings) as DIR/<name>.npy, "
+                       "float32 / float64, under 64 MB in all; with --gpus N, rank 0's buildings")
   args = ap.parse_args()
+  if args.dump_outputs and args.stub_step:
+    ap.error("--dump-outputs: the stub step computes nothing to dump")
   launch_ranks_if_needed(args)
   if args.stub_step:
     return stub_rank(args)
@@ -794,6 +844,9 @@ def main() -> None:
     gather_ms = (time.perf_counter() - g0) * 1e3
     n_gathered = int(all_returns.numel())
     assert n_gathered == world * B
+  if args.dump_outputs and rank == 0:   # before the steady-state leg steps the environment on
+    dump_outputs(args.dump_outputs, {"observation": env._obs, "reward": env._reward, "info": env._info,
+                                     "zone_temps": env.sim.zone_temps(), "returns": returns}, {"temps": env.sim.temps})
 
   steady = None
   if world == 1 and not args.no_also and not args.through_env_api and args.iteration_limit == 100:

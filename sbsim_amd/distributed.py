@@ -134,11 +134,15 @@ def gather_returns_by_class(local_returns: torch.Tensor, class_totals) -> torch.
 def barrier(device: torch.device | None = None) -> None:
   """dist.barrier() that names the rank's device under RCCL (without device_ids the first barrier of a
   process binds NCCL/RCCL to "the current device" with a warning, and to the wrong one if set_device was
-  forgotten); a plain barrier on gloo; nothing when single-process."""
+  forgotten); on gloo an all_reduce of one host value; nothing when single-process."""
   if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
     return
   if dist.get_backend() == "nccl" and device is not None and device.type == "cuda":
     dist.barrier(device_ids=[device.index if device.index is not None else torch.cuda.current_device()])
+  elif dist.get_backend() == "gloo":
+    # (not dist.barrier(): it probes the machine's accelerator first, which on a GPU host starts the HIP runtime --
+    # opens the device -- in every rank, the CPU-only ranks of the gloo tests included)
+    dist.all_reduce(torch.zeros(1))
   else:
     dist.barrier()
 

@@ -46,7 +46,7 @@ def _worker(rank: int, world: int, port: int, n_total: int):
   assert torch.equal(full, expect), (rank, full, expect)
   slowest = sd.max_over_ranks(1.0 + rank, torch.device("cpu"))
   assert slowest == float(world)
-  dist.barrier()
+  sd.barrier(torch.device("cpu"))
   dist.destroy_process_group()
 
 
