@@ -1,0 +1,433 @@
+// runtime.hip -- the step runtime behind the C ABI (include/sbsim_amd.h): the state kernels (reset, observe, copies,
+// k_pre / k_post around the sweep), the dispatch to the sweep kernel sb_create chose, and every entry point but
+// sb_plan_info / sb_create (sbsim_hip.hip).
+//
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (fma only where written).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "sb_host.h"
+
+using namespace sb;
+
+namespace {
+
+// ---------------------------------------------------------------- kernels
+// Simulator.reset(): grid (either state layout), zone means, device scalars.
+// temps_only (sb_set_temps): the grid inside the building and the zone means follow `temps`; every device state stays.
+__global__ void k_reset(Dev a, double initial_temp, const double *temps, int first, int steps_since_reset, int temps_only) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int nwaves = gridDim.x * (blockDim.x >> 6);
+  for (int b = wave; b < a.B; b += nwaves) {
+    double s = 0.0, rlo = INFINITY, rhi = -INFINITY;
+    if (a.reg) {
+      double *T = a.temp + (size_t)b * a.state_doubles;
+      const double *S0 = a.scal + (size_t)b * kNScal;
+      const bool ring_uniform = S0[16] == S0[17]; // (temps_only) the ring holds one value: the ambient temperature of the last step
+      for (int g = lane; g < a.N; g += 64) {
+        double v = temps ? temps[(size_t)b * a.N + g] : initial_temp;
+        const int cs = a.cell_state[g];
+        if (cs >= 0) {
+          T[cs] = v;
+        } else if (!temps_only) {
+          a.ring[(size_t)b * a.n_ring + (-cs - 1)] = v;
+          rlo = fmin(rlo, v);
+          rhi = fmax(rhi, v);
+        } else { // sb_set_temps leaves exterior space alone: the grid mean counts what the ring holds, not what `temps` says
+          v = ring_uniform ? S0[16] : a.ring[(size_t)b * a.n_ring + (-cs - 1)];
+        }
+        s += v;
+      }
+      rlo = wave_min(rlo);
+      rhi = wave_max(rhi);
+    } else {
+      double *T = a.temp + (size_t)b * a.Np;
+      for (int i = lane; i < a.Np; i += 64) {
+        const int g = i - kPad;
+        double v = (g >= 0 && g < a.N) ? (temps ? temps[(size_t)b * a.N + g] : initial_temp) : 0.0;
+        T[i] = v;
+        s += v;
+      }
+    }
+    s = wave_sum(s);
+    for (int z = 0; z < a.Z; ++z) {
+      double zs = 0.0;
+      const int b0 = a.zone_off[z], b1 = a.zone_off[z + 1];
+      for (int i = b0 + lane; i < b1; i += 64) {
+        int li = a.zone_cells_l[i];
+        int g = a.pitch == a.W ? li : (li / a.pitch) * a.W + (li % a.pitch);
+        zs += temps ? temps[(size_t)b * a.N + g] : initial_temp;
+      }
+      zs = wave_sum(zs);
+      if (lane == 0) {
+        size_t o = (size_t)b * a.Z + z;
+        a.zmean[o] = zs / (double)(b1 - b0);
+        if (temps_only) continue;
+        a.zair[o] = 0.0;   // vav.py:93-99
+        a.damper[o] = 0.1;
+        a.mode[o] &= kModeMask; // ... the reheat valve closes; the thermostat keeps its mode
+        a.qz[o] = 0.0;     // building.py:791 input_q <- 0
+      }
+    }
+    // sb_set_temps: the recirculation temperature of the next step is the mean of the NEW grid (simulator.py:423-426 takes
+    // building.temp.mean() every step; S[11] caches it between steps)
+    if (lane == 0 && temps_only) a.scal[(size_t)b * kNScal + 11] = s / (double)a.N;
+    if (lane == 0 && !temps_only) {
+      double *S = a.scal + (size_t)b * kNScal;
+      S[0] = a.p.ahu_heat_sp; S[1] = a.p.ahu_cool_sp; S[2] = 0.0; S[3] = 0.0; // air_handler.py:131-139
+      S[4] = a.p.blr_setpoint; S[5] = 0.0; S[6] = 0.0; S[7] = 0.0;           // boiler.py:110-121
+      S[8] = a.p.blr_setpoint; S[9] = 0.0; S[10] = 0.0;
+      S[11] = s / (double)a.N;
+      S[12] = S[13] = S[14] = S[15] = 0.0;
+      S[16] = a.reg && a.n_ring > 0 ? rlo : 0.0; // extremes of the exterior-space ring (register path)
+      S[17] = a.reg && a.n_ring > 0 ? rhi : 0.0;
+      // Thermostat._previous_timestamp and SmartDevice._action_timestamp are construction state:
+      // Simulator.reset() leaves them alone (thermostat.py:66-69, smart_device.py:71-72)
+      // ... but the clock rewinds under them: the boiler's age of its last action goes negative
+      if (first) { S[18] = -1.0; S[19] = kAgeNone; }
+      else if (!age_is_none(S[19])) S[19] -= (double)steps_since_reset;
+    }
+  }
+}
+
+__global__ void k_observe(Dev a, float *obs, float aux0, float aux1, float aux2, float aux3,
+                          float aux4, float aux5, float aux6, double t_amb, const double *t_amb_b,
+                          const float *num_occupants, double occ_norm) {
+  const float aux[SB_NUM_AUX] = {aux0, aux1, aux2, aux3, aux4, aux5, aux6};
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) {
+    double *S = a.scal + (size_t)b * kNScal;
+    observe_boiler(a, S);
+    write_obs(a, b, obs, aux, t_amb_b ? t_amb_b[b] : t_amb, S, num_occupants, occ_norm);
+  }
+}
+
+// Thermostat modes without the valve bit.
+__global__ void k_copy_modes(Dev a, int32_t *out) {
+  const size_t n = (size_t)a.B * a.Z;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = a.mode[i] & kModeMask;
+}
+
+// building.temp in the caller's row-major layout, whichever state layout the handle uses.
+__global__ void k_copy_temps(Dev a, double *out) {
+  size_t n = (size_t)a.B * a.N;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
+       i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / a.N;
+    const int g = (int)(i - b * a.N);
+    if (a.reg) {
+      const int cs = a.cell_state[g];
+      if (cs >= 0) {
+        out[i] = a.temp[b * a.state_doubles + cs];
+      } else { // exterior space: T_ambient of the last step, or what sb_reset stored
+        const double *S = a.scal + b * kNScal;
+        out[i] = S[16] == S[17] ? S[16] : a.ring[b * a.n_ring + (-cs - 1)];
+      }
+    } else {
+      out[i] = a.temp[b * a.Np + kPad + g];
+    }
+  }
+}
+
+__global__ void k_copy_scalars(Dev a, double *out) {
+  size_t n = (size_t)a.B * kNScalOut;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
+       i += (size_t)gridDim.x * blockDim.x)
+    out[i] = a.scal[(i / kNScalOut) * kNScal + (i % kNScalOut)];
+}
+
+// Per-building algebra before / after the sweep kernel (sb_device.h).  k_pre: one 16-lane row of a wavefront per building,
+// lanes = zones -- four buildings per wavefront, sixteen per workgroup; the building's demand sums in the reference's zone
+// order through DPP row broadcasts.  k_post: one thread per building (the row shape was measured slower: sb_device.h).
+// only >= 0: that building alone (the known-answer taps).
+constexpr int kRowsPerBlock = 16; // buildings per workgroup of 256 threads
+__global__ void __launch_bounds__(16 * kRowsPerBlock) k_pre(Dev a, StepArgs s, int only) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { // the sweep kernel's draw counter; mode 3: the redo list's counters
+    *a.next_b = 0;
+    if (a.redo_ctr) a.redo_ctr[0] = a.redo_ctr[1] = 0;
+  }
+  const int i = threadIdx.x & 15, r = threadIdx.x >> 4;
+  if (only >= 0) {
+    if (blockIdx.x == 0 && r == 0) pre_building(a, s, only, i);
+    return;
+  }
+  for (int b = blockIdx.x * kRowsPerBlock + r; b < a.B; b += gridDim.x * kRowsPerBlock) pre_building(a, s, b, i);
+}
+
+__global__ void __launch_bounds__(64) k_post(Dev a, StepArgs s, int only) { // one thread per building: see sb_device.h
+  if (only >= 0) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) post_building(a, s, only);
+    return;
+  }
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) post_building(a, s, b);
+}
+
+} // namespace
+
+int prepare_sweep(const sb_handle *h) {
+  const Dev &d = h->d;
+  const int waves = h->info.waves_per_workgroup;
+  switch (h->kernel) {
+    case SB_KERNEL_LDS: return prepare_sweep_lds((size_t)h->info.lds_bytes_per_workgroup);
+    case SB_KERNEL_REG: case SB_KERNEL_REG_PAIR: return prepare_sweep_reg(d);
+    case SB_KERNEL_ROLL: return prepare_sweep_roll(d);
+    case SB_KERNEL_TWO_ROWS: return prepare_sweep_two(d);
+    case SB_KERNEL_BAND: return prepare_sweep_band(d);
+    case SB_KERNEL_STREAM:
+      if (h->stream_variant == kStreamMs) return prepare_sweep_stream_ms(d, waves);
+      if (h->stream_variant == kStreamRoll) return prepare_sweep_stream_roll(d, waves);
+      return prepare_sweep_stream(d, waves);
+  }
+  return (int)hipErrorInvalidValue;
+}
+
+int launch_sweep(const sb_handle *h, hipStream_t stream) {
+  const Dev &d = h->d;
+  const int waves = h->info.waves_per_workgroup;
+  switch (h->kernel) {
+    case SB_KERNEL_LDS: return launch_sweep_lds(d, h->info.workgroups, waves, (size_t)h->info.lds_bytes_per_workgroup, stream);
+    case SB_KERNEL_REG: case SB_KERNEL_REG_PAIR: return launch_sweep_reg(d, h->cus, stream);
+    case SB_KERNEL_ROLL: return launch_sweep_roll(d, stream);
+    case SB_KERNEL_TWO_ROWS: return launch_sweep_two(d, stream);
+    case SB_KERNEL_BAND: return launch_sweep_band(d, stream);
+    case SB_KERNEL_STREAM:
+      if (h->stream_variant == kStreamMs) return launch_sweep_stream_ms(d, h->abuf.p, h->ebuf.p, waves, stream);
+      if (h->stream_variant == kStreamRoll) return launch_sweep_stream_roll(d, h->abuf.p, h->ebuf.p, waves, stream);
+      return launch_sweep_stream(d, h->abuf.p, waves, stream);
+  }
+  return (int)hipErrorInvalidValue;
+}
+
+extern "C" {
+
+int sb_abi_version(void) { return SB_ABI_VERSION; }
+int sb_has_experimental_kernels(void) { return kExperimental ? 1 : 0; }
+const char *sb_last_error(void) { return sb::host::g_err.c_str(); }
+
+void sb_destroy(sb_handle *h) {
+  if (!h) return;
+  DeviceGuard guard(h->device);
+  delete h;
+}
+
+int sb_get_launch_info(const sb_handle *h, sb_launch_info *out) {
+  if (!h || !out) return fail(SB_ERR_INVALID, "sb_get_launch_info: null argument");
+  *out = h->info;
+  return SB_OK;
+}
+
+int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *stream) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_reset: null handle");
+  SB_ON_DEVICE(h->device);
+  const int wpb = 4;
+  const int blocks = std::min((h->d.B + wpb - 1) / wpb, 4096);
+  hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream, h->d, initial_temp,
+                     temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset, 0);
+  h->was_reset = true;
+  h->steps_since_reset = 0;
+  h->counters_zeroed_on = (void *)(uintptr_t)1; // (whatever came before a reset is no promise about the draw counters)
+  SB_HIP(hipGetLastError());
+  return SB_OK;
+}
+
+int sb_set_temps(sb_handle *h, const double *temps_dev, void *stream) {
+  if (!h || !temps_dev) return fail(SB_ERR_INVALID, "sb_set_temps: null argument");
+  if (!h->was_reset) return fail(SB_ERR_INVALID, "sb_set_temps: sb_reset first");
+  SB_ON_DEVICE(h->device);
+  const int wpb = 4;
+  const int blocks = std::min((h->d.B + wpb - 1) / wpb, 4096);
+  hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream, h->d, 0.0, temps_dev, 0, 0, 1);
+  SB_HIP(hipGetLastError());
+  return SB_OK;
+}
+
+int sb_observe_occupancy(sb_handle *h, const float aux[SB_NUM_AUX], double t_amb, const double *t_amb_dev,
+                         const float *num_occupants_dev, double occupancy_norm, float *obs_dev, void *stream) {
+  if (!h || !aux || !obs_dev) return fail(SB_ERR_INVALID, "sb_observe: null argument");
+  SB_ON_DEVICE(h->device);
+  const int blocks = std::max(1, std::min((h->d.B + 63) / 64, 4096));
+  hipLaunchKernelGGL(k_observe, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->d, obs_dev, aux[0],
+                     aux[1], aux[2], aux[3], aux[4], aux[5], aux[6], t_amb, t_amb_dev, num_occupants_dev,
+                     occupancy_norm);
+  SB_HIP(hipGetLastError());
+  return SB_OK;
+}
+
+int sb_observe(sb_handle *h, const float aux[SB_NUM_AUX], double t_amb, const double *t_amb_dev,
+               float *obs_dev, void *stream) {
+  return sb_observe_occupancy(h, aux, t_amb, t_amb_dev, nullptr, 0.0, obs_dev, stream);
+}
+
+int sb_step_phases(sb_handle *h, const float *actions_dev, const sb_step_in *in, float *obs_dev,
+                   float *reward_dev, float *info_dev, void *stream, int32_t phases) {
+  if (!h || !in || !reward_dev) return fail(SB_ERR_INVALID, "sb_step: null argument");
+  if (in->has_action && !actions_dev) return fail(SB_ERR_INVALID, "sb_step: has_action set but actions_dev is NULL");
+  SB_ON_DEVICE(h->device);
+  StepArgs s;
+  s.actions = actions_dev; s.obs = obs_dev; s.reward = reward_dev; s.info = info_dev; s.in = *in;
+  const Dev &d = h->d;
+  const int blocks = std::max(1, std::min((d.B + kRowsPerBlock - 1) / kRowsPerBlock, h->cus * 32)); // a 16-lane row per building
+  if (phases & SB_PHASE_PRE) {
+    hipLaunchKernelGGL(k_pre, dim3(blocks), dim3(16 * kRowsPerBlock), 0, (hipStream_t)stream, d, s, -1);
+    SB_HIP(hipGetLastError());
+    h->counters_zeroed_on = stream; // k_pre zeroes the sweep kernel's draw counters
+  }
+  if (phases & SB_PHASE_SWEEP) {
+    // without a k_pre in front of it ON THIS STREAM since the last sweep launch (phase by phase: bench.py brackets the
+    // sweep with events, so k_pre came with the previous call), the counters are zeroed here -- two more dispatches
+    if (h->counters_zeroed_on != stream) {
+      SB_HIP(hipMemsetAsync(d.next_b, 0, sizeof(int), (hipStream_t)stream));
+      if (d.redo_ctr) SB_HIP(hipMemsetAsync(d.redo_ctr, 0, 2 * sizeof(int), (hipStream_t)stream));
+    }
+    h->counters_zeroed_on = (void *)(uintptr_t)1; // (no stream)
+    const int e = launch_sweep(h, (hipStream_t)stream);
+    if (e != (int)hipSuccess)
+      return fail(SB_ERR_HIP, std::string("sweep kernel launch: ") + hipGetErrorString((hipError_t)e));
+  }
+  if (phases & SB_PHASE_POST) {
+    if (h->conv_attached) { // simulator_flexible_floor_plan.py:156: after the FD update; the zone sums of
+      const int rc = sb_launch_convection(h, (hipStream_t)stream); // k_post do not change (values move inside rooms)
+      if (rc != SB_OK) return rc;
+    }
+    hipLaunchKernelGGL(k_post, dim3(std::max(1, std::min((d.B + 63) / 64, h->cus * 16))), dim3(64), 0, (hipStream_t)stream, d, s, -1);
+    ++h->steps_since_reset;
+    SB_HIP(hipGetLastError());
+  }
+  return SB_OK;
+}
+
+int sb_step(sb_handle *h, const float *actions_dev, const sb_step_in *in, float *obs_dev,
+            float *reward_dev, float *info_dev, void *stream) {
+  return sb_step_phases(h, actions_dev, in, obs_dev, reward_dev, info_dev, stream,
+                        SB_PHASE_PRE | SB_PHASE_SWEEP | SB_PHASE_POST);
+}
+
+int sb_get_temps(sb_handle *h, double *out_dev, void *stream) {
+  if (!h || !out_dev) return fail(SB_ERR_INVALID, "sb_get_temps: null argument");
+  SB_ON_DEVICE(h->device);
+  hipLaunchKernelGGL(k_copy_temps, dim3(2048), dim3(256), 0, (hipStream_t)stream, h->d, out_dev);
+  SB_HIP(hipGetLastError());
+  return SB_OK;
+}
+
+int sb_get_scalars(sb_handle *h, double *out_dev, void *stream) {
+  if (!h || !out_dev) return fail(SB_ERR_INVALID, "sb_get_scalars: null argument");
+  SB_ON_DEVICE(h->device);
+  hipLaunchKernelGGL(k_copy_scalars, dim3(256), dim3(256), 0, (hipStream_t)stream, h->d, out_dev);
+  SB_HIP(hipGetLastError());
+  return SB_OK;
+}
+
+#define SB_COPY_OUT(name, src, count, type)                                                       \
+  int name(sb_handle *h, type *out_dev, void *stream) {                                           \
+    if (!h || !out_dev) return fail(SB_ERR_INVALID, #name ": null argument");                     \
+    SB_ON_DEVICE(h->device);                                                              \
+    SB_HIP(hipMemcpyAsync(out_dev, src, (size_t)(count) * sizeof(type), hipMemcpyDeviceToDevice,  \
+                          (hipStream_t)stream));                                                  \
+    return SB_OK;                                                                                 \
+  }
+SB_COPY_OUT(sb_get_zone_temps, h->d.zmean, (size_t)h->d.B *h->d.Z, double)
+int sb_get_modes(sb_handle *h, int32_t *out_dev, void *stream) {
+  if (!h || !out_dev) return fail(SB_ERR_INVALID, "sb_get_modes: null argument");
+  SB_ON_DEVICE(h->device);
+  hipLaunchKernelGGL(k_copy_modes, dim3(256), dim3(256), 0, (hipStream_t)stream, h->d, out_dev);
+  SB_HIP(hipGetLastError());
+  return SB_OK;
+}
+SB_COPY_OUT(sb_get_zone_power, h->d.qz, (size_t)h->d.B *h->d.Z, double)
+
+/* ---- known-answer taps: k_pre / k_post on prescribed state of one building ---- */
+int sb_tap_pre(sb_handle *h, int32_t building, const double *zone_temps, const int32_t *modes,
+               const double *scalars, const float *actions, const sb_step_in *in, sb_tap_bld *bld,
+               double *q_zone, double *damper, int32_t *modes_out) {
+  if (!h || !zone_temps || !in) return fail(SB_ERR_INVALID, "sb_tap_pre: null argument");
+  const Dev &d = h->d;
+  if (building < 0 || building >= d.B) return fail(SB_ERR_INVALID, "sb_tap_pre: building out of range");
+  SB_ON_DEVICE(h->device);
+  h->counters_zeroed_on = (void *)(uintptr_t)1; // the tap's k_pre runs on one building: the next sweep launch zeroes its counters itself
+  SB_HIP(hipDeviceSynchronize());
+  const size_t zb = (size_t)building * d.Z;
+  SB_HIP(hipMemcpy(d.zmean + zb, zone_temps, sizeof(double) * d.Z, hipMemcpyHostToDevice));
+  if (modes) SB_HIP(hipMemcpy(d.mode + zb, modes, sizeof(int32_t) * d.Z, hipMemcpyHostToDevice));
+  if (scalars) SB_HIP(hipMemcpy(d.scal + (size_t)building * kNScal, scalars, sizeof(double) * kNScalOut, hipMemcpyHostToDevice));
+  DevBuf<float> act;
+  if (actions) {
+    std::vector<float> all((size_t)d.B * d.p.n_actions, 0.0f);
+    for (int i = 0; i < d.p.n_actions; ++i) all[(size_t)building * d.p.n_actions + i] = actions[i];
+    int rc = upload(act, all.data(), all.size());
+    if (rc != SB_OK) return rc;
+  } else if (in->has_action) {
+    return fail(SB_ERR_INVALID, "sb_tap_pre: has_action without actions");
+  }
+  StepArgs s{};
+  s.actions = act.p; s.in = *in;
+  hipLaunchKernelGGL(k_pre, dim3(1), dim3(16 * kRowsPerBlock), 0, nullptr, d, s, building); // this building alone
+  SB_HIP(hipGetLastError());
+  SB_HIP(hipDeviceSynchronize());
+  if (bld) {
+    Bld v;
+    SB_HIP(hipMemcpy(&v, d.bld + building, sizeof(Bld), hipMemcpyDeviceToHost));
+    *bld = sb_tap_bld{v.t_now, v.t_next, v.heat_sp, v.cool_sp, v.blr_sp, v.t_sa, v.ahu_flow, v.blr_flow, v.blr_return,
+                      v.ahu_count, v.blr_count, v.tank, v.tank_change, v.duration, v.rejected};
+  }
+  if (q_zone) SB_HIP(hipMemcpy(q_zone, d.qz + zb, sizeof(double) * d.Z, hipMemcpyDeviceToHost));
+  if (damper) SB_HIP(hipMemcpy(damper, d.damper + zb, sizeof(double) * d.Z, hipMemcpyDeviceToHost));
+  if (modes_out) {
+    SB_HIP(hipMemcpy(modes_out, d.mode + zb, sizeof(int32_t) * d.Z, hipMemcpyDeviceToHost));
+    for (int z = 0; z < d.Z; ++z) modes_out[z] &= kModeMask;
+  }
+  return SB_OK;
+}
+
+int sb_tap_post(sb_handle *h, int32_t building, const sb_tap_bld *bld, const double *zone_temps,
+                double grid_mean, int32_t n_sweeps, const sb_step_in *in, float *reward, float *info) {
+  if (!h || !bld || !zone_temps || !in || !reward) return fail(SB_ERR_INVALID, "sb_tap_post: null argument");
+  const Dev &d = h->d;
+  if (building < 0 || building >= d.B) return fail(SB_ERR_INVALID, "sb_tap_post: building out of range");
+  SB_ON_DEVICE(h->device);
+  SB_HIP(hipDeviceSynchronize());
+  Bld v;
+  SB_HIP(hipMemcpy(&v, d.bld + building, sizeof(Bld), hipMemcpyDeviceToHost)); // keeps the fields the tap does not expose
+  v.t_now = bld->t_now; v.t_next = bld->t_next; v.heat_sp = bld->heat_sp; v.cool_sp = bld->cool_sp;
+  v.blr_sp = bld->blr_sp; v.t_sa = bld->t_sa; v.ahu_flow = bld->ahu_flow; v.blr_flow = bld->blr_flow;
+  v.blr_return = bld->blr_return; v.ahu_count = bld->ahu_count; v.blr_count = bld->blr_count;
+  v.tank = bld->tank; v.tank_change = bld->tank_change; v.duration = bld->duration; v.rejected = bld->rejected;
+  SB_HIP(hipMemcpy(d.bld + building, &v, sizeof(Bld), hipMemcpyHostToDevice));
+  std::vector<double> zs(d.Z);
+  for (int z = 0; z < d.Z; ++z) zs[z] = zone_temps[z] * (double)(h->h_zone_off[z + 1] - h->h_zone_off[z]);
+  SB_HIP(hipMemcpy(d.zsum + (size_t)building * d.Z, zs.data(), sizeof(double) * d.Z, hipMemcpyHostToDevice));
+  const double gs = grid_mean * (double)d.N;
+  const int nsw = n_sweeps | (1 << 16);
+  SB_HIP(hipMemcpy(d.gsum + building, &gs, sizeof(double), hipMemcpyHostToDevice));
+  SB_HIP(hipMemcpy(d.nsw + building, &nsw, sizeof(int), hipMemcpyHostToDevice));
+  DevBuf<float> rew, inf;
+  int rc = alloc_zero(rew, (size_t)d.B);
+  if (rc == SB_OK) rc = alloc_zero(inf, (size_t)d.B * SB_INFO_STRIDE);
+  if (rc != SB_OK) return rc;
+  StepArgs s{};
+  s.reward = rew.p; s.info = inf.p; s.in = *in;
+  hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, nullptr, d, s, building); // this building alone
+  SB_HIP(hipGetLastError());
+  SB_HIP(hipDeviceSynchronize());
+  SB_HIP(hipMemcpy(reward, rew.p + building, sizeof(float), hipMemcpyDeviceToHost));
+  if (info) SB_HIP(hipMemcpy(info, inf.p + (size_t)building * SB_INFO_STRIDE, sizeof(float) * SB_INFO_STRIDE, hipMemcpyDeviceToHost));
+  return SB_OK;
+}
+
+/* Developer aid (not part of the parity/bench path): 16 int64 cycle stamps, host pointer (16 + 2048 when the handle
+   was created under SBSIM_DEBUG_TIMELINE=1). */
+int sb_debug_phase_cycles(sb_handle *h, long long *out_host) {
+  if (!h || !out_host) return fail(SB_ERR_INVALID, "sb_debug_phase_cycles: null argument");
+  if (!h->d.dbg) return fail(SB_ERR_INVALID, "sb_debug_phase_cycles: set SBSIM_PHASE_TIMING=1 before sb_create");
+  SB_ON_DEVICE(h->device);
+  SB_HIP(hipDeviceSynchronize());
+  SB_HIP(hipMemcpy(out_host, h->d.dbg, (16 + (h->d.dbg_timeline ? 2048 : 0)) * sizeof(long long), hipMemcpyDeviceToHost));
+  return SB_OK;
+}
+
+} // extern "C"

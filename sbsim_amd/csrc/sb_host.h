@@ -1,5 +1,5 @@
-// sb_host.h -- what the host-side translation units (sbsim_hip.hip, generators.hip) share: error
-// reporting, device buffers, the handle behind the C ABI.
+// sb_host.h -- what the host-side translation units (sbsim_hip.hip: the planner and sb_create; runtime.hip: the step
+// runtime; generators.hip) share: error reporting, device buffers, the handle behind the C ABI, the sweep-kernel dispatch.
 #ifndef SBSIM_AMD_SB_HOST_H_
 #define SBSIM_AMD_SB_HOST_H_
 #include <hip/hip_runtime.h>
@@ -9,6 +9,25 @@
 #include <vector>
 
 #include "sb_device.h"
+
+// The experimental sweep kernels (step_stream_ms.hip, step_stream.hip's k_sweep_stream_roll: exact, tested, slower than what
+// they were meant to replace) are in the library only when it is built with SBSIM_BUILD_EXPERIMENTAL=1 (-DSB_EXPERIMENTAL,
+// sbsim_amd/build.py); the default build answers for step_stream_ms.hip's entry points (sbsim_hip.hip) and never plans them.
+#ifdef SB_EXPERIMENTAL
+constexpr bool kExperimental = true;
+#else
+constexpr bool kExperimental = false;
+#endif
+
+// step_stream.hip's overlapped-sweeps kernel (declared here: sb_device.h is part of the traffic profile's source hash)
+namespace sb {
+int launch_sweep_stream_roll(const Dev &d, double *abuf, double *ebuf, int waves, hipStream_t stream);
+int prepare_sweep_stream_roll(const Dev &d, int waves);
+int sweep_stream_roll_xchg_extra_doubles();
+} // namespace sb
+
+// SB_KERNEL_STREAM's variants (= Dev::stream_ms): k_sweep_stream; the experimental k_sweep_stream_ms, k_sweep_stream_roll
+enum { kStreamPlain = 0, kStreamMs = 1, kStreamRoll = 2 };
 
 namespace sb {
 namespace host {
@@ -26,6 +45,11 @@ inline int fail(int code, const std::string &msg) {
     hipError_t e_ = (call);                                                              \
     if (e_ != hipSuccess)                                                                \
       return fail(SB_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));        \
+  } while (0)
+#define SB_CHECK(call)                                                                   \
+  do {                                                                                   \
+    const int rc_ = (call);                                                              \
+    if (rc_ != SB_OK) return rc_;                                                        \
   } while (0)
 
 // Entry points run on the handle's device and leave the calling thread's current device as
@@ -79,6 +103,8 @@ struct ConvCell {
 
 struct sb_handle {
   sb::Dev d{};
+  sb_sweep_kernel kernel = SB_KERNEL_LDS; // which sweep kernel runs (prepare_sweep / launch_sweep); Dev::reg / P / stream_ms follow it
+  int stream_variant = kStreamPlain;      // SB_KERNEL_STREAM: kStreamPlain / kStreamMs / kStreamRoll
   int device = 0, cus = 256;
   bool was_reset = false; // the first sb_reset also sets the construction-time device state
   int steps_since_reset = 0; // how far a reset rewinds the clock (the boiler's action age, scal[19])
@@ -125,6 +151,10 @@ struct sb_handle {
   bool occ_attached = false;
 };
 
+
+// runtime.hip: the one dispatch on sb_handle::kernel -- the sweep kernel's LDS attribute (sb_create), its launch (sb_step)
+int prepare_sweep(const sb_handle *h);
+int launch_sweep(const sb_handle *h, hipStream_t stream);
 
 // generators.hip: the convection shuffle between the sweep and the reward (sb_step)
 int sb_launch_convection(sb_handle *h, hipStream_t stream);
