@@ -147,7 +147,7 @@ __global__ void k_copy_scalars(Dev a, double *out) {
 // only >= 0: that building alone (the known-answer taps).
 constexpr int kRowsPerBlock = 16; // buildings per workgroup of 256 threads
 __global__ void __launch_bounds__(16 * kRowsPerBlock) k_pre(Dev a, StepArgs s, int only) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) { // the sweep kernel's draw counter; mode 3: the redo list's counters
+  if (blockIdx.x == 0 && threadIdx.x == 0) { // the sweep kernel's draw counter; k_sweep_roll: the redo list's counters
     *a.next_b = 0;
     if (a.redo_ctr) a.redo_ctr[0] = a.redo_ctr[1] = 0;
   }

@@ -1,15 +1,15 @@
 // sb_device.h -- device-side definitions shared by the step kernels of libsbsim_amd.so.
 //
 // One environment step (include/sbsim_amd.h, sb_step) is three launches on the caller's stream:
-//   k_pre   (sbsim_hip.hip)  thermostats, setpoints, VAV / air handler / boiler demand, the
-//                            per-building g table; one 16-lane DPP row of a wavefront per building, lanes = zones
+//   k_pre   (runtime.hip)  thermostats, setpoints, VAV / air handler / boiler demand, the
+//                          per-building g table; one 16-lane DPP row of a wavefront per building, lanes = zones
 //   sweep   step_roll.hip k_sweep_roll   <= 66 rows (R9): one wavefront + tail rows, the grid in registers, sweeps overlapped
 //           step_two.hip  k_sweep_two    67..130 rows: two rows per lane
 //           step_band.hip k_sweep_band   131..258 rows: two to four wavefronts per building
-//           step_reg.hip  k_sweep_reg    small plans (one / two wavefronts, no overlap)
+//           step_reg.hip  k_sweep_reg    small plans: mode 1 (one wavefront) and mode 2 (two), no overlap
 //           step_lds.hip  k_sweep_lds    the grid in LDS (any floor-plan shape that fits a CU)
 //           step_stream.hip k_sweep_stream  the grid in global memory (everything else)
-//   k_post  (sbsim_hip.hip)  reward_info, regret reward, observation row, scalar state; one thread per building
+//   k_post  (runtime.hip)  reward_info, regret reward, observation row, scalar state; one thread per building
 // The sweep kernel is > 95 % of the time and is kept free of everything else: its unrolled
 // code already fills the instruction cache, and a lone wavefront per SIMD pays one issue slot per instruction
 // whatever the number of lanes that work -- the per-building algebra (~650 instructions with lanes = zones) would cost the
@@ -56,7 +56,7 @@ struct Dev {
   unsigned S_magic;        // floor(2^32 / S) + 1
   int nbands, fast;        // fast: register/DPP sweep is legal for this shape (LDS-grid kernel)
   int ts;                  // coefficient-table stride in entries (32, 128 or 256; > ncls on the register path)
-  int lds_wave_doubles;    // per-wave LDS region, in doubles (LDS-grid kernel; mode 3)
+  int lds_wave_doubles;    // per-wave LDS region, in doubles (LDS-grid kernel; k_sweep_roll)
   int off_agtab, off_zscr, off_zmode; // offsets inside the per-wave region (doubles)
   // static tables
   const uint8_t *cls;      // [kPad + N + kPad], grid at +kPad
@@ -75,40 +75,40 @@ struct Dev {
   // ---- register path (step_reg.hip); reg == 0 when the floor plan is not eligible ----
   int reg;                 // 1: k_step_reg owns the step
   int NR;                  // slots per lane (>= trimmed width), one of the instantiated sizes
-  int P;                   // kernel mode: 1 / 2 wavefronts per building, 3 = 1 wavefront + tail rows, 4 = two rows per lane, 5 = two to four wavefronts in blocks, 6 = grid in global memory
-  int T;                   // mode 3: rows 64..64+T-1 are finished by the tail scan (T <= 2)
+  int P;                   // the sweep kernel (sb_sweep_kernel); for k_sweep_reg its mode: 1 / 2 wavefronts per building
+  int T;                   // k_sweep_roll: rows 64..64+T-1 are finished by the tail scan (T <= 2)
   int state_doubles;       // doubles of HBM state per building
-  const uint8_t *tcls;     // mode 3: [T][NR] classes of the tail cells (class * 8)
-  const uint8_t *tcset;    // mode 3: [T][NR] coefficient sets of the tail cells (set * 8)
-  const double *tmulS;     // mode 3: the tail scan's static multipliers (sweep_common.h, tail_pass_static), tmul_doubles of them
+  const uint8_t *tcls;     // k_sweep_roll: [T][NR] classes of the tail cells (class * 8)
+  const uint8_t *tcset;    // k_sweep_roll: [T][NR] coefficient sets of the tail cells (set * 8)
+  const double *tmulS;     // k_sweep_roll: the tail scan's static multipliers (sweep_common.h, tail_pass_static), tmul_doubles of them
   int tmul_doubles;
-  const double *csetab;    // mode 3: [ncset][4] distinct (bU, bD, bL, bR); the sweep's class bytes index this table
+  const double *csetab;    // k_sweep_roll: [ncset][4] distinct (bU, bD, bL, bR); the sweep's class bytes index this table
   int ncset;
-  int csetab_doubles;      // doubles of csetab (mode 4 with two_sym: [sets][2] for the wavefront's cells, then [sets][4] for the tail cells)
-  int two_sym, two_level;  // mode 4 (step_two.hip): two-coefficient cells (bV, bH); how much of A stays in LDS (0 / 1 / 2: two / three / four buildings per CU)
-  double *two_abuf;        // mode 4: [workgroups][NR - NL][64][2] the slots of A that do not fit in LDS (L2-resident)
-  const int *zs_off;       // mode 4: [Z + 2] the compact zone-sum scratch (slots of zone z: zs_off[z] .. zs_off[z + 1] - 1; zone Z: every other cell, a slot per lane)
-  int tail_set_base, tail_pad_set; // mode 4: LDS byte offset of the tail cells' (bU, bD, bL, bR) table, and of its pad set
+  int csetab_doubles;      // doubles of csetab (k_sweep_two with two_sym: [sets][2] for the wavefront's cells, then [sets][4] for the tail cells)
+  int two_sym, two_level;  // k_sweep_two: two-coefficient cells (bV, bH); how much of A stays in LDS (0 / 1 / 2: two / three / four buildings per CU)
+  double *two_abuf;        // k_sweep_two: [workgroups][NR - NL][64][2] the slots of A that do not fit in LDS (L2-resident)
+  const int *zs_off;       // k_sweep_two: [Z + 2] the compact zone-sum scratch (slots of zone z: zs_off[z] .. zs_off[z + 1] - 1; zone Z: every other cell, a slot per lane)
+  int tail_set_base, tail_pad_set; // k_sweep_two: LDS byte offset of the tail cells' (bU, bD, bL, bR) table, and of its pad set
   int RS;                  // rows of the trimmed grid = row stride of the HBM state [NR][RS]
   int AS;                  // row stride of A in LDS (odd when it fits: bank-conflict free)
   int ZRS;                 // row stride of the zone-sum scratch [Z+1][ZRS] that aliases A (RS | 1)
   int Ws;                  // trimmed width
-  int stream_ms;           // mode 6: 1 = step_stream_ms.hip (several sweeps per pass over the grid), 0 = step_stream.hip
+  int stream_ms;           // k_sweep_stream: 1 = step_stream_ms.hip (several sweeps per pass over the grid), 0 = step_stream.hip
   int n_ring;              // exterior-space cells outside the trim box (all of class "ambient")
   double n_ring_f64;       // (double)n_ring: a kernel argument, not a conversion the compiler keeps in a VGPR pair for the kernel's lifetime
-  int lw[4], l0[2], rowbase[2], nch[2]; // per wave: rows (mode 5: up to four wavefronts), first lane, first row, 8-step chunks
+  int lw[4], l0[2], rowbase[2], nch[2]; // per wave: rows (k_sweep_band: up to four wavefronts), first lane, first row, 8-step chunks
   int lag;                 // wave 1 runs `lag` chunk slots behind wave 0
   int nslots;              // chunk slots (barriers) per sweep
-  float pred_haste;        // mode 4: when may the next sweep overlap (step_two.hip may_roll)
+  float pred_haste;        // k_sweep_two: when may the next sweep overlap (step_two.hip may_roll)
   float pred_slack;
-  int two_skip;            // mode 4: rolling periods far from the step's last sweep run without max|delta| (step_two_impl.h, Hist; the planner checks the coefficients)
-  float skip_kappa;        // mode 4: the next measurement is due this fraction of the predicted sweeps-to-go ahead
-  int pred_first;          // mode 4: a step's first block rolls pred_first - 1 periods unseen when the previous step took >= 6 sweeps (1: never)
-  int lds_reg_bytes;       // dynamic LDS per workgroup (one building; mode 3: four)
+  int two_skip;            // k_sweep_two: rolling periods far from the step's last sweep run without max|delta| (step_two_impl.h, Hist; the planner checks the coefficients)
+  float skip_kappa;        // k_sweep_two: the next measurement is due this fraction of the predicted sweeps-to-go ahead
+  int pred_first;          // k_sweep_two: a step's first block rolls pred_first - 1 periods unseen when the previous step took >= 6 sweeps (1: never)
+  int lds_reg_bytes;       // dynamic LDS per workgroup (one building; k_sweep_roll: four)
   int wg_per_cu;
-  int r_seam, r_A, r_zscr, r_xchg, r_zoff, r_zmode; // LDS offsets in doubles (mode 3: r_seam, r_A inside a wavefront's region of lds_wave_doubles)
-  int r_cmap;              // mode 3: the workgroup's shared class words [NR / 8][64]
-  const unsigned long long *cmapS; // [P][maxch+3][64] class bytes by local step (mode 3: [NR / 8][64] coefficient sets by step mod NR)
+  int r_seam, r_A, r_zscr, r_xchg, r_zoff, r_zmode; // LDS offsets in doubles (k_sweep_roll: r_seam, r_A inside a wavefront's region of lds_wave_doubles)
+  int r_cmap;              // k_sweep_roll: the workgroup's shared class words [NR / 8][64]
+  const unsigned long long *cmapS; // [P][maxch+3][64] class bytes by local step (k_sweep_roll: [NR / 8][64] coefficient sets by step mod NR)
   const unsigned long long *amapS; // [P][ceil(NR/8)][64] class bytes by slot
   const unsigned long long *zmapS; // [P][ceil(NR/4)][64] 4 x u16 byte offsets into the zone-sum scratch
   const int *cell_state;   // [N] >= 0: index into the building's state; < 0: -(ring index + 1)
@@ -129,7 +129,7 @@ struct Dev {
   int *nsw;                // [B] sweeps | converged << 16
   int *next_b;             // draw counter of the sweep kernel (zeroed before every launch)
   int sweep_wgs;           // buildings handed out statically (one per workgroup / wavefront) before the draws
-  // mode 3 (step_roll.hip): buildings whose stopping decision the fast kernel's 32-bit maximum cannot make
+  // k_sweep_roll (step_roll.hip): buildings whose stopping decision the fast kernel's 32-bit maximum cannot make
   int *redo_ctr;           // [0] entries of redo_list, [1] the exact kernel's draw counter (both zeroed with next_b)
   int *redo_list;          // [B]
   double *redo_scratch;    // [wavefronts][state_doubles]: where such a building's rows go instead of its state
@@ -168,10 +168,9 @@ bool sweep_reg_supported(int NR, int P);     // is there an instantiation for th
 int sweep_reg_table_stride(int NR, int P);   // coefficient-table stride of the instantiation (classes + 1 <= stride)
 int sweep_reg_lds_slots(int NR, int P);      // slots of A the instantiation keeps in LDS (the rest: registers)
 int sweep_reg_waves_per_simd(int NR, int P); // register budget of the instantiation: wavefronts per SIMD
-bool sweep_reg_overlaps_sweeps(int NR, int P); // a sweep costs NR steps (lanes start the next sweep while others finish)
-// step_roll.hip: mode 3 (one wavefront + tail rows, overlapped sweeps)
+// step_roll.hip: k_sweep_roll (one wavefront + tail rows, overlapped sweeps)
 int launch_sweep_roll(const Dev &d, hipStream_t stream);
-// step_two.hip: mode 4 (one wavefront, two rows per lane: 67..130 rows, <= 80 columns)
+// step_two.hip: k_sweep_two (one wavefront, two rows per lane: 67..130 rows, <= 80 columns)
 int launch_sweep_two(const Dev &d, hipStream_t stream);
 int prepare_sweep_two(const Dev &d);
 bool sweep_two_supported(int NR);
@@ -180,7 +179,7 @@ int sweep_two_lds_slots(int NR, int level);
 int sweep_two_a_stride(int NR, int level);
 int sweep_two_seam_doubles(int NR);
 int sweep_two_set_table();
-// step_band.hip: mode 5 (two wavefronts, one row per lane: 67..130 rows, <= 80 columns, sweeps overlapped in blocks)
+// step_band.hip: k_sweep_band (two wavefronts, one row per lane: 67..130 rows, <= 80 columns, sweeps overlapped in blocks)
 int launch_sweep_band(const Dev &d, hipStream_t stream);
 int prepare_sweep_band(const Dev &d);
 bool sweep_band_supported(int NR);
@@ -190,12 +189,12 @@ int sweep_band_seam_doubles(int NR, int W); // LDS doubles of the seam rows and 
 int sweep_band_sync_doubles(int W);     // LDS doubles of the progress counters and the published max|delta| parts
 int sweep_band_decision_lag(int NR, int W); // periods until a sweep's max|delta| is known in every wavefront
 int sweep_band_set_table();
-// step_stream.hip: mode 6 (the grid in global memory: plans that fit no other kernel)
+// step_stream.hip: k_sweep_stream (the grid in global memory: plans that fit no other kernel)
 int launch_sweep_stream(const Dev &d, double *abuf, int waves, hipStream_t stream);
 int prepare_sweep_stream(const Dev &d, int waves);
 int sweep_stream_set_table();
 int sweep_stream_zone_columns();
-// step_stream_ms.hip: mode 6 with several sweeps per pass (two grids in global memory take turns)
+// step_stream_ms.hip: k_sweep_stream_ms (k_sweep_stream with several sweeps per pass: two grids in global memory take turns)
 int launch_sweep_stream_ms(const Dev &d, double *abuf, double *ebuf, int waves, hipStream_t stream);
 int prepare_sweep_stream_ms(const Dev &d, int waves);
 int sweep_stream_ms_sweeps();                      // sweeps per pass, at most

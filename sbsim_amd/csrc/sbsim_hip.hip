@@ -83,17 +83,17 @@ struct RegPlan {
   sb_sweep_kernel kernel = SB_KERNEL_LDS; // when ok: the register or streaming kernel this plan is for
   int NR = 0, RS = 0, Ws = 0, r0 = 0, c0 = 0, n_ring = 0, T = 0, state_doubles = 0, ts = 32;
   std::vector<uint8_t> tcls, tcset;
-  std::vector<double> csetab; // mode 3: distinct (bU, bD, bL, bR), the pad set (all zero) last
-  std::vector<double> tmul;   // mode 3: the tail scan's static multipliers (sweep_common.h, tail_pass_static)
+  std::vector<double> csetab; // k_sweep_roll: distinct (bU, bD, bL, bR), the pad set (all zero) last
+  std::vector<double> tmul;   // k_sweep_roll: the tail scan's static multipliers (sweep_common.h, tail_pass_static)
   int lw[4] = {0, 0, 0, 0}, l0[2] = {0, 0}, rowbase[2] = {0, 0}, nch[2] = {0, 0};
   int lag = 0, nslots = 0, steps = 0;
   int r_seam = 0, r_A = 0, r_xchg = 0, lds_bytes = 0, wg_per_cu = 0, AS = 0;
-  int r_cmap = 0, wave_doubles = 0, waves_per_wg = 1; // mode 3: four buildings per workgroup share the class words
-  int ZRS = 0; // modes 1..3: row stride of the zone-sum scratch
+  int r_cmap = 0, wave_doubles = 0, waves_per_wg = 1; // k_sweep_roll: four buildings per workgroup share the class words
+  int ZRS = 0; // k_sweep_reg, k_sweep_roll: row stride of the zone-sum scratch
   int stream_variant = kStreamPlain; // SB_KERNEL_STREAM: kStreamMs / kStreamRoll (experimental)
   std::vector<unsigned long long> cmapS, amapS, zmapS;
   std::vector<int> cell_state;
-  // mode 4 (plan_two)
+  // k_sweep_two (plan_two)
   int two_sym = 0, two_level = 0, tail_set_base = 0, tail_pad_set = 0;
   std::vector<int> zs_off; // [Z + 2] the compact zone-sum scratch: slots of zone z are zs_off[z] .. zs_off[z + 1] - 1
 };
@@ -159,7 +159,7 @@ std::vector<int> coefficient_sets(const sb_plan_desc *plan, std::vector<double> 
   return set_of;
 }
 
-// Mode 4 (step_two.hip): one wavefront, two rows per lane, up to 128 + 2 rows and 80 columns
+// k_sweep_two (step_two.hip): one wavefront, two rows per lane, up to 128 + 2 rows and 80 columns
 // inside the exterior ring.  (x0, y0): the trim box's corner; zone_of: zone of every cell or -1.
 // Three variants (the kernel's template parameters SYM, DENSE):
 //   * general: four coefficients per cell, lane l owns rows 2l, 2l + 1, A's slots 72 / 74 in LDS: two
@@ -363,7 +363,7 @@ bool plan_two(const sb_plan_desc *plan, int Hs, int Ws, int x0, int y0, const st
   return true;
 }
 
-// Mode 5 (step_band.hip): two to four wavefronts per building, one row per lane (rows 64 w .. 64 w + 63) + at
+// k_sweep_band (step_band.hip): two to four wavefronts per building, one row per lane (rows 64 w .. 64 w + 63) + at
 // most two tail rows, up to 96 columns inside the exterior ring; sweeps overlapped in predicted blocks.
 bool plan_band(const sb_plan_desc *plan, int Hs, int Ws, int x0, int y0, const std::vector<int> &zone_of, const Knobs &k, RegPlan &r) {
   const int W = plan->W, Z = plan->Z, ncls = plan->n_classes, N = plan->H * plan->W;
@@ -485,7 +485,7 @@ bool plan_band(const sb_plan_desc *plan, int Hs, int Ws, int x0, int y0, const s
   return true;
 }
 
-// Mode 6 (step_stream.hip): the grid stays in global memory; W = ceil(rows / 64) wavefronts per building
+// k_sweep_stream (step_stream.hip): the grid stays in global memory; W = ceil(rows / 64) wavefronts per building
 // (W <= 16), any width whose seam rows fit in LDS.  For floor plans no other kernel holds.
 bool plan_stream(const sb_plan_desc *plan, const Trim &t, const Knobs &k, RegPlan &r, std::string &why) {
   const int H = plan->H, W = plan->W, Z = plan->Z, ncls = plan->n_classes, N = H * W;
@@ -578,14 +578,14 @@ void plan_reg(const sb_plan_desc *plan, const Trim &t, int lds_per_cu, const Kno
   if (!t.why.empty()) { r.why = t.why; return; }
   const int x0 = t.x0, x1 = t.x1, y0 = t.y0, y1 = t.y1, Hs = t.Hs, Ws = t.Ws;
   const std::vector<int> &zone_of = t.zone_of;
-  // mode 5: two wavefronts, one row per lane, sweeps overlapped in blocks (67..130 rows, <= 80 columns).
-  // Measured level with mode 4 (profiles/r04_band_vs_two_rows.txt): all four SIMDs run, but four
+  // k_sweep_band: two wavefronts, one row per lane, sweeps overlapped in blocks (67..130 rows, <= 80 columns).
+  // Measured level with k_sweep_two (profiles/r04_band_vs_two_rows.txt): all four SIMDs run, but four
   // wavefronts share the CU's LDS pipe, every block starts with wavefront 1's 64-step lag and the tail
   // scan sits on wavefront 1's critical path.  Kept, tested, behind SBSIM_BAND_PATH=1.
   if (Hs > 64 + 2 && k.band_path && plan_band(plan, Hs, Ws, x0, y0, zone_of, k, r)) return;
-  // mode 4: one wavefront, two rows per lane (67..130 rows, <= 80 columns)
+  // k_sweep_two: one wavefront, two rows per lane (67..130 rows, <= 80 columns)
   if (Hs > 64 + 2 && !k.no_two_row && plan_two(plan, Hs, Ws, x0, y0, zone_of, k, r)) return;
-  // mode 5 again, for what mode 4 does not hold: beyond 128 rows (up to 258) three or four wavefronts share a
+  // k_sweep_band again, for what k_sweep_two does not hold: beyond 128 rows (up to 258) three or four wavefronts share a
   // building; 67..130 rows with 81..96 columns two (measured 1.2-2.6x the two-wavefront k_sweep_reg / the LDS-grid
   // kernel on 109 x 92, 113 x 93 and 125 x 97: tools/bench_mid_plans.py)
   if (Hs > 64 + 2 && !k.no_band && plan_band(plan, Hs, Ws, x0, y0, zone_of, k, r)) return;
@@ -636,8 +636,8 @@ void plan_reg(const sb_plan_desc *plan, const Trim &t, int lds_per_cu, const Kno
   const int nl_slots = roll ? sweep_roll_lds_slots(NR) : sweep_reg_lds_slots(NR, kernel);
   r.ts = TS;
   const int RS = roll ? 64 : Hs;
-  // the zone-sum scratch aliases A.  Modes 1, 2: [Z + 1][ZRS = rows | 1] (odd stride: the zone reduce reads 16 zone rows at once),
-  // 16-bit byte offsets.  Mode 3 (step_roll.hip): [64 rows][ZRS = (Z + 1) | 1], a slot's offset inside its lane's row is zone * 8:
+  // the zone-sum scratch aliases A.  k_sweep_reg: [Z + 1][ZRS = rows | 1] (odd stride: the zone reduce reads 16 zone rows at once),
+  // 16-bit byte offsets.  k_sweep_roll: [64 rows][ZRS = (Z + 1) | 1], a slot's offset inside its lane's row is zone * 8:
   // one byte (Z <= 31: every zone has a cell class of its own and the class table holds 32)
   const int ZRS = roll ? ((Z + 1) | 1) : (RS | 1);
   if (roll ? (Z > 31 || ZRS > nl_slots) : ((size_t)(Z + 1) * ZRS > (size_t)RS * nl_slots || (size_t)(Z + 1) * ZRS * 8 > 65535)) {
@@ -658,7 +658,7 @@ void plan_reg(const sb_plan_desc *plan, const Trim &t, int lds_per_cu, const Kno
     r.lw[0] = Hs; r.l0[0] = 0; r.rowbase[0] = 0;
     r.nch[0] = (NR + Hs - 1 + 7) / 8;
     r.lag = 0; r.nslots = r.nch[0];
-    r.steps = sweep_reg_overlaps_sweeps(NR, 1) ? NR : NR + Hs - 1;
+    r.steps = NR + Hs - 1;
   } else {
     int best = -1, best_slots = 1 << 30;
     for (int a0 = Hs - 64; a0 <= 64; ++a0) {
@@ -715,7 +715,7 @@ void plan_reg(const sb_plan_desc *plan, const Trim &t, int lds_per_cu, const Kno
   if (r.wg_per_cu < 1) { r.why = "one building does not fit in LDS"; return; }
 
   const int pad = ncls;
-  // mode 3: the sweep looks its four neighbour coefficients up by coefficient SET (classes that
+  // k_sweep_roll: the sweep looks its four neighbour coefficients up by coefficient SET (classes that
   // differ only in ap / g share one): fewer distinct LDS addresses per wavefront read
   std::vector<int> set_of(ncls + 1, 0);
   if (roll) {
@@ -832,7 +832,7 @@ void plan_reg(const sb_plan_desc *plan, const Trim &t, int lds_per_cu, const Kno
           const int j = 4 * g + k;
           const int col = ((j - lp) % NR + NR) % NR;
           int z = Z; // dump row
-          if (valid && R < Hs && j < NR && col < Ws) { // (mode 3 below 64 rows: the lanes beyond the plan own pad rows)
+          if (valid && R < Hs && j < NR && col < Ws) { // (k_sweep_roll below 64 rows: the lanes beyond the plan own pad rows)
             const int zz = zone_of[(x0 + R) * W + (y0 + col)];
             if (zz >= 0) z = zz;
           }

@@ -36,8 +36,6 @@
 //     building's previous step took until its own parts say more.
 // The iterates and the sweep count are always those of the plain schedule (tests: oracle twins,
 // step_lds.hip on the same batch); the prediction only decides the speed.
-#include <type_traits>
-
 #include "step_band_cfg.h"
 #include "sweep_common.h"
 
@@ -70,7 +68,6 @@ constexpr int kPD = SB_BAND_PD, kPR = kPD + 1; // ... and the ring of pair buffe
 
 typedef const double __attribute__((address_space(3))) *lds_d;
 typedef double __attribute__((address_space(3))) *lds_dw;
-typedef volatile int __attribute__((address_space(3))) *lds_vi;
 typedef volatile double __attribute__((address_space(3))) *lds_vd;
 
 struct PairBuf { // LDS values of two consecutive steps (the first one odd)
@@ -111,13 +108,6 @@ __device__ __forceinline__ void tl_mark(const Sync &sy, int code) {
 __device__ __forceinline__ void tl_mark(const Sync &, int) {}
 #endif
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 // Class words: one 32-bit word per step = the LDS byte offset (set * 32) of the cell's coefficient
 // set, read from global memory (L2 hits) kWA steps ahead; [wavefront][NR + 63 steps][64 lanes].

@@ -3,14 +3,17 @@
 // One 64-lane wavefront owns one building instance for the whole step: the float64 grid
 // lives in LDS, the Gauss-Seidel sweep walks it in a skewed (anti-diagonal) order that
 // reproduces the reference's row-major in-place update exactly.
-// step_reg.hip holds the faster register-resident variant for floor plans that fit it; this
-// kernel is the general path (and the cross-check of the other one in the GPU tests).
+// The register-resident kernels (k_sweep_reg, k_sweep_roll, k_sweep_two, k_sweep_band) are
+// faster for the floor plans that fit them; this kernel is the general path (and the
+// cross-check of the others in the GPU tests).
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (fma only where written).
-#include "sb_device.h"
+#include "sweep_common.h"
 
 namespace sb {
 namespace {
+
+using namespace sweep;
 
 __device__ __forceinline__ int lds_index(const Dev &a, int gidx) {
   if (a.pitch == a.W) return gidx;
@@ -33,20 +36,6 @@ __device__ __forceinline__ int lds_index(const Dev &a, int gidx) {
 // with ds_read_b128 costs ~45 cycles per instruction here, ds_read_b64 ~6.
 
 __device__ __forceinline__ int clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
-
-// lane l <- lane l-1 (lane 0 keeps its own value) / lane l <- lane l+1 (lane 63 keeps).
-__device__ __forceinline__ double wave_shr1(double x) {
-  int lo = __double2loint(x), hi = __double2hiint(x);
-  lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_shl1(double x) {
-  int lo = __double2loint(x), hi = __double2hiint(x);
-  lo = __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
 
 // -- generic sweep: every neighbour through LDS; legal for any shape (fallback) ----------
 struct Chunk {
@@ -198,14 +187,10 @@ __device__ __forceinline__ void load_slot(const double *E, const double *gtab, c
 // lane l <- lane l-1's x; lane 0 (no source lane) keeps `seam` (MULTI) or reads 0.
 template <bool MULTI>
 __device__ __forceinline__ double shr1_seam(double x, double seam) {
-  int lo, hi;
-  if (MULTI) { // the DPP `old` operand is the seam value: no extra instruction
-    lo = __builtin_amdgcn_update_dpp(__double2loint(seam), __double2loint(x), 0x138, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(__double2hiint(seam), __double2hiint(x), 0x138, 0xf, 0xf, false);
-  } else {     // bound_ctrl: out-of-range source reads 0, `old` is a don't-care (no v_mov to set it up)
-    lo = __builtin_amdgcn_update_dpp(__double2loint(x), __double2loint(x), 0x138, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(__double2hiint(x), __double2hiint(x), 0x138, 0xf, 0xf, true);
-  }
+  if (MULTI) return wave_shift1<0x138, true>(x, seam); // the DPP `old` operand is the seam value: no extra instruction
+  // bound_ctrl: out-of-range source reads 0, `old` is a don't-care (no v_mov to set it up)
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(x), __double2loint(x), 0x138, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(x), __double2hiint(x), 0x138, 0xf, 0xf, true);
   return __hiloint2double(hi, lo);
 }
 

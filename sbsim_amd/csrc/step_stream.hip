@@ -19,10 +19,12 @@
 // steps of loads in flight, so what counts is wavefronts per CU (round 5: 128 registers per lane -- 132-144 B of them spilled
 // -- for four wavefronts per SIMD and a zone-sum scratch of 8 instead of 16 columns so that three workgroups of a
 // 299 x 401 plan share a CU instead of two: 1.0e11 -> 1.35e11 cell-sweeps/s at 3,072 buildings).
-#include "sb_device.h"
+#include "sweep_common.h"
 
 namespace sb {
 namespace {
+
+using namespace sweep;
 
 constexpr int kSets = 32;   // entries of the coefficient-set table (at LDS address 0)
 // (developer knobs of tools/build_variant.sh: prefetch depth, zone-sum columns, wavefronts per SIMD asked of the compiler)
@@ -38,17 +40,6 @@ constexpr int kSets = 32;   // entries of the coefficient-set table (at LDS addr
 constexpr int kSpinMax = 1 << 24; // a wait that long is a protocol error: trap instead of hanging the GPU (overlapped sweeps)
 constexpr int kPF = SB_STREAM_PF; // steps between a global load and its use
 constexpr int kZC = SB_STREAM_ZC; // columns of the zone-sum scratch per zone (16 lane columns + 1: odd stride)
-
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef const d2 __attribute__((address_space(3))) *lds_d2;
-typedef volatile int __attribute__((address_space(3))) *lds_vi;
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_seam(double x, double old) { // lanes without a source keep `old`
-  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(x), CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(x), CTRL, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
 
 extern __shared__ __attribute__((aligned(16))) double lds[];
 
@@ -172,8 +163,8 @@ k_sweep_stream(Dev a, double *Abuf) {
           const int c0 = t, c63 = t - 63;   // columns of lane 0 / lane 63 at this step
           const double rU = has_prev && c0 < NS ? up_prev[c0] : 0.0;
           const double rD = has_next && c63 >= 0 ? dn_next[c63] : 0.0;
-          const double Dn = dpp_seam<0x130>(eR, rD);    // lane l + 1's right-hand value is this lane's lower neighbour
-          const double U = dpp_seam<0x138>(nv, rU);     // lane l - 1's previous result
+          const double Dn = wave_shift1<0x130, true>(eR, rD);    // lane l + 1's right-hand value is this lane's lower neighbour
+          const double U = wave_shift1<0x138, true>(nv, rU);     // lane l - 1's previous result
           double tt = fma(ud.y, Dn, Av);
           tt = fma(lr.y, eR, tt);
           tt = fma(lr.x, nv, tt);
@@ -373,8 +364,8 @@ k_sweep_stream_roll(Dev a, double *Abuf, double *Ebuf) {
           const int c0 = t, c63 = t - 63;
           const double rU = has_prev && c0 < NS ? up_prev[c0] : 0.0;
           const double rD = has_next && c63 >= 0 ? dn_next[c63] : 0.0;
-          const double Dn = dpp_seam<0x130>(eR, rD);
-          const double U = dpp_seam<0x138>(nv, rU);
+          const double Dn = wave_shift1<0x130, true>(eR, rD);
+          const double U = wave_shift1<0x138, true>(nv, rU);
           double tt = fma(ud.y, Dn, Av);
           tt = fma(lr.y, eR, tt);
           tt = fma(lr.x, nv, tt);

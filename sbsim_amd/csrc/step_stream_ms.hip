@@ -25,10 +25,12 @@
 // one, the pass is run again from the same input with j + 1 sweeps -- the iterates and the sweep count are always
 // those of the plain schedule; how many sweeps a pass carries (the decay of max |delta| extrapolated to the
 // threshold, like step_two.hip / step_band.hip) only decides the speed.
-#include "sb_device.h"
+#include "sweep_common.h"
 
 namespace sb {
 namespace {
+
+using namespace sweep;
 
 constexpr int kSets = 32;   // entries of the coefficient-set table (at LDS address 0)
 constexpr int kPF = 8;      // steps between sweep 0's global loads and their use
@@ -39,21 +41,10 @@ constexpr int kZC = 9;      // columns of the zone-sum scratch per zone (8 lane 
 #endif
 constexpr int kS = SB_STREAM_S; // sweeps per pass, at most
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef const d2 __attribute__((address_space(3))) *lds_d2;
-typedef volatile int __attribute__((address_space(3))) *lds_vi;
-
 // (the compiler must not fold `word & 0xffff` into the load that fills the read-ahead ring: it then waits for the load at once)
 __device__ __forceinline__ unsigned used_now(unsigned v) {
   asm volatile("" : "+v"(v));
   return v;
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_seam(double x, double old) { // lanes without a source keep `old`
-  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(x), CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(x), CTRL, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
 }
 
 extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -216,9 +207,9 @@ __global__ void __launch_bounds__(64 * WMAX) k_sweep_stream_ms(Dev a, double *Ab
               c0 = c0 < 0 ? 0 : (c0 > NS - 1 ? NS - 1 : c0);
               const double *upj = up + ((size_t)j * W + (wv > 0 ? wv - 1 : 0)) * NSP, *upm = up + ((size_t)(j - 1) * W + (wv > 0 ? wv - 1 : 0)) * NSP;
               const double sU = upj[c0], sR = upm[c0 + 1], sO = upm[c0];
-              const double R = dpp_seam<0x138>(r[j - 1], sR);   // lane l - 1's sweep j - 1 result of the last step
-              const double O = dpp_seam<0x138>(pr[j - 1], sO);  // ... of the step before: the cell's own old value
-              const double U = dpp_seam<0x138>(r[j], sU);       // lane l - 1's sweep j result of the last step
+              const double R = wave_shift1<0x138, true>(r[j - 1], sR);   // lane l - 1's sweep j - 1 result of the last step
+              const double O = wave_shift1<0x138, true>(pr[j - 1], sO);  // ... of the step before: the cell's own old value
+              const double U = wave_shift1<0x138, true>(r[j], sU);       // lane l - 1's sweep j result of the last step
               const double D = r[j - 1], L = r[j];
               double tt = fma(ud.y, D, Av);
               tt = fma(lr.y, R, tt);
@@ -247,8 +238,8 @@ __global__ void __launch_bounds__(64 * WMAX) k_sweep_stream_ms(Dev a, double *Ab
             const int c0 = t, c63 = t - 63;   // columns of lane 0 / lane 63 at this step
             const double rU = has_prev && c0 < NS ? up[(size_t)(wv > 0 ? wv - 1 : 0) * NSP + c0] : 0.0;
             const double rD = has_next && c63 >= 0 && c63 < NS ? dn_next[c63] : 0.0;
-            const double Dn = dpp_seam<0x130>(eR, rD);    // lane l + 1's right-hand value is this lane's lower neighbour
-            const double U = dpp_seam<0x138>(r[0], rU);   // lane l - 1's previous result
+            const double Dn = wave_shift1<0x130, true>(eR, rD);    // lane l + 1's right-hand value is this lane's lower neighbour
+            const double U = wave_shift1<0x138, true>(r[0], rU);   // lane l - 1's previous result
             double tt = fma(ud.y, Dn, Av);
             tt = fma(lr.y, eR, tt);
             tt = fma(lr.x, r[0], tt);

@@ -32,8 +32,6 @@
 // those of the plain schedule; the prediction only decides the speed.  max|delta| of the two sweeps
 // in flight is separated by its sign (a lane mask OR-ed into |delta|'s high word, one running max and one
 // running min).  Two, three or four buildings per CU (LEVEL: how much of A stays in LDS).
-#include <type_traits>
-
 #include "step_two_cfg.h"
 #include "sweep_common.h"
 
@@ -182,14 +180,6 @@ struct Grid {
 struct Win {
   double pa, pb, ca, cb;
 };
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 // Class words: a byte per cell and step -- the coefficient set (its LDS byte offset is set * 32) of the
 // lane's upper (even bytes) and lower cell (odd bytes), four steps per 64-bit word.  The sets of a step

@@ -1,7 +1,10 @@
-// sweep_common.h -- what the register-resident sweep kernels share (step_roll.hip, step_two.hip):
-// lane predicates and DPP moves, and the tail rows -- the rows below the wavefront's (at most two),
-// finished by an affine scan with lanes = columns.  simulator.py:278-371.
+// sweep_common.h -- what the sweep kernels share: value hiding, lane predicates, DPP moves and LDS
+// pointer types (step_reg.hip, step_roll.hip, step_two.hip, step_band.hip, step_lds.hip, step_stream.hip,
+// step_stream_ms.hip), and the tail rows -- the rows below the wavefront's (at most two), finished by an
+// affine scan with lanes = columns (step_roll.hip, step_two.hip, step_band.hip).  simulator.py:278-371.
 #pragma once
+
+#include <type_traits>
 
 #include "sb_device.h"
 
@@ -10,9 +13,25 @@ namespace sweep {
 
 constexpr int kTailMax = 2;
 
+// Hides a value from loop-invariant code motion: without it the compiler precomputes every
+// table address of the unrolled loops once per kernel and spills them to scratch.
+// (An integer offset is hidden, not the pointer: the pointer keeps its address space.)
 __device__ __forceinline__ int opaque(int v) {
   asm volatile("" : "+v"(v));
   return v;
+}
+__device__ __forceinline__ int opaque_s(int v) { // the same for a wave-uniform value (stays in an SGPR)
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
+// f(std::integral_constant<int, i>{}) for i = I .. N - 1, unrolled at compile time
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    static_for<I + 1, N>(f);
+  }
 }
 
 template <int J>
@@ -23,7 +42,8 @@ __device__ __forceinline__ bool lanes_upto() { // lanes 0..J as a lane predicate
 }
 
 // lane l <- lane l-1 (CTRL 0x138, wave_shr:1) / lane l+1 (0x130, wave_shl:1) / rotate (0x13c,
-// wave_ror:1).  SEAM: the lane without a source keeps `old`; otherwise it reads 0.
+// wave_ror:1).  SEAM: the lane without a source keeps `old` (bound_ctrl = 0: the DPP destination
+// is pre-loaded with `old`); otherwise it reads 0.
 template <int CTRL, bool SEAM>
 __device__ __forceinline__ double wave_shift1(double x, double old) {
   int lo, hi;
@@ -39,6 +59,7 @@ __device__ __forceinline__ double wave_shift1(double x, double old) {
 
 typedef double d2 __attribute__((ext_vector_type(2))); // two doubles = one ds_read_b128
 typedef const d2 __attribute__((address_space(3))) *lds_d2;
+typedef volatile int __attribute__((address_space(3))) *lds_vi;
 
 // ---------------------------------------------------------------- tail rows
 // Along a row the Gauss-Seidel update is x_c = bL_c * x_{c-1} + q_c: an inclusive scan over the

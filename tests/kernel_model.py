@@ -210,12 +210,13 @@ class FastSweepModel:
 
 
 # ----------------------------------------------------------------------------------------
-# Model of the register-resident sweep (sbsim_amd/csrc/step_reg.hip) and of its launch
-# planning (plan_reg in sbsim_hip.hip): trim box, cyclic-skewed slots, DPP neighbours, lane
-# predicates, the tail-row recurrence (mode 3) and the two-wavefront seam protocol with its
-# chunk lag and 2-step-early seam reads (mode 2).  The two-wavefront model can run wave 1 as
-# early as the progress counter allows ("tight") or only after wave 0 finished ("late"): every
-# admissible interleaving must give the same grid.
+# Model of the register-resident sweeps and of their launch planning (plan_reg in sbsim_hip.hip):
+# trim box, cyclic-skewed slots, DPP neighbours, lane predicates; k_sweep_reg's one-wavefront
+# mode (mode 1) and its two-wavefront seam protocol with the chunk lag and 2-step-early seam
+# reads (mode 2) (sbsim_amd/csrc/step_reg.hip); k_sweep_roll's tail-row recurrence (mode 3) and
+# its overlapped sweeps (the "rolling" schedule) (step_roll.hip).  The two-wavefront model can
+# run wave 1 as early as the progress counter allows ("tight") or only after wave 0 finished
+# ("late"): every admissible interleaving must give the same grid.
 K_LOOK = 2
 REG_SLOTS = (32, 66, 96)
 
