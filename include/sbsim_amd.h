@@ -418,6 +418,47 @@ int sb_tap_pre(sb_handle *h, int32_t building, const double *zone_temps, const i
 int sb_tap_post(sb_handle *h, int32_t building, const sb_tap_bld *bld, const double *zone_temps,
                 double grid_mean, int32_t n_sweeps, const sb_step_in *in, float *reward, float *info);
 
+/* State snapshots (no reference counterpart: the reference has no simulator checkpoint).  A snapshot is a set of
+ * caller-owned DEVICE buffers holding everything a later step reads before it writes it, one row per building, in a
+ * form that does not depend on the handle's state layout (register / LDS / streaming kernel) or orientation: a snapshot
+ * saved on one handle loads on any handle of the same floor plan and sb_params.  The per-step hand-over between the
+ * step's kernels (what k_pre hands to the sweep and k_post) is rewritten by every step and is not part of it. */
+#define SB_STATE_NUM_SCALARS 20 /* doubles per row of sb_state_view.scal */
+typedef struct sb_state_view {
+  int32_t n;        /* rows */
+  int32_t reserved;
+  double *grid;     /* [n][H*W] building.temp (models/building.py, Building._temp), row-major in the CALLER's
+                     * orientation (see `transposed` below); 16-byte aligned */
+  double *zone;     /* [n][4][Z]: the zone means of the grid (Building.get_zone_average_temps), Vav._zone_air_temperature,
+                     * Vav.damper_setting (vav.py:93-99) and the VAV heat input of the last step (building.py:791 input_q) */
+  int32_t *mode;    /* [n][Z] Thermostat._current_mode (thermostat.py:60-69), bit 8: Vav.reheat_valve_setting */
+  double *scal;     /* [n][SB_STATE_NUM_SCALARS]: the AHU / boiler state of sb_get_scalars' 16 columns, then the extremes of
+                     * the exterior ring (a property of the layout: recomputed from `grid` on load), is_comfort_mode at the
+                     * last thermostat update (Thermostat._previous_timestamp) and the boiler's action age
+                     * (SmartDevice._action_timestamp, boiler.py:158-217) */
+  int32_t *nsw;     /* [n] sweeps | converged << 16 of the last step (simulator.py:318-371): the sweep kernels' first guess */
+  uint32_t *occ;    /* [n][Z] RandomizedArrivalDepartureOccupancy's occupants (randomized_arrival_departure_occupancy.py:
+                     * 150-218), one bit per occupant: non-NULL exactly when sb_occupancy_attach ran */
+} sb_state_view;
+/* The handle's counters a snapshot carries besides the rows (host values). */
+typedef struct sb_state_clock {
+  uint32_t occ_queries;      /* sb_occupancy_peek calls since sb_occupancy_attach: the occupancy draws' counter */
+  uint32_t conv_calls;       /* convection shuffles since sb_convection_attach: the shuffle draws' counter */
+  int32_t steps_since_reset; /* how far the next sb_reset rewinds the boiler's action age */
+  int32_t was_reset;         /* 0 until the first sb_reset has set the construction-time device state */
+} sb_state_clock;
+/* Save: row i of `view` <- building pick_dev[i] of the handle (pick_dev: DEVICE [n] int32, or NULL: row i <- building i,
+ * n == B), for i < n <= view->n; *clock_out (may be NULL) <- the handle's counters.  Load: building b <- row
+ * pick_dev[b] of `view` (DEVICE [B] int32; < 0: building b keeps its state; NULL: row b, view->n == B); with clock_in
+ * non-NULL the handle's counters <- *clock_in.  transposed: the handle's floor plan is the transpose of the caller's
+ * (as for sb_convection_attach).  Stream-ordered: no allocation, copy or synchronisation, so both can be captured
+ * into a graph.  Draws of the device occupancy and convection are keyed by (seed, global building, counter): a
+ * building that takes another's state keeps its own slot's random stream. */
+int sb_state_save(sb_handle *h, const int32_t *pick_dev, int32_t n, const sb_state_view *view,
+                  sb_state_clock *clock_out, int32_t transposed, void *stream);
+int sb_state_load(sb_handle *h, const int32_t *pick_dev, const sb_state_view *view, const sb_state_clock *clock_in,
+                  int32_t transposed, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

@@ -103,6 +103,19 @@ class LaunchInfo(C.Structure):
               ("kernel", C.c_int32), ("reserved", C.c_int32)]
 
 
+SB_STATE_NUM_SCALARS = 20   # doubles per row of sb_state_view.scal
+
+
+class StateView(C.Structure):   # sb_state_view: DEVICE pointers of one snapshot
+  _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("grid", C.c_void_p), ("zone", C.c_void_p),
+              ("mode", C.c_void_p), ("scal", C.c_void_p), ("nsw", C.c_void_p), ("occ", C.c_void_p)]
+
+
+class StateClock(C.Structure):   # sb_state_clock
+  _fields_ = [("occ_queries", C.c_uint32), ("conv_calls", C.c_uint32), ("steps_since_reset", C.c_int32),
+              ("was_reset", C.c_int32)]
+
+
 # sb_sweep_kernel
 SWEEP_KERNELS = {0: "k_sweep_lds", 1: "k_sweep_reg", 2: "k_sweep_reg (two wavefronts)", 3: "k_sweep_roll", 4: "k_sweep_two",
                  5: "k_sweep_band", 6: "k_sweep_stream"}
@@ -113,7 +126,10 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_get_scalars", "sb_get_modes", "sb_get_zone_power", "sb_debug_phase_cycles",
            "sb_floorplan_padded_shape", "sb_floorplan_preprocess", "sb_floorplan_diffusers", "sb_debug_numpy_choice", "sb_pb_reward_info", "sb_pb_reward_response",
            "sb_pb_observation_response", "sb_pb_action_response", "sb_shard_append", "sb_pb_device_info",
-           "sb_pb_zone_info", "sb_pb_variable_info", "sb_record_append", "sb_tap_pre", "sb_tap_post")
+           "sb_pb_zone_info", "sb_pb_variable_info", "sb_record_append", "sb_tap_pre", "sb_tap_post",
+           "sb_state_save", "sb_state_load")
+# entries a library of ABI 8 may predate (load() binds them when present; state_entry() raises without them)
+STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 
 _lib = None
 
@@ -184,8 +200,20 @@ def load():
   L.sb_floorplan_preprocess.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
   L.sb_floorplan_diffusers.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
   L.sb_debug_numpy_choice.argtypes = [C.c_uint32, C.c_int64, C.c_int64, vp]
+  if all(hasattr(L, name) for name in STATE_ENTRIES):
+    L.sb_state_save.argtypes = [vp, vp, C.c_int32, C.POINTER(StateView), C.POINTER(StateClock), C.c_int32, vp]
+    L.sb_state_load.argtypes = [vp, vp, C.POINTER(StateView), C.POINTER(StateClock), C.c_int32, vp]
   _lib = L
   return L
+
+
+def state_entry(name: str):
+  """The state-snapshot entry `name` of the loaded library; a library built before it existed (same ABI version)
+  gets the usual request to rebuild, not an AttributeError."""
+  L = load()
+  if not hasattr(L, name):
+    raise SbsimError(f"{LIB_PATH} has no {name}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+  return getattr(L, name)
 
 
 def check(rc: int, what: str) -> None:

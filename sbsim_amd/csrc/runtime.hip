@@ -141,6 +141,117 @@ __global__ void k_copy_scalars(Dev a, double *out) {
     out[i] = a.scal[(i / kNScalOut) * kNScal + (i % kNScalOut)];
 }
 
+// sb_state_save / sb_state_load: one workgroup per snapshot row (save) / building (load), grid-stride.  The grid is
+// converted between the handle's layout and the caller's row-major [H*W] the way k_copy_temps / k_reset do; on the
+// snapshot side every lane moves 16 bytes at a time (a row that starts at an odd double has a lone cell in front).
+// Load recomputes scal[16..17], which describe the register layout's exterior ring, from the grid's ring cells (k_reset).
+// Padding slots of the register state are written by neither direction.
+constexpr int kStateThreads = 256, kStateUnroll = 4;
+template <bool SAVE>
+__global__ void __launch_bounds__(kStateThreads) k_state(Dev a, sb_state_view v, uint32_t *occ, const int *pick,
+                                                         int rows, int transposed) {
+  __shared__ double red[2][kStateThreads / 64];
+  const int tid = threadIdx.x;
+  const int count = SAVE ? rows : a.B;
+  for (int i = blockIdx.x; i < count; i += gridDim.x) {
+    const int p = pick ? pick[i] : i;
+    const int b = SAVE ? p : i, r = SAVE ? i : p;
+    if (b < 0 || b >= a.B || r < 0 || r >= v.n) continue; // (load: pick < 0 keeps the building; the host checks the rest)
+    double *G = v.grid + (size_t)r * a.N;
+    const int head = (int)(((size_t)r * a.N) & 1);
+    double *T = a.temp + (size_t)b * (a.reg ? (size_t)a.state_doubles : (size_t)a.Np);
+    double *ring = a.ring + (size_t)b * a.n_ring;
+    const double *S = a.scal + (size_t)b * kNScal;
+    const bool ring_uniform = S[16] == S[17]; // (save) after a step the ring holds the ambient temperature of the step
+    const bool plain = !a.reg && !transposed && ((kPad + head) & 1) == 0; // both sides contiguous and 16-byte aligned
+    auto hcell = [&](int g0) { return transposed ? (g0 % a.H) * a.W + g0 / a.H : g0; };
+    auto get = [&](int g0) -> double {
+      const int g = hcell(g0);
+      if (!a.reg) return T[kPad + g];
+      const int cs = a.cell_state[g];
+      return cs >= 0 ? T[cs] : ring_uniform ? S[16] : ring[-cs - 1];
+    };
+    double lo = INFINITY, hi = -INFINITY;
+    auto put = [&](int g0, double x) {
+      const int g = hcell(g0);
+      if (!a.reg) { T[kPad + g] = x; return; }
+      const int cs = a.cell_state[g];
+      if (cs >= 0) { T[cs] = x; return; }
+      ring[-cs - 1] = x;
+      lo = fmin(lo, x);
+      hi = fmax(hi, x);
+    };
+    // cells head + 2k, head + 2k + 1: kStateUnroll pairs per lane in flight
+    for (int j0 = head + 2 * tid; j0 + 1 < a.N; j0 += 2 * kStateThreads * kStateUnroll) {
+      double2 x[kStateUnroll];
+#pragma unroll
+      for (int u = 0; u < kStateUnroll; ++u) {
+        const int j = j0 + 2 * kStateThreads * u;
+        if (j + 1 >= a.N) break;
+        if (!SAVE) x[u] = *(const double2 *)(G + j);
+        else if (plain) x[u] = *(const double2 *)(T + kPad + j);
+        else x[u] = make_double2(get(j), get(j + 1));
+      }
+#pragma unroll
+      for (int u = 0; u < kStateUnroll; ++u) {
+        const int j = j0 + 2 * kStateThreads * u;
+        if (j + 1 >= a.N) break;
+        if (SAVE) *(double2 *)(G + j) = x[u];
+        else if (plain) *(double2 *)(T + kPad + j) = x[u];
+        else { put(j, x[u].x); put(j + 1, x[u].y); }
+      }
+    }
+    const int lone = tid == 0 && head ? 0 : tid == 1 && ((a.N - head) & 1) ? a.N - 1 : -1;
+    if (lone >= 0) {
+      if (SAVE) G[lone] = get(lone);
+      else put(lone, G[lone]);
+    }
+    // the per-building rows: zone arrays, modes, scalars, sweep count, occupants
+    const size_t zb = (size_t)b * a.Z;
+    double *zs = v.zone + (size_t)r * 4 * a.Z;
+    double *zh[4] = {a.zmean + zb, a.zair + zb, a.damper + zb, a.qz + zb};
+    for (int k = tid; k < 4 * a.Z; k += kStateThreads) {
+      double *h = zh[k / a.Z] + k % a.Z;
+      if (SAVE) zs[k] = *h;
+      else *h = zs[k];
+    }
+    for (int z = tid; z < a.Z; z += kStateThreads) {
+      int *m = a.mode + zb + z, *ms = v.mode + (size_t)r * a.Z + z;
+      if (SAVE) *ms = *m;
+      else *m = *ms;
+      if (occ) {
+        uint32_t *o = occ + zb + z, *os = v.occ + (size_t)r * a.Z + z;
+        if (SAVE) *os = *o;
+        else *o = *os;
+      }
+    }
+    double *Ss = v.scal + (size_t)r * kNScal, *Sh = a.scal + (size_t)b * kNScal;
+    if (SAVE) {
+      if (tid < kNScal) Ss[tid] = Sh[tid];
+      if (tid == 0) v.nsw[r] = a.nsw[b];
+      continue;
+    }
+    if (tid < kNScal && tid != 16 && tid != 17) Sh[tid] = Ss[tid];
+    if (tid == 0) a.nsw[b] = v.nsw[r];
+    if (a.reg && a.n_ring > 0) { // the ring's extremes, as k_reset computes them (every lane of the workgroup holds cells)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        lo = fmin(lo, __shfl_xor(lo, o, 64));
+        hi = fmax(hi, __shfl_xor(hi, o, 64));
+      }
+      if ((tid & 63) == 0) { red[0][tid >> 6] = lo; red[1][tid >> 6] = hi; }
+      __syncthreads();
+      if (tid == 0) {
+        for (int w = 1; w < kStateThreads / 64; ++w) { lo = fmin(lo, red[0][w]); hi = fmax(hi, red[1][w]); }
+        Sh[16] = lo; Sh[17] = hi;
+      }
+      __syncthreads(); // red is reused by the workgroup's next building
+    } else if (tid == 0) {
+      Sh[16] = Sh[17] = 0.0;
+    }
+  }
+}
+
 // Per-building algebra before / after the sweep kernel (sb_device.h).  k_pre: one 16-lane row of a wavefront per building,
 // lanes = zones -- four buildings per wavefront, sixteen per workgroup; the building's demand sums in the reference's zone
 // order through DPP row broadcasts.  k_post: one thread per building (the row shape was measured slower: sb_device.h).
@@ -340,6 +451,59 @@ int sb_get_modes(sb_handle *h, int32_t *out_dev, void *stream) {
   return SB_OK;
 }
 SB_COPY_OUT(sb_get_zone_power, h->d.qz, (size_t)h->d.B *h->d.Z, double)
+
+/* ---- state snapshots ---- */
+static int check_state_view(const sb_handle *h, const sb_state_view *v, const char *who) {
+  const std::string w(who);
+  if (!v) return fail(SB_ERR_INVALID, w + ": null view");
+  if (v->n <= 0) return fail(SB_ERR_INVALID, w + ": the view needs n > 0 rows");
+  if (!v->grid || !v->zone || !v->mode || !v->scal || !v->nsw) return fail(SB_ERR_INVALID, w + ": null view field");
+  if ((uintptr_t)v->grid % 16) return fail(SB_ERR_INVALID, w + ": grid must be 16-byte aligned");
+  if ((v->occ != nullptr) != h->occ_attached)
+    return fail(SB_ERR_INVALID, w + (h->occ_attached ? ": the handle has device occupancy: occ is needed"
+                                                     : ": occ given, but the handle has no device occupancy"));
+  return SB_OK;
+}
+
+static void launch_state(const sb_handle *h, bool save, const int32_t *pick, int rows, const sb_state_view *v,
+                         int transposed, hipStream_t stream) {
+  const int count = save ? rows : h->d.B;
+  const dim3 grid(std::max(1, std::min(count, h->cus * 8))), block(kStateThreads);
+  uint32_t *occ = v->occ ? h->occ_state.p : nullptr;
+  if (save) hipLaunchKernelGGL(k_state<true>, grid, block, 0, stream, h->d, *v, occ, pick, rows, transposed);
+  else hipLaunchKernelGGL(k_state<false>, grid, block, 0, stream, h->d, *v, occ, pick, rows, transposed);
+}
+
+int sb_state_save(sb_handle *h, const int32_t *pick_dev, int32_t n, const sb_state_view *view,
+                  sb_state_clock *clock_out, int32_t transposed, void *stream) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_state_save: null handle");
+  SB_CHECK(check_state_view(h, view, "sb_state_save"));
+  if (n <= 0 || n > view->n) return fail(SB_ERR_INVALID, "sb_state_save: need 0 < n <= view->n");
+  if (!pick_dev && n != h->d.B) return fail(SB_ERR_INVALID, "sb_state_save: without pick_dev, n must be the batch size");
+  SB_ON_DEVICE(h->device);
+  launch_state(h, true, pick_dev, n, view, transposed, (hipStream_t)stream);
+  SB_HIP(hipGetLastError());
+  if (clock_out) *clock_out = sb_state_clock{h->occ_queries, h->conv_calls, h->steps_since_reset, h->was_reset ? 1 : 0};
+  return SB_OK;
+}
+
+int sb_state_load(sb_handle *h, const int32_t *pick_dev, const sb_state_view *view, const sb_state_clock *clock_in,
+                  int32_t transposed, void *stream) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_state_load: null handle");
+  SB_CHECK(check_state_view(h, view, "sb_state_load"));
+  if (!pick_dev && view->n != h->d.B) return fail(SB_ERR_INVALID, "sb_state_load: without pick_dev, view->n must be the batch size");
+  if (clock_in && clock_in->steps_since_reset < 0) return fail(SB_ERR_INVALID, "sb_state_load: negative steps_since_reset");
+  SB_ON_DEVICE(h->device);
+  launch_state(h, false, pick_dev, 0, view, transposed, (hipStream_t)stream);
+  SB_HIP(hipGetLastError());
+  if (clock_in) {
+    h->occ_queries = clock_in->occ_queries;
+    h->conv_calls = clock_in->conv_calls;
+    h->steps_since_reset = clock_in->steps_since_reset;
+    h->was_reset = clock_in->was_reset != 0;
+  }
+  return SB_OK;
+}
 
 /* ---- known-answer taps: k_pre / k_post on prescribed state of one building ---- */
 int sb_tap_pre(sb_handle *h, int32_t building, const double *zone_temps, const int32_t *modes,

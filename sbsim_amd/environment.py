@@ -27,8 +27,10 @@ import copy
 import ctypes as C
 import dataclasses
 import datetime as dt
+import hashlib
 import math
 import os
+import pickle
 from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
@@ -258,6 +260,64 @@ def histogram_reducer_layout(source_names: Sequence[str],
   return names, src_dest, hist_col, hist_off, hist_bins
 
 
+@dataclasses.dataclass
+class SimState:
+  """A snapshot of a ``BatchedSimulator``'s buildings (sb_state_save): device tensors of ``n`` rows in a form that does
+  not depend on the state layout, the sweep kernel or the orientation the library chose, the handle's counters
+  (``clock``: occupancy queries, convection calls, steps since the last reset, reset once), and a fingerprint of what
+  the rows mean -- floor plan and zone count, the compiled plan tables, ``SimConfig.to_params()``, the device
+  generators attached and their ``first_building``.  ``BatchedSimulator.load_state`` refuses another fingerprint."""
+  grid: torch.Tensor              # [n, H*W] float64, the caller's orientation
+  zone: torch.Tensor              # [n, 4, Z] float64: zone means, VAV zone-air temperature, damper, zone heat input
+  mode: torch.Tensor              # [n, Z] int32: thermostat mode | reheat valve << 8
+  scal: torch.Tensor              # [n, 20] float64
+  nsw: torch.Tensor               # [n] int32: sweeps | converged << 16 of the last step
+  occ: Optional[torch.Tensor]     # [n, Z] int32 (occupant bits) when device occupancy is attached
+  clock: Tuple[int, int, int, int]
+  fingerprint: Tuple
+
+  @property
+  def n(self) -> int:
+    return int(self.grid.shape[0])
+
+  def tensors(self) -> Dict[str, Optional[torch.Tensor]]:
+    return dict(grid=self.grid, zone=self.zone, mode=self.mode, scal=self.scal, nsw=self.nsw, occ=self.occ)
+
+  def view(self) -> _ffi.StateView:
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    v = _ffi.StateView()
+    v.n = self.n
+    v.grid, v.zone, v.mode, v.scal, v.nsw, v.occ = (ptr(self.grid), ptr(self.zone), ptr(self.mode), ptr(self.scal),
+                                                     ptr(self.nsw), ptr(self.occ))
+    return v
+
+  def state_dict(self) -> dict:
+    d = {k: (None if t is None else t.cpu()) for k, t in self.tensors().items()}
+    d.update(clock=list(self.clock), fingerprint=list(self.fingerprint))
+    return d
+
+  @staticmethod
+  def from_state_dict(d: Mapping, device) -> "SimState":
+    if not isinstance(d, Mapping) or "fingerprint" not in d or "clock" not in d:
+      raise ValueError("not a SimState state_dict: fingerprint or clock missing")
+    to = lambda t: None if t is None else t.to(device).contiguous()
+    return SimState(to(d["grid"]), to(d["zone"]), to(d["mode"]), to(d["scal"]), to(d["nsw"]), to(d.get("occ")),
+                    tuple(int(x) for x in d["clock"]), _as_fingerprint(d["fingerprint"]))
+
+
+def _as_fingerprint(f) -> Tuple:
+  return tuple(_as_fingerprint(x) if isinstance(x, (list, tuple)) else x for x in f)
+
+
+def _sha(*arrays) -> str:
+  h = hashlib.sha256()
+  for a in arrays:
+    a = np.ascontiguousarray(a)
+    h.update(str((a.dtype.str, a.shape)).encode())
+    h.update(a.tobytes())
+  return h.hexdigest()
+
+
 class BatchedSimulator:
   """Thin owner of the C-ABI handle: B building instances of one floor plan on one GPU.
 
@@ -274,6 +334,9 @@ class BatchedSimulator:
     if not torch.cuda.is_available():
       raise _ffi.SbsimError("sbsim_amd needs a HIP device (MI355X); there is no CPU path")
     self.plan, self.config, self.B, self.device = plan, config, int(n_buildings), int(device)
+    self._h_conv = float(h_conv)
+    self._occ_attached = self._conv_attached = None   # the arguments of the device generators (SimState fingerprint)
+    self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
     if orientation not in ("auto", "rows", "columns"):
@@ -390,12 +453,16 @@ class BatchedSimulator:
     cfg = _ffi.OccupancyConfig(int(zone_assignment), int(hours[0]), int(hours[1]), int(hours[2]), int(hours[3]),
                                float(time_step_sec), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_building))
     _ffi.check(self._lib.sb_occupancy_attach(self._h, C.byref(cfg)), "sb_occupancy_attach")
+    self._occ_attached = (int(zone_assignment), tuple(int(x) for x in hours[:4]), float(time_step_sec),
+                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_building))
 
   def convection_attach(self, p: float, distance: int, seed: int, first_building: int = 0) -> None:
     """sb_convection_attach: StochasticConvectionSimulator(p, distance, seed) after every FD update
     (stochastic_convection_simulator.py:62-145), counter-based draws per building."""
     _ffi.check(self._lib.sb_convection_attach(self._h, float(p), int(distance), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                               int(first_building), int(self.transposed)), "sb_convection_attach")
+    self._conv_attached = (None if p == 0.0 or distance == 0
+                           else (float(p), int(distance), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_building)))
 
   def occupancy_peek(self, local_hour: int, is_work_day: bool, count: Optional[torch.Tensor] = None,
                      total: Optional[torch.Tensor] = None) -> None:
@@ -448,6 +515,89 @@ class BatchedSimulator:
       return
     _ffi.check(self._lib.sb_step_phases(*args, int(phases)), "sb_step")
 
+  # ---- state snapshots (sb_state_save / sb_state_load) ----
+  def state_fingerprint(self) -> Tuple:
+    """What a SimState of this simulator means: plan shape and zones, a hash of the compiled plan tables (in the
+    caller's orientation) and of SimConfig.to_params(), the attached device generators.  Not the layout, the
+    orientation or the sweep kernel: a snapshot moves between them."""
+    if self._fingerprint is None:
+      cp = self.plan.compile(self.config.time_step_sec, self._h_conv)
+      prm = self.config.to_params()
+      vals = []
+      for name, ctype in _ffi.PARAM_FIELDS:
+        v = getattr(prm, name)
+        vals.append(repr([v[i] for i in range(prm.n_actions)]) if name.startswith("act_") else repr(v))
+      params_hash = hashlib.sha256(repr(vals).encode()).hexdigest()
+      self._fingerprint = ((self.H, self.W, self.Z),
+                           _sha(cp.cell_class, cp.class_coef, cp.class_zone, cp.zone_off, cp.zone_cells), params_hash)
+    return self._fingerprint + (self._occ_attached, self._conv_attached)
+
+  def save_state(self, rows: Optional[torch.Tensor] = None) -> SimState:
+    """Snapshot of every building (``rows`` None) or of buildings ``rows`` (int32 / int64 [n] on the device; row i of
+    the snapshot holds building rows[i]).  Stream-ordered on the current stream."""
+    pick, n = None, self.B
+    if rows is not None:
+      pick = self._check_index(rows, None, 0, self.B, "rows")
+      n = int(pick.shape[0])
+    dev = self.tdev
+    st = SimState(torch.empty((n, self.H * self.W), dtype=torch.float64, device=dev),
+                  torch.empty((n, 4, self.Z), dtype=torch.float64, device=dev),
+                  torch.empty((n, self.Z), dtype=torch.int32, device=dev),
+                  torch.empty((n, _ffi.SB_STATE_NUM_SCALARS), dtype=torch.float64, device=dev),
+                  torch.empty((n,), dtype=torch.int32, device=dev),
+                  torch.empty((n, self.Z), dtype=torch.int32, device=dev) if self._occ_attached else None,
+                  (0, 0, 0, 0), self.state_fingerprint())
+    clk = _ffi.StateClock()
+    _ffi.check(_ffi.state_entry("sb_state_save")(
+        self._h, None if pick is None else C.c_void_p(pick.data_ptr()), n, C.byref(st.view()), C.byref(clk),
+        int(self.transposed), self._stream()), "sb_state_save")
+    st.clock = (clk.occ_queries, clk.conv_calls, clk.steps_since_reset, clk.was_reset)
+    return st
+
+  def load_state(self, state: SimState, pick: Optional[torch.Tensor] = None, clock: bool = True) -> None:
+    """Building b <- row pick[b] of ``state`` (pick: int32 / int64 [B] on the device, < 0 keeps building b; None:
+    row b, state.n == B).  clock: also set the handle's counters (occupancy / convection draws, steps since reset) to
+    the snapshot's -- a restore; False for a fork, whose counters go on.  Raises ValueError for a state of another
+    fingerprint, or a pick of the wrong shape, dtype, device or range, before anything is launched."""
+    if not isinstance(state, SimState):
+      raise ValueError("load_state needs a SimState")
+    if state.fingerprint != self.state_fingerprint():
+      raise ValueError("this SimState belongs to another floor plan, configuration or generator set: "
+                       f"{state.fingerprint} != {self.state_fingerprint()}")
+    n = state.n
+    shapes = dict(grid=(n, self.H * self.W), zone=(n, 4, self.Z), mode=(n, self.Z),
+                  scal=(n, _ffi.SB_STATE_NUM_SCALARS), nsw=(n,), occ=(n, self.Z))
+    dtypes = dict(grid=torch.float64, zone=torch.float64, scal=torch.float64, mode=torch.int32, nsw=torch.int32,
+                  occ=torch.int32)
+    for k, t in state.tensors().items():
+      if t is None:
+        continue
+      if (tuple(t.shape) != shapes[k] or t.dtype != dtypes[k] or t.device != self.tdev or not t.is_contiguous()
+          or t.data_ptr() % 16):
+        raise ValueError(f"SimState.{k}: expected a contiguous {dtypes[k]} {shapes[k]} tensor on {self.tdev}")
+    if pick is None:
+      if n != self.B:
+        raise ValueError(f"a SimState of {n} rows loads into {self.B} buildings only with a pick")
+    else:
+      pick = self._check_index(pick, self.B, -(1 << 31), n, "pick")
+    clk = _ffi.StateClock(*state.clock) if clock else None
+    _ffi.check(_ffi.state_entry("sb_state_load")(
+        self._h, None if pick is None else C.c_void_p(pick.data_ptr()), C.byref(state.view()),
+        C.byref(clk) if clk is not None else None, int(self.transposed), self._stream()), "sb_state_load")
+
+  def _check_index(self, t: torch.Tensor, length: Optional[int], lo: int, hi: int, what: str) -> torch.Tensor:
+    """A device index vector, checked on the host: int32 / int64, 1-D (of `length`), values in [lo, hi) (lo < 0: a
+    negative value is allowed and means "none").  Returns it as contiguous int32."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64):
+      raise ValueError(f"{what} must be an int32 or int64 tensor")
+    if t.dim() != 1 or (length is not None and t.shape[0] != length) or t.shape[0] == 0:
+      raise ValueError(f"{what} must be a non-empty 1-D tensor" + (f" of {length}" if length is not None else ""))
+    if t.device != self.tdev:
+      raise ValueError(f"{what} must be on {self.tdev}")
+    if int(t.max()) >= hi or int(t.min()) < lo:
+      raise ValueError(f"{what} out of range: its values must be below {hi}" + ("" if lo < 0 else f" and >= {lo}"))
+    return t.to(torch.int32).contiguous()
+
   # ---- parity taps ----
   def _get(self, fn, shape, dtype):
     out = torch.empty(shape, dtype=dtype, device=self.tdev)
@@ -479,6 +629,41 @@ class BatchedSimulator:
 
   def zone_power(self) -> torch.Tensor:
     return self._get(self._lib.sb_get_zone_power, (self.B, self.Z), torch.float64)
+
+
+@dataclasses.dataclass
+class EnvSnapshot:
+  """``BatchedEnvironment.snapshot()``: the simulator's ``SimState``, the environment's host clock, deep copies of its
+  stateful host models (a shared ``RandomizedArrivalDepartureOccupancy`` draws from its ``np.random.RandomState``
+  every step) and copies of the current TimeStep and info.  ``state_dict()`` / ``from_state_dict`` give a form
+  ``torch.save`` / ``torch.load`` (``weights_only`` too) take, so that another process can restore it into an environment of the
+  same floor plan and configuration; the host models travel pickled inside it -- load checkpoints you trust."""
+  sim: SimState
+  host: Dict              # _now, _step_count, _episode_count, _episode_ended, _needs_reset, _prev_thermostat_ts
+  rejected: Optional[torch.Tensor]   # the per-building rejection flags of the last step that had any (or None)
+  models: Dict            # attribute name -> deep copy of a stateful host model
+  observation: torch.Tensor
+  reward: torch.Tensor
+  info: Optional[torch.Tensor]
+
+  def state_dict(self) -> dict:
+    cpu = lambda t: None if t is None else t.cpu()
+    enc = lambda v: (["datetime", v.isoformat()] if isinstance(v, dt.datetime) else v)
+    return dict(kind="sbsim_amd.EnvSnapshot", sim=self.sim.state_dict(), host={k: enc(v) for k, v in self.host.items()},
+                rejected=cpu(self.rejected), models=pickle.dumps(self.models), observation=cpu(self.observation),
+                reward=cpu(self.reward), info=cpu(self.info), fingerprint=list(self.sim.fingerprint))
+
+  @staticmethod
+  def from_state_dict(d: Mapping, device) -> "EnvSnapshot":
+    if not isinstance(d, Mapping) or d.get("kind") != "sbsim_amd.EnvSnapshot" or "sim" not in d:
+      raise ValueError("not an EnvSnapshot state_dict")
+    if "fingerprint" not in d or _as_fingerprint(d["fingerprint"]) != _as_fingerprint(d["sim"].get("fingerprint", ())):
+      raise ValueError("EnvSnapshot state_dict: fingerprint missing or not that of its simulator state")
+    dec = lambda v: (dt.datetime.fromisoformat(v[1]) if isinstance(v, (list, tuple)) and len(v) == 2
+                     and v[0] == "datetime" else v)
+    to = lambda t: None if t is None else t.to(device).contiguous()
+    return EnvSnapshot(SimState.from_state_dict(d["sim"], device), {k: dec(v) for k, v in d["host"].items()},
+                       to(d["rejected"]), pickle.loads(d["models"]), to(d["observation"]), to(d["reward"]), to(d["info"]))
 
 
 class BatchedEnvironment:
@@ -692,6 +877,89 @@ class BatchedEnvironment:
     mid = torch.full((self.batch_size,), STEP_MID, dtype=torch.int32, device=dev)
     return TimeStep(mid, self._reward, self._discount, self._obs)
 
+
+  # ---- snapshots ----
+  _HOST_CLOCK = ("_now", "_step_count", "_episode_count", "_episode_ended", "_needs_reset", "_prev_thermostat_ts")
+
+  def _stateful_models(self) -> Dict:
+    """Host models whose answers depend on what they answered before (the device-side occupancy keeps its state on
+    the device: it is in the SimState)."""
+    out = {}
+    if (isinstance(self.occupancy, host_inputs.RandomizedArrivalDepartureOccupancy)
+        and self._occ_count is None):
+      out["occupancy"] = self.occupancy
+    return out
+
+  def snapshot(self) -> EnvSnapshot:
+    """Everything ``restore`` needs to put this environment back where it is now: the simulator state of every
+    building, the host clock and episode bookkeeping, stateful host models, the current TimeStep and info."""
+    if self._needs_reset:
+      raise ValueError("snapshot() needs a current TimeStep: reset() first")
+    clone = lambda t: None if t is None else t.clone()
+    return EnvSnapshot(self.sim.save_state(), {k: getattr(self, k) for k in self._HOST_CLOCK},
+                       clone(getattr(self, "_rejected", None)),
+                       {k: copy.deepcopy(v) for k, v in self._stateful_models().items()},
+                       self._obs.clone(), self._reward.clone(), clone(self._info))
+
+  def _timestep(self) -> TimeStep:
+    """The TimeStep that reset() / step() returned last, rebuilt from the host clock and the current buffers."""
+    dev = self.sim.tdev
+    if self._episode_ended:
+      return TimeStep(torch.full((self.batch_size,), STEP_LAST, dtype=torch.int32, device=dev), self._reward,
+                      self._zero, self._obs)
+    if self._step_count == 0:
+      return TimeStep(torch.full((self.batch_size,), STEP_FIRST, dtype=torch.int32, device=dev), self._zero,
+                      torch.ones_like(self._discount), self._obs)
+    return TimeStep(torch.full((self.batch_size,), STEP_MID, dtype=torch.int32, device=dev), self._reward,
+                    self._discount, self._obs)
+
+  def restore(self, snap: EnvSnapshot) -> TimeStep:
+    """Puts the environment back to ``snap`` (of this environment, or of one of the same floor plan, configuration
+    and batch size) and returns the TimeStep that was current then.  The simulator's draw counters rewind with it,
+    so the device occupancy and convection draw what they drew after the snapshot: a restored batch replays exactly."""
+    if not isinstance(snap, EnvSnapshot):
+      raise ValueError("restore needs an EnvSnapshot")
+    if tuple(snap.observation.shape) != tuple(self._obs.shape) or (snap.info is None) != (self._info is None):
+      raise ValueError("this EnvSnapshot belongs to an environment of another batch size, observation or info layout")
+    models = {k: copy.deepcopy(v) for k, v in snap.models.items()}
+    if set(models) != set(self._stateful_models()):
+      raise ValueError(f"this EnvSnapshot carries host models {sorted(models)}, the environment has "
+                       f"{sorted(self._stateful_models())}")
+    self.sim.load_state(snap.sim)   # (checks the fingerprint before anything changes)
+    for k, v in snap.host.items():
+      setattr(self, k, v)
+    for k, v in models.items():
+      setattr(self, k, v)
+    if snap.rejected is not None:
+      self._rejected = snap.rejected.clone()
+    elif getattr(self, "_rejected", None) is not None:
+      self._rejected = None
+    self._obs.copy_(snap.observation)
+    self._reward.copy_(snap.reward)
+    if self._info is not None:
+      self._info.copy_(snap.info)
+    return self._timestep()
+
+  def fork(self, src: torch.Tensor) -> None:
+    """Building b takes building src[b]'s current state (src: int64 [B] on the device; repeats and aliasing allowed):
+    one save of the distinct source buildings and one load with a pick.  The clock does not move; the current
+    observation, reward and info rows follow their buildings.  Random streams: the device occupancy and convection
+    draw by (seed, global building, counter), so a forked building keeps its own slot's stream -- forked replicas
+    of one building diverge under those stochastic models and stay identical without them."""
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.int64 or tuple(src.shape) != (self.batch_size,):
+      raise ValueError(f"src must be an int64 [{self.batch_size}] tensor")
+    if src.device != self.sim.tdev:
+      raise ValueError(f"src must be on {self.sim.tdev}")
+    if int(src.min()) < 0 or int(src.max()) >= self.batch_size:
+      raise ValueError(f"src out of range [0, {self.batch_size})")
+    uniq, inv = torch.unique(src, return_inverse=True)
+    state = self.sim.save_state(rows=uniq)
+    self.sim.load_state(state, pick=inv, clock=False)
+    self._obs.copy_(self._obs[src])
+    self._reward.copy_(self._reward[src])
+    if self._info is not None:
+      self._info.copy_(self._info[src])
+
   def close(self) -> None:
     self.sim.close()
 
@@ -837,6 +1105,47 @@ class MixedBatchedEnvironment:
     action = action.contiguous()
     return self._each(lambda k, env: env.step(action[self.slices[k][0]:self.slices[k][1]],
                                               None if rejected is None else rejected[self.slices[k][0]:self.slices[k][1]]))
+
+
+  def _on_streams(self, fn) -> list:
+    """fn(class index, env) on every class's stream between two joins with the caller's stream (as _each)."""
+    cur = torch.cuda.current_stream(self.tdev)
+    ready = torch.cuda.Event()
+    ready.record(cur)
+    out = []
+    for k, (env, stream) in enumerate(zip(self.envs, self.streams)):
+      stream.wait_event(ready)
+      with torch.cuda.stream(stream):
+        out.append(fn(k, env))
+        done = torch.cuda.Event()
+        done.record(stream)
+      cur.wait_event(done)
+    return out
+
+  def snapshot(self) -> List[EnvSnapshot]:
+    """One ``EnvSnapshot`` per class (``BatchedEnvironment.snapshot``), taken on the class streams."""
+    return self._on_streams(lambda k, env: env.snapshot())
+
+  def restore(self, snaps: Sequence[EnvSnapshot]) -> TimeStep:
+    if len(snaps) != len(self.envs):
+      raise ValueError(f"restore needs one EnvSnapshot per class ({len(self.envs)})")
+    return self._each(lambda k, env: env.restore(snaps[k]))
+
+  def fork(self, src: torch.Tensor) -> None:
+    """Building b takes building src[b]'s state (GLOBAL indices, int64 [B_total] on the device); a building takes
+    state only from its own class (ValueError otherwise).  See ``BatchedEnvironment.fork``."""
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.int64 or tuple(src.shape) != (self.batch_size,):
+      raise ValueError(f"src must be an int64 [{self.batch_size}] tensor")
+    if src.device != self.tdev:
+      raise ValueError(f"src must be on {self.tdev}")
+    if int(src.min()) < 0 or int(src.max()) >= self.batch_size:
+      raise ValueError(f"src out of range [0, {self.batch_size})")
+    if not bool((self.class_of_building[src] == self.class_of_building).all()):
+      raise ValueError("fork: a building can only take the state of a building of its own floor-plan class")
+    self._on_streams(lambda k, env: env.fork(src[self.slices[k][0]:self.slices[k][1]] - self.slices[k][0]))
+    for k, (a, b) in enumerate(self.slices):   # the mixed TimeStep buffers follow
+      self._obs[a:b, : self.observation_widths[k]].copy_(self.envs[k]._obs)
+      self._reward[a:b].copy_(self.envs[k]._reward)
 
   def close(self) -> None:
     for env in self.envs:
