@@ -185,7 +185,8 @@ typedef enum sb_sweep_kernel {
   SB_KERNEL_ROLL = 3,     /* k_sweep_roll: one wavefront + tail rows, overlapped sweeps (step_roll.hip) */
   SB_KERNEL_TWO_ROWS = 4, /* k_sweep_two: two rows per lane, 67..130 rows, sweeps overlapped in blocks (step_two.hip) */
   SB_KERNEL_BAND = 5,     /* k_sweep_band: two wavefronts, one row per lane, 67..130 rows, sweeps overlapped in blocks (step_band.hip) */
-  SB_KERNEL_STREAM = 6    /* k_sweep_stream: the grid stays in global memory, up to 16 wavefronts per building (step_stream.hip) */
+  SB_KERNEL_STREAM = 6,   /* k_sweep_stream: the grid stays in global memory, up to 16 wavefronts per building (step_stream.hip) */
+  SB_KERNEL_JACOBI = 7    /* k_sweep_jacobi: TFSimulator's float32 Jacobi update, not Gauss-Seidel (step_jacobi.hip; sb_create_jacobi) */
 } sb_sweep_kernel;
 
 /* Launch geometry chosen for the floor plan (reported for DESIGN.md / bench.py). */
@@ -458,6 +459,40 @@ int sb_state_save(sb_handle *h, const int32_t *pick_dev, int32_t n, const sb_sta
                   sb_state_clock *clock_out, int32_t transposed, void *stream);
 int sb_state_load(sb_handle *h, const int32_t *pick_dev, const sb_state_view *view, const sb_state_clock *clock_in,
                   int32_t transposed, void *stream);
+
+/* The other finite-difference solver of the reference: TFSimulator (simulator/tf_simulator.py:502-853), the one SB1's
+ * shipped configuration selects.  One iteration computes every control volume (CV) from the previous iterate, in
+ * binary32, one rounding per operation in the reference's order (sbsim_amd/floorplan.py FloorPlan.compile_jacobi):
+ *   den = (vz*(((k1u + k3u) + hL) + hR) + uz*(((k2v + k4v) + hB) + hT)) + M/dt                  (per class, host)
+ *   num = ((vz*(((k1u*TL + k3u*TR) + Tinf*hL) + Tinf*hR) + uz*(((k2v*Tbelow + k4v*Tabove) + Tinf*hB) + Tinf*hT))
+ *          + (M*Tprev)/dt) + q,    T' = num / den,    exterior CVs (0-1 neighbours) T' = Tinf
+ * with TL = T[i][j+1], TR = T[i][j-1], Tabove = T[i-1][j], Tbelow = T[i+1][j] (the reference's names: the horizontal pair
+ * is swapped, the vertical one is not), Tinf outside the grid, q = (float)(q_zone * diffuser), Tprev the grid at the start
+ * of the step.  The loop stops at max|T' - T| <= (float)conv_threshold or iter_limit.  Every CV of the [H][W] grid is
+ * state (no trim), in the caller's orientation (never transposed: that would move the swap to the other axis). */
+#define SB_JACOBI_COEFS 16 /* floats per class row of sb_jacobi_desc.class_f32 */
+typedef struct sb_jacobi_desc {
+  int32_t H, W, n_classes, reserved;
+  const uint8_t *cell_class;     /* [H*W] class per CV, row-major */
+  const float *class_f32;        /* [n_classes][SB_JACOBI_COEFS]: k1u k3u k2v k4v uz vz den M hL hR hT hB exterior(0/1) 0 0 0 */
+  const double *class_diffuser;  /* [n_classes] diffuser weight (building.py:873-889 input_q = q_zone * weight) */
+  const int32_t *class_zone;     /* [n_classes] the zone whose VAV power feeds q, or -1 */
+} sb_jacobi_desc;
+/* A handle whose sweep kernel is k_sweep_jacobi (SB_KERNEL_JACOBI).  `plan` supplies H, W, the zones and their cells
+ * (its class tables are not used); everything else is sb_create's.  The state is a float32 grid [B][H*W]: sb_reset
+ * rounds temps_dev to float32 (the zone means and grid mean of the first step come from the float64 values, which the
+ * reference reads before its first FD update rounds them); sb_get_temps widens it to float64.  SB_ERR_TOO_LARGE when two
+ * float32 grids and the class table do not fit 160 KiB of LDS.  sb_set_temps, sb_state_save / sb_state_load and
+ * sb_convection_attach return SB_ERR_UNSUPPORTED on such a handle.  sb_step's info column 4 counts Jacobi iterations. */
+int sb_create_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, const sb_params *params,
+                     const sb_obs_layout *obs, int32_t n_buildings, int32_t device, sb_handle **out);
+/* Known-answer tap of k_sweep_jacobi: finite_differences_timestep (simulator.py:318-371 with TFSimulator's update) of
+ * buildings 0 .. n-1 of a Jacobi handle from prescribed Tprev [n][H*W] float32, q [n][H*W] float32 (input_q as the
+ * reference converts it) and Tinf [n] (float64, rounded to float32 as the reference's constant is).  Outputs: the grid
+ * [n][H*W], the iterations and the converged flag per building (any output may be NULL).  HOST pointers; synchronous.
+ * Overwrites those buildings' grids and step hand-over: not for use inside a rollout. */
+int sb_tap_jacobi(sb_handle *h, int32_t n, const float *tprev, const float *q, const double *tinf, float *grid_out,
+                  int32_t *iterations, int32_t *converged);
 
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */

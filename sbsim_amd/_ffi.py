@@ -116,9 +116,18 @@ class StateClock(C.Structure):   # sb_state_clock
               ("was_reset", C.c_int32)]
 
 
+SB_JACOBI_COEFS = 16   # floats per class row of sb_jacobi_desc.class_f32
+
+
+class JacobiDesc(C.Structure):   # sb_jacobi_desc
+  _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("n_classes", C.c_int32), ("reserved", C.c_int32),
+              ("cell_class", C.POINTER(C.c_uint8)), ("class_f32", _fp), ("class_diffuser", _dp), ("class_zone", _ip)]
+
+
 # sb_sweep_kernel
 SWEEP_KERNELS = {0: "k_sweep_lds", 1: "k_sweep_reg", 2: "k_sweep_reg (two wavefronts)", 3: "k_sweep_roll", 4: "k_sweep_two",
-                 5: "k_sweep_band", 6: "k_sweep_stream"}
+                 5: "k_sweep_band", 6: "k_sweep_stream", 7: "k_sweep_jacobi"}
+SB_KERNEL_JACOBI = 7
 
 
 EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb_plan_info", "sb_create", "sb_destroy", "sb_get_launch_info",
@@ -127,9 +136,10 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_floorplan_padded_shape", "sb_floorplan_preprocess", "sb_floorplan_diffusers", "sb_debug_numpy_choice", "sb_pb_reward_info", "sb_pb_reward_response",
            "sb_pb_observation_response", "sb_pb_action_response", "sb_shard_append", "sb_pb_device_info",
            "sb_pb_zone_info", "sb_pb_variable_info", "sb_record_append", "sb_tap_pre", "sb_tap_post",
-           "sb_state_save", "sb_state_load")
-# entries a library of ABI 8 may predate (load() binds them when present; state_entry() raises without them)
+           "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi")
+# entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
+JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
 
 _lib = None
 
@@ -203,6 +213,10 @@ def load():
   if all(hasattr(L, name) for name in STATE_ENTRIES):
     L.sb_state_save.argtypes = [vp, vp, C.c_int32, C.POINTER(StateView), C.POINTER(StateClock), C.c_int32, vp]
     L.sb_state_load.argtypes = [vp, vp, C.POINTER(StateView), C.POINTER(StateClock), C.c_int32, vp]
+  if all(hasattr(L, name) for name in JACOBI_ENTRIES):
+    L.sb_create_jacobi.argtypes = [C.POINTER(PlanDesc), C.POINTER(JacobiDesc), C.POINTER(Params), C.POINTER(ObsLayout),
+                                   C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.sb_tap_jacobi.argtypes = [vp, C.c_int32, _fp, _fp, _dp, _fp, _ip, _ip]
   _lib = L
   return L
 
@@ -210,6 +224,15 @@ def load():
 def state_entry(name: str):
   """The state-snapshot entry `name` of the loaded library; a library built before it existed (same ABI version)
   gets the usual request to rebuild, not an AttributeError."""
+  L = load()
+  if not hasattr(L, name):
+    raise SbsimError(f"{LIB_PATH} has no {name}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+  return getattr(L, name)
+
+
+def jacobi_entry(name: str):
+  """The Jacobi-solver entry `name` of the loaded library (sb_create_jacobi, sb_tap_jacobi); a library built before it
+  existed (same ABI version) gets the usual request to rebuild, not an AttributeError."""
   L = load()
   if not hasattr(L, name):
     raise SbsimError(f"{LIB_PATH} has no {name}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")

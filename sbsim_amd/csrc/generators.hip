@@ -471,6 +471,7 @@ int sb_occupancy_peek(sb_handle *h, int32_t local_hour, int32_t is_work_day, flo
 int sb_convection_attach(sb_handle *h, double p, int32_t distance, uint64_t seed, int64_t first_building,
                          int32_t transposed) {
   if (!h) return fail(SB_ERR_INVALID, "sb_convection_attach: null handle");
+  if (h->kernel == SB_KERNEL_JACOBI) return fail(SB_ERR_UNSUPPORTED, "sb_convection_attach: not implemented for the Jacobi solver");
   if (!(p >= 0.0 && p <= 1.0)) return fail(SB_ERR_INVALID, "sb_convection_attach: p must be in [0, 1]");
   if (first_building < 0) return fail(SB_ERR_INVALID, "sb_convection_attach: first_building must be >= 0");
   if (p == 0.0 || distance == 0) { h->conv_attached = false; return SB_OK; } // stochastic_convection_simulator.py:70-71

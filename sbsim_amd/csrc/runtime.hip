@@ -252,6 +252,54 @@ __global__ void __launch_bounds__(kStateThreads) k_state(Dev a, sb_state_view v,
   }
 }
 
+// SB_KERNEL_JACOBI: Simulator.reset() on the float32 grid.  The grid is stored rounded to float32 (as the reference's first
+// FD update reads it); the zone means and the grid mean the first step reads are the float64 values, as the reference's
+// are.  The scalars as k_reset sets them.  One wavefront per building.
+__global__ void k_reset_jacobi(Dev a, float *grid, double initial_temp, const double *temps, int first, int steps_since_reset) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int nwaves = gridDim.x * (blockDim.x >> 6);
+  for (int b = wave; b < a.B; b += nwaves) {
+    double s = 0.0;
+    for (int g = lane; g < a.N; g += 64) {
+      const double v = temps ? temps[(size_t)b * a.N + g] : initial_temp;
+      grid[(size_t)b * a.N + g] = (float)v;
+      s += v;
+    }
+    s = wave_sum(s);
+    for (int z = 0; z < a.Z; ++z) {
+      double zs = 0.0;
+      const int b0 = a.zone_off[z], b1 = a.zone_off[z + 1];
+      for (int i = b0 + lane; i < b1; i += 64) zs += temps ? temps[(size_t)b * a.N + a.zone_cells_l[i]] : initial_temp;
+      zs = wave_sum(zs);
+      if (lane == 0) {
+        const size_t o = (size_t)b * a.Z + z;
+        a.zmean[o] = zs / (double)(b1 - b0);
+        a.zair[o] = 0.0;   // vav.py:93-99
+        a.damper[o] = 0.1;
+        a.mode[o] &= kModeMask;
+        a.qz[o] = 0.0;     // building.py:791 input_q <- 0
+      }
+    }
+    if (lane == 0) {
+      double *S = a.scal + (size_t)b * kNScal;
+      S[0] = a.p.ahu_heat_sp; S[1] = a.p.ahu_cool_sp; S[2] = 0.0; S[3] = 0.0; // air_handler.py:131-139
+      S[4] = a.p.blr_setpoint; S[5] = 0.0; S[6] = 0.0; S[7] = 0.0;           // boiler.py:110-121
+      S[8] = a.p.blr_setpoint; S[9] = 0.0; S[10] = 0.0;
+      S[11] = s / (double)a.N;
+      S[12] = S[13] = S[14] = S[15] = 0.0;
+      S[16] = S[17] = 0.0; // (the register path's ring extremes: no ring here)
+      if (first) { S[18] = -1.0; S[19] = kAgeNone; }
+      else if (!age_is_none(S[19])) S[19] -= (double)steps_since_reset;
+    }
+  }
+}
+
+__global__ void k_copy_temps_jacobi(const float *grid, size_t n, double *out) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = (double)grid[i];
+}
+
 // Per-building algebra before / after the sweep kernel (sb_device.h).  k_pre: one 16-lane row of a wavefront per building,
 // lanes = zones -- four buildings per wavefront, sixteen per workgroup; the building's demand sums in the reference's zone
 // order through DPP row broadcasts.  k_post: one thread per building (the row shape was measured slower: sb_device.h).
@@ -293,6 +341,7 @@ int prepare_sweep(const sb_handle *h) {
       if (h->stream_variant == kStreamMs) return prepare_sweep_stream_ms(d, waves);
       if (h->stream_variant == kStreamRoll) return prepare_sweep_stream_roll(d, waves);
       return prepare_sweep_stream(d, waves);
+    case SB_KERNEL_JACOBI: return prepare_sweep_jacobi(d.H, d.W, d.ncls);
   }
   return (int)hipErrorInvalidValue;
 }
@@ -310,6 +359,7 @@ int launch_sweep(const sb_handle *h, hipStream_t stream) {
       if (h->stream_variant == kStreamMs) return launch_sweep_stream_ms(d, h->abuf.p, h->ebuf.p, waves, stream);
       if (h->stream_variant == kStreamRoll) return launch_sweep_stream_roll(d, h->abuf.p, h->ebuf.p, waves, stream);
       return launch_sweep_stream(d, h->abuf.p, waves, stream);
+    case SB_KERNEL_JACOBI: return launch_sweep_jacobi(d, h->jac, h->info.workgroups, stream);
   }
   return (int)hipErrorInvalidValue;
 }
@@ -337,8 +387,12 @@ int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *s
   SB_ON_DEVICE(h->device);
   const int wpb = 4;
   const int blocks = std::min((h->d.B + wpb - 1) / wpb, 4096);
-  hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream, h->d, initial_temp,
-                     temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset, 0);
+  if (h->kernel == SB_KERNEL_JACOBI)
+    hipLaunchKernelGGL(k_reset_jacobi, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream, h->d, h->jgrid.p,
+                       initial_temp, temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset);
+  else
+    hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream, h->d, initial_temp,
+                       temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset, 0);
   h->was_reset = true;
   h->steps_since_reset = 0;
   h->counters_zeroed_on = (void *)(uintptr_t)1; // (whatever came before a reset is no promise about the draw counters)
@@ -349,6 +403,7 @@ int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *s
 int sb_set_temps(sb_handle *h, const double *temps_dev, void *stream) {
   if (!h || !temps_dev) return fail(SB_ERR_INVALID, "sb_set_temps: null argument");
   if (!h->was_reset) return fail(SB_ERR_INVALID, "sb_set_temps: sb_reset first");
+  if (h->kernel == SB_KERNEL_JACOBI) return fail(SB_ERR_UNSUPPORTED, "sb_set_temps: not implemented for the Jacobi solver");
   SB_ON_DEVICE(h->device);
   const int wpb = 4;
   const int blocks = std::min((h->d.B + wpb - 1) / wpb, 4096);
@@ -421,7 +476,11 @@ int sb_step(sb_handle *h, const float *actions_dev, const sb_step_in *in, float 
 int sb_get_temps(sb_handle *h, double *out_dev, void *stream) {
   if (!h || !out_dev) return fail(SB_ERR_INVALID, "sb_get_temps: null argument");
   SB_ON_DEVICE(h->device);
-  hipLaunchKernelGGL(k_copy_temps, dim3(2048), dim3(256), 0, (hipStream_t)stream, h->d, out_dev);
+  if (h->kernel == SB_KERNEL_JACOBI)
+    hipLaunchKernelGGL(k_copy_temps_jacobi, dim3(2048), dim3(256), 0, (hipStream_t)stream, h->jgrid.p,
+                       (size_t)h->d.B * h->d.N, out_dev);
+  else
+    hipLaunchKernelGGL(k_copy_temps, dim3(2048), dim3(256), 0, (hipStream_t)stream, h->d, out_dev);
   SB_HIP(hipGetLastError());
   return SB_OK;
 }
@@ -477,6 +536,7 @@ static void launch_state(const sb_handle *h, bool save, const int32_t *pick, int
 int sb_state_save(sb_handle *h, const int32_t *pick_dev, int32_t n, const sb_state_view *view,
                   sb_state_clock *clock_out, int32_t transposed, void *stream) {
   if (!h) return fail(SB_ERR_INVALID, "sb_state_save: null handle");
+  if (h->kernel == SB_KERNEL_JACOBI) return fail(SB_ERR_UNSUPPORTED, "sb_state_save: not implemented for the Jacobi solver");
   SB_CHECK(check_state_view(h, view, "sb_state_save"));
   if (n <= 0 || n > view->n) return fail(SB_ERR_INVALID, "sb_state_save: need 0 < n <= view->n");
   if (!pick_dev && n != h->d.B) return fail(SB_ERR_INVALID, "sb_state_save: without pick_dev, n must be the batch size");
@@ -490,6 +550,7 @@ int sb_state_save(sb_handle *h, const int32_t *pick_dev, int32_t n, const sb_sta
 int sb_state_load(sb_handle *h, const int32_t *pick_dev, const sb_state_view *view, const sb_state_clock *clock_in,
                   int32_t transposed, void *stream) {
   if (!h) return fail(SB_ERR_INVALID, "sb_state_load: null handle");
+  if (h->kernel == SB_KERNEL_JACOBI) return fail(SB_ERR_UNSUPPORTED, "sb_state_load: not implemented for the Jacobi solver");
   SB_CHECK(check_state_view(h, view, "sb_state_load"));
   if (!pick_dev && view->n != h->d.B) return fail(SB_ERR_INVALID, "sb_state_load: without pick_dev, view->n must be the batch size");
   if (clock_in && clock_in->steps_since_reset < 0) return fail(SB_ERR_INVALID, "sb_state_load: negative steps_since_reset");
@@ -580,6 +641,37 @@ int sb_tap_post(sb_handle *h, int32_t building, const sb_tap_bld *bld, const dou
   SB_HIP(hipDeviceSynchronize());
   SB_HIP(hipMemcpy(reward, rew.p + building, sizeof(float), hipMemcpyDeviceToHost));
   if (info) SB_HIP(hipMemcpy(info, inf.p + (size_t)building * SB_INFO_STRIDE, sizeof(float) * SB_INFO_STRIDE, hipMemcpyDeviceToHost));
+  return SB_OK;
+}
+
+int sb_tap_jacobi(sb_handle *h, int32_t n, const float *tprev, const float *q, const double *tinf, float *grid_out,
+                  int32_t *iterations, int32_t *converged) {
+  if (!h || !tprev || !q || !tinf) return fail(SB_ERR_INVALID, "sb_tap_jacobi: null argument");
+  if (h->kernel != SB_KERNEL_JACOBI) return fail(SB_ERR_INVALID, "sb_tap_jacobi: not a Jacobi handle (sb_create_jacobi)");
+  const Dev &d = h->d;
+  if (n < 1 || n > d.B) return fail(SB_ERR_INVALID, "sb_tap_jacobi: need 1 <= n <= n_buildings");
+  SB_ON_DEVICE(h->device);
+  h->counters_zeroed_on = (void *)(uintptr_t)1; // the next sweep launch zeroes the draw counter itself
+  SB_HIP(hipDeviceSynchronize());
+  const size_t cells = (size_t)n * d.N;
+  SB_HIP(hipMemcpy(h->jgrid.p, tprev, cells * sizeof(float), hipMemcpyHostToDevice));
+  DevBuf<float> qb;
+  DevBuf<double> tb;
+  SB_CHECK(upload(qb, q, cells));
+  SB_CHECK(upload(tb, tinf, (size_t)n));
+  SB_HIP(hipMemset(d.next_b, 0, sizeof(int)));
+  JacArgs j = h->jac;
+  j.nb = n; j.q = qb.p; j.tinf = tb.p;
+  const int e = launch_sweep_jacobi(d, j, h->info.workgroups, nullptr);
+  if (e != (int)hipSuccess) return fail(SB_ERR_HIP, std::string("sb_tap_jacobi: ") + hipGetErrorString((hipError_t)e));
+  SB_HIP(hipDeviceSynchronize());
+  if (grid_out) SB_HIP(hipMemcpy(grid_out, h->jgrid.p, cells * sizeof(float), hipMemcpyDeviceToHost));
+  std::vector<int> nsw((size_t)n);
+  SB_HIP(hipMemcpy(nsw.data(), d.nsw, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i) {
+    if (iterations) iterations[i] = nsw[i] & 0xffff;
+    if (converged) converged[i] = nsw[i] >> 16;
+  }
   return SB_OK;
 }
 

@@ -26,6 +26,29 @@ int prepare_sweep_stream_roll(const Dev &d, int waves);
 int sweep_stream_roll_xchg_extra_doubles();
 } // namespace sb
 
+// step_jacobi.hip: k_sweep_jacobi (SB_KERNEL_JACOBI), TFSimulator's float32 Jacobi update.  Its own arguments besides Dev:
+// Dev carries the step hand-over (Bld::t_now, gtabg, zsum, gsum, nsw, next_b) and the zones as for every sweep kernel.
+namespace sb {
+struct JacArgs {
+  float *grid;         // [B][N] the float32 state, row-major in the caller's orientation
+  const uint8_t *cls;  // [N] class per CV
+  const float *tab;    // [ncls][SB_JACOBI_COEFS] sb_jacobi_desc.class_f32
+  const double *rden;  // [ncls] 1.0 / (double)den, correctly rounded (host)
+  int ncls;
+  int n_pad;           // floats per LDS grid buffer (sweep_jacobi_slots: the grid with its T_inf padding)
+  int nb;              // buildings of this launch (B; sb_tap_jacobi: its n)
+  const float *q;      // sb_tap_jacobi: [nb][N] input_q; NULL: q = (float)gtabg[class]
+  const double *tinf;  // sb_tap_jacobi: [nb] T_inf; NULL: Bld::t_now
+};
+bool sweep_jacobi_supported(int N);                // an instantiation holds N CVs (N <= 20,480)
+int sweep_jacobi_threads(int N);                   // threads per workgroup of that instantiation
+int sweep_jacobi_slots(int H, int W);              // floats of one LDS grid buffer
+size_t sweep_jacobi_lds_bytes(int H, int W, int ncls); // LDS per workgroup (dynamic + static)
+int prepare_sweep_jacobi(int H, int W, int ncls);
+int sweep_jacobi_blocks_per_cu(int H, int W, int ncls); // resident workgroups per CU (registers, LDS, waves); 0: unknown
+int launch_sweep_jacobi(const Dev &d, const JacArgs &j, int workgroups, hipStream_t stream);
+} // namespace sb
+
 // SB_KERNEL_STREAM's variants (= Dev::stream_ms): k_sweep_stream; the experimental k_sweep_stream_ms, k_sweep_stream_roll
 enum { kStreamPlain = 0, kStreamMs = 1, kStreamRoll = 2 };
 
@@ -149,6 +172,11 @@ struct sb_handle {
   sb_occupancy_config occ{};
   uint32_t occ_queries = 0;
   bool occ_attached = false;
+  // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
+  DevBuf<float> jgrid, jtab;
+  DevBuf<double> jrden;
+  DevBuf<uint8_t> jcls;
+  sb::JacArgs jac{};
 };
 
 

@@ -1263,6 +1263,22 @@ int prepare_and_reset(sb_handle *h) {
   return SB_OK;
 }
 
+// sb_create_jacobi: the plan the shared state sees has the Jacobi classes, with g = diffuser weight * q_zone (gc = 0,
+// sc = weight: k_pre's g table then holds the reference's float64 input_q of every class, fma(w, q, 0) = w * q)
+int check_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, std::vector<double> &coef, sb_plan_desc &jp) {
+  if (!jac->cell_class || !jac->class_f32 || !jac->class_diffuser || !jac->class_zone)
+    return fail(SB_ERR_INVALID, "sb_create_jacobi: null class table");
+  if (jac->H != plan->H || jac->W != plan->W) return fail(SB_ERR_INVALID, "sb_create_jacobi: plan and Jacobi tables differ in shape");
+  if (jac->n_classes < 1 || jac->n_classes > 255) return fail(SB_ERR_INVALID, "sb_create_jacobi: 1 .. 255 classes");
+  for (int c = 0; c < jac->n_classes; ++c)
+    if (!(jac->class_f32[c * SB_JACOBI_COEFS + 6] > 0.0f)) return fail(SB_ERR_INVALID, "sb_create_jacobi: a class with den <= 0");
+  coef.assign((size_t)jac->n_classes * 8, 0.0);
+  for (int c = 0; c < jac->n_classes; ++c) coef[(size_t)c * 8 + 6] = jac->class_diffuser[c];
+  jp = *plan;
+  jp.n_classes = jac->n_classes; jp.cell_class = jac->cell_class; jp.class_coef = coef.data(); jp.class_zone = jac->class_zone;
+  return SB_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1317,6 +1333,70 @@ int sb_create(const sb_plan_desc *plan, const sb_params *params, const sb_obs_la
   SB_CHECK(setup_obs_tables(h.get(), params, obs, acts));
   SB_CHECK(setup_state(h.get(), plan));
   setup_debug(h.get(), k);
+  SB_CHECK(prepare_and_reset(h.get()));
+  *out = h.release();
+  return SB_OK;
+}
+
+int sb_create_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, const sb_params *params,
+                     const sb_obs_layout *obs, int32_t n_buildings, int32_t device, sb_handle **out) {
+  if (!plan || !jac || !params || !obs || !out) return fail(SB_ERR_INVALID, "sb_create_jacobi: null argument");
+  std::vector<double> coef;
+  sb_plan_desc jp;
+  SB_CHECK(check_jacobi(plan, jac, coef, jp));
+  ActionTable acts;
+  SB_CHECK(check_create_args(&jp, params, obs, n_buildings, acts));
+  const int N = jp.H * jp.W, ncls = jp.n_classes;
+  const size_t lds = sweep_jacobi_lds_bytes(jp.H, jp.W, ncls);
+  if (!sweep_jacobi_supported(N) || lds > (size_t)kLdsCap)
+    return fail(SB_ERR_TOO_LARGE, "k_sweep_jacobi: two float32 grids of " + std::to_string(N) +
+                                      " CVs and the class table do not fit 160 KiB of LDS");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(SB_ERR_NO_DEVICE, "sb_create_jacobi: no HIP device visible (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return fail(SB_ERR_INVALID, "sb_create_jacobi: bad device ordinal");
+  SB_ON_DEVICE(device);
+  hipDeviceProp_t prop;
+  SB_HIP(hipGetDeviceProperties(&prop, device));
+
+  auto h = std::make_unique<sb_handle>();
+  h->device = device;
+  h->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  h->kernel = SB_KERNEL_JACOBI;
+  Dev &d = h->d;
+  d.B = n_buildings; d.H = jp.H; d.W = jp.W; d.Z = jp.Z;
+  d.N = N; d.Np = N; d.pitch = d.W; d.NL = N;
+  d.ncls = ncls; d.ts = (ncls + 15) & ~15;
+  d.p = *params;
+  d.p.act_kind = d.p.act_zone = nullptr; d.p.act_lo = d.p.act_hi = nullptr;
+  d.reg = 0; d.P = SB_KERNEL_JACOBI;
+  { // launch geometry: the workgroups resident at once (the runtime's occupancy for this instantiation: registers, LDS,
+    // wavefronts), one building each at a time; more would only start after others retire
+    const int threads = sweep_jacobi_threads(N);
+    const int occ = sweep_jacobi_blocks_per_cu(jp.H, jp.W, ncls);
+    const int per_cu = std::max(1, occ > 0 ? occ : std::min((int)((size_t)kLdsCap / lds), 32 / (threads / 64)));
+    sb_launch_info &li = h->info;
+    li.kernel = SB_KERNEL_JACOBI;
+    li.path = 0;
+    li.waves_per_building = li.waves_per_workgroup = threads / 64;
+    li.workgroups = std::max(1, std::min(n_buildings, h->cus * per_cu));
+    li.lds_bytes_per_workgroup = (int32_t)lds;
+    li.sweep_steps = 1; // (no wavefront schedule: every CV of an iteration at once)
+    li.algorithmic_bytes_per_env_step = 8ll * N + 24ll * d.Z + 4ll * params->n_actions + 4ll * obs->n_obs + 44;
+    li.state_bytes_per_env_step = 8ll * N; // the float32 grid, read once and written once
+  }
+  h->h_state_index.resize((size_t)N);
+  for (int g = 0; g < N; ++g) h->h_state_index[g] = g;
+  SB_CHECK(upload(h->zone_cells_l, jp.zone_cells, (size_t)jp.zone_off[jp.Z])); // flat grid indices
+  SB_CHECK(setup_obs_tables(h.get(), params, obs, acts));
+  SB_CHECK(setup_state(h.get(), &jp));
+  std::vector<double> rden((size_t)ncls);
+  for (int c = 0; c < ncls; ++c) rden[c] = 1.0 / (double)jac->class_f32[c * SB_JACOBI_COEFS + 6];
+  SB_CHECK(upload(h->jcls, jac->cell_class, (size_t)N));
+  SB_CHECK(upload(h->jtab, jac->class_f32, (size_t)ncls * SB_JACOBI_COEFS));
+  SB_CHECK(upload(h->jrden, rden.data(), rden.size()));
+  SB_CHECK(alloc_zero(h->jgrid, (size_t)d.B * N));
+  h->jac = JacArgs{h->jgrid.p, h->jcls.p, h->jtab.p, h->jrden.p, ncls, sweep_jacobi_slots(jp.H, jp.W), d.B, nullptr, nullptr};
   SB_CHECK(prepare_and_reset(h.get()));
   *out = h.release();
   return SB_OK;

@@ -318,6 +318,9 @@ def _sha(*arrays) -> str:
   return h.hexdigest()
 
 
+SOLVERS = ("gauss_seidel", "jacobi_fp32")   # BatchedSimulator / BatchedEnvironment(solver=...)
+
+
 class BatchedSimulator:
   """Thin owner of the C-ABI handle: B building instances of one floor plan on one GPU.
 
@@ -329,7 +332,16 @@ class BatchedSimulator:
                observation_normalization: Optional[Mapping[str, Tuple[float, float]]] = None,
                zone_names: Optional[Sequence[str]] = None, orientation: str = "auto",
                histogram_parameters: Optional[Sequence[Tuple[str, Sequence[float]]]] = None,
-               normalize_reduce: bool = False):
+               normalize_reduce: bool = False, solver: str = "gauss_seidel"):
+    """``solver``: "gauss_seidel" -- SimulatorFlexibleGeometries' float64 sweep (simulator.py:278-371), the library's
+    own kernels; "jacobi_fp32" -- TFSimulator's float32 Jacobi update (tf_simulator.py:502-853), the solver of SB1's
+    shipped sim_config.gin, on k_sweep_jacobi (grid in the caller's orientation only; no snapshots, no convection)."""
+    if solver not in SOLVERS:
+      raise ValueError(f"solver must be one of {SOLVERS}")
+    if solver == "jacobi_fp32" and orientation not in ("auto", "rows"):
+      raise ValueError("solver='jacobi_fp32' keeps the caller's orientation (transposing would move TFSimulator's "
+                       "swapped horizontal neighbours to the other axis): orientation must be 'auto' or 'rows'")
+    self.solver = solver
     self._lib = _ffi.load()
     if not torch.cuda.is_available():
       raise _ffi.SbsimError("sbsim_amd needs a HIP device (MI355X); there is no CPU path")
@@ -374,20 +386,24 @@ class BatchedSimulator:
     # device-side orientation (internal to the library; reset()/temps() convert, so callers
     # always see the reference's [H, W] layout): the library reports, per orientation, which
     # step kernel it would use, how many wavefront steps one sweep takes and on how many wavefronts
-    if orientation == "auto" and os.environ.get("SBSIM_ORIENTATION") in ("rows", "columns"):   # developer knob
-      orientation = os.environ["SBSIM_ORIENTATION"]
-    cands = {"rows": [False], "columns": [True], "auto": [False, True]}[orientation]
-    best = None
-    for tr in cands:
-      cand = describe(plan.transposed() if tr else plan)
-      rc, info = cand[3]
-      # SIMD steps per building-sweep: a kernel that spreads a building over two wavefronts holds half as many
-      pref = {1: 0, 0: 1, 2: 2}.get(info.path, 3) if rc == 0 else 9   # registers, then LDS, then the streaming kernel
-      key = (rc != 0, pref, info.sweep_steps * max(info.waves_per_building, 1) if rc == 0 else 0)
-      if best is None or key < best[0]:
-        best = (key, tr, cand)
-    self.transposed = best[1]
-    self.compiled, keep, pd_, _ = best[2]
+    if orientation == "auto" and os.environ.get("SBSIM_ORIENTATION") in ("rows", "columns") and solver == "gauss_seidel":
+      orientation = os.environ["SBSIM_ORIENTATION"]   # (developer knob)
+    if solver == "jacobi_fp32":
+      self.transposed = False
+      self.compiled, keep, pd_, jd = self._describe_jacobi(plan, config.time_step_sec, h_conv)
+    else:
+      cands = {"rows": [False], "columns": [True], "auto": [False, True]}[orientation]
+      best = None
+      for tr in cands:
+        cand = describe(plan.transposed() if tr else plan)
+        rc, info = cand[3]
+        # SIMD steps per building-sweep: a kernel that spreads a building over two wavefronts holds half as many
+        pref = {1: 0, 0: 1, 2: 2}.get(info.path, 3) if rc == 0 else 9   # registers, then LDS, then the streaming kernel
+        key = (rc != 0, pref, info.sweep_steps * max(info.waves_per_building, 1) if rc == 0 else 0)
+        if best is None or key < best[0]:
+          best = (key, tr, cand)
+      self.transposed = best[1]
+      self.compiled, keep, pd_, _ = best[2]
     norm = dict(observation_normalization or {})
     mean = np.zeros(max(self.O, n_src))     # by source index
     sigma = np.ones(max(self.O, n_src))
@@ -412,14 +428,59 @@ class BatchedSimulator:
     params = config.to_params()
     h = C.c_void_p()
     with torch.cuda.device(self.device):
-      _ffi.check(self._lib.sb_create(C.byref(pd_), C.byref(params), C.byref(ol), self.B, self.device,
-                                     C.byref(h)), "sb_create")
+      if solver == "jacobi_fp32":
+        _ffi.check(_ffi.jacobi_entry("sb_create_jacobi")(C.byref(pd_), C.byref(jd), C.byref(params), C.byref(ol), self.B,
+                                                         self.device, C.byref(h)), "sb_create_jacobi")
+      else:
+        _ffi.check(self._lib.sb_create(C.byref(pd_), C.byref(params), C.byref(ol), self.B, self.device,
+                                       C.byref(h)), "sb_create")
     self._h = h
     self.tdev = torch.device("cuda", self.device)
     info = _ffi.LaunchInfo()
     _ffi.check(self._lib.sb_get_launch_info(self._h, C.byref(info)), "sb_get_launch_info")
     self.launch_info = {f[0]: getattr(info, f[0]) for f in _ffi.LaunchInfo._fields_}
     self.sweep_events = None   # a list: step() appends (start, end) HIP events of every sweep-kernel launch (bench.py)
+
+  @staticmethod
+  def _describe_jacobi(plan: FloorPlan, dt: float, h_conv: float):
+    """FloorPlan.compile_jacobi's tables as sb_create_jacobi's arguments (the plan descriptor carries the zones)."""
+    jp = plan.compile_jacobi(dt, h_conv)
+    keep = dict(cls=np.ascontiguousarray(jp.cell_class), f32=np.ascontiguousarray(jp.class_f32),
+                diff=np.ascontiguousarray(jp.class_diffuser), czone=np.ascontiguousarray(jp.class_zone),
+                coef=np.zeros((jp.n_classes, 8)), zoff=np.ascontiguousarray(jp.zone_off),
+                zcells=np.ascontiguousarray(jp.zone_cells))
+    keep["coef"][:, 6] = jp.class_diffuser
+    pd_ = _ffi.PlanDesc(jp.H, jp.W, jp.Z, jp.n_classes, keep["cls"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                        keep["coef"].ctypes.data_as(_ffi._dp), keep["czone"].ctypes.data_as(_ffi._ip),
+                        keep["zoff"].ctypes.data_as(_ffi._ip), keep["zcells"].ctypes.data_as(_ffi._ip))
+    jd = _ffi.JacobiDesc(jp.H, jp.W, jp.n_classes, 0, keep["cls"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                         keep["f32"].ctypes.data_as(_ffi._fp), keep["diff"].ctypes.data_as(_ffi._dp),
+                         keep["czone"].ctypes.data_as(_ffi._ip))
+    return jp, keep, pd_, jd
+
+  def _refuse_on_jacobi(self, what: str) -> None:
+    if self.solver == "jacobi_fp32":
+      raise ValueError(f"{what} is not implemented for solver='jacobi_fp32' (the Jacobi path keeps a float32 grid the "
+                       "snapshot format and the convection shuffle do not handle yet); use solver='gauss_seidel'")
+
+  def tap_jacobi(self, tprev: np.ndarray, q: np.ndarray, tinf: np.ndarray):
+    """sb_tap_jacobi: one finite_differences_timestep of TFSimulator on buildings 0 .. n-1 from prescribed float32
+    grids Tprev [n, H, W], float32 input_q [n, H, W] and T_inf [n].  Returns (grid [n, H, W] float32, iterations [n],
+    converged [n]).  Overwrites those buildings' grids: not inside a rollout."""
+    if self.solver != "jacobi_fp32":
+      raise ValueError("tap_jacobi needs solver='jacobi_fp32'")
+    n = int(tprev.shape[0])
+    tp = np.ascontiguousarray(tprev, dtype=np.float32).reshape(n, -1)
+    qq = np.ascontiguousarray(q, dtype=np.float32).reshape(n, -1)
+    ti = np.ascontiguousarray(tinf, dtype=np.float64).reshape(n)
+    grid = np.zeros_like(tp)
+    iters, conv = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    torch.cuda.synchronize(self.tdev)
+    with torch.cuda.device(self.device):
+      _ffi.check(_ffi.jacobi_entry("sb_tap_jacobi")(
+          self._h, n, tp.ctypes.data_as(_ffi._fp), qq.ctypes.data_as(_ffi._fp), ti.ctypes.data_as(_ffi._dp),
+          grid.ctypes.data_as(_ffi._fp), iters.ctypes.data_as(_ffi._ip), conv.ctypes.data_as(_ffi._ip)), "sb_tap_jacobi")
+    return grid.reshape(n, self.H, self.W), iters, conv
 
   def close(self) -> None:
     if getattr(self, "_h", None):
@@ -459,6 +520,7 @@ class BatchedSimulator:
   def convection_attach(self, p: float, distance: int, seed: int, first_building: int = 0) -> None:
     """sb_convection_attach: StochasticConvectionSimulator(p, distance, seed) after every FD update
     (stochastic_convection_simulator.py:62-145), counter-based draws per building."""
+    self._refuse_on_jacobi("the convection shuffle")
     _ffi.check(self._lib.sb_convection_attach(self._h, float(p), int(distance), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                               int(first_building), int(self.transposed)), "sb_convection_attach")
     self._conv_attached = (None if p == 0.0 or distance == 0
@@ -535,6 +597,7 @@ class BatchedSimulator:
   def save_state(self, rows: Optional[torch.Tensor] = None) -> SimState:
     """Snapshot of every building (``rows`` None) or of buildings ``rows`` (int32 / int64 [n] on the device; row i of
     the snapshot holds building rows[i]).  Stream-ordered on the current stream."""
+    self._refuse_on_jacobi("save_state")
     pick, n = None, self.B
     if rows is not None:
       pick = self._check_index(rows, None, 0, self.B, "rows")
@@ -559,6 +622,7 @@ class BatchedSimulator:
     row b, state.n == B).  clock: also set the handle's counters (occupancy / convection draws, steps since reset) to
     the snapshot's -- a restore; False for a fork, whose counters go on.  Raises ValueError for a state of another
     fingerprint, or a pick of the wrong shape, dtype, device or range, before anything is launched."""
+    self._refuse_on_jacobi("load_state")
     if not isinstance(state, SimState):
       raise ValueError("load_state needs a SimState")
     if state.fingerprint != self.state_fingerprint():
@@ -613,6 +677,7 @@ class BatchedSimulator:
   def set_temps(self, temps: torch.Tensor) -> None:
     """sb_set_temps: building.temp <- temps ([B, H, W] float64 on the device) between two steps; every
     device state stays (what Building.apply_convection does to the reference's array, building.py:891-893)."""
+    self._refuse_on_jacobi("set_temps")
     if temps.dtype != torch.float64 or tuple(temps.shape) != (self.B, self.H, self.W):
       raise ValueError(f"temps must be float64 [{self.B}, {self.H}, {self.W}]")
     t = temps.transpose(1, 2).contiguous() if self.transposed else temps.contiguous()
@@ -680,9 +745,13 @@ class BatchedEnvironment:
                occupancy_normalization_constant: float = 0.0, holiday_calendar="us",
                electricity_energy_cost=None, natural_gas_energy_cost=None, collect_info: bool = False,
                observation_histogram_parameters: Optional[Sequence[Tuple[str, Sequence[float]]]] = None,
-               normalize_reduce: bool = False, convection_simulator=None):
+               normalize_reduce: bool = False, convection_simulator=None, solver: str = "gauss_seidel"):
+    """``solver``: the finite-difference solver (BatchedSimulator): "gauss_seidel" (default) or "jacobi_fp32"
+    (TFSimulator, SB1's shipped configuration; no convection_simulator, snapshot, restore or fork)."""
     if discount_factor <= 0 or discount_factor > 1:
       raise ValueError("Discount factor must be in (0,1]")   # environment.py:454-455
+    if solver == "jacobi_fp32" and convection_simulator is not None:
+      raise ValueError("a convection_simulator is not implemented for solver='jacobi_fp32'")
     self.config = config or SimConfig.sb1()
     self.weather = weather or host_inputs.WeatherController(273.0, 283.0, convection_coefficient=100.0)
     self.occupancy = occupancy or host_inputs.StepFunctionOccupancy(
@@ -698,7 +767,7 @@ class BatchedEnvironment:
     self.sim = BatchedSimulator(plan, self.config, n_buildings, h_conv, device,
                                 observation_normalization,
                                 histogram_parameters=observation_histogram_parameters,
-                                normalize_reduce=normalize_reduce)
+                                normalize_reduce=normalize_reduce, solver=solver)
     self.batch_size = self.sim.B
     self._weather_lohi = self._weather_replay = None
     if isinstance(self.weather, host_inputs.BatchedReplayWeather):
@@ -893,6 +962,7 @@ class BatchedEnvironment:
   def snapshot(self) -> EnvSnapshot:
     """Everything ``restore`` needs to put this environment back where it is now: the simulator state of every
     building, the host clock and episode bookkeeping, stateful host models, the current TimeStep and info."""
+    self.sim._refuse_on_jacobi("snapshot()")
     if self._needs_reset:
       raise ValueError("snapshot() needs a current TimeStep: reset() first")
     clone = lambda t: None if t is None else t.clone()
@@ -917,6 +987,7 @@ class BatchedEnvironment:
     """Puts the environment back to ``snap`` (of this environment, or of one of the same floor plan, configuration
     and batch size) and returns the TimeStep that was current then.  The simulator's draw counters rewind with it,
     so the device occupancy and convection draw what they drew after the snapshot: a restored batch replays exactly."""
+    self.sim._refuse_on_jacobi("restore()")
     if not isinstance(snap, EnvSnapshot):
       raise ValueError("restore needs an EnvSnapshot")
     if tuple(snap.observation.shape) != tuple(self._obs.shape) or (snap.info is None) != (self._info is None):
@@ -946,6 +1017,7 @@ class BatchedEnvironment:
     observation, reward and info rows follow their buildings.  Random streams: the device occupancy and convection
     draw by (seed, global building, counter), so a forked building keeps its own slot's stream -- forked replicas
     of one building diverge under those stochastic models and stay identical without them."""
+    self.sim._refuse_on_jacobi("fork()")
     if not isinstance(src, torch.Tensor) or src.dtype != torch.int64 or tuple(src.shape) != (self.batch_size,):
       raise ValueError(f"src must be an int64 [{self.batch_size}] tensor")
     if src.device != self.sim.tdev:
@@ -982,7 +1054,8 @@ class MixedBatchedEnvironment:
   mixed observation is ``[B_total, max width]``; a building's row holds its class's fields first (the layout
   of ``BatchedEnvironment.field_names`` of its class, ``self.envs[k].field_names``) and zeros after
   ``self.observation_widths[k]``; ``self.class_of_building`` ([B_total] int32 in HBM) and ``self.slices``
-  say which class a building belongs to.  Every keyword argument goes to each class's ``BatchedEnvironment``;
+  say which class a building belongs to.  Every keyword argument goes to each class's ``BatchedEnvironment``
+  (``solver`` may also be a sequence: one finite-difference solver per class);
   a seeded per-building generator among them (``convection_simulator``, randomized ``occupancy``) gets its
   ``first_building`` moved to the class's first GLOBAL building on this rank, so every building of the mixed batch
   draws from its own stream whatever the sharding.
@@ -1018,6 +1091,10 @@ class MixedBatchedEnvironment:
       # rank it lives -- so the draws do not depend on the sharding, and no two buildings share a stream
       first = sum(self.class_totals[:k]) + self.class_ranges[k][0]
       kw = dict(env_kwargs)
+      if isinstance(kw.get("solver"), (list, tuple)):   # one finite-difference solver per class
+        if len(kw["solver"]) != len(classes):
+          raise ValueError(f"solver: one per class ({len(classes)}), or one for all")
+        kw["solver"] = kw["solver"][k]
       for key in ("convection_simulator", "occupancy"):
         gen = kw.get(key)
         if gen is not None and hasattr(gen, "first_building"):

@@ -329,6 +329,108 @@ class FloorPlan:
         zone_cells=(np.concatenate(zlists) if zlists else np.zeros(0)).astype(np.int32),
         dt=float(dt), h_conv=float(h_conv))
 
+  def compile_jacobi(self, dt: float, h_conv: float) -> "JacobiPlan":
+    """Folds TFSimulator's per-CV tensors (jacobi_cv_tensors, bitwise what the reference computes in float32) into a
+    one-byte class per CV and a per-class table: the float32 constants, the exterior flag, the float64 diffuser weight
+    and its zone.  Every CV of the grid is kept: nothing is trimmed and nothing is transposed."""
+    t = jacobi_cv_tensors(self, dt, h_conv)
+    H, W = self.shape
+    cols = [t[name] for name in JACOBI_FIELDS[:-1]] + [t["exterior"].astype(np.float32)]
+    table = np.zeros((H, W, JACOBI_COEFS), dtype=np.float32)
+    table[:, :, :len(cols)] = np.stack(cols, axis=2)
+    dw = np.where((self.diffusers > 0.0) & (self.zone_label >= 0) & ~t["exterior"], self.diffusers, 0.0)
+    zone = np.where(dw > 0.0, self.zone_label, -1).astype(np.int32)
+    keys, rows, diff, zones = {}, [], [], []
+    cell_class = np.zeros(H * W, dtype=np.int64)
+    for x in range(H):
+      for y in range(W):
+        key = (table[x, y].tobytes(), float(dw[x, y]), int(zone[x, y]))
+        if key not in keys:
+          keys[key] = len(rows)
+          rows.append(table[x, y])
+          diff.append(float(dw[x, y]))
+          zones.append(int(zone[x, y]))
+        cell_class[x * W + y] = keys[key]
+    if len(rows) > 255:
+      raise ValueError(f"floor plan needs {len(rows)} Jacobi classes; the device format holds 255")
+    zlists = self.zone_cell_lists()
+    zone_off = np.zeros(len(zlists) + 1, dtype=np.int32)
+    zone_off[1:] = np.cumsum([len(zl) for zl in zlists])
+    return JacobiPlan(H=H, W=W, Z=len(zlists), n_classes=len(rows), cell_class=cell_class.astype(np.uint8),
+                      class_f32=np.asarray(rows, dtype=np.float32).reshape(-1, JACOBI_COEFS),
+                      class_diffuser=np.asarray(diff, dtype=np.float64), class_zone=np.asarray(zones, dtype=np.int32),
+                      zone_off=zone_off,
+                      zone_cells=(np.concatenate(zlists) if zlists else np.zeros(0)).astype(np.int32),
+                      dt=float(dt), h_conv=float(h_conv))
+
+
+JACOBI_COEFS = 16   # floats per class row (include/sbsim_amd.h SB_JACOBI_COEFS)
+# columns of JacobiPlan.class_f32
+JACOBI_FIELDS = ("k1u", "k3u", "k2v", "k4v", "uz", "vz", "den", "M", "hL", "hR", "hT", "hB", "exterior")
+
+
+@dataclasses.dataclass
+class JacobiPlan:
+  """Device-ready tables of TFSimulator's Jacobi update for one floor plan (FloorPlan.compile_jacobi)."""
+  H: int
+  W: int
+  Z: int
+  n_classes: int
+  cell_class: np.ndarray      # [H*W] uint8, row-major
+  class_f32: np.ndarray       # [n_classes, JACOBI_COEFS] float32, columns JACOBI_FIELDS then zeros
+  class_diffuser: np.ndarray  # [n_classes] float64 diffuser weight (input_q = q_zone * weight)
+  class_zone: np.ndarray      # [n_classes] int32 zone whose VAV power feeds q, or -1
+  zone_off: np.ndarray        # [Z+1] int32
+  zone_cells: np.ndarray      # [sum] int32 flat cell indices
+  dt: float
+  h_conv: float
+
+  def expand(self) -> dict:
+    """Per-CV [H, W] arrays of every class column (float32; "exterior" as bool) and the diffuser weight."""
+    c = self.cell_class.reshape(self.H, self.W)
+    out = {name: self.class_f32[c, k] for k, name in enumerate(JACOBI_FIELDS)}
+    out["exterior"] = out["exterior"] != 0
+    out["diffuser"] = self.class_diffuser[c]
+    out["zone"] = self.class_zone[c]
+    return out
+
+
+def jacobi_cv_tensors(plan: "FloorPlan", dt: float, h_conv: float) -> dict:
+  """TFSimulator's per-CV tensors (tf_simulator.py:180-499, 573-853) in NumPy float32, each op one rounding in the
+  reference's order: the CV classes of classify_cv, u / v, the oriented k and h tensors, k/u, k/v, z*u, z*v, the
+  heat-capacity term M (c applied twice, :676-681) and den.  Raises the reference's ValueError for a two-neighbour CV
+  whose neighbours face each other."""
+  f32 = np.float32
+  present, count = plan.neighbor_masks()           # up, down, left, right
+  up, down, left, right = (present[:, :, k] for k in range(4))
+  opposite = (count == 2) & ((up & down) | (left & right))
+  if opposite.any():
+    i, j = (int(x) for x in np.argwhere(opposite)[0])
+    raise ValueError(f"wasn't able to determine which corner the CV {(i, j)} is.")   # tf_simulator.py:216-218
+  exterior = count <= 1
+  boundary = (count == 2) | (count == 3)
+  # a boundary CV's sides without a neighbour face outside: k = 0 and h = h_conv there (:332-456); the sides' axis is
+  # halved in the CV's dimensions (:283-329: TOP / BOTTOM edges halve v, LEFT / RIGHT halve u, corners both)
+  out_t, out_b, out_l, out_r = (boundary & ~m for m in (up, down, left, right))
+  cv = plan.cv_size_cm / 100.0
+  u = np.where(out_l | out_r, cv * 0.5, cv).astype(f32)
+  v = np.where(out_t | out_b, cv * 0.5, cv).astype(f32)
+  k = plan.conductivity
+  kL, kR, kT, kB = (np.where(m, 0.0, k).astype(f32) for m in (out_l, out_r, out_t, out_b))
+  h = f32(h_conv)
+  hL, hR, hT, hB = (np.where(m, h, f32(0.0)).astype(f32) for m in (out_l, out_r, out_t, out_b))
+  z = f32(plan.floor_height_cm / 100.0)
+  dtf = f32(dt)
+  rho, c = plan.density.astype(f32), plan.heat_capacity.astype(f32)
+  uz, vz = z * u, z * v
+  k1u, k3u, k2v, k4v = kL / u, kR / u, kB / v, kT / v
+  dt1 = vz * (((k1u + k3u) + hL) + hR)
+  dt2 = uz * (((k2v + k4v) + hB) + hT)
+  M = (z * (((rho * u) * v) * c)) * c
+  den = (dt1 + dt2) + M / dtf
+  return dict(u=u, v=v, kL=kL, kR=kR, kT=kT, kB=kB, hL=hL, hR=hR, hT=hT, hB=hB, k1u=k1u, k3u=k3u, k2v=k2v, k4v=k4v,
+              uz=uz, vz=vz, M=M, den=den, exterior=exterior)
+
 
 def rectangular_floor_plan(rooms: Tuple[int, int], room_shape: Tuple[int, int]) -> np.ndarray:
   """File-format plan of ``rooms[0] x rooms[1]`` rectangular rooms of ``room_shape`` air
