@@ -120,12 +120,17 @@ def lib():
     L.sbo_fd_timestep.restype = C.c_int32
     L.sbo_fd_timestep.argtypes = [C.POINTER(_Plan), _dp, _dp, _dp, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_int32, _ip]
+    L.sbo_fd_timestep_trace.restype = C.c_int32
+    L.sbo_fd_timestep_trace.argtypes = [C.POINTER(_Plan), _dp, _dp, _dp, C.c_double, C.c_double,
+                                        C.c_double, C.c_double, C.c_int32, _ip, _dp]
     L.sbo_reset.argtypes = [C.POINTER(_Plan), C.POINTER(_Params), C.POINTER(_State),
                             C.c_double, _dp]
     L.sbo_setup_step.argtypes = [C.POINTER(_Plan), C.POINTER(_Params), C.POINTER(_State),
                                  C.c_int32, C.c_int32]
     L.sbo_step.argtypes = [C.POINTER(_Plan), C.POINTER(_Params), C.POINTER(_State),
                            C.POINTER(_StepIn), C.POINTER(_StepOut)]
+    L.sbo_step_trace.argtypes = [C.POINTER(_Plan), C.POINTER(_Params), C.POINTER(_State),
+                                 C.POINTER(_StepIn), C.POINTER(_StepOut), _dp]
     L.sbo_boiler_dissipation.restype = C.c_double
     L.sbo_boiler_dissipation.argtypes = [C.POINTER(_Params), C.c_double, C.c_double]
     d = C.c_double
@@ -274,14 +279,18 @@ def sweep(plan: OraclePlan, prev, est, q, t_amb, h, dt) -> float:
   return lib().sbo_sweep(plan.cptr(), _d(prev), _d(est), _d(q), t_amb, h, dt)
 
 
-def fd_timestep(plan: OraclePlan, temp, q, t_amb, h, dt, thr, iter_limit):
-  """simulator.py:318-371 on a copy; returns (new_temp, n_sweeps, converged)."""
+def fd_timestep(plan: OraclePlan, temp, q, t_amb, h, dt, thr, iter_limit, trace: bool = False):
+  """simulator.py:318-371 on a copy; returns (new_temp, n_sweeps, converged), and with ``trace`` also
+  the max|delta| of every sweep run (the values compared with ``thr``)."""
   t = np.array(temp, dtype=np.float64, order="C")
   scratch = np.empty_like(t)
   q = np.ascontiguousarray(q, dtype=np.float64)
   n = C.c_int32(0)
-  conv = lib().sbo_fd_timestep(plan.cptr(), _d(t), _d(scratch), _d(q), t_amb, h, dt, thr,
-                               iter_limit, C.byref(n))
+  md = np.zeros(max(int(iter_limit), 1))
+  conv = lib().sbo_fd_timestep_trace(plan.cptr(), _d(t), _d(scratch), _d(q), t_amb, h, dt, thr,
+                                     iter_limit, C.byref(n), _d(md) if trace else None)
+  if trace:
+    return t, n.value, bool(conv), md[:n.value].copy()
   return t, n.value, bool(conv)
 
 
@@ -379,9 +388,12 @@ class OracleBuilding:
            comfort_now: bool, comfort_prev: bool, comfort_next: bool, occupancy,
            e_price: float, e_carbon: float, g_price: float, g_carbon: float,
            action: Optional[Sequence[float]] = None, observe: bool = True, reject: bool = False,
-           cool_sp: Optional[float] = None, damper_cmd: Optional[Sequence[float]] = None) -> dict:
+           cool_sp: Optional[float] = None, damper_cmd: Optional[Sequence[float]] = None,
+           trace: bool = False) -> dict:
     """One Environment._step (H2 ordering).  ``action`` = (boiler supply-water setpoint,
-    AHU heating setpoint) in native units as the proto would carry them (fp32)."""
+    AHU heating setpoint) in native units as the proto would carry them (fp32).  ``trace``: the
+    result also holds ``max_delta``, the max|delta| of every Gauss-Seidel sweep of the step (the
+    values compared with the convergence threshold)."""
     Z = self.plan.Z
     occ = np.ascontiguousarray(np.broadcast_to(np.asarray(occupancy, dtype=np.float64), (Z,)))
     tz_pre, tz_post, qz = np.zeros(Z), np.zeros(Z), np.zeros(Z)
@@ -404,11 +416,17 @@ class OracleBuilding:
     si.e_price, si.e_carbon, si.g_price, si.g_carbon = e_price, e_carbon, g_price, g_carbon
     so = _StepOut()
     so.zone_temp_pre, so.zone_temp_post, so.q_zone = _d(tz_pre), _d(tz_post), _d(qz)
-    lib().sbo_step(self.plan.cptr(), C.byref(self._pc), C.byref(self._s), C.byref(si),
-                   C.byref(so))
+    if trace:
+      md = np.zeros(max(int(self.params.iter_limit), 1))
+      lib().sbo_step_trace(self.plan.cptr(), C.byref(self._pc), C.byref(self._s), C.byref(si),
+                           C.byref(so), _d(md))
+    else:
+      lib().sbo_step(self.plan.cptr(), C.byref(self._pc), C.byref(self._s), C.byref(si),
+                     C.byref(so))
     s = self._s
+    extra = dict(max_delta=md[:so.n_sweeps].copy()) if trace else {}
     return dict(
-        n_sweeps=so.n_sweeps, converged=bool(so.converged), action_accepted=bool(so.action_accepted),
+        **extra, n_sweeps=so.n_sweeps, converged=bool(so.converged), action_accepted=bool(so.action_accepted),
         t_supply_air=so.t_supply_air,
         recirc_pre=so.recirc_pre, zone_temp_pre=tz_pre, zone_temp_post=tz_post, q_zone=qz,
         blower_rate=so.blower_rate, ac_rate=so.ac_rate, gas_rate=so.gas_rate,

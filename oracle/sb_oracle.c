@@ -141,14 +141,15 @@ double sbo_sweep(const sbo_plan *p, const double *prev, double *est, const doubl
 }
 
 /* ---- simulator.py:318-371 finite_differences_timestep ------------------------------ */
-int32_t sbo_fd_timestep(const sbo_plan *p, double *temp, double *scratch, const double *q,
-                        double t_amb, double h, double dt, double thr, int32_t iter_limit,
-                        int32_t *n_sweeps) {
+int32_t sbo_fd_timestep_trace(const sbo_plan *p, double *temp, double *scratch, const double *q,
+                              double t_amb, double h, double dt, double thr, int32_t iter_limit,
+                              int32_t *n_sweeps, double *max_delta) {
   const int N = p->H * p->W;
   memcpy(scratch, temp, sizeof(double) * (size_t)N); /* temp_estimate = temp.copy() */
   int32_t converged = 0, it = 0;
   for (it = 0; it < iter_limit; it++) {
     double md = sbo_sweep(p, temp, scratch, q, t_amb, h, dt);
+    if (max_delta) max_delta[it] = md;
     if (md <= thr) {
       converged = 1;
       it++;
@@ -158,6 +159,12 @@ int32_t sbo_fd_timestep(const sbo_plan *p, double *temp, double *scratch, const 
   if (n_sweeps) *n_sweeps = it;
   memcpy(temp, scratch, sizeof(double) * (size_t)N); /* building.temp = temp_estimate */
   return converged;
+}
+
+int32_t sbo_fd_timestep(const sbo_plan *p, double *temp, double *scratch, const double *q,
+                        double t_amb, double h, double dt, double thr, int32_t iter_limit,
+                        int32_t *n_sweeps) {
+  return sbo_fd_timestep_trace(p, temp, scratch, q, t_amb, h, dt, thr, iter_limit, n_sweeps, NULL);
 }
 
 /* ---- reset: simulator.py:80-84, building.py:784-791, vav.py:93-99, -------------------
@@ -390,8 +397,8 @@ double sbo_reward(const sbo_params *prm, int32_t Z, const float *zone_temp, cons
  *   wait_time:      execute_step_sim (simulator_flexible_floor_plan.py:124-190)
  *   _get_observation: one read of boiler.supply_water_temperature_sensor
  *   _get_reward:    reward_info (simulator.py:548-576) + compute_reward */
-void sbo_step(const sbo_plan *p, const sbo_params *prm, sbo_state *s, const sbo_step_in *in,
-              sbo_step_out *out) {
+void sbo_step_trace(const sbo_plan *p, const sbo_params *prm, sbo_state *s, const sbo_step_in *in,
+                    sbo_step_out *out, double *max_delta) {
   const int Z = p->Z, N = p->H * p->W;
   double buf[N];
   double tz_pre[Z], tzs[Z];
@@ -430,8 +437,8 @@ void sbo_step(const sbo_plan *p, const sbo_params *prm, sbo_state *s, const sbo_
   double t_sa = ahu_supply(s, mixed);
 
   int32_t n_sweeps = 0;
-  int32_t conv = sbo_fd_timestep(p, s->temp, s->scratch, s->input_q, in->t_amb_now, in->h_conv,
-                                 prm->dt, prm->conv_threshold, prm->iter_limit, &n_sweeps);
+  int32_t conv = sbo_fd_timestep_trace(p, s->temp, s->scratch, s->input_q, in->t_amb_now, in->h_conv,
+                                       prm->dt, prm->conv_threshold, prm->iter_limit, &n_sweeps, max_delta);
 
   s->ahu_flow = 0.0; s->ahu_count = 0; /* air_handler.py:250-252 */
   s->blr_flow = 0.0; s->blr_count = 0; /* boiler.py:155-157 */
@@ -513,4 +520,9 @@ void sbo_step(const sbo_plan *p, const sbo_params *prm, sbo_state *s, const sbo_
   out->norm_prod_regret = diag[1];
   out->norm_energy_cost = diag[2];
   out->norm_carbon = diag[3];
+}
+
+void sbo_step(const sbo_plan *p, const sbo_params *prm, sbo_state *s, const sbo_step_in *in,
+              sbo_step_out *out) {
+  sbo_step_trace(p, prm, s, in, out, NULL);
 }

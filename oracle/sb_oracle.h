@@ -131,12 +131,20 @@ double sbo_sweep(const sbo_plan *p, const double *prev, double *est, const doubl
 int32_t sbo_fd_timestep(const sbo_plan *p, double *temp, double *scratch, const double *q,
                         double t_amb, double h, double dt, double thr, int32_t iter_limit,
                         int32_t *n_sweeps);
+/* the same, and max_delta[j] (if not NULL: room for iter_limit values) = the max|delta| that sweep j + 1
+ * compared with the threshold */
+int32_t sbo_fd_timestep_trace(const sbo_plan *p, double *temp, double *scratch, const double *q,
+                              double t_amb, double h, double dt, double thr, int32_t iter_limit,
+                              int32_t *n_sweeps, double *max_delta);
 void sbo_reset(const sbo_plan *p, const sbo_params *prm, sbo_state *s, double initial_temp,
                const double *reset_temps);
 void sbo_setup_step(const sbo_plan *p, const sbo_params *prm, sbo_state *s,
                     int32_t comfort_now, int32_t comfort_prev);
 void sbo_step(const sbo_plan *p, const sbo_params *prm, sbo_state *s, const sbo_step_in *in,
               sbo_step_out *out);
+/* the same, and max_delta[j] (if not NULL: room for prm->iter_limit values) = the max|delta| of sweep j + 1 */
+void sbo_step_trace(const sbo_plan *p, const sbo_params *prm, sbo_state *s, const sbo_step_in *in,
+                    sbo_step_out *out, double *max_delta);
 double sbo_boiler_dissipation(const sbo_params *prm, double water_temp, double outside_temp);
 /* The device formulas sbo_step is made of, callable on their own: the reference's device tests
  * (boiler_test.py, air_handler_test.py, vav_test.py) pin them (tests/test_device_kats.py). */

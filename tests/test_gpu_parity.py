@@ -25,6 +25,7 @@ from sbsim_amd.environment import (BatchedEnvironment, BatchedSimulator, SimConf
                                    observation_field_names)
 from sbsim_amd.floorplan import FloorPlan, Material, Materials  # noqa: E402
 from tests.golden_util import load, oracle_params, oracle_plan  # noqa: E402
+from tests.threshold_cases import oracle_twin  # noqa: E402
 
 T_TOL = 1e-8
 TEST_SMALL = Materials(Material(50., 700., 1.), Material(2., 500., 1800.), Material(.05, 500., 3000.))
@@ -329,6 +330,7 @@ def test_iteration_limit_ends_the_step(limit):
           e_carbon=float(g["e_carbon"][tt]), g_price=float(g["g_price"][tt]),
           g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
       assert i[b, 4] == o["n_sweeps"] <= limit, (t, b, i[b, 4], o["n_sweeps"])
+      assert i[b, 5] == o["converged"], (t, b, i[b, 5], o["converged"])
       hit += int(o["n_sweeps"] == limit)
   assert hit > 0
   grid = sim.temps().cpu().numpy()
@@ -698,20 +700,7 @@ def test_abi_error_paths():
 
 
 def _oracle_twin(plan, cfg, init_flat):
-  oplan = orc.OraclePlan(plan.conductivity, plan.density, plan.heat_capacity, plan.exterior_space,
-                         plan.zone_cell_lists(), plan.diffusers, plan.cv_size_cm, plan.floor_height_cm)
-  c = cfg
-  oprm = orc.OracleParams(
-      dt=c.time_step_sec, conv_threshold=c.convergence_threshold, iter_limit=c.iteration_limit,
-      vav_max_air_flow=c.vav_max_air_flow_rate, vav_max_water_flow=c.vav_reheat_max_water_flow_rate,
-      ahu_recirc=c.ahu_recirculation, ahu_heat_sp=c.ahu_heating_air_temp_setpoint,
-      ahu_cool_sp=c.ahu_cooling_air_temp_setpoint, ahu_dp=c.ahu_fan_differential_pressure,
-      ahu_eff=c.ahu_fan_efficiency, blr_setpoint=c.boiler_reheat_water_setpoint,
-      blr_head=c.boiler_water_pump_differential_head, blr_pump_eff=c.boiler_water_pump_efficiency,
-      comfort_lo=c.comfort_temp_window[0], comfort_hi=c.comfort_temp_window[1],
-      eco_lo=c.eco_temp_window[0], eco_hi=c.eco_temp_window[1],
-      blr_heating_rate=c.boiler_heating_rate, blr_cooling_rate=c.boiler_cooling_rate, ahu_has_weather=1)
-  return orc.OracleBuilding(oplan, oprm, 0.0, reset_temps=init_flat)
+  return oracle_twin(plan, cfg, init_flat)
 
 
 @pytest.mark.parametrize("rooms,room_shape,orientation,path", [
@@ -872,15 +861,21 @@ def _need_experimental_kernels(variant, monkeypatch):
 
 
 def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatch, expect_steps=None,
-                               iteration_limit=None, expect_kernel=None, B=6, T=14, expect_waves=None):
+                               iteration_limit=None, expect_kernel=None, B=6, T=14, expect_waves=None,
+                               init=None, acts=None, cfg=None):
+  """Every building against its oracle twin at every step.  `file_plan` may be a FloorPlan; `init` [B, H*W], `acts`
+  [T, B, 2] and `cfg` replace the seeded initial grids, actions and SimConfig.sb1().  Returns the info rows and the
+  grids after every step."""
   _need_gpu()
   g = load("h2_sb1_r9_random.npz")
-  plan = FloorPlan.from_file_input(file_plan, Materials.sb1(), 10.0, 300.0)
+  plan = file_plan if isinstance(file_plan, FloorPlan) else FloorPlan.from_file_input(file_plan, Materials.sb1(), 10.0, 300.0)
   H, W = plan.shape
   rs = np.random.RandomState(11)
-  init = np.clip(294.0 + 2.0 * rs.randn(B, 1) + 0.2 * rs.randn(B, H * W), 285.0, 305.0)
-  acts = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
-  cfg = SimConfig.sb1()
+  init_r = np.clip(294.0 + 2.0 * rs.randn(B, 1) + 0.2 * rs.randn(B, H * W), 285.0, 305.0)
+  acts_r = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
+  init = init_r if init is None else init
+  acts = acts_r if acts is None else acts
+  cfg = SimConfig.sb1() if cfg is None else cfg
   if iteration_limit is not None:
     import dataclasses
     cfg = dataclasses.replace(cfg, iteration_limit=iteration_limit)
@@ -905,12 +900,15 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
   rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
   info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
   lo, hi = cfg.action_ranges
+  infos, grids = [], []
   for t in range(T):
     tt = 96 + t   # mid-morning: occupied, comfort mode
     sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, tt), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     zt = sim.zone_temps().cpu().numpy()
     r = rew.cpu().numpy()
+    infos.append(i)
+    grids.append(sim.temps().cpu().numpy())
     for b in range(B):
       a = acts[t, b]
       native = [np.float32((float(a[0]) + 1.0) / 2.0 * (lo[1] - lo[0]) + lo[0]),
@@ -923,6 +921,7 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
           e_carbon=float(g["e_carbon"][tt]), g_price=float(g["g_price"][tt]),
           g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
       assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
+      assert i[b, 5] == o["converged"], (t, b, i[b, 5], o["converged"])
       assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
       ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
       assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b)
@@ -930,6 +929,8 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
   grid = sim.temps().cpu().numpy()
   for b in range(B):
     assert np.abs(grid[b] - twins[b].grid()).max() < T_TOL, b
+  sim.close()
+  return infos, grids
 
 
 @pytest.mark.parametrize("rooms,room_shape,orientation,waves", [

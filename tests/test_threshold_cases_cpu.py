@@ -1,0 +1,116 @@
+"""The boundary cases of tests/threshold_cases.py, checked on the CPU: the oracle's max|delta| trace is the quantity the
+stopping rule compares, every threshold placement the GPU suite (tests/test_threshold_boundary_gpu.py) runs satisfies
+its invariants and gives the expected (sweeps, converged) on the oracle, and the float32 Jacobi placements flip
+tests/jacobi_restatement.py's iteration count exactly where they should."""
+import dataclasses
+
+import numpy as np
+import pytest
+
+from oracle import oracle as orc
+from sbsim_amd.environment import SimConfig
+from tests import jacobi_restatement as jr
+from tests import threshold_cases as tc
+from tests.golden_util import load
+
+
+def _oplan(plan):
+  return orc.OraclePlan(plan.conductivity, plan.density, plan.heat_capacity, plan.exterior_space,
+                        plan.zone_cell_lists(), plan.diffusers, plan.cv_size_cm, plan.floor_height_cm)
+
+
+@pytest.mark.parametrize("name", ["R9", "47x48", "narrow"])
+def test_trace_is_the_max_delta_between_consecutive_grids(name):
+  """m_k == max|g_k - g_(k-1)| bit for bit, g_k the grid after the same timestep run with iter_limit = k (g_0 the
+  initial grid); the trace leaves the timestep's results alone, and OracleBuilding.step(trace=True) reports the same
+  series for the first step after a reset (no zone power yet)."""
+  plan = tc.floor_plan(name)
+  op = _oplan(plan)
+  g = load("h2_sb1_r9_random.npz")
+  init, acts = tc.case_inputs(plan.shape[0] * plan.shape[1])
+  t_amb, h = float(g["t_amb_now"][tc.TT0]), float(g["h_conv"])
+  q = np.zeros(op.n_cells)
+  L = 12
+  t_full, n, conv, m = orc.fd_timestep(op, init[1], q, t_amb, h, 300.0, 0.0, L, trace=True)
+  assert (n, conv, len(m)) == (L, False, L)
+  prev = init[1]
+  for k in range(1, L + 1):
+    gk, nk, ck = orc.fd_timestep(op, init[1], q, t_amb, h, 300.0, 0.0, k)
+    assert (nk, ck) == (k, False)
+    assert m[k - 1] == np.abs(gk - prev).max(), k
+    prev = gk
+  assert np.array_equal(prev, t_full)
+  # a threshold that stops the step: the trace ends at the stopping sweep, the results are the untraced ones
+  thr = float(m[4])
+  t1, n1, c1 = orc.fd_timestep(op, init[1], q, t_amb, h, 300.0, thr, L)
+  t2, n2, c2, m2 = orc.fd_timestep(op, init[1], q, t_amb, h, 300.0, thr, L, trace=True)
+  assert (n1, c1) == (n2, c2) == (5, True) and np.array_equal(t1, t2) and np.array_equal(m2, m[:5])
+  cfg = dataclasses.replace(SimConfig.sb1(), convergence_threshold=0.0, iteration_limit=L)
+  o = tc.oracle_twin(plan, cfg, init[1]).step(**tc.oracle_step_kwargs(g, 0, cfg, acts[0, 1]), trace=True)
+  assert np.array_equal(o["max_delta"], m)
+  plain = tc.oracle_twin(plan, cfg, init[1]).step(**tc.oracle_step_kwargs(g, 0, cfg, acts[0, 1]))
+  assert "max_delta" not in plain and plain["n_sweeps"] == o["n_sweeps"] and plain["reward"] == o["reward"]
+
+
+@pytest.mark.parametrize("name", list(tc.PLANS))
+def test_placements_hold_on_the_oracle(name):
+  """Every placement the GPU suite builds on this plan: its invariants hold, and the oracle twin run with its threshold
+  and limit gives the expected sweep count and converged flag on every target building."""
+  plan = tc.floor_plan(name)
+  g = load("h2_sb1_r9_random.npz")
+  cfg = SimConfig.sb1()
+  init, acts = tc.case_inputs(plan.shape[0] * plan.shape[1])
+  m = tc.series(plan, cfg, g, init[tc.TARGETS[0]], acts[0, tc.TARGETS[0]])
+  for b in tc.TARGETS[1:]:        # the first step's sweeps see no zone power: the action does not matter
+    assert np.array_equal(tc.series(plan, cfg, g, init[b], acts[0, b]), m)
+  assert len(m) == cfg.iteration_limit and (np.diff(m[1:]) <= 0).all()
+  ks = tc.chosen_sweeps(m, cfg.convergence_threshold)
+  pl = tc.placements(m, cfg.convergence_threshold, cfg.iteration_limit)
+  print(f"\n{name}: natural stop {tc.natural_stop(m, cfg.convergence_threshold)}, k = {ks}")
+  for p in pl.values():
+    print(f"  {p.id:16s} theta = {p.theta!r:24} limit {p.limit:3d} -> n = {p.n}, converged = {p.converged}")
+    assert tc.check(m, p) is None
+    for b in tc.TARGETS:
+      c = dataclasses.replace(cfg, convergence_threshold=p.theta, iteration_limit=p.limit)
+      o = tc.oracle_twin(plan, c, init[b]).step(**tc.oracle_step_kwargs(g, 0, c, acts[0, b]))
+      assert (o["n_sweeps"], o["converged"]) == (p.n, p.converged), (p, b)
+  # every chosen sweep has an 'above' and a 'below' placement with the limit and without
+  assert len(pl) >= 3 * len(ks) and {p.k for p in pl.values()} == set(ks), sorted(pl)
+  for p in pl.values():
+    if p.kind == "below":
+      assert p.n > p.k and p.converged
+
+
+def test_builder_refuses_placements_that_break_an_invariant():
+  m = np.array([4.0, 0.5, 0.4, 0.1 + 1e-8, 0.1, 0.05])
+  assert tc.place(m, 2, "above", 100) is not None
+  assert tc.place(m, 5, "above", 100) is None                    # m_4 is within 1e-6 theta of theta
+  hi_edge = float(np.array(0x3FC0000000000000, dtype=np.uint64).view(np.float64))   # 0.125: the low word is 0
+  assert tc.place(np.array([1.0, hi_edge, 0.01]), 2, "below", 100) is None        # theta falls to the next high word
+  assert tc.place(np.array([1.0, hi_edge, 0.01]), 2, "above", 100) is not None
+  assert tc.place(m, 2, "below", 100, delta=2e-9) is None                           # outside the thr_far band
+  p = tc.place(m, 3, "limit-below", 100)
+  assert (p.limit, p.n, p.converged) == (3, 3, False)
+
+
+@pytest.mark.parametrize("kind", tc.JACOBI_KINDS)
+def test_jacobi_placements_flip_the_restatement(kind):
+  fp, tprev, q, tinf = tc.jacobi_tap()
+  cfg = SimConfig.sb1()
+  tt = jr.tensors(fp, cfg.time_step_sec, 100.0)
+  d = tc.jacobi_series(tt, tprev[0], q[0], tinf[0], cfg.time_step_sec, cfg.iteration_limit)
+  k = tc.JACOBI_K
+  th = tc.jacobi_theta(d[k - 1], kind)
+  assert (np.diff(d[:k + 2]) < 0).all()     # the series falls: nothing before sweep k is at or below theta
+  p = np.nextafter(d[k - 1], np.float32(0))
+  want = {"exact": d[k - 1], "mid-up": d[k - 1], "mid-down": p,
+          "mid": d[k - 1] if int(d[k - 1].view(np.uint32)) % 2 == 0 else p}[kind]
+  assert np.float32(th) == want
+  if kind != "exact":
+    assert th < float(d[k - 1])
+  for limit in (cfg.iteration_limit, k):
+    n, conv = tc.jacobi_expected(d, th, limit)
+    stops = np.float32(th) == d[k - 1]
+    assert (n == k) == (stops or limit == k) and conv == (stops or n > k)
+    _, wi, wc = jr.fd_timestep(tt, tprev[0], q[0], tinf[0], cfg.time_step_sec, th, limit)
+    assert (wi, wc) == (n, conv), (kind, limit)
