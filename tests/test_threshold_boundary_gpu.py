@@ -44,6 +44,7 @@ KERNELS = {
     "two-SB1-k40": ("SB1-synth", "auto", 1, {"SBSIM_DEBUG_SKIP_KAPPA": "40"}, 4, None, False),
     "two-SB1-noskip": ("SB1-synth", "auto", 1, {"SBSIM_TWO_NO_SKIP": "1"}, 4, None, False),
     "two-general": ("SB2-synth", "auto", 1, {"SBSIM_TWO_GENERAL": "1"}, 4, None, False),
+    "two-general-U": ("U-shape", "rows", 1, {}, 4, None, False),     # the general variant by the library's own choice
     "two-max-level-0": ("SB2-synth", "auto", 1, {"SBSIM_TWO_MAX_LEVEL": "0"}, 4, None, False),
     "band-2": ("SB2-synth", "auto", 1, {"SBSIM_BAND_PATH": "1"}, 5, 2, False),
     "band-3": ("156x75", "rows", 1, {}, 5, 3, False),

@@ -34,7 +34,8 @@ SEED = 23
 KINDS = ("above", "below", "limit-above", "limit-below")
 
 
-# The floor plans of the GPU cases: (rooms, room shape) of rectangular_floor_plan, or a golden plan file.  Every
+# The floor plans of the GPU cases: (rooms, room shape) of rectangular_floor_plan, a golden plan file, or
+# "irregular:<case>" of tests/irregular_plans.py (the plan in the file's orientation).  Every
 # placement on them is checked on the CPU by tests/test_threshold_cases_cpu.py.
 PLANS = {
     "R9": "plan_r9_sb1.npz",             # 66 x 96 inside the exterior ring
@@ -46,12 +47,16 @@ PLANS = {
     "SB1-synth": ((14, 9), (8, 7)),      # 131 x 78: the two-rows kernel's tail row
     "156x75": ((9, 4), (16, 17)),        # three wavefronts of k_sweep_band
     "203x87": ((10, 4), (19, 20)),       # four wavefronts of k_sweep_band
+    "U-shape": "irregular:U",            # 110 x 70 around a courtyard: k_sweep_two's general variant, no switch
 }
 
 
 def floor_plan(name: str):
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
   spec = PLANS[name]
+  if isinstance(spec, str) and spec.startswith("irregular:"):
+    from tests import irregular_plans
+    return irregular_plans.plan(spec[len("irregular:"):])
   if isinstance(spec, str):
     from tests.golden_util import load
     p = load(spec)
