@@ -108,6 +108,21 @@ typedef struct sb_params {
   const double *act_lo, *act_hi; /* [n_actions] native range of the column's normaliser */
 } sb_params;
 
+/* The double fields of sb_params from vav_max_air_flow to w_carbon, in declaration order: what
+ * sb_set_building_params may set per building (the HVAC devices, the setpoint windows, the reward
+ * constants).  Everything else in sb_params -- dt, the convergence threshold, the iteration limit, the
+ * weather sensor, the action vector -- stays one value per handle. */
+typedef enum sb_building_param {
+  SB_BP_VAV_MAX_AIR_FLOW = 0, SB_BP_VAV_MAX_WATER_FLOW,
+  SB_BP_AHU_RECIRC, SB_BP_AHU_HEAT_SP, SB_BP_AHU_COOL_SP, SB_BP_AHU_DP, SB_BP_AHU_EFF, SB_BP_AHU_MAX_FLOW,
+  SB_BP_BLR_SETPOINT, SB_BP_BLR_HEAD, SB_BP_BLR_PUMP_EFF, SB_BP_BLR_HEATING_RATE, SB_BP_BLR_COOLING_RATE,
+  SB_BP_BLR_CONV, SB_BP_BLR_LEN, SB_BP_BLR_RADIUS, SB_BP_BLR_CAPACITY, SB_BP_BLR_INS_K, SB_BP_BLR_INS_THICK,
+  SB_BP_COMFORT_LO, SB_BP_COMFORT_HI, SB_BP_ECO_LO, SB_BP_ECO_HI,
+  SB_BP_MAX_PROD, SB_BP_MIN_PROD, SB_BP_MAX_ELEC, SB_BP_MAX_GAS, SB_BP_PROD_DELTA, SB_BP_PROD_STIFF,
+  SB_BP_W_PROD, SB_BP_W_COST, SB_BP_W_CARBON,
+  SB_NUM_BUILDING_PARAMS /* 32 */
+} sb_building_param;
+
 /* Observation vector layout (environment.py:543-553,783-813): the device fields in sorted
  * (device_id, field) order -- the "source" order -- then the auxiliary features.  Without a
  * reducer (n_src == 0) source index == output column.  With the optional HistogramReducer
@@ -493,6 +508,29 @@ int sb_create_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, const 
  * Overwrites those buildings' grids and step hand-over: not for use inside a rollout. */
 int sb_tap_jacobi(sb_handle *h, int32_t n, const float *tprev, const float *q, const double *tinf, float *grid_out,
                   int32_t *iterations, int32_t *converged);
+
+/* Per-building plant, setpoint and reward parameters (no reference counterpart: the reference builds one
+ * Simulator, one set of devices and one reward function per building; a batch here shares one sb_params).
+ * values: HOST [n_fields][B], row k holding field fields[k] (sb_building_param) of every building; a field that
+ * is not named keeps sb_params' value for every building.  n_fields == 0 drops the table: the handle runs
+ * exactly as without one.  Refused with SB_ERR_INVALID, the message naming the building and the field, before
+ * anything changes: an unknown or repeated field, a non-finite value, ahu_cool_sp <= ahu_heat_sp
+ * (air_handler.py:60-64), comfort_lo > comfort_hi or eco_lo > eco_hi (setpoint_schedule.py:66-75), a value <= 0
+ * of a field the device algebra divides by (vav_max_air_flow, ahu_eff, ahu_max_flow, blr_pump_eff, blr_conv,
+ * blr_radius, blr_ins_k) or of the boiler's other geometry (blr_len, blr_ins_thick), and w_prod + w_cost +
+ * w_carbon <= 0 (the reward's denominator).
+ * Semantics:
+ *  - a row configures the building's SLOT, it is not state: sb_state_save / sb_state_load do not carry it, and a
+ *    building that takes another's state keeps its own slot's row (as it keeps its own random streams);
+ *  - a new table applies from the next sb_reset, step or observation; it does not rewrite device state already
+ *    set (the AHU and boiler setpoints in force).  Every sb_reset sets the AHU heating / cooling and the boiler
+ *    setpoints it rewinds (air_handler.py:131-139, boiler.py:110-121) from the building's row; sb_set_temps
+ *    leaves them alone;
+ *  - sb_tap_pre / sb_tap_post use the row of the building they are given.
+ * Ordered on `stream` (the upload follows the work already queued there) and synchronises it before it
+ * returns: it must not be called while the stream is being captured into a graph (SB_ERR_INVALID). */
+int sb_set_building_params(sb_handle *h, int32_t n_fields, const int32_t *fields,
+                           const double *values /* HOST [n_fields][B] */, void *stream);
 
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */

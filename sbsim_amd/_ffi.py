@@ -55,6 +55,13 @@ class Params(C.Structure):
   _fields_ = PARAM_FIELDS
 
 
+# enum sb_building_param: the double fields of sb_params from vav_max_air_flow to w_carbon, in declaration order (what
+# sb_set_building_params sets per building); index = the enum value
+BUILDING_PARAM_FIELDS = tuple(name for name, _ in PARAM_FIELDS[PARAM_FIELDS.index(("vav_max_air_flow", C.c_double)):
+                                                                PARAM_FIELDS.index(("w_carbon", C.c_double)) + 1])
+SB_NUM_BUILDING_PARAMS = len(BUILDING_PARAM_FIELDS)   # 32
+
+
 class ObsLayout(C.Structure):
   _fields_ = [("n_obs", C.c_int32), ("col_ahu", C.c_int32), ("col_boiler", C.c_int32),
               ("col_aux", C.c_int32), ("col_zone", _ip), ("mean", _dp), ("sigma", _dp),
@@ -136,10 +143,11 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_floorplan_padded_shape", "sb_floorplan_preprocess", "sb_floorplan_diffusers", "sb_debug_numpy_choice", "sb_pb_reward_info", "sb_pb_reward_response",
            "sb_pb_observation_response", "sb_pb_action_response", "sb_shard_append", "sb_pb_device_info",
            "sb_pb_zone_info", "sb_pb_variable_info", "sb_record_append", "sb_tap_pre", "sb_tap_post",
-           "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi")
+           "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi", "sb_set_building_params")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
+BUILDING_PARAM_ENTRIES = ("sb_set_building_params",)
 
 _lib = None
 
@@ -168,6 +176,9 @@ def load():
     raise SbsimError(f"{LIB_PATH} has ABI version {L.sb_abi_version()}, this package needs {SB_ABI_VERSION}: "
                      "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
   L.sb_last_error.restype = C.c_char_p
+  if hasattr(L, "sb_has_experimental_kernels"):   # (has_experimental_kernels() asks for a rebuild without it)
+    L.sb_has_experimental_kernels.argtypes = []
+    L.sb_has_experimental_kernels.restype = C.c_int
   L.sb_create.argtypes = [C.POINTER(PlanDesc), C.POINTER(Params), C.POINTER(ObsLayout),
                           C.c_int32, C.c_int32, C.POINTER(vp)]
   L.sb_plan_info.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.c_int32, C.POINTER(LaunchInfo)]
@@ -217,26 +228,34 @@ def load():
     L.sb_create_jacobi.argtypes = [C.POINTER(PlanDesc), C.POINTER(JacobiDesc), C.POINTER(Params), C.POINTER(ObsLayout),
                                    C.c_int32, C.c_int32, C.POINTER(vp)]
     L.sb_tap_jacobi.argtypes = [vp, C.c_int32, _fp, _fp, _dp, _fp, _ip, _ip]
+  if all(hasattr(L, name) for name in BUILDING_PARAM_ENTRIES):
+    L.sb_set_building_params.argtypes = [vp, C.c_int32, vp, vp, vp]
   _lib = L
   return L
 
 
-def state_entry(name: str):
-  """The state-snapshot entry `name` of the loaded library; a library built before it existed (same ABI version)
-  gets the usual request to rebuild, not an AttributeError."""
+def entry(name: str):
+  """The entry `name` of the loaded library.  A library built before it existed (same ABI version) gets the usual
+  request to rebuild -- an SbsimError, not ctypes' bare AttributeError."""
   L = load()
   if not hasattr(L, name):
     raise SbsimError(f"{LIB_PATH} has no {name}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
   return getattr(L, name)
+
+
+def state_entry(name: str):
+  """The state-snapshot entry `name` (sb_state_save, sb_state_load): see entry()."""
+  return entry(name)
 
 
 def jacobi_entry(name: str):
-  """The Jacobi-solver entry `name` of the loaded library (sb_create_jacobi, sb_tap_jacobi); a library built before it
-  existed (same ABI version) gets the usual request to rebuild, not an AttributeError."""
-  L = load()
-  if not hasattr(L, name):
-    raise SbsimError(f"{LIB_PATH} has no {name}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-  return getattr(L, name)
+  """The Jacobi-solver entry `name` (sb_create_jacobi, sb_tap_jacobi): see entry()."""
+  return entry(name)
+
+
+def has_experimental_kernels() -> bool:
+  """sb_has_experimental_kernels(): whether the library was built with SBSIM_BUILD_EXPERIMENTAL=1 (see entry())."""
+  return bool(entry("sb_has_experimental_kernels")())
 
 
 def check(rc: int, what: str) -> None:

@@ -79,9 +79,10 @@ __global__ void k_reset(Dev a, double initial_temp, const double *temps, int fir
     if (lane == 0 && temps_only) a.scal[(size_t)b * kNScal + 11] = s / (double)a.N;
     if (lane == 0 && !temps_only) {
       double *S = a.scal + (size_t)b * kNScal;
-      S[0] = a.p.ahu_heat_sp; S[1] = a.p.ahu_cool_sp; S[2] = 0.0; S[3] = 0.0; // air_handler.py:131-139
-      S[4] = a.p.blr_setpoint; S[5] = 0.0; S[6] = 0.0; S[7] = 0.0;           // boiler.py:110-121
-      S[8] = a.p.blr_setpoint; S[9] = 0.0; S[10] = 0.0;
+      const double blr_sp = bparam(a, SB_BP_BLR_SETPOINT, b); // the building's own row (sb_set_building_params)
+      S[0] = bparam(a, SB_BP_AHU_HEAT_SP, b); S[1] = bparam(a, SB_BP_AHU_COOL_SP, b); S[2] = 0.0; S[3] = 0.0; // air_handler.py:131-139
+      S[4] = blr_sp; S[5] = 0.0; S[6] = 0.0; S[7] = 0.0;                      // boiler.py:110-121
+      S[8] = blr_sp; S[9] = 0.0; S[10] = 0.0;
       S[11] = s / (double)a.N;
       S[12] = S[13] = S[14] = S[15] = 0.0;
       S[16] = a.reg && a.n_ring > 0 ? rlo : 0.0; // extremes of the exterior-space ring (register path)
@@ -101,7 +102,7 @@ __global__ void k_observe(Dev a, float *obs, float aux0, float aux1, float aux2,
   const float aux[SB_NUM_AUX] = {aux0, aux1, aux2, aux3, aux4, aux5, aux6};
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) {
     double *S = a.scal + (size_t)b * kNScal;
-    observe_boiler(a, S);
+    observe_boiler(a, S, b);
     write_obs(a, b, obs, aux, t_amb_b ? t_amb_b[b] : t_amb, S, num_occupants, occ_norm);
   }
 }
@@ -283,9 +284,10 @@ __global__ void k_reset_jacobi(Dev a, float *grid, double initial_temp, const do
     }
     if (lane == 0) {
       double *S = a.scal + (size_t)b * kNScal;
-      S[0] = a.p.ahu_heat_sp; S[1] = a.p.ahu_cool_sp; S[2] = 0.0; S[3] = 0.0; // air_handler.py:131-139
-      S[4] = a.p.blr_setpoint; S[5] = 0.0; S[6] = 0.0; S[7] = 0.0;           // boiler.py:110-121
-      S[8] = a.p.blr_setpoint; S[9] = 0.0; S[10] = 0.0;
+      const double blr_sp = bparam(a, SB_BP_BLR_SETPOINT, b); // the building's own row (sb_set_building_params)
+      S[0] = bparam(a, SB_BP_AHU_HEAT_SP, b); S[1] = bparam(a, SB_BP_AHU_COOL_SP, b); S[2] = 0.0; S[3] = 0.0; // air_handler.py:131-139
+      S[4] = blr_sp; S[5] = 0.0; S[6] = 0.0; S[7] = 0.0;                      // boiler.py:110-121
+      S[8] = blr_sp; S[9] = 0.0; S[10] = 0.0;
       S[11] = s / (double)a.N;
       S[12] = S[13] = S[14] = S[15] = 0.0;
       S[16] = S[17] = 0.0; // (the register path's ring extremes: no ring here)
@@ -563,6 +565,85 @@ int sb_state_load(sb_handle *h, const int32_t *pick_dev, const sb_state_view *vi
     h->steps_since_reset = clock_in->steps_since_reset;
     h->was_reset = clock_in->was_reset != 0;
   }
+  return SB_OK;
+}
+
+/* ---- per-building parameters ---- */
+static_assert(offsetof(sb_params, w_carbon) - offsetof(sb_params, vav_max_air_flow) ==
+                  (SB_NUM_BUILDING_PARAMS - 1) * sizeof(double),
+              "sb_building_param numbers the contiguous double fields vav_max_air_flow .. w_carbon of sb_params");
+
+static const char *const kBuildingParamNames[SB_NUM_BUILDING_PARAMS] = {
+    "vav_max_air_flow", "vav_max_water_flow", "ahu_recirc", "ahu_heat_sp", "ahu_cool_sp", "ahu_dp", "ahu_eff",
+    "ahu_max_flow", "blr_setpoint", "blr_head", "blr_pump_eff", "blr_heating_rate", "blr_cooling_rate", "blr_conv",
+    "blr_len", "blr_radius", "blr_capacity", "blr_ins_k", "blr_ins_thick", "comfort_lo", "comfort_hi", "eco_lo",
+    "eco_hi", "max_prod", "min_prod", "max_elec", "max_gas", "prod_delta", "prod_stiff", "w_prod", "w_cost",
+    "w_carbon"};
+
+// Building b's effective row (tab: [SB_NUM_BUILDING_PARAMS][B]) against the reference's constructor checks.
+static int check_building_row(const std::vector<double> &tab, int B, int b) {
+  auto v = [&](int k) { return tab[(size_t)k * B + b]; };
+  const std::string at = "sb_set_building_params: building " + std::to_string(b) + ": ";
+  for (int k = 0; k < SB_NUM_BUILDING_PARAMS; ++k)
+    if (!std::isfinite(v(k))) return fail(SB_ERR_INVALID, at + kBuildingParamNames[k] + " is not finite");
+  // fields the device algebra divides by (sb_device.h: the VAV's supply temperature, the fan power and speed, the pump,
+  // the tank's heat loss) and the rest of the boiler's geometry
+  static const int positive[] = {SB_BP_VAV_MAX_AIR_FLOW, SB_BP_AHU_EFF, SB_BP_AHU_MAX_FLOW, SB_BP_BLR_PUMP_EFF,
+                                 SB_BP_BLR_CONV, SB_BP_BLR_LEN, SB_BP_BLR_RADIUS, SB_BP_BLR_INS_K, SB_BP_BLR_INS_THICK};
+  for (const int k : positive)
+    if (!(v(k) > 0.0)) return fail(SB_ERR_INVALID, at + kBuildingParamNames[k] + " must be positive");
+  if (!(v(SB_BP_W_PROD) + v(SB_BP_W_COST) + v(SB_BP_W_CARBON) > 0.0))
+    return fail(SB_ERR_INVALID, at + "w_prod + w_cost + w_carbon must be positive");
+  if (v(SB_BP_AHU_COOL_SP) <= v(SB_BP_AHU_HEAT_SP)) // air_handler.py:60-64
+    return fail(SB_ERR_INVALID, at + "ahu_cool_sp: cooling_air_temp_setpoint must greater than heating_air_temp_setpoint");
+  if (v(SB_BP_COMFORT_LO) > v(SB_BP_COMFORT_HI)) // setpoint_schedule.py:66-75
+    return fail(SB_ERR_INVALID, at + "comfort_lo: comfort_temp_window[0] must be less than comfort_temp_window[1]");
+  if (v(SB_BP_ECO_LO) > v(SB_BP_ECO_HI))
+    return fail(SB_ERR_INVALID, at + "eco_lo: eco_temp_window[0] must be less than eco_temp_window[1]");
+  return SB_OK;
+}
+
+int sb_set_building_params(sb_handle *h, int32_t n_fields, const int32_t *fields, const double *values, void *stream) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_set_building_params: null handle");
+  if (n_fields < 0 || n_fields > SB_NUM_BUILDING_PARAMS)
+    return fail(SB_ERR_INVALID, "sb_set_building_params: n_fields must be in 0 .. SB_NUM_BUILDING_PARAMS");
+  if (n_fields > 0 && (!fields || !values)) return fail(SB_ERR_INVALID, "sb_set_building_params: null argument");
+  const int B = h->d.B;
+  std::vector<double> tab;
+  if (n_fields > 0) {
+    bool named[SB_NUM_BUILDING_PARAMS] = {};
+    for (int i = 0; i < n_fields; ++i) {
+      const int k = fields[i];
+      if (k < 0 || k >= SB_NUM_BUILDING_PARAMS)
+        return fail(SB_ERR_INVALID, "sb_set_building_params: unknown field " + std::to_string(k));
+      if (named[k]) return fail(SB_ERR_INVALID, std::string("sb_set_building_params: field ") + kBuildingParamNames[k] + " named twice");
+      named[k] = true;
+    }
+    tab.resize((size_t)SB_NUM_BUILDING_PARAMS * B); // every field sb_params' value, then the named rows over it
+    for (int k = 0; k < SB_NUM_BUILDING_PARAMS; ++k) std::fill_n(tab.begin() + (size_t)k * B, B, param_field(h->d.p, k));
+    for (int i = 0; i < n_fields; ++i) std::copy_n(values + (size_t)i * B, B, tab.begin() + (size_t)fields[i] * B);
+    for (int b = 0; b < B; ++b) SB_CHECK(check_building_row(tab, B, b));
+  }
+  SB_ON_DEVICE(h->device);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  SB_HIP(hipStreamIsCapturing((hipStream_t)stream, &cap));
+  if (cap != hipStreamCaptureStatusNone)
+    return fail(SB_ERR_INVALID, "sb_set_building_params: not while the stream is being captured into a graph");
+  // the kernels already queued on `stream` read the old table: the new one is copied after them, and the stream is
+  // drained before the old buffer goes (a dropped table) or the call returns (the host rows may be freed)
+  if (n_fields == 0) {
+    SB_HIP(hipStreamSynchronize((hipStream_t)stream));
+    h->d.bp = nullptr;
+    if (h->bp.p) {
+      SB_HIP(hipFree(h->bp.p));
+      h->bp.p = nullptr;
+    }
+    return SB_OK;
+  }
+  if (!h->bp.p) SB_HIP(hipMalloc((void **)&h->bp.p, tab.size() * sizeof(double)));
+  SB_HIP(hipMemcpyAsync(h->bp.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
+  SB_HIP(hipStreamSynchronize((hipStream_t)stream));
+  h->d.bp = h->bp.p;
   return SB_OK;
 }
 

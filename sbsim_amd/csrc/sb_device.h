@@ -151,7 +151,56 @@ struct Dev {
   long long *dbg;          // optional [16] phase time stamps of wave 0's first building (+ [2048] with dbg_timeline)
   int dbg_timeline;        // SBSIM_DEBUG_TIMELINE=1 (developer builds of step_band.hip)
   sb_params p;
+  // sb_set_building_params: [SB_NUM_BUILDING_PARAMS][B] per-building values of sb_params' vav_max_air_flow .. w_carbon
+  // (structure of arrays: k_post's one-thread-per-building reads coalesce); NULL: every building uses `p`.  Read only
+  // through bparam(), and only by k_pre, k_post, k_observe and the reset kernels -- no sweep kernel looks at it.
+  const double *bp;
 };
+
+// sb_params' double fields vav_max_air_flow .. w_carbon by sb_building_param (constant k: folds to the field)
+__host__ __device__ __forceinline__ double param_field(const sb_params &p, int k) {
+  switch (k) {
+    case SB_BP_VAV_MAX_AIR_FLOW: return p.vav_max_air_flow;
+    case SB_BP_VAV_MAX_WATER_FLOW: return p.vav_max_water_flow;
+    case SB_BP_AHU_RECIRC: return p.ahu_recirc;
+    case SB_BP_AHU_HEAT_SP: return p.ahu_heat_sp;
+    case SB_BP_AHU_COOL_SP: return p.ahu_cool_sp;
+    case SB_BP_AHU_DP: return p.ahu_dp;
+    case SB_BP_AHU_EFF: return p.ahu_eff;
+    case SB_BP_AHU_MAX_FLOW: return p.ahu_max_flow;
+    case SB_BP_BLR_SETPOINT: return p.blr_setpoint;
+    case SB_BP_BLR_HEAD: return p.blr_head;
+    case SB_BP_BLR_PUMP_EFF: return p.blr_pump_eff;
+    case SB_BP_BLR_HEATING_RATE: return p.blr_heating_rate;
+    case SB_BP_BLR_COOLING_RATE: return p.blr_cooling_rate;
+    case SB_BP_BLR_CONV: return p.blr_conv;
+    case SB_BP_BLR_LEN: return p.blr_len;
+    case SB_BP_BLR_RADIUS: return p.blr_radius;
+    case SB_BP_BLR_CAPACITY: return p.blr_capacity;
+    case SB_BP_BLR_INS_K: return p.blr_ins_k;
+    case SB_BP_BLR_INS_THICK: return p.blr_ins_thick;
+    case SB_BP_COMFORT_LO: return p.comfort_lo;
+    case SB_BP_COMFORT_HI: return p.comfort_hi;
+    case SB_BP_ECO_LO: return p.eco_lo;
+    case SB_BP_ECO_HI: return p.eco_hi;
+    case SB_BP_MAX_PROD: return p.max_prod;
+    case SB_BP_MIN_PROD: return p.min_prod;
+    case SB_BP_MAX_ELEC: return p.max_elec;
+    case SB_BP_MAX_GAS: return p.max_gas;
+    case SB_BP_PROD_DELTA: return p.prod_delta;
+    case SB_BP_PROD_STIFF: return p.prod_stiff;
+    case SB_BP_W_PROD: return p.w_prod;
+    case SB_BP_W_COST: return p.w_cost;
+    default: return p.w_carbon;
+  }
+}
+
+// Field k of building b's parameters: its row of the table when there is one, else sb_params' value.  a.bp is a kernel
+// argument, so the test is wave-uniform; without a table the value -- and every result computed from it -- is
+// sb_params' own, bit for bit.
+__device__ __forceinline__ double bparam(const Dev &a, int k, int b) {
+  return a.bp ? a.bp[(size_t)k * a.B + b] : param_field(a.p, k);
+}
 
 struct StepArgs {
   const float *actions;
@@ -325,6 +374,8 @@ __device__ inline void write_obs_plant(const Dev &a, float *row, const float *au
                                        const float *num_occupants, double occ_norm, int b) {
   const int n_ahu = a.p.ahu_has_weather ? 9 : 8;
   const double flow = S[2];
+  const double ahu_dp = bparam(a, SB_BP_AHU_DP, b), ahu_max_flow = bparam(a, SB_BP_AHU_MAX_FLOW, b);
+  const double ahu_recirc = bparam(a, SB_BP_AHU_RECIRC, b);
   int src[12];
   double val[12];
 #pragma unroll
@@ -334,14 +385,14 @@ __device__ inline void write_obs_plant(const Dev &a, float *row, const float *au
     double v;
     switch (f) {
       case 0: v = S[3]; break;                              // cooling_request_count
-      case 1: v = a.p.ahu_dp; break;                        // differential_pressure_setpoint
-      case 2: v = flow / a.p.ahu_max_flow; break;           // discharge_fan_speed_percentage_command
-      case 3: v = (1.0 - a.p.ahu_recirc) * flow; break;     // outside_air_flowrate_sensor
+      case 1: v = ahu_dp; break;                            // differential_pressure_setpoint
+      case 2: v = flow / ahu_max_flow; break;               // discharge_fan_speed_percentage_command
+      case 3: v = (1.0 - ahu_recirc) * flow; break;         // outside_air_flowrate_sensor
       case 4: v = t_amb_obs; break;                         // outside_air_temperature_sensor
       case 5: v = S[1]; break;                              // supply_air_cooling_temperature_setpoint
       case 6: v = flow; break;                              // supply_air_flowrate_sensor
       case 7: v = S[0]; break;                              // supply_air_heating_temperature_setpoint
-      default: v = flow / a.p.ahu_max_flow; break;          // supply_fan_speed_percentage_command
+      default: v = flow / ahu_max_flow; break;              // supply_fan_speed_percentage_command
     }
     src[i] = a.col_ahu + i; val[i] = v;
   }
@@ -375,6 +426,7 @@ __device__ inline void write_obs(const Dev &a, int b, float *obs, const float *a
   float *row = obs + (size_t)b * a.O;
   for (int k = 0; k < a.n_hist; ++k)
     for (int j = a.hist_off[k]; j < a.hist_off[k + 1]; ++j) row[a.hist_col[k] + j - a.hist_off[k]] = 0.0f;
+  const double vav_max_air_flow = bparam(a, SB_BP_VAV_MAX_AIR_FLOW, b);
   for (int z0 = 0; z0 < a.Z; z0 += 4) { // four zones = twelve values at a time
     int src[12];
     double val[12];
@@ -383,7 +435,7 @@ __device__ inline void write_obs(const Dev &a, int b, float *obs, const float *a
       const int z = z0 + k < a.Z ? z0 + k : z0, c0 = a.col_zone[z];
       src[3 * k] = c0; src[3 * k + 1] = c0 + 1; src[3 * k + 2] = c0 + 2;
       val[3 * k] = a.damper[(size_t)b * a.Z + z];   // supply_air_damper_percentage_command
-      val[3 * k + 1] = a.p.vav_max_air_flow;        // supply_air_flowrate_setpoint
+      val[3 * k + 1] = vav_max_air_flow;            // supply_air_flowrate_setpoint
       val[3 * k + 2] = a.zair[(size_t)b * a.Z + z]; // zone_air_temperature_sensor
     }
     put_obs_n<12>(a, row, 3 * (a.Z - z0 < 4 ? a.Z - z0 : 4), src, val);
@@ -408,15 +460,16 @@ struct Bld {
 // boiler.py:158-217: one read of supply_water_temperature_sensor outside a step (Environment.reset()'s
 // observation, environment.py:1165-1176; sb_observe) stamps the observation, turns it into the action
 // time stamp when there is none, and advances the tank lag by the duration since the action.
-__device__ inline void observe_boiler(const Dev &a, double *S) {
+__device__ inline void observe_boiler(const Dev &a, double *S, int b) {
   const sb_params &p = a.p;
   if (age_is_none(S[19])) S[19] = 0.0;
   else S[10] = S[19] * p.dt;
-  if (p.blr_cooling_rate > 0.0 && p.blr_heating_rate > 0.0) {
+  const double heating_rate = bparam(a, SB_BP_BLR_HEATING_RATE, b), cooling_rate = bparam(a, SB_BP_BLR_COOLING_RATE, b);
+  if (cooling_rate > 0.0 && heating_rate > 0.0) {
     const double begin = S[8], sp = S[4];
     double cur = sp;
-    if (sp > begin) cur = fmin(begin + p.blr_heating_rate * S[10] / 60.0, sp);
-    else if (sp < begin) cur = fmax(begin - p.blr_cooling_rate * S[10] / 60.0, sp);
+    if (sp > begin) cur = fmin(begin + heating_rate * S[10] / 60.0, sp);
+    else if (sp < begin) cur = fmax(begin - cooling_rate * S[10] / 60.0, sp);
     S[8] = cur;
     S[9] = cur - begin;
   } else {
@@ -515,7 +568,9 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
         if (native < 0.0 || native > 1.0) v.rejected = 1;
     }
   }
-  const double mixed = p.ahu_recirc * recirc + (1 - p.ahu_recirc) * v.t_now;
+  // the building's own parameters (bparam): the 16 lanes of the row read the same address -- one transaction per row
+  const double ahu_recirc = bparam(a, SB_BP_AHU_RECIRC, b);
+  const double mixed = ahu_recirc * recirc + (1 - ahu_recirc) * v.t_now;
   v.t_sa = ahu_supply(mixed, v.heat_sp, v.cool_sp);
   // g[class]: a lane per class, 16 at a time.  q is the PREVIOUS step's: every read of qz here is issued before the zone
   // loop below stores this step's (one instruction stream: a wavefront's memory operations on an address stay in order)
@@ -529,8 +584,11 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
     }
     gt[c] = gg;
   }
-  const double hsp = in.comfort_now ? p.comfort_lo : p.eco_lo;
-  const double csp = in.comfort_now ? p.comfort_hi : p.eco_hi;
+  const double hsp = in.comfort_now ? bparam(a, SB_BP_COMFORT_LO, b) : bparam(a, SB_BP_ECO_LO, b);
+  const double csp = in.comfort_now ? bparam(a, SB_BP_COMFORT_HI, b) : bparam(a, SB_BP_ECO_HI, b);
+  const double vav_max_air_flow = bparam(a, SB_BP_VAV_MAX_AIR_FLOW, b);
+  const double vav_max_water_flow = bparam(a, SB_BP_VAV_MAX_WATER_FLOW, b);
+  const double ahu_max_flow = bparam(a, SB_BP_AHU_MAX_FLOW, b);
   // Thermostat._previous_timestamp (thermostat.py:88): the host's value, or the building's own when
   // buildings can skip thermostat updates (scal[18]: -1 none, else is_comfort_mode of the last update)
   const int comfort_prev = in.reject_dev ? (int)S18 : in.comfort_prev;
@@ -562,8 +620,8 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
       }
     }
     const double valve = valve_open ? 1.0 : 0.0;
-    const double reheat = valve * p.vav_max_water_flow;
-    const double air = damper * p.vav_max_air_flow;
+    const double reheat = valve * vav_max_water_flow;
+    const double air = damper * vav_max_air_flow;
     const double heat_diff = kCAir * air - kCWater * reheat;     // vav.py:181-195
     const double water_heat = v.blr_sp * kCWater * reheat;
     const double tzs = (v.t_sa * heat_diff + water_heat) / air / kCAir;
@@ -576,7 +634,7 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
     row_each(a.Z - z0, air, reheat, valve, tzs, [&](double air_k, double reheat_k, double valve_k, double tzs_k) {
       if (air_k > 0) {
         ahu_flow += air_k;
-        if (ahu_flow > p.ahu_max_flow) ahu_flow = p.ahu_max_flow;
+        if (ahu_flow > ahu_max_flow) ahu_flow = ahu_max_flow;
         ++ahu_count;
       }
       if (reheat_k > 0) { blr_flow += reheat_k; ++blr_count; }
@@ -601,10 +659,11 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
   }
   v.action_age = age;
   v.comfort_seen = rejected ? (int)S18 : in.comfort_now;
-  if (p.blr_cooling_rate > 0.0 && p.blr_heating_rate > 0.0) {
+  const double heating_rate = bparam(a, SB_BP_BLR_HEATING_RATE, b), cooling_rate = bparam(a, SB_BP_BLR_COOLING_RATE, b);
+  if (cooling_rate > 0.0 && heating_rate > 0.0) {
     const double begin = v.tank;
-    if (v.blr_sp > begin) v.tank = fmin(begin + p.blr_heating_rate * v.duration / 60.0, v.blr_sp);
-    else if (v.blr_sp < begin) v.tank = fmax(begin - p.blr_cooling_rate * v.duration / 60.0, v.blr_sp);
+    if (v.blr_sp > begin) v.tank = fmin(begin + heating_rate * v.duration / 60.0, v.blr_sp);
+    else if (v.blr_sp < begin) v.tank = fmax(begin - cooling_rate * v.duration / 60.0, v.blr_sp);
     else v.tank = v.blr_sp;
     v.tank_change = v.tank - begin;
   } else {
@@ -627,8 +686,9 @@ __device__ inline void post_building(const Dev &a, const StepArgs &s, int b) {
   const size_t zb = (size_t)b * a.Z;
   const double recirc2 = a.gsum[b] / (double)a.N;
   const int n_sweeps = a.nsw[b] & 0xffff, converged = a.nsw[b] >> 16;
-  const double hsp2 = (double)(float)(in.comfort_next ? p.comfort_lo : p.eco_lo);
-  const double csp2 = (double)(float)(in.comfort_next ? p.comfort_hi : p.eco_hi);
+  // the building's own parameters (bparam) are read where they are used: one coalesced load per field and wavefront
+  const double hsp2 = (double)(float)(in.comfort_next ? bparam(a, SB_BP_COMFORT_LO, b) : bparam(a, SB_BP_ECO_LO, b));
+  const double csp2 = (double)(float)(in.comfort_next ? bparam(a, SB_BP_COMFORT_HI, b) : bparam(a, SB_BP_ECO_HI, b));
   double cumulative = 0.0, total_occ = 0.0;
   for (int z0 = 0; z0 < a.Z; z0 += 8) { // eight zones' inputs first (as in pre_building), then their arithmetic in zone order
    double zs8[8], oc8[8];
@@ -650,46 +710,55 @@ __device__ inline void post_building(const Dev &a, const StepArgs &s, int b) {
     const double t = (double)(float)tzp;
     const double occ = oc8[k];
     double prod; // base_setpoint_energy_carbon_reward.py:78-123
-    if (t < hsp2) prod = p.max_prod / (1.0 + exp(-p.prod_stiff * (t - (hsp2 - p.prod_delta))));
+    // (the three constants are read here, per zone, not held across the loop: k_post has no registers to spare)
+    const double max_prod = bparam(a, SB_BP_MAX_PROD, b);
+    if (t < hsp2)
+      prod = max_prod / (1.0 + exp(-bparam(a, SB_BP_PROD_STIFF, b) * (t - (hsp2 - bparam(a, SB_BP_PROD_DELTA, b)))));
     else if (t > csp2)
-      prod = p.max_prod * (1.0 - 1.0 / (1.0 + exp(-p.prod_stiff * (t - (csp2 + p.prod_delta)))));
-    else prod = p.max_prod;
+      prod = max_prod * (1.0 - 1.0 / (1.0 + exp(-bparam(a, SB_BP_PROD_STIFF, b) * (t - (csp2 + bparam(a, SB_BP_PROD_DELTA, b))))));
+    else prod = max_prod;
     cumulative += prod * occ * p.dt / 3600.0;
     total_occ += occ;
    }
   }
 
-  const double intake = v.ahu_flow * p.ahu_dp / p.ahu_eff;                         // air_handler.py:287-320
-  const double exhaust = (v.ahu_flow * (1.0 - p.ahu_recirc)) * p.ahu_dp / p.ahu_eff;
-  const double mixed2 = p.ahu_recirc * recirc2 + (1 - p.ahu_recirc) * v.t_next;
+  const double ahu_dp = bparam(a, SB_BP_AHU_DP, b), ahu_eff = bparam(a, SB_BP_AHU_EFF, b);
+  const double ahu_recirc = bparam(a, SB_BP_AHU_RECIRC, b);
+  const double intake = v.ahu_flow * ahu_dp / ahu_eff;                             // air_handler.py:287-320
+  const double exhaust = (v.ahu_flow * (1.0 - ahu_recirc)) * ahu_dp / ahu_eff;
+  const double mixed2 = ahu_recirc * recirc2 + (1 - ahu_recirc) * v.t_next;
   const double supply2 = ahu_supply(mixed2, v.heat_sp, v.cool_sp);
   const double supply_w = v.blr_sp > v.blr_return ? v.blr_sp : v.blr_return;       // boiler.py:244-247
-  const double r2 = p.blr_radius + p.blr_ins_thick;                                // boiler.py:275-320
-  const double diss = (p.blr_len * 2.0 * M_PI * (supply_w - v.t_next)) /
-                      (log(r2 / p.blr_radius) / p.blr_ins_k + 1.0 / p.blr_conv / r2);
+  const double blr_radius = bparam(a, SB_BP_BLR_RADIUS, b);
+  const double r2 = blr_radius + bparam(a, SB_BP_BLR_INS_THICK, b);                // boiler.py:275-320
+  const double diss = (bparam(a, SB_BP_BLR_LEN, b) * 2.0 * M_PI * (supply_w - v.t_next)) /
+                      (log(r2 / blr_radius) / bparam(a, SB_BP_BLR_INS_K, b) + 1.0 / bparam(a, SB_BP_BLR_CONV, b) / r2);
   double tank_rate = 0.0;
-  if (v.duration > 0) tank_rate = kCWater * p.blr_capacity * v.tank_change / v.duration;
+  if (v.duration > 0) tank_rate = kCWater * bparam(a, SB_BP_BLR_CAPACITY, b) * v.tank_change / v.duration;
   const float blower = (float)(intake + exhaust);
   const float ac = (float)(v.ahu_flow * kCAir * (supply2 - mixed2));
   const float gas = (float)(kCWater * v.blr_flow * (supply_w - v.blr_return) + diss + tank_rate);
-  const float pump = (float)(v.blr_flow * kRhoWater * kGravity * p.blr_head / p.blr_pump_eff);
+  const float pump = (float)(v.blr_flow * kRhoWater * kGravity * bparam(a, SB_BP_BLR_HEAD, b) / bparam(a, SB_BP_BLR_PUMP_EFF, b));
 
   // setpoint_energy_carbon_regret.py:142-291
-  const double max_p = p.max_prod * total_occ * p.dt / 3600.0;
-  const double min_p = p.min_prod * total_occ * p.dt / 3600.0;
+  const double max_elec = bparam(a, SB_BP_MAX_ELEC, b), max_gas = bparam(a, SB_BP_MAX_GAS, b);
+  const double w_prod = bparam(a, SB_BP_W_PROD, b), w_cost = bparam(a, SB_BP_W_COST, b), w_carbon = bparam(a, SB_BP_W_CARBON, b);
+  const double max_prod = bparam(a, SB_BP_MAX_PROD, b);
+  const double max_p = max_prod * total_occ * p.dt / 3600.0;
+  const double min_p = bparam(a, SB_BP_MIN_PROD, b) * total_occ * p.dt / 3600.0;
   const double actual = fmax(cumulative, min_p);
   const double npr = total_occ > 0.0 ? (actual - min_p) / (max_p - min_p) - 1.0 : 0.0;
   const double elec = ((double)blower + fabs((double)ac)) + (double)pump;
-  const double cap_e = fmin(elec, p.max_elec);
-  const double cap_g = fmax(fmin((double)gas, p.max_gas), 0.0);
-  const double ce = in.e_price * fabs(cap_e) * p.dt, ce_max = in.e_price * fabs(p.max_elec) * p.dt;
-  const double ke = in.e_carbon * fabs(cap_e) * p.dt, ke_max = in.e_carbon * fabs(p.max_elec) * p.dt;
-  const double cg = in.g_price * (cap_g * p.dt), cg_max = in.g_price * (p.max_gas * p.dt);
-  const double kg = in.g_carbon * (cap_g * p.dt), kg_max = in.g_carbon * (p.max_gas * p.dt);
+  const double cap_e = fmin(elec, max_elec);
+  const double cap_g = fmax(fmin((double)gas, max_gas), 0.0);
+  const double ce = in.e_price * fabs(cap_e) * p.dt, ce_max = in.e_price * fabs(max_elec) * p.dt;
+  const double ke = in.e_carbon * fabs(cap_e) * p.dt, ke_max = in.e_carbon * fabs(max_elec) * p.dt;
+  const double cg = in.g_price * (cap_g * p.dt), cg_max = in.g_price * (max_gas * p.dt);
+  const double kg = in.g_carbon * (cap_g * p.dt), kg_max = in.g_carbon * (max_gas * p.dt);
   const double nec = (ce + cg) / (ce_max + cg_max);
   const double nce = (ke + kg) / (ke_max + kg_max);
   const double reward =
-      (npr * p.w_prod - nec * p.w_cost - nce * p.w_carbon) / (p.w_prod + p.w_cost + p.w_carbon);
+      (npr * w_prod - nec * w_cost - nce * w_carbon) / (w_prod + w_cost + w_carbon);
 
   S[0] = v.heat_sp; S[1] = v.cool_sp; S[2] = v.ahu_flow; S[3] = (double)v.ahu_count;
   S[4] = v.blr_sp; S[5] = v.blr_flow; S[6] = (double)v.blr_count; S[7] = v.blr_return;
@@ -705,7 +774,7 @@ __device__ inline void post_building(const Dev &a, const StepArgs &s, int b) {
     I[4] = (float)n_sweeps; I[5] = (float)converged; I[6] = (float)v.t_sa; I[7] = (float)reward;
     // RewardResponse fields 2..17 (setpoint_energy_carbon_regret.py:239-291), proto floats
     I[8] = (float)actual; I[9] = (float)ce; I[10] = (float)cg; I[11] = (float)(ke + kg); I[12] = 0.0f;
-    I[13] = (float)p.w_prod; I[14] = (float)p.w_cost; I[15] = (float)p.w_carbon; I[16] = (float)p.max_prod;
+    I[13] = (float)w_prod; I[14] = (float)w_cost; I[15] = (float)w_carbon; I[16] = (float)max_prod;
     I[17] = (float)total_occ; I[18] = 1.0f; I[19] = 0.0f; I[20] = (float)(actual - max_p);
     I[21] = (float)npr; I[22] = (float)nec; I[23] = (float)nce;
   }

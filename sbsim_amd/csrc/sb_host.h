@@ -141,6 +141,7 @@ struct sb_handle {
   DevBuf<int> act_kind, act_zone, zone_act; // the action vector's tables (sb_params.act_*) on the device
   DevBuf<double> act_lo, act_hi;
   DevBuf<double> tmul; // step_roll.hip: the tail scan's static multipliers
+  DevBuf<double> bp;   // sb_set_building_params: [SB_NUM_BUILDING_PARAMS][B] (Dev::bp points here while a table is set)
   DevBuf<double> ctab, csetab, temp, zmean, zair, damper, qz, scal, obs_mean, obs_sigma, ring, gtabg, zsum, gsum,
       hist_bins;
   DevBuf<int> czone, zone_off, zone_cells_l, mode, col_zone, zblk_zone, cell_state, nsw, next_b, src_dest,

@@ -50,6 +50,17 @@ def class_shard_ranges(class_totals, rank: int, world_size: int) -> List[Tuple[i
   return [shard_range(int(n), rank, world_size) for n in class_totals]
 
 
+def class_global_rows(class_totals, rank: int, world_size: int) -> List[Tuple[int, int]]:
+  """The GLOBAL building numbers [lo, hi) this rank holds of every class: class k's building i is building
+  sum(totals[:k]) + i of the whole mixed batch (class-major), on whichever rank it lives.  What the per-building
+  generators key their draws by and what indexes a mixed batch's per-building parameters."""
+  out, base = [], 0
+  for n, (lo, hi) in zip(class_totals, class_shard_ranges(class_totals, rank, world_size)):
+    out.append((base + lo, base + hi))
+    base += int(n)
+  return out
+
+
 def shard_seed(base_seed: int, rank: int) -> int:
   """Per-rank RNG seed of the synthetic workload (1234 + rank)."""
   return base_seed + rank

@@ -348,6 +348,7 @@ class BatchedSimulator:
     self.plan, self.config, self.B, self.device = plan, config, int(n_buildings), int(device)
     self._h_conv = float(h_conv)
     self._occ_attached = self._conv_attached = None   # the arguments of the device generators (SimState fingerprint)
+    self._building_params = None   # set_building_params: the per-building table in force (None: the config's values)
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -577,6 +578,33 @@ class BatchedSimulator:
       return
     _ffi.check(self._lib.sb_step_phases(*args, int(phases)), "sb_step")
 
+  # ---- per-building parameters (sb_set_building_params) ----
+  def set_building_params(self, params: Optional[host_inputs.BuildingParams]) -> None:
+    """Per-building HVAC, setpoint-window and reward parameters (``host_inputs.BuildingParams``, one row per building;
+    None clears the table: every building back to the SimConfig's values).  Checked on the host, then ordered on the
+    current stream and synchronised with it; not while that stream is being captured into a graph.  A row belongs to
+    the building's slot, not to its state: snapshots do not carry it and a forked building keeps its own row.  It
+    applies from the next reset, step or observation; a reset sets the AHU and boiler setpoints from it."""
+    fn = _ffi.entry("sb_set_building_params")
+    if params is None:
+      _ffi.check(fn(self._h, 0, None, None, self._stream()), "sb_set_building_params")
+      self._building_params = None
+      return
+    if not isinstance(params, host_inputs.BuildingParams):
+      raise ValueError("set_building_params needs a host_inputs.BuildingParams (or None)")
+    if params.n_buildings != self.B:
+      raise ValueError(f"BuildingParams has {params.n_buildings} rows, the simulator {self.B} buildings")
+    params.validate(self.config)
+    fields, values = params.c_table()
+    with torch.cuda.device(self.device):
+      _ffi.check(fn(self._h, int(fields.shape[0]), fields.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+                    self._stream()), "sb_set_building_params")
+    self._building_params = params
+
+  def building_params(self) -> Dict[str, np.ndarray]:
+    """The parameters every building runs with: SimConfig field name -> float64 [B] ([B, 2] for the windows)."""
+    return host_inputs.effective_building_params(self._building_params, self.config, self.B)
+
   # ---- state snapshots (sb_state_save / sb_state_load) ----
   def state_fingerprint(self) -> Tuple:
     """What a SimState of this simulator means: plan shape and zones, a hash of the compiled plan tables (in the
@@ -745,9 +773,11 @@ class BatchedEnvironment:
                occupancy_normalization_constant: float = 0.0, holiday_calendar="us",
                electricity_energy_cost=None, natural_gas_energy_cost=None, collect_info: bool = False,
                observation_histogram_parameters: Optional[Sequence[Tuple[str, Sequence[float]]]] = None,
-               normalize_reduce: bool = False, convection_simulator=None, solver: str = "gauss_seidel"):
+               normalize_reduce: bool = False, convection_simulator=None, solver: str = "gauss_seidel",
+               building_params: Optional[host_inputs.BuildingParams] = None):
     """``solver``: the finite-difference solver (BatchedSimulator): "gauss_seidel" (default) or "jacobi_fp32"
-    (TFSimulator, SB1's shipped configuration; no convection_simulator, snapshot, restore or fork)."""
+    (TFSimulator, SB1's shipped configuration; no convection_simulator, snapshot, restore or fork).
+    ``building_params``: per-building plant, setpoint and reward parameters (``set_building_params``)."""
     if discount_factor <= 0 or discount_factor > 1:
       raise ValueError("Discount factor must be in (0,1]")   # environment.py:454-455
     if solver == "jacobi_fp32" and convection_simulator is not None:
@@ -769,6 +799,8 @@ class BatchedEnvironment:
                                 histogram_parameters=observation_histogram_parameters,
                                 normalize_reduce=normalize_reduce, solver=solver)
     self.batch_size = self.sim.B
+    if building_params is not None:
+      self.sim.set_building_params(building_params)
     self._weather_lohi = self._weather_replay = None
     if isinstance(self.weather, host_inputs.BatchedReplayWeather):
       if self.weather.offsets_sec.shape[0] != self.batch_size:
@@ -947,6 +979,14 @@ class BatchedEnvironment:
     return TimeStep(mid, self._reward, self._discount, self._obs)
 
 
+  def set_building_params(self, params: Optional[host_inputs.BuildingParams]) -> None:
+    """BatchedSimulator.set_building_params between steps; the usual place is just before ``reset()``, which sets
+    the AHU and boiler setpoints of the new episode from the new rows."""
+    self.sim.set_building_params(params)
+
+  def building_params(self) -> Dict[str, np.ndarray]:
+    return self.sim.building_params()
+
   # ---- snapshots ----
   _HOST_CLOCK = ("_now", "_step_count", "_episode_count", "_episode_ended", "_needs_reset", "_prev_thermostat_ts")
 
@@ -1068,7 +1108,9 @@ class MixedBatchedEnvironment:
   global (class-major) order."""
 
   def __init__(self, classes: Sequence[Tuple[FloorPlan, int]], device: int = 0, rank: int = 0, world: int = 1,
-               **env_kwargs):
+               building_params: Optional[host_inputs.BuildingParams] = None, **env_kwargs):
+    """``building_params``: one row per GLOBAL building of the mixed batch (``sum(class_totals)`` rows, class-major);
+    each class on this rank takes its buildings' rows (``distributed.class_global_rows``), whatever the sharding."""
     if not classes:
       raise ValueError("MixedBatchedEnvironment needs at least one (floor plan, number of buildings) class")
     from . import distributed as _sd
@@ -1084,12 +1126,14 @@ class MixedBatchedEnvironment:
     if any(n < self.world for n in self.class_totals):
       raise ValueError(f"every class needs at least one building per rank: totals {self.class_totals}, {world} ranks")
     classes = [(plan, hi - lo_) for (plan, _), (lo_, hi) in zip(classes, self.class_ranges)]
+    self.global_rows = _sd.class_global_rows(self.class_totals, self.rank, self.world)
+    self._check_building_params(building_params)
     lo = 0
     for k, (plan, n) in enumerate(classes):
       # per-building generators (convection shuffle, randomized occupancy) draw from streams keyed by the GLOBAL
       # building index: class k's building i is building sum(totals[:k]) + i of the whole mixed batch, on whichever
       # rank it lives -- so the draws do not depend on the sharding, and no two buildings share a stream
-      first = sum(self.class_totals[:k]) + self.class_ranges[k][0]
+      first = self.global_rows[k][0]
       kw = dict(env_kwargs)
       if isinstance(kw.get("solver"), (list, tuple)):   # one finite-difference solver per class
         if len(kw["solver"]) != len(classes):
@@ -1102,6 +1146,8 @@ class MixedBatchedEnvironment:
           gen.first_building = int(gen.first_building) + first
           kw[key] = gen
       stream = torch.cuda.Stream(device=self.tdev)
+      if building_params is not None:
+        kw["building_params"] = building_params.rows(*self.global_rows[k])
       with torch.cuda.stream(stream):
         env = BatchedEnvironment(plan, int(n), device=self.device, **kw)
       self.envs.append(env)
@@ -1145,6 +1191,18 @@ class MixedBatchedEnvironment:
   @property
   def current_simulation_timestamp(self) -> dt.datetime:
     return self.envs[0].current_simulation_timestamp
+
+  def _check_building_params(self, params: Optional[host_inputs.BuildingParams]) -> None:
+    total = sum(self.class_totals)
+    if params is not None and params.n_buildings != total:
+      raise ValueError(f"building_params has {params.n_buildings} rows; the mixed batch has {total} buildings "
+                       "(rows are indexed by the global building number, over every rank)")
+
+  def set_building_params(self, params: Optional[host_inputs.BuildingParams]) -> None:
+    """Per-building parameters of the whole mixed batch (global rows, as the constructor's ``building_params``);
+    None clears every class's table."""
+    self._check_building_params(params)
+    self._on_streams(lambda k, env: env.set_building_params(None if params is None else params.rows(*self.global_rows[k])))
 
   def _each(self, fn) -> TimeStep:
     """Runs fn(class index, env) -> TimeStep on every class's stream between two joins with the caller's stream."""

@@ -265,7 +265,10 @@ class BuildingLogger:
     info = env.info[self.buildings].cpu().numpy()
     zt = env.sim.zone_temps()[self.buildings].cpu().numpy()
     flow = env.sim.scalars()[self.buildings, 2].cpu().numpy()
-    hsp, csp = env.schedule.get_temperature_window(now)
+    # the building's own setpoint window and VAV flow setpoint (BatchedEnvironment(building_params=...))
+    bp = env.sim.building_params()
+    window = bp["comfort_temp_window" if env.schedule.is_comfort_mode(now) else "eco_temp_window"][self.buildings]
+    vav_flow = bp["vav_max_air_flow_rate"][self.buildings]
     occ = (env._occ_count[self.buildings].cpu().numpy() if env._occ_count is not None
            else np.full((len(self.buildings), env.sim.Z), info[:, 17:18] / env.sim.Z))
     self._log_observation(now)
@@ -274,8 +277,8 @@ class BuildingLogger:
       w.write_action_response(w.encode_action_response(
           timestamp_before, [self.boiler_id, self.ahu_id],
           ["supply_water_setpoint", "supply_air_heating_temperature_setpoint"], native[k]), timestamp_before)
-      zone_vals = np.stack([np.full(env.sim.Z, hsp), np.full(env.sim.Z, csp), zt[k],
-                            np.full(env.sim.Z, cfg.vav_max_air_flow_rate), np.full(env.sim.Z, flow[k]), occ[k]], axis=1)
+      zone_vals = np.stack([np.full(env.sim.Z, window[k, 0]), np.full(env.sim.Z, window[k, 1]), zt[k],
+                            np.full(env.sim.Z, vav_flow[k]), np.full(env.sim.Z, flow[k]), occ[k]], axis=1)
       w.write_reward_info(w.encode_reward_info(now, end, self.zone_ids, zone_vals, [self.ahu_id], info[k, 0:2],
                                                [self.boiler_id], info[k, 2:4], self.agent_id, self.scenario_id), now)
       resp = np.concatenate([info[k, 7:8], info[k, 8:24]])

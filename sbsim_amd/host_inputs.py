@@ -524,3 +524,142 @@ def get_radian_time(ts, hour_of_day: bool) -> float:
   else:
     frac = float(ts.weekday()) / 7.0
   return 2.0 * np.pi * frac
+
+
+# --------------------------------------------------------------------------- per-building plant parameters
+# SimConfig field -> the sb_params fields it sets (include/sbsim_amd.h sb_building_param), in the enum's order
+BUILDING_PARAM_NAMES: Dict[str, Tuple[str, ...]] = {
+    "vav_max_air_flow_rate": ("vav_max_air_flow",),
+    "vav_reheat_max_water_flow_rate": ("vav_max_water_flow",),
+    "ahu_recirculation": ("ahu_recirc",),
+    "ahu_heating_air_temp_setpoint": ("ahu_heat_sp",),
+    "ahu_cooling_air_temp_setpoint": ("ahu_cool_sp",),
+    "ahu_fan_differential_pressure": ("ahu_dp",),
+    "ahu_fan_efficiency": ("ahu_eff",),
+    "ahu_max_air_flow_rate": ("ahu_max_flow",),
+    "boiler_reheat_water_setpoint": ("blr_setpoint",),
+    "boiler_water_pump_differential_head": ("blr_head",),
+    "boiler_water_pump_efficiency": ("blr_pump_eff",),
+    "boiler_heating_rate": ("blr_heating_rate",),
+    "boiler_cooling_rate": ("blr_cooling_rate",),
+    "boiler_convection_coefficient": ("blr_conv",),
+    "boiler_tank_length": ("blr_len",),
+    "boiler_tank_radius": ("blr_radius",),
+    "boiler_water_capacity": ("blr_capacity",),
+    "boiler_insulation_conductivity": ("blr_ins_k",),
+    "boiler_insulation_thickness": ("blr_ins_thick",),
+    "comfort_temp_window": ("comfort_lo", "comfort_hi"),
+    "eco_temp_window": ("eco_lo", "eco_hi"),
+    "max_productivity_personhour_usd": ("max_prod",),
+    "min_productivity_personhour_usd": ("min_prod",),
+    "max_electricity_rate": ("max_elec",),
+    "max_natural_gas_rate": ("max_gas",),
+    "productivity_midpoint_delta": ("prod_delta",),
+    "productivity_decay_stiffness": ("prod_stiff",),
+    "productivity_weight": ("w_prod",),
+    "energy_cost_weight": ("w_cost",),
+    "carbon_emission_weight": ("w_carbon",),
+}
+# SimConfig fields that stay one value per batch: the solver's (dt, threshold, iteration limit, the plan's materials and
+# geometry), the host's (schedule hours, holidays, time zone: resolved once per step), the observation and action layout
+PER_BATCH_CONFIG_FIELDS = ("time_step_sec", "convergence_threshold", "iteration_limit", "cv_size_cm", "floor_height_cm",
+                           "initial_temp", "materials", "morning_start_hour", "evening_start_hour", "schedule_holidays",
+                           "time_zone", "ahu_has_weather_sensor", "action_ranges", "action_names", "action_zones")
+# fields the device algebra divides by (sb_device.h), and the rest of the boiler's geometry: must be > 0
+_POSITIVE_PARAMS = ("vav_max_air_flow_rate", "ahu_fan_efficiency", "ahu_max_air_flow_rate", "boiler_water_pump_efficiency",
+                    "boiler_convection_coefficient", "boiler_tank_length", "boiler_tank_radius",
+                    "boiler_insulation_conductivity", "boiler_insulation_thickness")
+_WINDOWS = {"comfort_temp_window": "comfort_temp_window[0] must be less than comfort_temp_window[1]",  # setpoint_schedule.py:66-75
+            "eco_temp_window": "eco_temp_window[0] must be less than eco_temp_window[1]"}
+
+
+class BuildingParams:
+  """Per-building plant, setpoint-window and reward parameters of one batch (sb_set_building_params): SimConfig field
+  names mapped to float64 arrays with one row per building -- shape [B], or [B, 2] for ``comfort_temp_window`` /
+  ``eco_temp_window``.  A field that is not given keeps the SimConfig's value for every building.
+
+      bp = BuildingParams({"ahu_fan_efficiency": eff, "comfort_temp_window": np.stack([lo, hi], axis=1)})
+      env = BatchedEnvironment(plan, B, building_params=bp)
+
+  Raises ValueError for an unknown name (listing the allowed ones), a per-batch SimConfig field, a wrong shape, and the
+  reference's constructor checks row by row; the checks that involve a field not given here run against the SimConfig
+  in ``validate``."""
+
+  def __init__(self, values: Optional[Mapping[str, object]] = None, **kw):
+    merged = dict(values or {}, **kw)
+    if not merged:
+      raise ValueError("BuildingParams needs at least one field (pass None instead of a table to clear one)")
+    self.fields: Dict[str, np.ndarray] = {}
+    self.n_buildings = None
+    for name, arr in merged.items():
+      if name in PER_BATCH_CONFIG_FIELDS:
+        raise ValueError(f"{name!r} is one value per batch (the sweep or the host reads it), not per building")
+      if name not in BUILDING_PARAM_NAMES:
+        raise ValueError(f"unknown per-building parameter {name!r}; allowed: {', '.join(BUILDING_PARAM_NAMES)}")
+      a = np.array(arr, dtype=np.float64)
+      width = len(BUILDING_PARAM_NAMES[name])
+      if a.ndim != (1 if width == 1 else 2) or (width > 1 and a.shape[1] != width) or a.shape[0] == 0:
+        raise ValueError(f"{name} must have shape [B]" + ("" if width == 1 else f" x {width}") + f", got {a.shape}")
+      if self.n_buildings is None:
+        self.n_buildings = int(a.shape[0])
+      elif a.shape[0] != self.n_buildings:
+        raise ValueError(f"{name} has {a.shape[0]} rows, the other fields {self.n_buildings}: one row per building")
+      bad = np.nonzero(~np.isfinite(a).reshape(a.shape[0], -1).all(axis=1))[0]
+      if bad.size:
+        raise ValueError(f"building {int(bad[0])}: {name} is not finite")
+      if name in _POSITIVE_PARAMS and not (a > 0.0).all():
+        raise ValueError(f"building {int(np.argmin(a > 0.0))}: {name} must be positive")
+      if name in _WINDOWS and not (a[:, 0] <= a[:, 1]).all():
+        raise ValueError(f"building {int(np.argmin(a[:, 0] <= a[:, 1]))}: {_WINDOWS[name]}")
+      a.setflags(write=False)
+      self.fields[name] = a
+
+  def rows(self, lo: int, hi: int) -> "BuildingParams":
+    """Buildings lo .. hi-1 (a class's or a rank's share of a larger batch)."""
+    if not 0 <= lo < hi <= self.n_buildings:
+      raise ValueError(f"rows [{lo}, {hi}) outside the table's {self.n_buildings} buildings")
+    return BuildingParams({k: v[lo:hi] for k, v in self.fields.items()})
+
+  def effective(self, config) -> Dict[str, np.ndarray]:
+    """Every per-building SimConfig field of every building: this table's rows, the SimConfig's value elsewhere."""
+    return effective_building_params(self, config, self.n_buildings)
+
+  def validate(self, config) -> None:
+    """The reference's checks that tie two fields together, on the effective rows (a field not given: the config's)."""
+    eff = self.effective(config)
+    heat, cool = eff["ahu_heating_air_temp_setpoint"], eff["ahu_cooling_air_temp_setpoint"]
+    if not (cool > heat).all():   # air_handler.py:60-64
+      raise ValueError(f"building {int(np.argmin(cool > heat))}: cooling_air_temp_setpoint must greater than "
+                       "heating_air_temp_setpoint")
+    for name, msg in _WINDOWS.items():
+      w = eff[name]
+      if not (w[:, 0] <= w[:, 1]).all():
+        raise ValueError(f"building {int(np.argmin(w[:, 0] <= w[:, 1]))}: {msg}")
+    wsum = eff["productivity_weight"] + eff["energy_cost_weight"] + eff["carbon_emission_weight"]
+    if not (wsum > 0.0).all():
+      raise ValueError(f"building {int(np.argmin(wsum > 0.0))}: productivity_weight + energy_cost_weight + "
+                       "carbon_emission_weight must be positive (the reward divides by it)")
+
+  def c_table(self) -> Tuple[np.ndarray, np.ndarray]:
+    """sb_set_building_params' arguments: the named sb_building_param fields (int32 [n]) and their rows ([n][B])."""
+    from . import _ffi
+    index = {name: k for k, name in enumerate(_ffi.BUILDING_PARAM_FIELDS)}
+    fields, rows = [], []
+    for name, a in self.fields.items():
+      for j, c_name in enumerate(BUILDING_PARAM_NAMES[name]):
+        fields.append(index[c_name])
+        rows.append(a if a.ndim == 1 else a[:, j])
+    return np.asarray(fields, dtype=np.int32), np.ascontiguousarray(np.stack(rows))
+
+
+def effective_building_params(params: Optional[BuildingParams], config, n_buildings: int) -> Dict[str, np.ndarray]:
+  """The per-building SimConfig fields of n_buildings buildings: ``params``' rows where it has the field, the config's
+  value elsewhere (``params`` None: every building the config's)."""
+  out = {}
+  for name, c_fields in BUILDING_PARAM_NAMES.items():
+    if params is not None and name in params.fields:
+      out[name] = params.fields[name].copy()
+    else:
+      v = np.asarray(getattr(config, name), dtype=np.float64)
+      out[name] = np.broadcast_to(v, (n_buildings,) + v.shape).copy()
+  return out
