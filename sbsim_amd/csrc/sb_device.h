@@ -136,6 +136,7 @@ struct Dev {
   int redo_mode;           // 1 in the exact kernel's launch on the list
   int roll_exact;          // SBSIM_ROLL_EXACT=1: the exact kernel alone (cross-check)
   int dbg_redo_mod;        // SBSIM_DEBUG_FORCE_REDO=m: every m-th building goes through the redo list (tests)
+  int roll_free;           // SBSIM_ROLL_FREE (default 1): periods whose sweep is proven unfinished at their top run without copies and max|delta|; 0: every period measures
   // observation layout (sb_obs_layout): sources in sorted (device, field) order
   int O, col_ahu, col_blr, col_aux;
   const int *col_zone;

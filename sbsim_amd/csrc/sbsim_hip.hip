@@ -66,6 +66,7 @@ struct Knobs {
   float skip_kappa = (float)std::min(100.0, std::max(0.0, env_double("SBSIM_DEBUG_SKIP_KAPPA", 0.9)));
   bool roll_exact = env_int("SBSIM_ROLL_EXACT", 0) != 0;    // k_sweep_roll's float64 instantiation alone
   int force_redo = std::max(0, env_int("SBSIM_DEBUG_FORCE_REDO", 0)); // every m-th building through the redo list
+  bool roll_free = env_int("SBSIM_ROLL_FREE", 1) != 0;      // k_sweep_roll: copy-free, measure-free periods where a sweep is proven unfinished
   bool force_generic = env_flag("SBSIM_FORCE_GENERIC_SWEEP"); // the LDS-grid kernel's generic sweep
   bool phase_timing = getenv("SBSIM_PHASE_TIMING") != nullptr;     // cycle stamps (sb_debug_phase_cycles)
   bool debug_timeline = getenv("SBSIM_DEBUG_TIMELINE") != nullptr; // ... plus step_band.hip's time line
@@ -1099,7 +1100,7 @@ int setup_reg(sb_handle *h, const sb_plan_desc *plan, const RegPlan &r, const Kn
     SB_CHECK(alloc_zero(h->redo_list, (size_t)d.B));
     SB_CHECK(alloc_zero(h->redo_scratch, (size_t)h->info.workgroups * h->info.waves_per_workgroup * d.state_doubles));
     d.redo_ctr = h->redo_ctr.p; d.redo_list = h->redo_list.p; d.redo_scratch = h->redo_scratch.p;
-    d.roll_exact = k.roll_exact; d.dbg_redo_mod = k.force_redo;
+    d.roll_exact = k.roll_exact; d.dbg_redo_mod = k.force_redo; d.roll_free = k.roll_free;
   }
   d.tcls = h->tcls.p;
   d.cmapS = h->cmapS.p; d.amapS = h->amapS.p; d.zmapS = h->zmapS.p; d.cell_state = h->cell_state.p;

@@ -189,9 +189,13 @@ __device__ __forceinline__ void track(Acc &acc, double d) {
   asm("v_max_f32_dpp %0, %0, |%1| wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(acc.tr) : "v"(__double2hiint(d)));
 }
 
-template <int NR, int S, bool EXACT>
+// FREE (the library's kernel only): a step of a period whose finishing sweep is already known not to be the step's last
+// one -- the arithmetic is the same, but nothing is kept for an undo (no bk[]) and the plain steps measure nothing; the
+// window steps still feed the accumulators of the lanes that have started the next sweep (the next period's top test).
+template <int NR, int S, bool EXACT, bool FREE = false>
 __device__ __forceinline__ void step(double (&e)[NR], double (&bk)[kWin], d2 ud, d2 lr, double A,
                                      double sm, Acc &acc) {
+  static_assert(!FREE || (!EXACT && S >= kWin), "free periods: the library's kernel, after the ramp-up");
   constexpr int r = S % NR, rm = (S + NR - 1) % NR, rp = (S + 1) % NR;
   const double Dn = wave_shift1<0x130, true>(e[rp], sm);
   // the chain starts in a register of its own (early clobber): accumulated in place in A's
@@ -215,13 +219,13 @@ __device__ __forceinline__ void step(double (&e)[NR], double (&bk)[kWin], d2 ud,
     e[r] = sel;
   } else if constexpr (S < NR) {
     if constexpr (EXACT) acc.cur = fmax(acc.cur, fabs(nv - e[r]));
-    else track(acc, nv - e[r]);
+    else if constexpr (!FREE) track(acc, nv - e[r]);
     e[r] = nv;
   } else if constexpr (!EXACT) {
     constexpr int J = S - NR;
     track(acc, nv - e[r]);
 #ifndef SB_EXP_NOCOPY // timing experiment: the window keeps no copies
-    bk[J] = e[r];
+    if constexpr (!FREE) bk[J] = e[r];
 #endif
     e[r] = nv;
   } else {
@@ -289,7 +293,7 @@ constexpr int kDepth = SB_DEPTH;          // pairs between the LDS reads of a st
 constexpr int kBufs = kDepth + 1;         // NR / 2 pairs per period: kBufs must divide that (checked per instantiation in k_sweep_roll)
 constexpr int pair_buf(int S) { return ((S - 1) / 2) % kBufs; }
 
-template <int NR, int S, int S1, bool WRAP, bool EXACT, bool APASS, int NAR>
+template <int NR, int S, int S1, bool WRAP, bool EXACT, bool APASS, bool FREE, int NAR>
 __device__ __forceinline__ void roll_pairs(double (&e)[NR], double (&bk)[kWin], double (&Areg)[NAR],
                                            PairBuf (&pb)[kBufs], Ctx<NR> &x, Acc &acc, const APass<NR, NAR> &ap) {
   if constexpr (S < S1) {
@@ -309,17 +313,17 @@ __device__ __forceinline__ void roll_pairs(double (&e)[NR], double (&bk)[kWin], 
     if constexpr (APASS && j0 + 1 < NR) pa1 = ap.template fetch<j0 + 1 < NR ? j0 + 1 : 0>();
     if constexpr (APASS && j0 + 2 < NR) pa2 = ap.template fetch<j0 + 2 < NR ? j0 + 2 : 0>();
     __builtin_amdgcn_sched_barrier(0);
-    step<NR, S, EXACT>(e, bk, cur.ud0, cur.lr0, cur.A.x, cur.sm.x, acc);
+    step<NR, S, EXACT, FREE>(e, bk, cur.ud0, cur.lr0, cur.A.x, cur.sm.x, acc);
     __builtin_amdgcn_sched_barrier(0);
     load_second<NR, N + 1>(nxt, x);
     __builtin_amdgcn_sched_barrier(0);
-    step<NR, S + 1, EXACT>(e, bk, cur.ud1, cur.lr1, cur.A.y, cur.sm.y, acc);
+    step<NR, S + 1, EXACT, FREE>(e, bk, cur.ud1, cur.lr1, cur.A.y, cur.sm.y, acc);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (APASS && j0 < NR) ap.template put<j0 < NR ? j0 : 0>(pa0, e[j0 < NR ? j0 : 0]);
     if constexpr (APASS && j0 + 1 < NR) ap.template put<j0 + 1 < NR ? j0 + 1 : 0>(pa1, e[j0 + 1 < NR ? j0 + 1 : 0]);
     if constexpr (APASS && j0 + 2 < NR) ap.template put<j0 + 2 < NR ? j0 + 2 : 0>(pa2, e[j0 + 2 < NR ? j0 + 2 : 0]);
     if constexpr (APASS) __builtin_amdgcn_sched_barrier(0);
-    roll_pairs<NR, S + 2, S1, WRAP, EXACT, APASS>(e, bk, Areg, pb, x, acc, ap);
+    roll_pairs<NR, S + 2, S1, WRAP, EXACT, APASS, FREE>(e, bk, Areg, pb, x, acc, ap);
   }
 }
 
@@ -357,6 +361,21 @@ __device__ __forceinline__ void hand_over(double (&e)[NR], const double (&bk)[kW
     if constexpr ((J & 7) == 6) __builtin_amdgcn_sched_barrier(0);
     hand_over<NR, J + 2>(e, bk, zw, tp, np_, zrow);
   }
+}
+
+// After a period's last step: row 63's last column (lane 63's result of that step) enters its shift register; then both
+// registers are reversed: lane l holds columns 2 (l - L0), 2 (l - L0) + 1, the tail scan's layout.
+template <int NR>
+__device__ __forceinline__ void row63_to_tail(const double (&e)[NR], Acc &acc, int lane, double &U0, double &U1) {
+  constexpr int last = (NR + kWin - 1) % NR;
+  const double ul = wave_shift1<0x13c, false>(e[last], 0.0);
+  double &sr = (NR - 1) % 2 == 0 ? acc.sre : acc.sro;
+  sr = wave_shift1<0x138, true>(sr, ul);
+  const int rev = (63 - lane) * 4;
+  U0 = __hiloint2double(__builtin_amdgcn_ds_bpermute(rev, __double2hiint(acc.sre)),
+                        __builtin_amdgcn_ds_bpermute(rev, __double2loint(acc.sre)));
+  U1 = __hiloint2double(__builtin_amdgcn_ds_bpermute(rev, __double2hiint(acc.sro)),
+                        __builtin_amdgcn_ds_bpermute(rev, __double2loint(acc.sro)));
 }
 
 extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -573,7 +592,7 @@ __global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_e
         step<NR, 0, EXACT>(e, bk, ud, lr, x.Arow[1], 0.0, acc);
       }
       __builtin_amdgcn_sched_barrier(0);
-      roll_pairs<NR, 1, kWin, false, EXACT, true>(e, bk, Areg, pb, x, acc, ap); // ramp-up (+ A of the slots from kA0 on); reads ahead for the first pairs of the period
+      roll_pairs<NR, 1, kWin, false, EXACT, true, false>(e, bk, Areg, pb, x, acc, ap); // ramp-up (+ A of the slots from kA0 on); reads ahead for the first pairs of the period
 #ifndef SB_STAMP_NEXT
       SB_STAMP(15);
 #endif
@@ -594,23 +613,44 @@ __global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_e
 #else
 #define SB_STAMP2(i) do { } while (0)
 #endif
-        SB_STAMP2(10);
-        roll_pairs<NR, kWin, NR + kWin, true, EXACT, false>(e, bk, Areg, pb, x, acc, ap);
-        SB_STAMP2(11);
-        // row 63's last column (lane 63's result of the period's last step) enters its shift register;
-        // then both are reversed: lane l holds columns 2 (l - L0), 2 (l - L0) + 1, the tail scan's layout
-        double U0, U1;
-        {
-          constexpr int last = (NR + kWin - 1) % NR;
-          const double ul = wave_shift1<0x13c, false>(e[last], 0.0);
-          double &sr = (NR - 1) % 2 == 0 ? acc.sre : acc.sro;
-          sr = wave_shift1<0x138, true>(sr, ul);
-          const int rev = (63 - lane) * 4;
-          U0 = __hiloint2double(__builtin_amdgcn_ds_bpermute(rev, __double2hiint(acc.sre)),
-                                __builtin_amdgcn_ds_bpermute(rev, __double2loint(acc.sre)));
-          U1 = __hiloint2double(__builtin_amdgcn_ds_bpermute(rev, __double2hiint(acc.sro)),
-                                __builtin_amdgcn_ds_bpermute(rev, __double2loint(acc.sro)));
+        // Free periods.  Here the sweep in progress has finished its upper-left triangle (lane l: columns 0 .. 62 - l), and
+        // the travelling accumulators of lanes 0..62 hold exactly those columns' partial max |delta| of THAT sweep (lane
+        // 63's is 0: cleared below, or never fed during the ramp-up).  One of them above the threshold -- high words,
+        // strictly: equal words prove nothing -- and the sweep's full max |delta| is above it: simulator.py:360 goes on to
+        // the next sweep, so the period that finishes this sweep needs neither the window's copies nor a measurement.
+        // (A building's first sweep: the ring's |delta| proves the same.)  The iteration limit ends a step whatever
+        // max |delta| is: the sweep that reaches it runs as a measuring period, so a step always ends in one and the
+        // hand-over's restore sees that period's copies.  A zero-trip loop of free periods, then ONE measuring period: the
+        // two bodies in the arms of a branch make the register allocator spill (LABNOTES.md 5.2).
+        if constexpr (!EXACT) {
+          if (a.roll_free) {
+            const int thr_top = __double2hiint(p.conv_threshold);
+            int top = wave_max_i32(acc.tr);
+            if (n_sweeps == 0) top = max(top, __double2hiint(ring_d));
+#pragma nounroll
+            while (top > thr_top && n_sweeps + 1 < p.iter_limit) {
+              __builtin_amdgcn_sched_barrier(0);
+              roll_pairs<NR, kWin, NR + kWin, true, false, false, true>(e, bk, Areg, pb, x, acc, ap);
+              double F0, F1;
+              row63_to_tail<NR>(e, acc, lane, F0, F1);
+              tail_pass_static_values<NR>(a.T, tmul + opaque(tc0), tE0 + opaque(tcw), F0, F1, tv, tset, At);
+              pb[pair_buf(kWin)].sm = *(const d2 *)(x.seam + kWin);
+              if constexpr (kDepth > 1) pb[pair_buf(kWin + 2)].sm = *(const d2 *)(x.seam + kWin + 2);
+              ++n_sweeps;
+              // the plain steps did not move the finished sweep's accumulators: the window pushed them, mixed, through lane
+              // 63 -- what lane 63 holds and has collected is dropped; lanes 0..62 hold the started sweep's columns 62 - l
+              acc.fin = 0;
+              acc.tr = lanes_upto<62>() ? acc.tr : 0;
+              top = wave_max_i32(acc.tr);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
         }
+        SB_STAMP2(10);
+        roll_pairs<NR, kWin, NR + kWin, true, EXACT, false, false>(e, bk, Areg, pb, x, acc, ap);
+        SB_STAMP2(11);
+        double U0, U1;
+        row63_to_tail<NR>(e, acc, lane, U0, U1);
         SB_STAMP2(12);
         const double dt_ = tail_pass_static<NR>(a.T, tmul + opaque(tc0), tE0 + opaque(tcw), U0, U1, tv, tset, At); // tmul + 2 l'
 

@@ -150,10 +150,11 @@ __device__ __forceinline__ void scan_level(double &q, double A, double &qs) {
 // set, A = 0, cells 0) compute zeros; their tE0c points at the zero guards in front of the row.
 // (Tried: the second row's LDS reads issued before the first row's scan, so that their latency hides behind it --
 // 26 more registers live across the scan, and k_sweep_roll<96> has none to spare: scratch.)
-template <int NR>
-__device__ __forceinline__ double tail_pass_static(int T, const double *tm, double *tE0c, double U0, double U1,
-                                                   double (&tv)[kTailMax][2], const int (&tset)[kTailMax],
-                                                   const double (&At)[kTailMax][2]) {
+// MEASURE = false: the values only (k_sweep_roll's free periods: a sweep already known not to be the step's last one).
+template <int NR, bool MEASURE>
+__device__ __forceinline__ double tail_pass_static_impl(int T, const double *tm, double *tE0c, double U0, double U1,
+                                                        double (&tv)[kTailMax][2], const int (&tset)[kTailMax],
+                                                        const double (&At)[kTailMax][2]) {
   static_assert(NR % 2 == 0 && NR <= 128, "two columns per lane");
   constexpr int n = NR / 2;
   double dmax = 0.0;
@@ -181,7 +182,7 @@ __device__ __forceinline__ double tail_pass_static(int T, const double *tm, doub
       scan_level<0x143, 0xc>(Q, tm[4 * n * T + t], qs);
       const double xl = wave_shift1<0x138, false>(Q, 0.0);
       const double x0 = fma(lr0.x, xl, q0);
-      dmax = fmax(dmax, fmax(fabs(x0 - old0), fabs(Q - old1)));
+      if constexpr (MEASURE) dmax = fmax(dmax, fmax(fabs(x0 - old0), fabs(Q - old1)));
       tv[t][0] = x0;
       tv[t][1] = Q;
       if (t == 0) *(d2 *)tE0c = d2{x0, Q};
@@ -190,6 +191,18 @@ __device__ __forceinline__ double tail_pass_static(int T, const double *tm, doub
     }
   }
   return dmax;
+}
+template <int NR>
+__device__ __forceinline__ double tail_pass_static(int T, const double *tm, double *tE0c, double U0, double U1,
+                                                   double (&tv)[kTailMax][2], const int (&tset)[kTailMax],
+                                                   const double (&At)[kTailMax][2]) {
+  return tail_pass_static_impl<NR, true>(T, tm, tE0c, U0, U1, tv, tset, At);
+}
+template <int NR>
+__device__ __forceinline__ void tail_pass_static_values(int T, const double *tm, double *tE0c, double U0, double U1,
+                                                        double (&tv)[kTailMax][2], const int (&tset)[kTailMax],
+                                                        const double (&At)[kTailMax][2]) {
+  (void)tail_pass_static_impl<NR, false>(T, tm, tE0c, U0, U1, tv, tset, At);
 }
 
 } // namespace sweep
