@@ -201,7 +201,8 @@ typedef enum sb_sweep_kernel {
   SB_KERNEL_TWO_ROWS = 4, /* k_sweep_two: two rows per lane, 67..130 rows, sweeps overlapped in blocks (step_two.hip) */
   SB_KERNEL_BAND = 5,     /* k_sweep_band: two wavefronts, one row per lane, 67..130 rows, sweeps overlapped in blocks (step_band.hip) */
   SB_KERNEL_STREAM = 6,   /* k_sweep_stream: the grid stays in global memory, up to 16 wavefronts per building (step_stream.hip) */
-  SB_KERNEL_JACOBI = 7    /* k_sweep_jacobi: TFSimulator's float32 Jacobi update, not Gauss-Seidel (step_jacobi.hip; sb_create_jacobi) */
+  SB_KERNEL_JACOBI = 7    /* TFSimulator's float32 Jacobi update, not Gauss-Seidel (sb_create_jacobi): k_sweep_jacobi, both grids in LDS
+                           * (step_jacobi.hip, path 0), or k_sweep_jacobi_g, the grids in global memory (step_jacobi_global.hip, path 2) */
 } sb_sweep_kernel;
 
 /* Launch geometry chosen for the floor plan (reported for DESIGN.md / bench.py). */
@@ -209,8 +210,8 @@ typedef struct sb_launch_info {
   int32_t waves_per_workgroup, workgroups, lds_bytes_per_workgroup, sweep_steps; /* SB_KERNEL_ROLL: four wavefronts = four buildings per workgroup (they share the steps' class words in LDS) */
   int64_t algorithmic_bytes_per_env_step; /* 8HW+24Z+4A+4O+44 (fp32 state) */
   int64_t state_bytes_per_env_step;       /* what this build really moves: fp64 grid r+w */
-  int32_t path;               /* 1: grid in registers, 0: grid in LDS (step_lds.hip), 2: grid in global memory (step_stream.hip) */
-  int32_t waves_per_building; /* wavefronts that share one building (1, 2, or up to 16 on path 2) */
+  int32_t path;               /* 1: grid in registers, 0: grid in LDS (step_lds.hip), 2: grid in global memory (step_stream.hip; SB_KERNEL_JACOBI: step_jacobi_global.hip) */
+  int32_t waves_per_building; /* wavefronts that share one building (1, 2, or up to 16 on path 2 and on SB_KERNEL_JACOBI) */
   int32_t kernel;             /* sb_sweep_kernel: which sweep kernel owns this floor plan */
   int32_t reserved;
 } sb_launch_info;
@@ -493,11 +494,15 @@ typedef struct sb_jacobi_desc {
   const double *class_diffuser;  /* [n_classes] diffuser weight (building.py:873-889 input_q = q_zone * weight) */
   const int32_t *class_zone;     /* [n_classes] the zone whose VAV power feeds q, or -1 */
 } sb_jacobi_desc;
-/* A handle whose sweep kernel is k_sweep_jacobi (SB_KERNEL_JACOBI).  `plan` supplies H, W, the zones and their cells
- * (its class tables are not used); everything else is sb_create's.  The state is a float32 grid [B][H*W]: sb_reset
- * rounds temps_dev to float32 (the zone means and grid mean of the first step come from the float64 values, which the
- * reference reads before its first FD update rounds them); sb_get_temps widens it to float64.  SB_ERR_TOO_LARGE when two
- * float32 grids and the class table do not fit 160 KiB of LDS.  sb_set_temps, sb_state_save / sb_state_load and
+/* A handle whose sweep kernel is k_sweep_jacobi or, for plans beyond it, k_sweep_jacobi_g (both SB_KERNEL_JACOBI).
+ * `plan` supplies H, W, the zones and their cells (its class tables are not used); everything else is sb_create's.
+ * The state is a float32 grid [B][H*W]: sb_reset rounds temps_dev to float32 (the zone means and grid mean of the
+ * first step come from the float64 values, which the reference reads before its first FD update rounds them);
+ * sb_get_temps widens it to float64.  A plan whose two float32 grids and class table fit 160 KiB of LDS (at most
+ * 20,480 CVs) runs on k_sweep_jacobi (sb_launch_info.path 0), any other plan of up to 2^20 = 1,048,576 CVs on
+ * k_sweep_jacobi_g (path 2), with the same results bit for bit; SB_ERR_TOO_LARGE beyond that.  A path-2 handle also
+ * allocates about 12 B per CV for each of its resident workgroups (sb_launch_info.workgroups, at most 256 on an
+ * MI355X): 0.37 GB for 299 x 401, 3.2 GB at the limit.  sb_set_temps, sb_state_save / sb_state_load and
  * sb_convection_attach return SB_ERR_UNSUPPORTED on such a handle.  sb_step's info column 4 counts Jacobi iterations. */
 int sb_create_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, const sb_params *params,
                      const sb_obs_layout *obs, int32_t n_buildings, int32_t device, sb_handle **out);

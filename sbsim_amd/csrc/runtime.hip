@@ -343,7 +343,7 @@ int prepare_sweep(const sb_handle *h) {
       if (h->stream_variant == kStreamMs) return prepare_sweep_stream_ms(d, waves);
       if (h->stream_variant == kStreamRoll) return prepare_sweep_stream_roll(d, waves);
       return prepare_sweep_stream(d, waves);
-    case SB_KERNEL_JACOBI: return prepare_sweep_jacobi(d.H, d.W, d.ncls);
+    case SB_KERNEL_JACOBI: return prepare_sweep_jacobi(d.H, d.W, d.ncls, h->jac.path);
   }
   return (int)hipErrorInvalidValue;
 }

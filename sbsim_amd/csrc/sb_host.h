@@ -26,8 +26,10 @@ int prepare_sweep_stream_roll(const Dev &d, int waves);
 int sweep_stream_roll_xchg_extra_doubles();
 } // namespace sb
 
-// step_jacobi.hip: k_sweep_jacobi (SB_KERNEL_JACOBI), TFSimulator's float32 Jacobi update.  Its own arguments besides Dev:
-// Dev carries the step hand-over (Bld::t_now, gtabg, zsum, gsum, nsw, next_b) and the zones as for every sweep kernel.
+// step_jacobi.hip: k_sweep_jacobi (SB_KERNEL_JACOBI), TFSimulator's float32 Jacobi update, both grids in LDS;
+// step_jacobi_global.hip: k_sweep_jacobi_g, the same step with the grids in global memory, for plans LDS does not hold.
+// Their own arguments besides Dev: Dev carries the step hand-over (Bld::t_now, gtabg, zsum, gsum, nsw, next_b) and the
+// zones as for every sweep kernel.
 namespace sb {
 struct JacArgs {
   float *grid;         // [B][N] the float32 state, row-major in the caller's orientation
@@ -35,18 +37,33 @@ struct JacArgs {
   const float *tab;    // [ncls][SB_JACOBI_COEFS] sb_jacobi_desc.class_f32
   const double *rden;  // [ncls] 1.0 / (double)den, correctly rounded (host)
   int ncls;
-  int n_pad;           // floats per LDS grid buffer (sweep_jacobi_slots: the grid with its T_inf padding)
+  int n_pad;           // floats per padded grid buffer (sweep_jacobi_slots: the grid with its T_inf padding)
   int nb;              // buildings of this launch (B; sb_tap_jacobi: its n)
   const float *q;      // sb_tap_jacobi: [nb][N] input_q; NULL: q = (float)gtabg[class]
   const double *tinf;  // sb_tap_jacobi: [nb] T_inf; NULL: Bld::t_now
+  int path;            // sweep_jacobi_path's answer: 0 k_sweep_jacobi, 2 k_sweep_jacobi_g
+  int sum_threads;     // k_sweep_jacobi_g: sweep_jacobi_threads(N), the thread count whose order the float64 grid sum keeps
+  float *scratch;      // k_sweep_jacobi_g: [workgroups][sweep_jacobi_g_scratch_floats] two padded grids and (M*Tprev)/dt
 };
-bool sweep_jacobi_supported(int N);                // an instantiation holds N CVs (N <= 20,480)
-int sweep_jacobi_threads(int N);                   // threads per workgroup of that instantiation
-int sweep_jacobi_slots(int H, int W);              // floats of one LDS grid buffer
-size_t sweep_jacobi_lds_bytes(int H, int W, int ncls); // LDS per workgroup (dynamic + static)
-int prepare_sweep_jacobi(int H, int W, int ncls);
-int sweep_jacobi_blocks_per_cu(int H, int W, int ncls); // resident workgroups per CU (registers, LDS, waves); 0: unknown
+// The one rule (sb_launch_info.path): 0 -- k_sweep_jacobi holds the plan (N <= 20,480 and 160 KiB of LDS) and
+// force_global is not set; 2 -- k_sweep_jacobi_g; -1 -- neither (more than sweep_jacobi_g_max_cvs() CVs).  The functions
+// below that take a path dispatch on its answer.
+int sweep_jacobi_path(int H, int W, int ncls, bool force_global);
+int sweep_jacobi_threads(int N);                   // threads per workgroup of k_sweep_jacobi's instantiation for N CVs
+int sweep_jacobi_threads(int N, int path);         // ... of the kernel of that path
+int sweep_jacobi_slots(int H, int W);              // floats of one padded grid buffer
+size_t sweep_jacobi_lds_bytes(int H, int W, int ncls, int path); // LDS per workgroup (dynamic + static)
+int prepare_sweep_jacobi(int H, int W, int ncls, int path);
+int sweep_jacobi_blocks_per_cu(int H, int W, int ncls, int path); // resident workgroups per CU (registers, LDS, waves); 0: unknown
 int launch_sweep_jacobi(const Dev &d, const JacArgs &j, int workgroups, hipStream_t stream);
+// step_jacobi_global.hip
+bool sweep_jacobi_g_supported(int H, int W);
+int sweep_jacobi_g_max_cvs();
+int sweep_jacobi_g_threads();
+size_t sweep_jacobi_g_lds_bytes();
+size_t sweep_jacobi_g_scratch_floats(int H, int W); // per resident workgroup
+int sweep_jacobi_g_blocks_per_cu();
+int launch_sweep_jacobi_g(const Dev &d, const JacArgs &j, int workgroups, hipStream_t stream);
 } // namespace sb
 
 // SB_KERNEL_STREAM's variants (= Dev::stream_ms): k_sweep_stream; the experimental k_sweep_stream_ms, k_sweep_stream_roll
@@ -174,7 +191,7 @@ struct sb_handle {
   uint32_t occ_queries = 0;
   bool occ_attached = false;
   // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
-  DevBuf<float> jgrid, jtab;
+  DevBuf<float> jgrid, jtab, jscratch; // (jscratch: k_sweep_jacobi_g's per-workgroup grids)
   DevBuf<double> jrden;
   DevBuf<uint8_t> jcls;
   sb::JacArgs jac{};

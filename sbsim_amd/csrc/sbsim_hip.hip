@@ -48,6 +48,8 @@ double env_double(const char *name, double unset) {
 // change them between calls.
 struct Knobs {
   bool force_stream = env_flag("SBSIM_FORCE_STREAM_PATH");  // every plan on k_sweep_stream
+  bool force_jacobi_global = env_flag("SBSIM_FORCE_JACOBI_GLOBAL"); // sb_create_jacobi: every plan on k_sweep_jacobi_g
+  int jacobi_global_wgs = std::max(0, env_int("SBSIM_DEBUG_JACOBI_GLOBAL_WGS", 0)); // k_sweep_jacobi_g: at most this many workgroups (0: what is resident)
   bool force_lds = env_flag("SBSIM_FORCE_LDS_PATH");        // no register kernel: the LDS-grid kernel (else streaming)
   bool band_path = env_flag("SBSIM_BAND_PATH");             // 67..130 rows: k_sweep_band before k_sweep_two
   bool no_two_row = env_flag("SBSIM_NO_TWO_ROW_PATH");      // no k_sweep_two
@@ -1341,17 +1343,20 @@ int sb_create(const sb_plan_desc *plan, const sb_params *params, const sb_obs_la
 
 int sb_create_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, const sb_params *params,
                      const sb_obs_layout *obs, int32_t n_buildings, int32_t device, sb_handle **out) {
+  const Knobs k;
   if (!plan || !jac || !params || !obs || !out) return fail(SB_ERR_INVALID, "sb_create_jacobi: null argument");
   std::vector<double> coef;
   sb_plan_desc jp;
   SB_CHECK(check_jacobi(plan, jac, coef, jp));
   ActionTable acts;
   SB_CHECK(check_create_args(&jp, params, obs, n_buildings, acts));
-  const int N = jp.H * jp.W, ncls = jp.n_classes;
-  const size_t lds = sweep_jacobi_lds_bytes(jp.H, jp.W, ncls);
-  if (!sweep_jacobi_supported(N) || lds > (size_t)kLdsCap)
-    return fail(SB_ERR_TOO_LARGE, "k_sweep_jacobi: two float32 grids of " + std::to_string(N) +
-                                      " CVs and the class table do not fit 160 KiB of LDS");
+  const int ncls = jp.n_classes;
+  const int path = sweep_jacobi_path(jp.H, jp.W, ncls, k.force_jacobi_global); // 0: k_sweep_jacobi, 2: k_sweep_jacobi_g
+  if (path < 0)
+    return fail(SB_ERR_TOO_LARGE, "sb_create_jacobi: " + std::to_string((long long)jp.H * jp.W) + " CVs; k_sweep_jacobi_g takes at most " +
+                                      std::to_string(sweep_jacobi_g_max_cvs()) + " (k_sweep_jacobi: 20480 CVs in 160 KiB of LDS)");
+  const int N = jp.H * jp.W;
+  const size_t lds = sweep_jacobi_lds_bytes(jp.H, jp.W, ncls, path);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(SB_ERR_NO_DEVICE, "sb_create_jacobi: no HIP device visible (this library has no CPU path)");
@@ -1373,14 +1378,15 @@ int sb_create_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, const 
   d.reg = 0; d.P = SB_KERNEL_JACOBI;
   { // launch geometry: the workgroups resident at once (the runtime's occupancy for this instantiation: registers, LDS,
     // wavefronts), one building each at a time; more would only start after others retire
-    const int threads = sweep_jacobi_threads(N);
-    const int occ = sweep_jacobi_blocks_per_cu(jp.H, jp.W, ncls);
+    const int threads = sweep_jacobi_threads(N, path);
+    const int occ = sweep_jacobi_blocks_per_cu(jp.H, jp.W, ncls, path);
     const int per_cu = std::max(1, occ > 0 ? occ : std::min((int)((size_t)kLdsCap / lds), 32 / (threads / 64)));
     sb_launch_info &li = h->info;
     li.kernel = SB_KERNEL_JACOBI;
-    li.path = 0;
+    li.path = path;
     li.waves_per_building = li.waves_per_workgroup = threads / 64;
     li.workgroups = std::max(1, std::min(n_buildings, h->cus * per_cu));
+    if (path == 2 && k.jacobi_global_wgs > 0) li.workgroups = std::min(li.workgroups, k.jacobi_global_wgs);
     li.lds_bytes_per_workgroup = (int32_t)lds;
     li.sweep_steps = 1; // (no wavefront schedule: every CV of an iteration at once)
     li.algorithmic_bytes_per_env_step = 8ll * N + 24ll * d.Z + 4ll * params->n_actions + 4ll * obs->n_obs + 44;
@@ -1397,7 +1403,10 @@ int sb_create_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, const 
   SB_CHECK(upload(h->jtab, jac->class_f32, (size_t)ncls * SB_JACOBI_COEFS));
   SB_CHECK(upload(h->jrden, rden.data(), rden.size()));
   SB_CHECK(alloc_zero(h->jgrid, (size_t)d.B * N));
-  h->jac = JacArgs{h->jgrid.p, h->jcls.p, h->jtab.p, h->jrden.p, ncls, sweep_jacobi_slots(jp.H, jp.W), d.B, nullptr, nullptr};
+  if (path == 2) // k_sweep_jacobi_g: two padded grids and (M*Tprev)/dt per resident workgroup (not zeroed: every slot is written before it is read)
+    SB_HIP(hipMalloc((void **)&h->jscratch.p, (size_t)h->info.workgroups * sweep_jacobi_g_scratch_floats(jp.H, jp.W) * sizeof(float)));
+  h->jac = JacArgs{h->jgrid.p, h->jcls.p, h->jtab.p, h->jrden.p, ncls, sweep_jacobi_slots(jp.H, jp.W), d.B, nullptr, nullptr,
+                   path, sweep_jacobi_threads(N), h->jscratch.p};
   SB_CHECK(prepare_and_reset(h.get()));
   *out = h.release();
   return SB_OK;

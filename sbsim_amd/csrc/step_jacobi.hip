@@ -201,34 +201,43 @@ size_t dyn_bytes(int H, int W, int ncls) { return (size_t)2 * jac_slots(H, W) * 
 
 } // namespace
 
-bool sweep_jacobi_supported(int N) { return N >= 1 && N <= kMaxN; }
+int sweep_jacobi_path(int H, int W, int ncls, bool force_global) {
+  const long long N = (long long)H * W;
+  if (!force_global && N >= 1 && N <= kMaxN && sweep_jacobi_lds_bytes(H, W, ncls, 0) <= (size_t)160 * 1024) return 0;
+  return sweep_jacobi_g_supported(H, W) ? 2 : -1;
+}
 
 int sweep_jacobi_threads(int N) { return N <= C2::cells ? C2::threads : C3::threads; }
+int sweep_jacobi_threads(int N, int path) { return path == 2 ? sweep_jacobi_g_threads() : sweep_jacobi_threads(N); }
 
 int sweep_jacobi_slots(int H, int W) { return jac_slots(H, W); }
 
-size_t sweep_jacobi_lds_bytes(int H, int W, int ncls) {
+size_t sweep_jacobi_lds_bytes(int H, int W, int ncls, int path) {
+  if (path == 2) return sweep_jacobi_g_lds_bytes();
   const int nw = sweep_jacobi_threads(H * W) / 64;
   return dyn_bytes(H, W, ncls) + (size_t)nw * (2 * sizeof(float) + sizeof(double)) + sizeof(int);
 }
 
-int sweep_jacobi_blocks_per_cu(int H, int W, int ncls) {
+int sweep_jacobi_blocks_per_cu(int H, int W, int ncls, int path) {
+  if (path == 2) return sweep_jacobi_g_blocks_per_cu();
   const int N = H * W;
   const void *fn = N <= C0::cells ? C0::fn() : N <= C1::cells ? C1::fn() : N <= C2::cells ? C2::fn() : C3::fn();
   int n = 0;
-  if (prepare_sweep_jacobi(H, W, ncls) != (int)hipSuccess ||
+  if (prepare_sweep_jacobi(H, W, ncls, path) != (int)hipSuccess ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, sweep_jacobi_threads(N), dyn_bytes(H, W, ncls)) != hipSuccess)
     return 0;
   return n;
 }
 
-int prepare_sweep_jacobi(int H, int W, int ncls) {
+int prepare_sweep_jacobi(int H, int W, int ncls, int path) {
+  if (path == 2) return (int)hipSuccess;        // (static LDS alone)
   const int N = H * W, bytes = (int)dyn_bytes(H, W, ncls);
   const void *fn = N <= C0::cells ? C0::fn() : N <= C1::cells ? C1::fn() : N <= C2::cells ? C2::fn() : C3::fn();
   return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
 int launch_sweep_jacobi(const Dev &d, const JacArgs &j, int workgroups, hipStream_t stream) {
+  if (j.path == 2) return launch_sweep_jacobi_g(d, j, workgroups, stream);
   const size_t lds = dyn_bytes(d.H, d.W, j.ncls);
   const int wgs = std::max(1, std::min(workgroups, j.nb));
   if (d.N <= C0::cells) C0::launch(d, j, wgs, lds, stream);

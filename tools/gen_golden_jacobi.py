@@ -20,6 +20,10 @@ Fixtures:
   jacobi_h1_r9_test.npz, jacobi_h2_sb1_r9_random.npz
                       (c) a 288-step thermostat-only rollout on r9_test and a seeded random-action rollout on SB1 R9
                       (oracle/gen_golden.py's harnesses with TFSimulator in place of SimulatorFlexibleGeometries)
+  jacobi_fd_large.npz (``--large``: writes this fixture alone) finite_differences_timestep on the 155 x 155 plan
+                      rectangular_floor_plan((6, 5), (24, 29)) with SB1's materials, beyond what k_sweep_jacobi holds in
+                      LDS: per seeded case and iteration limit the grid, iterations, converged.  The plan, Tprev, the
+                      zone powers and T_inf are not stored: large_case() regenerates them from the stored seeds.
 """
 from __future__ import annotations
 
@@ -131,9 +135,59 @@ def tensors_of(tfs, sim, b, h, t_amb):
               exterior=np.asarray(sim._t_exerior_temps_mask, bool))
 
 
+LARGE_ROOMS, LARGE_ROOM_SHAPE = (6, 5), (24, 29)   # 155 x 155 = 24,025 CVs, 30 zones
+LARGE_SEEDS, LARGE_LIMITS = (20261016, 20261017), (100, 2)
+
+
+def large_case(seed: int, shape, n_zones: int):
+  """(Tprev float32, zone powers, T_inf) of one seeded case of jacobi_fd_large.npz (tests/test_jacobi_large_*.py draw
+  the same)."""
+  rs = np.random.RandomState(seed)
+  prev = (285.0 + 12.0 * rs.rand(*shape)).astype(f32)
+  qz = rs.uniform(-4000.0, 4000.0, n_zones)
+  return prev, qz, float(rs.uniform(265.0, 305.0))
+
+
+def main_large() -> None:
+  from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
+  from tests import jacobi_restatement as jr
+  tfs = load_tf_simulator()
+  m = gg._mods()
+  tfm = dict(m, simulator_flexible_floor_plan=types.SimpleNamespace(SimulatorFlexibleGeometries=tfs.TFSimulator))
+  file_plan = rectangular_floor_plan(LARGE_ROOMS, LARGE_ROOM_SHAPE)
+  sim, b, *_ = gg.build_sb1(tfm, np.asarray(file_plan), pd.Timestamp("2012-12-21"))
+  fp = FloorPlan.from_file_input(file_plan, Materials.sb1(), gg.SB1["cv_size_cm"], gg.SB1["floor_height_cm"])
+  H, W = b.temp.shape
+  assert (H, W) == fp.shape
+  out = {"numpy_version": np.array(np.__version__), "h": 100.0, "dt": 300.0, "thr": 0.1,
+         "rooms": np.array(LARGE_ROOMS), "room_shape": np.array(LARGE_ROOM_SHAPE), "seeds": np.array(LARGE_SEEDS),
+         "limits": np.array(LARGE_LIMITS), "cv_size_cm": gg.SB1["cv_size_cm"], "floor_height_cm": gg.SB1["floor_height_cm"]}
+  for seed in LARGE_SEEDS:
+    prev, qz, t_amb = large_case(seed, (H, W), fp.n_zones)
+    for limit in LARGE_LIMITS:
+      sim._iteration_limit = limit
+      b.temp = prev.astype(np.float64)
+      b.input_q = np.zeros((H, W))
+      for z, name in enumerate(fp.zone_names):
+        b.apply_thermal_power_zone(name, float(qz[z]))
+      # what a test regenerates is what the reference saw
+      assert np.array_equal(jr.input_q(fp, qz), b.input_q.astype(f32))
+      counter = gg.SweepCounter(sim)
+      conv = sim.finite_differences_timestep(ambient_temperature=t_amb, convection_coefficient=100.0)
+      key = f"{seed}_{limit}"
+      out[key + "_grid"] = np.asarray(b.temp, f32)
+      out[key + "_iterations"] = counter.take()
+      out[key + "_converged"] = bool(conv)
+      print(f"  {key}: {out[key + '_iterations']} iterations, converged={conv}")
+  np.savez_compressed(os.path.join(OUT, "jacobi_fd_large.npz"), **out)
+
+
 def main() -> None:
   if not refshim.available():
     print("reference tree not present; nothing to do")
+    return
+  if "--large" in sys.argv[1:]:
+    main_large()
     return
   tfs = load_tf_simulator()
   m = gg._mods()
