@@ -50,6 +50,7 @@ struct Knobs {
   bool force_stream = env_flag("SBSIM_FORCE_STREAM_PATH");  // every plan on k_sweep_stream
   bool force_jacobi_global = env_flag("SBSIM_FORCE_JACOBI_GLOBAL"); // sb_create_jacobi: every plan on k_sweep_jacobi_g
   int jacobi_global_wgs = std::max(0, env_int("SBSIM_DEBUG_JACOBI_GLOBAL_WGS", 0)); // k_sweep_jacobi_g: at most this many workgroups (0: what is resident)
+  int debug_cus = std::max(0, env_int("SBSIM_DEBUG_CUS", 0)); // launch geometry as on a device of at most this many CUs (0: the device's own; speed only)
   bool force_lds = env_flag("SBSIM_FORCE_LDS_PATH");        // no register kernel: the LDS-grid kernel (else streaming)
   bool band_path = env_flag("SBSIM_BAND_PATH");             // 67..130 rows: k_sweep_band before k_sweep_two
   bool no_two_row = env_flag("SBSIM_NO_TWO_ROW_PATH");      // no k_sweep_two
@@ -75,6 +76,10 @@ struct Knobs {
   bool stream_ms = kExperimental && env_flag("SBSIM_STREAM_MS");     // streaming plans on k_sweep_stream_ms
   bool stream_roll = kExperimental && env_flag("SBSIM_STREAM_ROLL"); // ... on k_sweep_stream_roll
 };
+
+// SBSIM_DEBUG_CUS=n: every per-workgroup buffer and every grid of a handle is sized from sb_handle::cus or from
+// sb_launch_info::workgroups, so a smaller count makes the persistent kernels' workgroups draw more buildings each.
+int capped_cus(int cus, const Knobs &k) { return k.debug_cus > 0 ? std::min(cus, k.debug_cus) : cus; }
 
 constexpr int kGuardHost = 16; // must match kGuard in step_lds.hip
 
@@ -1295,7 +1300,7 @@ int sb_plan_info(const sb_plan_desc *plan, int32_t n_obs, int32_t n_buildings, s
   const LdsPlan q = plan_lds(plan);
   rc = choose_kernel(plan, q, k, r);
   if (rc != SB_OK) return rc;
-  fill_launch_info(plan, r, q, n_obs, 256, std::max(n_buildings, 1), out);
+  fill_launch_info(plan, r, q, n_obs, capped_cus(256, k), std::max(n_buildings, 1), out);
   return SB_OK;
 }
 
@@ -1319,7 +1324,7 @@ int sb_create(const sb_plan_desc *plan, const sb_params *params, const sb_obs_la
 
   auto h = std::make_unique<sb_handle>(); // (declared after the device guard: an early return frees it on the device)
   h->device = device;
-  h->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  h->cus = capped_cus(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256, k);
   Dev &d = h->d;
   d.B = n_buildings; d.H = plan->H; d.W = plan->W; d.Z = plan->Z;
   d.N = plan->H * plan->W;
@@ -1367,7 +1372,7 @@ int sb_create_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, const 
 
   auto h = std::make_unique<sb_handle>();
   h->device = device;
-  h->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  h->cus = capped_cus(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256, k);
   h->kernel = SB_KERNEL_JACOBI;
   Dev &d = h->d;
   d.B = n_buildings; d.H = jp.H; d.W = jp.W; d.Z = jp.Z;

@@ -862,11 +862,14 @@ def _need_experimental_kernels(variant, monkeypatch):
 
 def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatch, expect_steps=None,
                                iteration_limit=None, expect_kernel=None, B=6, T=14, expect_waves=None,
-                               init=None, acts=None, cfg=None):
+                               init=None, acts=None, cfg=None, env=None, buildings=None, on_launch=None):
   """Every building against its oracle twin at every step.  `file_plan` may be a FloorPlan; `init` [B, H*W], `acts`
-  [T, B, 2] and `cfg` replace the seeded initial grids, actions and SimConfig.sb1().  Returns the info rows and the
-  grids after every step."""
+  [T, B, 2] and `cfg` replace the seeded initial grids, actions and SimConfig.sb1(); `env` sets developer switches;
+  `buildings` names the buildings that get a twin (default: every one); `on_launch` is called with the launch_info.
+  Returns the info rows and the grids after every step."""
   _need_gpu()
+  for k, v in dict(env or {}).items():
+    monkeypatch.setenv(k, v)
   g = load("h2_sb1_r9_random.npz")
   plan = file_plan if isinstance(file_plan, FloorPlan) else FloorPlan.from_file_input(file_plan, Materials.sb1(), 10.0, 300.0)
   H, W = plan.shape
@@ -894,8 +897,11 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
     assert sim.launch_info["kernel"] == expect_kernel
   if expect_waves is not None:
     assert sim.launch_info["waves_per_building"] == expect_waves
+  if on_launch is not None:
+    on_launch(sim.launch_info)
   sim.reset(temps=torch.tensor(init, dtype=torch.float64, device="cuda"))
-  twins = [_oracle_twin(plan, cfg, init[b]) for b in range(B)]
+  checked = list(range(B)) if buildings is None else [int(b) for b in buildings]
+  twins = {b: _oracle_twin(plan, cfg, init[b]) for b in checked}
   obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
   rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
   info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
@@ -909,7 +915,7 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
     r = rew.cpu().numpy()
     infos.append(i)
     grids.append(sim.temps().cpu().numpy())
-    for b in range(B):
+    for b in checked:
       a = acts[t, b]
       native = [np.float32((float(a[0]) + 1.0) / 2.0 * (lo[1] - lo[0]) + lo[0]),
                 np.float32((float(a[1]) + 1.0) / 2.0 * (hi[1] - hi[0]) + hi[0])]
@@ -927,7 +933,7 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
       assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b)
       assert abs(float(r[b]) - o["reward"]) < 2e-6, (t, b)
   grid = sim.temps().cpu().numpy()
-  for b in range(B):
+  for b in checked:
     assert np.abs(grid[b] - twins[b].grid()).max() < T_TOL, b
   sim.close()
   return infos, grids
