@@ -259,7 +259,9 @@ int sb_observe_occupancy(sb_handle *h, const float aux[SB_NUM_AUX], double t_amb
  * (proto/smart_control_reward.proto:124-181; setpoint_energy_carbon_regret.py:239-291):
  * productivity_reward, electricity_energy_cost, natural_gas_energy_cost, carbon_emitted,
  * carbon_cost (0), the three weights, person_productivity, total_occupancy, reward_scale (1),
- * reward_shift (0), productivity_regret, normalized productivity regret / energy cost / carbon}. */
+ * reward_shift (0), productivity_regret, normalized productivity regret / energy cost / carbon}.
+ * That is the default reward function (SB_REWARD_REGRET); sb_set_reward_function documents columns 7..23 under the
+ * other one. */
 int sb_step(sb_handle *h, const float *actions_dev, const sb_step_in *in, float *obs_dev,
             float *reward_dev, float *info_dev, void *stream);
 
@@ -536,6 +538,39 @@ int sb_tap_jacobi(sb_handle *h, int32_t n, const float *tprev, const float *q, c
  * returns: it must not be called while the stream is being captured into a graph (SB_ERR_INVALID). */
 int sb_set_building_params(sb_handle *h, int32_t n_fields, const int32_t *fields,
                            const double *values /* HOST [n_fields][B] */, void *stream);
+
+/* The reward function k_post computes (the reference ships two under smart_control/reward/).
+ *   SB_REWARD_REGRET                  SetpointEnergyCarbonRegretFunction (setpoint_energy_carbon_regret.py:142-291), the
+ *                                     default: sb_params' min_prod, max_elec, max_gas and w_* are its arguments.
+ *   SB_REWARD_SETPOINT_ENERGY_CARBON  SetpointEnergyCarbonRewardFunction (setpoint_energy_carbon_reward.py:127-190), the
+ *                                     absolute reward in dollars on the same fp32 RewardInfo fields:
+ *       productivity = sum over zones of prod(zone temperature) * occupancy * dt / 3600   (no floor at min_prod)
+ *       electricity  = (blower + |air conditioning|) + pump,   gas = the boiler's rate     (no cap at max_elec / max_gas)
+ *       cost, carbon = price * rate * dt with the step's e_* / g_* rates (sb_step_in), |rate| for electricity and a
+ *                      negative gas rate read as 0, as the reference's ElectricityEnergyCost / NaturalGasEnergyCost do
+ *       carbon_cost  = (float)((electricity carbon + gas carbon) * carbon_cost_factor)     (the proto's float field)
+ *       raw          = productivity - energy_cost_weight * (electricity cost + gas cost) - carbon_cost_weight * carbon_cost
+ *       reward       = (raw - normalizer_shift) / normalizer_scale
+ *     It reads sb_params' (or the building's row of) max_prod, prod_delta, prod_stiff and the setpoint windows, and
+ *     ignores min_prod, max_elec, max_gas and w_prod / w_cost / w_carbon.
+ * sb_step's info columns 7..23 under it: the reward before the fp32 store, productivity_reward, electricity_energy_cost,
+ * natural_gas_energy_cost, carbon_emitted, carbon_cost; columns 13..23 are 0 (the RewardResponse fields this reward
+ * function leaves at the proto's default, reward_scale and reward_shift among them).  Columns 0..6 do not depend on
+ * the kind. */
+enum sb_reward_kind { SB_REWARD_REGRET = 0, SB_REWARD_SETPOINT_ENERGY_CARBON = 1 };
+typedef struct sb_reward_config {
+  int32_t kind; /* sb_reward_kind */
+  double energy_cost_weight, carbon_cost_weight; /* u, w */
+  double carbon_cost_factor;                     /* USD per kg of carbon emitted */
+  double normalizer_shift, normalizer_scale;
+} sb_reward_config;
+/* Selects the handle's reward function from the next step on (sb_step, sb_step_phases with SB_PHASE_POST, sb_tap_post),
+ * for every building and on every handle kind (sb_create, sb_create_jacobi: one k_post).  cfg == NULL or kind ==
+ * SB_REWARD_REGRET restores the default, whose results do not depend on a kind having been set in between.  A host
+ * value of the handle: nothing is uploaded or synchronised; steps already queued keep the kind they were launched
+ * with.  Not state: sb_state_save / sb_state_load do not carry it.  SB_ERR_INVALID, the handle unchanged: an unknown
+ * kind, a non-finite field, normalizer_scale == 0 (kind 1 only: the default ignores the other fields). */
+int sb_set_reward_function(sb_handle *h, const sb_reward_config *cfg);
 
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */

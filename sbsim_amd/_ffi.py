@@ -123,6 +123,14 @@ class StateClock(C.Structure):   # sb_state_clock
               ("was_reset", C.c_int32)]
 
 
+SB_REWARD_REGRET, SB_REWARD_SETPOINT_ENERGY_CARBON = 0, 1   # sb_reward_kind
+
+
+class RewardConfig(C.Structure):   # sb_reward_config
+  _fields_ = [("kind", C.c_int32), ("energy_cost_weight", C.c_double), ("carbon_cost_weight", C.c_double),
+              ("carbon_cost_factor", C.c_double), ("normalizer_shift", C.c_double), ("normalizer_scale", C.c_double)]
+
+
 SB_JACOBI_COEFS = 16   # floats per class row of sb_jacobi_desc.class_f32
 
 
@@ -143,11 +151,13 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_floorplan_padded_shape", "sb_floorplan_preprocess", "sb_floorplan_diffusers", "sb_debug_numpy_choice", "sb_pb_reward_info", "sb_pb_reward_response",
            "sb_pb_observation_response", "sb_pb_action_response", "sb_shard_append", "sb_pb_device_info",
            "sb_pb_zone_info", "sb_pb_variable_info", "sb_record_append", "sb_tap_pre", "sb_tap_post",
-           "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi", "sb_set_building_params")
+           "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi", "sb_set_building_params",
+           "sb_set_reward_function")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
 BUILDING_PARAM_ENTRIES = ("sb_set_building_params",)
+REWARD_ENTRIES = ("sb_set_reward_function",)
 
 _lib = None
 
@@ -230,6 +240,8 @@ def load():
     L.sb_tap_jacobi.argtypes = [vp, C.c_int32, _fp, _fp, _dp, _fp, _ip, _ip]
   if all(hasattr(L, name) for name in BUILDING_PARAM_ENTRIES):
     L.sb_set_building_params.argtypes = [vp, C.c_int32, vp, vp, vp]
+  if all(hasattr(L, name) for name in REWARD_ENTRIES):
+    L.sb_set_reward_function.argtypes = [vp, C.POINTER(RewardConfig)]
   _lib = L
   return L
 
@@ -250,6 +262,11 @@ def state_entry(name: str):
 
 def jacobi_entry(name: str):
   """The Jacobi-solver entry `name` (sb_create_jacobi, sb_tap_jacobi): see entry()."""
+  return entry(name)
+
+
+def reward_entry(name: str):
+  """The reward-function entry `name` (sb_set_reward_function): see entry()."""
   return entry(name)
 
 

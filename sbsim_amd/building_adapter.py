@@ -189,12 +189,13 @@ class HipSimulatorBuilding:
                device: int = 0, weather=None, occupancy=None, start_timestamp=dt.datetime(2023, 7, 6, 7, 0, 0),
                holiday_calendar="us", agent_id: str = "", scenario_id: str = "",
                air_handler_id: str = "air_handler_id", boiler_id: str = "boiler_id",
-               convection_simulator=None, reproducible_convection: bool = False):
+               convection_simulator=None, reproducible_convection: bool = False, reward_function=None):
     """convection_simulator: host_inputs.StochasticConvectionSimulator(p, distance, seed) -- the shuffle after every
     finite-difference update (simulator_flexible_floor_plan.py:71, 156).  By default it runs on the device
     (statistically the reference's process); reproducible_convection=True (one building only) runs the
     reference's seeded shuffle on the host instead, draw for draw (host_convection.py): the temperature array
-    is then bit-identical to the reference's for the same seed."""
+    is then bit-identical to the reference's for the same seed.
+    reward_function: BatchedEnvironment's (None: the regret function; host_inputs.SetpointEnergyCarbonReward)."""
     self.config = config or SimConfig.sb1()
     self._host_convection = None
     if convection_simulator is not None and reproducible_convection:
@@ -209,7 +210,7 @@ class HipSimulatorBuilding:
     self.env = BatchedEnvironment(plan, n_replicas, config=self.config, weather=weather, occupancy=occupancy,
                                   start_timestamp=start_timestamp, device=device, observation_normalization=None,
                                   holiday_calendar=holiday_calendar, collect_info=True,
-                                  convection_simulator=convection_simulator)
+                                  convection_simulator=convection_simulator, reward_function=reward_function)
     if self.env._occ_count is not None:
       raise ValueError("HipSimulatorBuilding takes a host-side occupancy model (one building)")
     sim = self.env.sim

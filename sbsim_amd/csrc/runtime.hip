@@ -320,12 +320,21 @@ __global__ void __launch_bounds__(16 * kRowsPerBlock) k_pre(Dev a, StepArgs s, i
   for (int b = blockIdx.x * kRowsPerBlock + r; b < a.B; b += gridDim.x * kRowsPerBlock) pre_building(a, s, b, i);
 }
 
-__global__ void __launch_bounds__(64) k_post(Dev a, StepArgs s, int only) { // one thread per building: see sb_device.h
+template <int KIND> // the reward function (sb_reward_kind): a kernel per kind, see post_building
+__global__ void __launch_bounds__(64) k_post(Dev a, StepArgs s, sb_reward_config rc, int only) { // one thread per building: see sb_device.h
   if (only >= 0) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) post_building(a, s, only);
+    if (blockIdx.x == 0 && threadIdx.x == 0) post_building<KIND>(a, s, rc, only);
     return;
   }
-  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) post_building(a, s, b);
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) post_building<KIND>(a, s, rc, b);
+}
+
+// k_post of the handle's reward function (sb_set_reward_function); only >= 0: that building alone
+void launch_post(const sb_handle *h, const StepArgs &s, dim3 grid, hipStream_t stream, int only) {
+  if (h->reward.kind == SB_REWARD_SETPOINT_ENERGY_CARBON)
+    hipLaunchKernelGGL(k_post<SB_REWARD_SETPOINT_ENERGY_CARBON>, grid, dim3(64), 0, stream, h->d, s, h->reward, only);
+  else
+    hipLaunchKernelGGL(k_post<SB_REWARD_REGRET>, grid, dim3(64), 0, stream, h->d, s, h->reward, only);
 }
 
 } // namespace
@@ -462,7 +471,7 @@ int sb_step_phases(sb_handle *h, const float *actions_dev, const sb_step_in *in,
       const int rc = sb_launch_convection(h, (hipStream_t)stream); // k_post do not change (values move inside rooms)
       if (rc != SB_OK) return rc;
     }
-    hipLaunchKernelGGL(k_post, dim3(std::max(1, std::min((d.B + 63) / 64, h->cus * 16))), dim3(64), 0, (hipStream_t)stream, d, s, -1);
+    launch_post(h, s, dim3(std::max(1, std::min((d.B + 63) / 64, h->cus * 16))), (hipStream_t)stream, -1);
     ++h->steps_since_reset;
     SB_HIP(hipGetLastError());
   }
@@ -647,6 +656,27 @@ int sb_set_building_params(sb_handle *h, int32_t n_fields, const int32_t *fields
   return SB_OK;
 }
 
+/* ---- the reward function ---- */
+int sb_set_reward_function(sb_handle *h, const sb_reward_config *cfg) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_set_reward_function: null handle");
+  if (!cfg || cfg->kind == SB_REWARD_REGRET) { // the default: sb_params' (or the buildings' rows of) regret arguments
+    h->reward = sb_reward_config{};
+    return SB_OK;
+  }
+  if (cfg->kind != SB_REWARD_SETPOINT_ENERGY_CARBON)
+    return fail(SB_ERR_INVALID, "sb_set_reward_function: unknown kind " + std::to_string(cfg->kind));
+  const struct { const char *name; double v; } fields[] = {
+      {"energy_cost_weight", cfg->energy_cost_weight}, {"carbon_cost_weight", cfg->carbon_cost_weight},
+      {"carbon_cost_factor", cfg->carbon_cost_factor}, {"normalizer_shift", cfg->normalizer_shift},
+      {"normalizer_scale", cfg->normalizer_scale}};
+  for (const auto &f : fields)
+    if (!std::isfinite(f.v)) return fail(SB_ERR_INVALID, std::string("sb_set_reward_function: ") + f.name + " is not finite");
+  if (cfg->normalizer_scale == 0.0)
+    return fail(SB_ERR_INVALID, "sb_set_reward_function: normalizer_scale must not be 0 (the reward divides by it)");
+  h->reward = *cfg;
+  return SB_OK;
+}
+
 /* ---- known-answer taps: k_pre / k_post on prescribed state of one building ---- */
 int sb_tap_pre(sb_handle *h, int32_t building, const double *zone_temps, const int32_t *modes,
                const double *scalars, const float *actions, const sb_step_in *in, sb_tap_bld *bld,
@@ -717,7 +747,7 @@ int sb_tap_post(sb_handle *h, int32_t building, const sb_tap_bld *bld, const dou
   if (rc != SB_OK) return rc;
   StepArgs s{};
   s.reward = rew.p; s.info = inf.p; s.in = *in;
-  hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, nullptr, d, s, building); // this building alone
+  launch_post(h, s, dim3(1), nullptr, building); // this building alone, under the handle's reward function
   SB_HIP(hipGetLastError());
   SB_HIP(hipDeviceSynchronize());
   SB_HIP(hipMemcpy(reward, rew.p + building, sizeof(float), hipMemcpyDeviceToHost));

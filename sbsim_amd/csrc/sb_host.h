@@ -150,6 +150,7 @@ struct sb_handle {
   int steps_since_reset = 0; // how far a reset rewinds the clock (the boiler's action age, scal[19])
   void *counters_zeroed_on = (void *)(uintptr_t)1; // the stream on which k_pre has zeroed the sweep kernel's draw counters since the last sweep launch (1: none)
   sb_launch_info info{};
+  sb_reward_config reward{};  // sb_set_reward_function: which k_post runs (kind 0: the regret, the default) and its constants
   DevBuf<uint8_t> cls, tcls, tcset;
   DevBuf<double> abuf; // step_stream.hip: A = ap*Tprev + g of the buildings in flight
   DevBuf<double> ebuf; // step_stream_ms.hip: the scratch grid a pass writes when it reads the building's state (per resident workgroup)

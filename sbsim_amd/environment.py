@@ -349,6 +349,7 @@ class BatchedSimulator:
     self._h_conv = float(h_conv)
     self._occ_attached = self._conv_attached = None   # the arguments of the device generators (SimState fingerprint)
     self._building_params = None   # set_building_params: the per-building table in force (None: the config's values)
+    self._reward_function = None   # set_reward_function: None -- the default regret function of the SimConfig
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -605,10 +606,36 @@ class BatchedSimulator:
     """The parameters every building runs with: SimConfig field name -> float64 [B] ([B, 2] for the windows)."""
     return host_inputs.effective_building_params(self._building_params, self.config, self.B)
 
+  # ---- the reward function (sb_set_reward_function) ----
+  def set_reward_function(self, reward_function: Optional[host_inputs.SetpointEnergyCarbonReward]) -> None:
+    """The reward every building's step returns from the next step on: a ``host_inputs.SetpointEnergyCarbonReward``
+    (the reference's absolute reward in dollars; info columns 8..12 then hold its RewardResponse fields, 13..23 are 0),
+    or None for the default, the SimConfig's regret function.  Works with both solvers and with a per-building table
+    (whose productivity and window rows keep applying).  A host value of the handle: no upload, no synchronisation."""
+    fn = _ffi.reward_entry("sb_set_reward_function")
+    if reward_function is None:
+      _ffi.check(fn(self._h, None), "sb_set_reward_function")
+      self._reward_function = None
+      return
+    if not isinstance(reward_function, host_inputs.SetpointEnergyCarbonReward):
+      raise ValueError("set_reward_function needs a host_inputs.SetpointEnergyCarbonReward (or None: the regret function)")
+    cfg = _ffi.RewardConfig(*reward_function.as_tuple())
+    try:
+      _ffi.check(fn(self._h, C.byref(cfg)), "sb_set_reward_function")
+    except _ffi.SbsimError as e:   # SB_ERR_INVALID: the reference's ValueError
+      raise ValueError(str(e)) from None
+    self._reward_function = reward_function
+
+  @property
+  def reward_function(self) -> Optional[host_inputs.SetpointEnergyCarbonReward]:
+    """The reward function in force (None: the default regret function)."""
+    return self._reward_function
+
   # ---- state snapshots (sb_state_save / sb_state_load) ----
   def state_fingerprint(self) -> Tuple:
     """What a SimState of this simulator means: plan shape and zones, a hash of the compiled plan tables (in the
-    caller's orientation) and of SimConfig.to_params(), the attached device generators.  Not the layout, the
+    caller's orientation) and of SimConfig.to_params(), the attached device generators -- and, when it is not the
+    default, the reward function (its kind and constants: the reward a restored batch replays).  Not the layout, the
     orientation or the sweep kernel: a snapshot moves between them."""
     if self._fingerprint is None:
       cp = self.plan.compile(self.config.time_step_sec, self._h_conv)
@@ -620,7 +647,10 @@ class BatchedSimulator:
       params_hash = hashlib.sha256(repr(vals).encode()).hexdigest()
       self._fingerprint = ((self.H, self.W, self.Z),
                            _sha(cp.cell_class, cp.class_coef, cp.class_zone, cp.zone_off, cp.zone_cells), params_hash)
-    return self._fingerprint + (self._occ_attached, self._conv_attached)
+    fp = self._fingerprint + (self._occ_attached, self._conv_attached)
+    if self._reward_function is not None:   # (the default adds nothing: checkpoints from before the option still load)
+      fp += (("reward_function",) + self._reward_function.as_tuple(),)
+    return fp
 
   def save_state(self, rows: Optional[torch.Tensor] = None) -> SimState:
     """Snapshot of every building (``rows`` None) or of buildings ``rows`` (int32 / int64 [n] on the device; row i of
@@ -774,10 +804,13 @@ class BatchedEnvironment:
                electricity_energy_cost=None, natural_gas_energy_cost=None, collect_info: bool = False,
                observation_histogram_parameters: Optional[Sequence[Tuple[str, Sequence[float]]]] = None,
                normalize_reduce: bool = False, convection_simulator=None, solver: str = "gauss_seidel",
-               building_params: Optional[host_inputs.BuildingParams] = None):
+               building_params: Optional[host_inputs.BuildingParams] = None,
+               reward_function: Optional[host_inputs.SetpointEnergyCarbonReward] = None):
     """``solver``: the finite-difference solver (BatchedSimulator): "gauss_seidel" (default) or "jacobi_fp32"
     (TFSimulator, SB1's shipped configuration; no convection_simulator, snapshot, restore or fork).
-    ``building_params``: per-building plant, setpoint and reward parameters (``set_building_params``)."""
+    ``building_params``: per-building plant, setpoint and reward parameters (``set_building_params``).
+    ``reward_function``: None -- the reference's SetpointEnergyCarbonRegretFunction with the SimConfig's arguments;
+    a ``host_inputs.SetpointEnergyCarbonReward`` -- its SetpointEnergyCarbonRewardFunction (``set_reward_function``)."""
     if discount_factor <= 0 or discount_factor > 1:
       raise ValueError("Discount factor must be in (0,1]")   # environment.py:454-455
     if solver == "jacobi_fp32" and convection_simulator is not None:
@@ -801,6 +834,8 @@ class BatchedEnvironment:
     self.batch_size = self.sim.B
     if building_params is not None:
       self.sim.set_building_params(building_params)
+    if reward_function is not None:
+      self.sim.set_reward_function(reward_function)
     self._weather_lohi = self._weather_replay = None
     if isinstance(self.weather, host_inputs.BatchedReplayWeather):
       if self.weather.offsets_sec.shape[0] != self.batch_size:
@@ -922,6 +957,7 @@ class BatchedEnvironment:
       si.occupancy_dev = self._occ_zone.data_ptr()
     else:
       si.occupancy = self.occupancy.average_zone_occupancy("", nxt, nxt + self._step_interval)
+    self._occ_host = occ if si.occupancy_dev else si.occupancy   # what the step's RewardInfo holds (episode_writer.py)
     start_utc = host_inputs.reward_start_time_utc(nxt)
     si.e_price, si.e_carbon = self.electricity.rates(start_utc)
     si.g_price, si.g_carbon = self.gas.rates(start_utc)
@@ -986,6 +1022,10 @@ class BatchedEnvironment:
 
   def building_params(self) -> Dict[str, np.ndarray]:
     return self.sim.building_params()
+
+  def set_reward_function(self, reward_function: Optional[host_inputs.SetpointEnergyCarbonReward]) -> None:
+    """BatchedSimulator.set_reward_function: the reward of the steps from now on (None: the default regret function)."""
+    self.sim.set_reward_function(reward_function)
 
   # ---- snapshots ----
   _HOST_CLOCK = ("_now", "_step_count", "_episode_count", "_episode_ended", "_needs_reset", "_prev_thermostat_ts")
@@ -1108,9 +1148,11 @@ class MixedBatchedEnvironment:
   global (class-major) order."""
 
   def __init__(self, classes: Sequence[Tuple[FloorPlan, int]], device: int = 0, rank: int = 0, world: int = 1,
-               building_params: Optional[host_inputs.BuildingParams] = None, **env_kwargs):
+               building_params: Optional[host_inputs.BuildingParams] = None, reward_function=None, **env_kwargs):
     """``building_params``: one row per GLOBAL building of the mixed batch (``sum(class_totals)`` rows, class-major);
-    each class on this rank takes its buildings' rows (``distributed.class_global_rows``), whatever the sharding."""
+    each class on this rank takes its buildings' rows (``distributed.class_global_rows``), whatever the sharding.
+    ``reward_function``: one for every class (None: the default regret function), or a list / tuple with one per
+    class (None entries: the default for that class)."""
     if not classes:
       raise ValueError("MixedBatchedEnvironment needs at least one (floor plan, number of buildings) class")
     from . import distributed as _sd
@@ -1128,6 +1170,7 @@ class MixedBatchedEnvironment:
     classes = [(plan, hi - lo_) for (plan, _), (lo_, hi) in zip(classes, self.class_ranges)]
     self.global_rows = _sd.class_global_rows(self.class_totals, self.rank, self.world)
     self._check_building_params(building_params)
+    rewards = self._per_class_rewards(reward_function, len(classes))
     lo = 0
     for k, (plan, n) in enumerate(classes):
       # per-building generators (convection shuffle, randomized occupancy) draw from streams keyed by the GLOBAL
@@ -1148,6 +1191,7 @@ class MixedBatchedEnvironment:
       stream = torch.cuda.Stream(device=self.tdev)
       if building_params is not None:
         kw["building_params"] = building_params.rows(*self.global_rows[k])
+      kw["reward_function"] = rewards[k]
       with torch.cuda.stream(stream):
         env = BatchedEnvironment(plan, int(n), device=self.device, **kw)
       self.envs.append(env)
@@ -1203,6 +1247,21 @@ class MixedBatchedEnvironment:
     None clears every class's table."""
     self._check_building_params(params)
     self._on_streams(lambda k, env: env.set_building_params(None if params is None else params.rows(*self.global_rows[k])))
+
+  @staticmethod
+  def _per_class_rewards(reward_function, n_classes: int) -> list:
+    if isinstance(reward_function, (list, tuple)):
+      if len(reward_function) != n_classes:
+        raise ValueError(f"reward_function: one per class ({n_classes}), or one for all")
+      return list(reward_function)
+    return [reward_function] * n_classes
+
+  def set_reward_function(self, reward_function) -> None:
+    """The reward function of every class (one ``host_inputs.SetpointEnergyCarbonReward`` or None), or a list / tuple
+    with one per class, from the next step on."""
+    rewards = self._per_class_rewards(reward_function, len(self.envs))
+    for env, r in zip(self.envs, rewards):   # a host value of each handle: nothing to order on the streams
+      env.set_reward_function(r)
 
   def _each(self, fn) -> TimeStep:
     """Runs fn(class index, env) -> TimeStep on every class's stream between two joins with the caller's stream."""

@@ -269,8 +269,12 @@ class BuildingLogger:
     bp = env.sim.building_params()
     window = bp["comfort_temp_window" if env.schedule.is_comfort_mode(now) else "eco_temp_window"][self.buildings]
     vav_flow = bp["vav_max_air_flow_rate"][self.buildings]
-    occ = (env._occ_count[self.buildings].cpu().numpy() if env._occ_count is not None
-           else np.full((len(self.buildings), env.sim.Z), info[:, 17:18] / env.sim.Z))
+    if env._occ_count is not None:
+      occ = env._occ_count[self.buildings].cpu().numpy()
+    elif env.sim.reward_function is None:   # the regret's RewardResponse carries total_occupancy
+      occ = np.full((len(self.buildings), env.sim.Z), info[:, 17:18] / env.sim.Z)
+    else:   # (SetpointEnergyCarbonReward leaves that field at 0: the host model's answer for this step)
+      occ = np.broadcast_to(np.asarray(env._occ_host, dtype=np.float32), (len(self.buildings), env.sim.Z))
     self._log_observation(now)
     for k, b in enumerate(self.buildings):
       w = self.writers[b]

@@ -510,6 +510,49 @@ class NaturalGasEnergyCost:
     return float(self.month_gas_price[start_time_utc.month - 1]), float(self.carbon_rate)
 
 
+class SetpointEnergyCarbonReward:
+  """reward/setpoint_energy_carbon_reward.py:84-190, SetpointEnergyCarbonRewardFunction: the absolute reward in dollars,
+  ``(productivity - energy_cost_weight * (electricity + gas cost) - carbon_cost_weight * carbon_cost -
+  reward_normalizer_shift) / reward_normalizer_scale`` with ``carbon_cost = carbon_emitted * carbon_cost_factor``.
+  The constructor's productivity arguments (max_productivity_personhour_usd, productivity_midpoint_delta,
+  productivity_decay_stiffness) and the energy cost models are the SimConfig's and the environment's, as for the default
+  regret function; the regret's own fields (min productivity, the rate caps, the three weights) play no part.
+
+      env = BatchedEnvironment(plan, B, reward_function=SetpointEnergyCarbonReward(1.0, 1.0, 0.2, 250.0, 5000.0))
+
+  The reference constructor checks nothing; the values here must be finite and the scale non-zero (the reward divides
+  by it) -- ValueError otherwise."""
+  kind = 1   # SB_REWARD_SETPOINT_ENERGY_CARBON
+
+  def __init__(self, energy_cost_weight: float, carbon_cost_weight: float, carbon_cost_factor: float,
+               reward_normalizer_shift: float = 0.0, reward_normalizer_scale: float = 1.0):
+    vals = dict(energy_cost_weight=energy_cost_weight, carbon_cost_weight=carbon_cost_weight,
+                carbon_cost_factor=carbon_cost_factor, reward_normalizer_shift=reward_normalizer_shift,
+                reward_normalizer_scale=reward_normalizer_scale)
+    for name, v in vals.items():
+      if isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} must be a number, got {v!r}")
+      if not np.isfinite(v):
+        raise ValueError(f"{name} is not finite")
+      setattr(self, name, float(v))
+    if self.reward_normalizer_scale == 0.0:
+      raise ValueError("reward_normalizer_scale must not be 0 (the reward divides by it)")
+
+  def as_tuple(self) -> Tuple:
+    """(kind, the five constants): what a snapshot's fingerprint carries."""
+    return (self.kind, self.energy_cost_weight, self.carbon_cost_weight, self.carbon_cost_factor,
+            self.reward_normalizer_shift, self.reward_normalizer_scale)
+
+  def __eq__(self, other) -> bool:
+    return isinstance(other, SetpointEnergyCarbonReward) and self.as_tuple() == other.as_tuple()
+
+  def __hash__(self) -> int:
+    return hash(self.as_tuple())
+
+  def __repr__(self) -> str:
+    return "SetpointEnergyCarbonReward(%r, %r, %r, %r, %r)" % self.as_tuple()[1:]
+
+
 def reward_start_time_utc(ts: dt.datetime) -> dt.datetime:
   """conversion_utils.py:39-59: the reward sees pandas_to_proto -> proto_to_pandas, i.e. UTC."""
   return dt.datetime.fromtimestamp(int(epoch_seconds(ts)), tz=UTC)
