@@ -572,6 +572,50 @@ typedef struct sb_reward_config {
  * kind, a non-finite field, normalizer_scale == 0 (kind 1 only: the default ignores the other fields). */
 int sb_set_reward_function(sb_handle *h, const sb_reward_config *cfg);
 
+/* Per-building materials and convection coefficient (no reference counterpart in one object: the reference builds one
+ * Simulator with its own MaterialProperties and weather controller per building).  The floor plan's classes are then
+ * STRUCTURAL (sbsim_amd/floorplan.py, compile_structural): a class says what a cell is, not what its coefficients are,
+ * and k_class_coef computes every building's [n_classes][8] coefficient rows on the device from the building's
+ * 3 * n_slots + 1 values, with FloorPlan.compile's arithmetic operation for operation (bitwise equal to it).
+ * Host pointers, copied by sb_create_materials. */
+typedef struct sb_struct_desc {
+  int32_t n_slots;              /* M: distinct (conductivity, heat_capacity, density) triples of the plan, 1 .. 255 */
+  int32_t reserved;
+  const int32_t *class_desc;    /* [n_classes][4]: material slot, neighbour count, present mask (bit j: neighbour j of
+                                   up, down, left, right exists), half-factor mask (that neighbour has < 4 neighbours) */
+  const double *class_diffuser; /* [n_classes] diffuser weight of the class's cells (0: none) */
+  const double *slot_table;     /* [M][3] the plan's own conductivity, heat_capacity, density per slot */
+  double h_conv;                /* the plan's own convection coefficient */
+  double dx, dx2, zh;           /* control-volume size (m), its square as the host computes it, floor height (m) */
+} sb_struct_desc;
+/* Field numbers of sb_set_building_materials for a handle of M slots: kind * M + slot, and 3 * M for h_conv. */
+enum sb_material_kind { SB_BM_CONDUCTIVITY = 0, SB_BM_HEAT_CAPACITY = 1, SB_BM_DENSITY = 2 };
+/* sb_create for a handle whose buildings have coefficient rows of their own.  plan->class_coef must hold the
+ * classes' coefficients for the plan's own values (used by nothing on the device; kept for sb_plan_desc's contract);
+ * plan->cell_class / class_zone are the structural classes.  The handle always runs SB_KERNEL_LDS (k_sweep_lds with
+ * the coefficient table per wavefront, reloaded for every building); SB_ERR_TOO_LARGE when the plan with that table
+ * does not fit one wavefront's share of 160 KiB of LDS.  Every building starts with the plan's own values.  Every
+ * other entry point works on such a handle as on sb_create's: they see the LDS state layout only. */
+int sb_create_materials(const sb_plan_desc *plan, const sb_struct_desc *desc, const sb_params *params,
+                        const sb_obs_layout *obs, int32_t n_buildings, int32_t device, sb_handle **out);
+
+/* sb_plan_info for a handle sb_create_materials would make: always SB_KERNEL_LDS, with the [5][ts] coefficient table in
+ * every wavefront's LDS area (lds_bytes_per_workgroup, waves_per_workgroup and workgroups say so).  SB_ERR_TOO_LARGE
+ * where sb_create_materials would refuse the plan.  No device needed. */
+int sb_plan_info_materials(const sb_plan_desc *plan, int32_t n_obs, int32_t n_buildings, sb_launch_info *out);
+
+/* values: HOST [n_fields][B], row k holding field fields[k] of every building; a field not named keeps the plan's own
+ * value for every building, n_fields == 0 restores them all.  Runs k_class_coef on `stream`, after the work already
+ * queued there: the new rows apply from the next step.  Configuration of the building's slot, not state (as
+ * sb_set_building_params: snapshots do not carry it, a forked building keeps its slot's row).  Synchronises `stream`
+ * before it returns; SB_ERR_INVALID while the stream is being captured, for an unknown or repeated field, and --
+ * naming the building and the field, nothing changed -- for a non-finite value, a material value <= 0 or h_conv < 0;
+ * SB_ERR_UNSUPPORTED on a handle that sb_create_materials did not make. */
+int sb_set_building_materials(sb_handle *h, int32_t n_fields, const int32_t *fields,
+                              const double *values /* HOST [n_fields][B] */, void *stream);
+/* The coefficient rows in force: DEVICE [B][n_classes][8] (bU bD bL bR ap gc sc pad), stream-ordered. */
+int sb_get_building_coef(sb_handle *h, double *out_dev, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

@@ -139,6 +139,11 @@ class JacobiDesc(C.Structure):   # sb_jacobi_desc
               ("cell_class", C.POINTER(C.c_uint8)), ("class_f32", _fp), ("class_diffuser", _dp), ("class_zone", _ip)]
 
 
+class StructDesc(C.Structure):   # sb_struct_desc
+  _fields_ = [("n_slots", C.c_int32), ("reserved", C.c_int32), ("class_desc", _ip), ("class_diffuser", _dp),
+              ("slot_table", _dp), ("h_conv", C.c_double), ("dx", C.c_double), ("dx2", C.c_double), ("zh", C.c_double)]
+
+
 # sb_sweep_kernel
 SWEEP_KERNELS = {0: "k_sweep_lds", 1: "k_sweep_reg", 2: "k_sweep_reg (two wavefronts)", 3: "k_sweep_roll", 4: "k_sweep_two",
                  5: "k_sweep_band", 6: "k_sweep_stream", 7: "k_sweep_jacobi"}
@@ -152,12 +157,14 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_pb_observation_response", "sb_pb_action_response", "sb_shard_append", "sb_pb_device_info",
            "sb_pb_zone_info", "sb_pb_variable_info", "sb_record_append", "sb_tap_pre", "sb_tap_post",
            "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi", "sb_set_building_params",
-           "sb_set_reward_function")
+           "sb_set_reward_function", "sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials",
+           "sb_get_building_coef")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
 BUILDING_PARAM_ENTRIES = ("sb_set_building_params",)
 REWARD_ENTRIES = ("sb_set_reward_function",)
+MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
 
@@ -242,6 +249,12 @@ def load():
     L.sb_set_building_params.argtypes = [vp, C.c_int32, vp, vp, vp]
   if all(hasattr(L, name) for name in REWARD_ENTRIES):
     L.sb_set_reward_function.argtypes = [vp, C.POINTER(RewardConfig)]
+  if all(hasattr(L, name) for name in MATERIALS_ENTRIES):
+    L.sb_create_materials.argtypes = [C.POINTER(PlanDesc), C.POINTER(StructDesc), C.POINTER(Params), C.POINTER(ObsLayout),
+                                      C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.sb_plan_info_materials.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.c_int32, C.POINTER(LaunchInfo)]
+    L.sb_set_building_materials.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.sb_get_building_coef.argtypes = [vp, vp, vp]
   _lib = L
   return L
 
@@ -267,6 +280,12 @@ def jacobi_entry(name: str):
 
 def reward_entry(name: str):
   """The reward-function entry `name` (sb_set_reward_function): see entry()."""
+  return entry(name)
+
+
+def materials_entry(name: str):
+  """The per-building-materials entry `name` (sb_create_materials, sb_plan_info_materials, sb_set_building_materials,
+  sb_get_building_coef): see entry()."""
   return entry(name)
 
 

@@ -307,6 +307,7 @@ __global__ void k_copy_temps_jacobi(const float *grid, size_t n, double *out) {
 // order through DPP row broadcasts.  k_post: one thread per building (the row shape was measured slower: sb_device.h).
 // only >= 0: that building alone (the known-answer taps).
 constexpr int kRowsPerBlock = 16; // buildings per workgroup of 256 threads
+template <bool MAT> // the building's own coefficient rows (sb_create_materials): a kernel per value, see pre_building
 __global__ void __launch_bounds__(16 * kRowsPerBlock) k_pre(Dev a, StepArgs s, int only) {
   if (blockIdx.x == 0 && threadIdx.x == 0) { // the sweep kernel's draw counter; k_sweep_roll: the redo list's counters
     *a.next_b = 0;
@@ -314,10 +315,16 @@ __global__ void __launch_bounds__(16 * kRowsPerBlock) k_pre(Dev a, StepArgs s, i
   }
   const int i = threadIdx.x & 15, r = threadIdx.x >> 4;
   if (only >= 0) {
-    if (blockIdx.x == 0 && r == 0) pre_building(a, s, only, i);
+    if (blockIdx.x == 0 && r == 0) pre_building<MAT>(a, s, only, i);
     return;
   }
-  for (int b = blockIdx.x * kRowsPerBlock + r; b < a.B; b += gridDim.x * kRowsPerBlock) pre_building(a, s, b, i);
+  for (int b = blockIdx.x * kRowsPerBlock + r; b < a.B; b += gridDim.x * kRowsPerBlock) pre_building<MAT>(a, s, b, i);
+}
+
+// k_pre of the handle (sb_create_materials: the variant that reads the building's own gc and sc); only >= 0: that building alone
+void launch_pre(const sb_handle *h, const StepArgs &s, dim3 grid, hipStream_t stream, int only) {
+  if (h->d.ctab_b) hipLaunchKernelGGL(k_pre<true>, grid, dim3(16 * kRowsPerBlock), 0, stream, h->d, s, only);
+  else hipLaunchKernelGGL(k_pre<false>, grid, dim3(16 * kRowsPerBlock), 0, stream, h->d, s, only);
 }
 
 template <int KIND> // the reward function (sb_reward_kind): a kernel per kind, see post_building
@@ -327,6 +334,54 @@ __global__ void __launch_bounds__(64) k_post(Dev a, StepArgs s, sb_reward_config
     return;
   }
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) post_building<KIND>(a, s, rc, b);
+}
+
+// sb_create_materials: every building's coefficient rows from its own materials and convection coefficient.  One thread
+// per (building, class); FloorPlan.compile's arithmetic (sbsim_amd/floorplan.py, structural_class_coef) operation for
+// operation -- this file is built with -ffp-contract=off, and float64 division is correctly rounded -- so a row equals the
+// host's bit for bit.  desc: {material slot, neighbour count, present mask, half-factor mask}; tab: [3 M + 1][B], field
+// kind * M + slot (conductivity, heat capacity, density), h_conv last; out: [B][ncls + 1][8], row ncls the pad class.
+__global__ void __launch_bounds__(256) k_class_coef(const int4 *desc, const double *diff, const double *tab, int B, int ncls,
+                                                    int M, double dt, double dx, double dx2, double zh, double *out) {
+  const size_t n = (size_t)B * (ncls + 1);
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int b = (int)(i / (ncls + 1)), c = (int)(i - (size_t)b * (ncls + 1));
+    double bn[4] = {0.0, 0.0, 0.0, 0.0}, ap = 0.0, gc = 0.0, sc = 0.0;
+    if (c == ncls) {
+      ap = 1.0; // the pad class: T' = Tprev
+    } else {
+      const int4 e = desc[c];
+      const double kk = tab[(size_t)e.x * B + b], cc = tab[(size_t)(M + e.x) * B + b], rr = tab[(size_t)(2 * M + e.x) * B + b];
+      const double h_conv = tab[(size_t)3 * M * B + b];
+      const int n_nb = e.y, present = e.z, half = e.w;
+      if (n_nb <= 1) { // simulator.py:256-258 exterior CVs return ambient
+        gc = 1.0;
+      } else if (n_nb == 2) { // corner :130-142
+        const double t0 = rr * dx2 * cc / dt / 2.0;
+        const double den = 2.0 * kk + 2.0 * h_conv * dx + t0;
+        for (int j = 0; j < 4; ++j)
+          if (present >> j & 1) bn[j] = kk / den;
+        ap = t0 / den; gc = 2.0 * h_conv * dx / den;
+      } else if (n_nb == 3) { // edge :176-195
+        const double t0 = rr * dx2 / 2.0 * cc / dt;
+        const double den = 2.0 * kk + h_conv * dx + t0;
+        for (int j = 0; j < 4; ++j)
+          if (present >> j & 1) bn[j] = kk * ((half >> j & 1) ? 0.5 : 1.0) / den;
+        ap = t0 / den; gc = h_conv * dx / den;
+      } else { // interior :225-237
+        const double alpha = kk / rr / cc;
+        const double t0 = dx2 / dt / alpha;
+        const double den = 4.0 + t0;
+        bn[0] = bn[1] = bn[2] = bn[3] = 1.0 / den;
+        ap = t0 / den;
+        const double dw = diff[c];
+        if (dw > 0.0) sc = dw / kk / zh / den; // building.py:873-889
+      }
+    }
+    double2 *o = (double2 *)(out + i * 8);
+    o[0] = make_double2(bn[0], bn[1]); o[1] = make_double2(bn[2], bn[3]);
+    o[2] = make_double2(ap, gc); o[3] = make_double2(sc, 0.0);
+  }
 }
 
 // k_post of the handle's reward function (sb_set_reward_function); only >= 0: that building alone
@@ -343,7 +398,7 @@ int prepare_sweep(const sb_handle *h) {
   const Dev &d = h->d;
   const int waves = h->info.waves_per_workgroup;
   switch (h->kernel) {
-    case SB_KERNEL_LDS: return prepare_sweep_lds((size_t)h->info.lds_bytes_per_workgroup);
+    case SB_KERNEL_LDS: return prepare_sweep_lds(d, (size_t)h->info.lds_bytes_per_workgroup);
     case SB_KERNEL_REG: case SB_KERNEL_REG_PAIR: return prepare_sweep_reg(d);
     case SB_KERNEL_ROLL: return prepare_sweep_roll(d);
     case SB_KERNEL_TWO_ROWS: return prepare_sweep_two(d);
@@ -373,6 +428,27 @@ int launch_sweep(const sb_handle *h, hipStream_t stream) {
     case SB_KERNEL_JACOBI: return launch_sweep_jacobi(d, h->jac, h->info.workgroups, stream);
   }
   return (int)hipErrorInvalidValue;
+}
+
+// sb_create_materials / sb_set_building_materials: the value table and k_class_coef on `stream`, and waits for them (the
+// copy reads host memory that goes away with this call)
+int apply_building_materials(sb_handle *h, const std::vector<double> &tab, hipStream_t stream) {
+  const Dev &d = h->d;
+  const int M = h->mat_slots, F = 3 * M + 1, B = d.B;
+  std::vector<double> own;
+  if (tab.empty()) { // the plan's own values in every row
+    own.resize((size_t)F * B);
+    for (int f = 0; f < F; ++f) std::fill_n(own.begin() + (size_t)f * B, B, h->mat_default[f]);
+  }
+  const std::vector<double> &src = tab.empty() ? own : tab;
+  SB_HIP(hipMemcpyAsync(h->mat_tab.p, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  const size_t n = (size_t)B * (d.ncls + 1);
+  const int blocks = (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)h->cus * 32));
+  hipLaunchKernelGGL(k_class_coef, dim3(blocks), dim3(256), 0, stream, h->mat_desc.p, h->mat_diff.p, h->mat_tab.p, B, d.ncls,
+                     M, d.p.dt, h->mat_dx, h->mat_dx2, h->mat_zh, h->ctab_b.p);
+  SB_HIP(hipGetLastError());
+  SB_HIP(hipStreamSynchronize(stream));
+  return SB_OK;
 }
 
 extern "C" {
@@ -450,7 +526,7 @@ int sb_step_phases(sb_handle *h, const float *actions_dev, const sb_step_in *in,
   const Dev &d = h->d;
   const int blocks = std::max(1, std::min((d.B + kRowsPerBlock - 1) / kRowsPerBlock, h->cus * 32)); // a 16-lane row per building
   if (phases & SB_PHASE_PRE) {
-    hipLaunchKernelGGL(k_pre, dim3(blocks), dim3(16 * kRowsPerBlock), 0, (hipStream_t)stream, d, s, -1);
+    launch_pre(h, s, dim3(blocks), (hipStream_t)stream, -1);
     SB_HIP(hipGetLastError());
     h->counters_zeroed_on = stream; // k_pre zeroes the sweep kernel's draw counters
   }
@@ -656,6 +732,65 @@ int sb_set_building_params(sb_handle *h, int32_t n_fields, const int32_t *fields
   return SB_OK;
 }
 
+/* ---- per-building materials ---- */
+static std::string material_field_name(int f, int M) {
+  static const char *const kinds[3] = {"conductivity", "heat_capacity", "density"};
+  if (f == 3 * M) return "h_conv";
+  return std::string(kinds[f / M]) + "[" + std::to_string(f % M) + "]";
+}
+
+int sb_set_building_materials(sb_handle *h, int32_t n_fields, const int32_t *fields, const double *values, void *stream) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_set_building_materials: null handle");
+  if (!h->materials)
+    return fail(SB_ERR_UNSUPPORTED, "sb_set_building_materials: the handle has one coefficient table for every building "
+                                    "(sb_create / sb_create_jacobi); create it with sb_create_materials");
+  const int M = h->mat_slots, F = 3 * M + 1, B = h->d.B;
+  if (n_fields < 0 || n_fields > F)
+    return fail(SB_ERR_INVALID, "sb_set_building_materials: n_fields must be in 0 .. 3 * n_slots + 1");
+  if (n_fields > 0 && (!fields || !values)) return fail(SB_ERR_INVALID, "sb_set_building_materials: null argument");
+  std::vector<double> tab;
+  if (n_fields > 0) {
+    std::vector<char> named((size_t)F, 0);
+    for (int i = 0; i < n_fields; ++i) {
+      const int f = fields[i];
+      if (f < 0 || f >= F) return fail(SB_ERR_INVALID, "sb_set_building_materials: unknown field " + std::to_string(f));
+      if (named[f]) return fail(SB_ERR_INVALID, "sb_set_building_materials: field " + material_field_name(f, M) + " named twice");
+      named[f] = 1;
+    }
+    tab.resize((size_t)F * B); // every field the plan's own value, then the named rows over it
+    for (int f = 0; f < F; ++f) std::fill_n(tab.begin() + (size_t)f * B, B, h->mat_default[f]);
+    for (int i = 0; i < n_fields; ++i) std::copy_n(values + (size_t)i * B, B, tab.begin() + (size_t)fields[i] * B);
+    for (int b = 0; b < B; ++b)
+      for (int f = 0; f < F; ++f) {
+        const double v = tab[(size_t)f * B + b];
+        const char *what = !std::isfinite(v) ? " is not finite" : f < 3 * M && !(v > 0.0) ? " must be positive"
+                           : f == 3 * M && v < 0.0 ? " must not be negative" : nullptr;
+        if (what)
+          return fail(SB_ERR_INVALID, "sb_set_building_materials: building " + std::to_string(b) + ": " +
+                                          material_field_name(f, M) + what);
+      }
+  }
+  SB_ON_DEVICE(h->device);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  SB_HIP(hipStreamIsCapturing((hipStream_t)stream, &cap));
+  if (cap != hipStreamCaptureStatusNone)
+    return fail(SB_ERR_INVALID, "sb_set_building_materials: not while the stream is being captured into a graph");
+  // ordered on `stream`: the steps already queued there read the old rows, k_class_coef writes the new ones after them
+  SB_CHECK(apply_building_materials(h, tab, (hipStream_t)stream));
+  return SB_OK;
+}
+
+int sb_get_building_coef(sb_handle *h, double *out_dev, void *stream) {
+  if (!h || !out_dev) return fail(SB_ERR_INVALID, "sb_get_building_coef: null argument");
+  if (!h->materials)
+    return fail(SB_ERR_UNSUPPORTED, "sb_get_building_coef: the handle has no coefficient rows per building (sb_create_materials)");
+  SB_ON_DEVICE(h->device);
+  const size_t row = (size_t)h->d.ncls * 8 * sizeof(double); // the pad row stays behind
+  SB_HIP(hipMemcpy2DAsync(out_dev, row, h->ctab_b.p, row + 8 * sizeof(double), row, (size_t)h->d.B, hipMemcpyDeviceToDevice,
+                          (hipStream_t)stream));
+  return SB_OK;
+}
+
 /* ---- the reward function ---- */
 int sb_set_reward_function(sb_handle *h, const sb_reward_config *cfg) {
   if (!h) return fail(SB_ERR_INVALID, "sb_set_reward_function: null handle");
@@ -702,7 +837,7 @@ int sb_tap_pre(sb_handle *h, int32_t building, const double *zone_temps, const i
   }
   StepArgs s{};
   s.actions = act.p; s.in = *in;
-  hipLaunchKernelGGL(k_pre, dim3(1), dim3(16 * kRowsPerBlock), 0, nullptr, d, s, building); // this building alone
+  launch_pre(h, s, dim3(1), nullptr, building); // this building alone
   SB_HIP(hipGetLastError());
   SB_HIP(hipDeviceSynchronize());
   if (bld) {

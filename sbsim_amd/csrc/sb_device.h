@@ -157,6 +157,10 @@ struct Dev {
   // (structure of arrays: k_post's one-thread-per-building reads coalesce); NULL: every building uses `p`.  Read only
   // through bparam(), and only by k_pre, k_post, k_observe and the reset kernels -- no sweep kernel looks at it.
   const double *bp;
+  // sb_create_materials: [B][ncls + 1][8] every building's own coefficient rows (k_class_coef, runtime.hip; the pad row
+  // last); NULL on every other handle.  Read by k_pre<true> (columns 5, 6) and k_sweep_lds<true> (columns 0..4) alone.
+  const double *ctab_b;
+  int off_wtab;            // k_sweep_lds<true>: the wavefront's own [5][ts] coefficient table inside its LDS region (doubles)
 };
 
 // sb_params' double fields vav_max_air_flow .. w_carbon by sb_building_param (constant k: folds to the field)
@@ -212,7 +216,7 @@ struct StepArgs {
 
 // Host launchers (one per translation unit that defines a sweep kernel).
 int launch_sweep_lds(const Dev &d, int workgroups, int waves_per_wg, size_t lds_bytes, hipStream_t stream);
-int prepare_sweep_lds(size_t lds_bytes);
+int prepare_sweep_lds(const Dev &d, size_t lds_bytes);
 int launch_sweep_reg(const Dev &d, int cus, hipStream_t stream);
 int prepare_sweep_reg(const Dev &d);         // sets the LDS attribute; fails if (NR, P) is not built
 bool sweep_reg_supported(int NR, int P);     // is there an instantiation for this shape?
@@ -524,6 +528,9 @@ __device__ __forceinline__ void row_each(int n, double x0, double x1, double x2,
 // VAV outputs from the PRE-update zone temperatures (simulator.py:433-448), demand accumulation
 // in the reference's zone order, boiler tank lag (boiler.py:158-217).
 // i: the lane's index in its row; every lane of the row runs the per-building (uniform) part -- same addresses, one transaction.
+// MAT (sb_create_materials): gc and sc come from the building's own coefficient rows (Dev::ctab_b); a kernel per value, as
+// k_post per reward kind -- a handle without such rows launches the code it always has.
+template <bool MAT>
 __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int i) {
   const sb_params &p = a.p;
   const sb_step_in &in = s.in;
@@ -577,12 +584,13 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
   // g[class]: a lane per class, 16 at a time.  q is the PREVIOUS step's: every read of qz here is issued before the zone
   // loop below stores this step's (one instruction stream: a wavefront's memory operations on an address stay in order)
   double *gt = a.gtabg + (size_t)b * a.ts;
+  const double *ct = MAT ? a.ctab_b + (size_t)b * (a.ncls + 1) * 8 : a.ctab;
   for (int c = i; c < a.ts; c += 16) {
     double gg = 0.0;
     if (c < a.ncls) {
       const int zc = a.czone[c];
       const double q = zc >= 0 ? a.qz[zb + zc] : 0.0;
-      gg = fma(a.ctab[c * 8 + 6], q, a.ctab[c * 8 + 5] * v.t_now);
+      gg = fma(ct[c * 8 + 6], q, ct[c * 8 + 5] * v.t_now);
     }
     gt[c] = gg;
   }

@@ -191,6 +191,15 @@ struct sb_handle {
   sb_occupancy_config occ{};
   uint32_t occ_queries = 0;
   bool occ_attached = false;
+  // sb_create_materials: the structural classes' descriptors, the buildings' values and their coefficient rows
+  bool materials = false;
+  int mat_slots = 0;                // M
+  std::vector<double> mat_default;  // [3 M + 1] the plan's own value of every field (kind * M + slot; 3 M: h_conv)
+  double mat_dx = 0.0, mat_dx2 = 0.0, mat_zh = 0.0;
+  DevBuf<int4> mat_desc;            // [ncls] {slot, neighbour count, present mask, half-factor mask}
+  DevBuf<double> mat_diff;          // [ncls] diffuser weight
+  DevBuf<double> mat_tab;           // [3 M + 1][B] the values in force
+  DevBuf<double> ctab_b;            // [B][ncls + 1][8] (Dev::ctab_b)
   // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
   DevBuf<float> jgrid, jtab, jscratch; // (jscratch: k_sweep_jacobi_g's per-workgroup grids)
   DevBuf<double> jrden;
@@ -202,6 +211,10 @@ struct sb_handle {
 // runtime.hip: the one dispatch on sb_handle::kernel -- the sweep kernel's LDS attribute (sb_create), its launch (sb_step)
 int prepare_sweep(const sb_handle *h);
 int launch_sweep(const sb_handle *h, hipStream_t stream);
+
+// runtime.hip: uploads the buildings' values (tab: [3 M + 1][B]; empty: the plan's own in every row) and runs k_class_coef
+// on `stream`, and waits for both
+int apply_building_materials(sb_handle *h, const std::vector<double> &tab, hipStream_t stream);
 
 // generators.hip: the convection shuffle between the sweep and the reward (sb_step)
 int sb_launch_convection(sb_handle *h, hipStream_t stream);

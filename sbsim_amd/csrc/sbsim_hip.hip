@@ -867,13 +867,14 @@ void plan_reg(const sb_plan_desc *plan, const Trim &t, int lds_per_cu, const Kno
 }
 
 struct LdsPlan { // launch geometry of the LDS-grid kernel
-  int pitch, NL, S, nsteps, nbands, fast, ts, off_agtab, off_zscr, off_zmode, lds_wave_doubles;
+  int pitch, NL, S, nsteps, nbands, fast, ts, off_agtab, off_zscr, off_zmode, off_wtab, lds_wave_doubles;
   unsigned S_magic;
   size_t shared_bytes, wave_bytes;
   bool fits;
 };
 
-LdsPlan plan_lds(const sb_plan_desc *plan) {
+// per_building (sb_create_materials): the [5][ts] coefficient table is the wavefront's own, not the workgroup's
+LdsPlan plan_lds(const sb_plan_desc *plan, bool per_building = false) {
   LdsPlan q{};
   const int H = plan->H, W = plan->W, Z = plan->Z;
   q.pitch = (W + 1) & ~1; // even pitch: skewed ds_read_b64 is bank-conflict free
@@ -891,8 +892,9 @@ LdsPlan plan_lds(const sb_plan_desc *plan) {
   q.off_agtab = off; off += q.ts;
   q.off_zscr = off; off += (3 * Z + 1) & ~1;
   q.off_zmode = off; off += ((Z + 1) / 2 + 1) & ~1;
+  q.off_wtab = off; off += per_building ? 5 * q.ts : 0;
   q.lds_wave_doubles = off;
-  q.shared_bytes = (size_t)5 * q.ts * 8 + (size_t)((Z + 2) >> 1) * 8;
+  q.shared_bytes = (size_t)(per_building ? 0 : 5 * q.ts) * 8 + (size_t)((Z + 2) >> 1) * 8;
   q.wave_bytes = (size_t)off * 8;
   q.fits = q.shared_bytes + q.wave_bytes <= (size_t)kLdsCap && q.NL < 65535;
   return q;
@@ -1122,7 +1124,7 @@ int setup_lds(sb_handle *h, const sb_plan_desc *plan, const LdsPlan &q, const Kn
   d.pitch = q.pitch; d.NL = q.NL; d.S = q.S; d.S_magic = q.S_magic; d.nsteps = q.nsteps;
   d.nbands = q.nbands; d.fast = q.fast; d.ts = q.ts;
   if (k.force_generic) d.fast = 0;
-  d.off_agtab = q.off_agtab; d.off_zscr = q.off_zscr; d.off_zmode = q.off_zmode;
+  d.off_agtab = q.off_agtab; d.off_zscr = q.off_zscr; d.off_zmode = q.off_zmode; d.off_wtab = q.off_wtab;
   d.lds_wave_doubles = q.lds_wave_doubles;
   std::vector<int> zl((size_t)plan->zone_off[plan->Z]);
   for (size_t i = 0; i < zl.size(); ++i) {
@@ -1287,29 +1289,66 @@ int check_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, std::vecto
   return SB_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int sb_plan_info(const sb_plan_desc *plan, int32_t n_obs, int32_t n_buildings, sb_launch_info *out) {
-  const Knobs k;
-  if (!out) return fail(SB_ERR_INVALID, "sb_plan_info: null argument");
-  int rc = check_plan(plan);
-  if (rc != SB_OK) return rc;
-  RegPlan r;
-  const LdsPlan q = plan_lds(plan);
-  rc = choose_kernel(plan, q, k, r);
-  if (rc != SB_OK) return rc;
-  fill_launch_info(plan, r, q, n_obs, capped_cus(256, k), std::max(n_buildings, 1), out);
+// sb_create_materials: the structural classes' descriptors against the plan, the plan's own values against the checks
+// sb_set_building_materials makes of a row.
+int check_struct_desc(const sb_plan_desc *plan, const sb_struct_desc *sd, const sb_params *params) {
+  const std::string w = "sb_create_materials: ";
+  if (!sd->class_desc || !sd->class_diffuser || !sd->slot_table) return fail(SB_ERR_INVALID, w + "null descriptor table");
+  if (sd->n_slots < 1 || sd->n_slots > 255) return fail(SB_ERR_INVALID, w + "n_slots must be in 1 .. 255");
+  if (!(sd->dx > 0.0) || !(sd->dx2 > 0.0) || !(sd->zh > 0.0) || !std::isfinite(sd->dx) || !std::isfinite(sd->dx2) ||
+      !std::isfinite(sd->zh))
+    return fail(SB_ERR_INVALID, w + "dx, dx2 and zh must be positive and finite");
+  if (!(sd->h_conv >= 0.0) || !std::isfinite(sd->h_conv)) return fail(SB_ERR_INVALID, w + "h_conv must be finite and >= 0");
+  if (!(params->dt > 0.0)) return fail(SB_ERR_INVALID, w + "time_step_sec must be positive");
+  for (int i = 0; i < 3 * sd->n_slots; ++i)
+    if (!(sd->slot_table[i] > 0.0) || !std::isfinite(sd->slot_table[i]))
+      return fail(SB_ERR_INVALID, w + "slot " + std::to_string(i / 3) + ": material values must be positive and finite");
+  for (int c = 0; c < plan->n_classes; ++c) {
+    const int32_t *e = sd->class_desc + 4 * c;
+    if (e[0] < 0 || e[0] >= sd->n_slots || e[1] < 0 || e[1] > 4 || (e[2] & ~15) || (e[3] & ~15))
+      return fail(SB_ERR_INVALID, w + "class " + std::to_string(c) + ": bad descriptor");
+    if (!(sd->class_diffuser[c] >= 0.0) || !std::isfinite(sd->class_diffuser[c]))
+      return fail(SB_ERR_INVALID, w + "class " + std::to_string(c) + ": bad diffuser weight");
+  }
   return SB_OK;
 }
 
-int sb_create(const sb_plan_desc *plan, const sb_params *params, const sb_obs_layout *obs,
-              int32_t n_buildings, int32_t device, sb_handle **out) {
+// sb_create_materials: the descriptors and the buildings' value table on the device, every building's coefficient rows
+// from the plan's own values (k_class_coef, runtime.hip).  Sets Dev::ctab_b, which selects k_pre<true> and
+// k_sweep_lds<true>.
+int setup_materials(sb_handle *h, const sb_plan_desc *plan, const sb_struct_desc *sd) {
+  Dev &d = h->d;
+  const int M = sd->n_slots, F = 3 * M + 1;
+  h->materials = true;
+  h->mat_slots = M;
+  h->mat_dx = sd->dx; h->mat_dx2 = sd->dx2; h->mat_zh = sd->zh;
+  h->mat_default.assign((size_t)F, sd->h_conv); // field kind * M + slot; 3 M: h_conv
+  for (int s = 0; s < M; ++s)
+    for (int kind = 0; kind < 3; ++kind) h->mat_default[(size_t)kind * M + s] = sd->slot_table[3 * s + kind];
+  std::vector<int4> desc((size_t)plan->n_classes);
+  for (int c = 0; c < plan->n_classes; ++c)
+    desc[c] = make_int4(sd->class_desc[4 * c], sd->class_desc[4 * c + 1], sd->class_desc[4 * c + 2], sd->class_desc[4 * c + 3]);
+  SB_CHECK(upload(h->mat_desc, desc.data(), desc.size()));
+  SB_CHECK(upload(h->mat_diff, sd->class_diffuser, (size_t)plan->n_classes));
+  SB_CHECK(alloc_zero(h->mat_tab, (size_t)F * d.B));
+  SB_CHECK(alloc_zero(h->ctab_b, (size_t)d.B * (d.ncls + 1) * 8));
+  d.ctab_b = h->ctab_b.p;
+  return apply_building_materials(h, std::vector<double>(), nullptr);
+}
+
+int materials_too_large(const char *who) {
+  return fail(SB_ERR_TOO_LARGE, std::string(who) + ": the floor plan with a coefficient table per wavefront does not fit "
+                                                   "one wavefront's share of 160 KiB of LDS (k_sweep_lds)");
+}
+
+// sb_create (sd == NULL) and sb_create_materials.
+int create_handle(const sb_plan_desc *plan, const sb_struct_desc *sd, const sb_params *params, const sb_obs_layout *obs,
+                  int32_t n_buildings, int32_t device, sb_handle **out) {
   const Knobs k;
   if (!plan || !params || !obs || !out) return fail(SB_ERR_INVALID, "sb_create: null argument");
   ActionTable acts;
   SB_CHECK(check_create_args(plan, params, obs, n_buildings, acts));
+  if (sd) SB_CHECK(check_struct_desc(plan, sd, params));
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(SB_ERR_NO_DEVICE, "sb_create: no HIP device visible (this library has no CPU path)");
@@ -1318,9 +1357,10 @@ int sb_create(const sb_plan_desc *plan, const sb_params *params, const sb_obs_la
   hipDeviceProp_t prop;
   SB_HIP(hipGetDeviceProperties(&prop, device));
 
-  RegPlan r;
-  const LdsPlan q = plan_lds(plan);
-  SB_CHECK(choose_kernel(plan, q, k, r));
+  RegPlan r; // (kernel = SB_KERNEL_LDS)
+  const LdsPlan q = plan_lds(plan, sd != nullptr);
+  if (!sd) SB_CHECK(choose_kernel(plan, q, k, r));
+  else if (!q.fits) return materials_too_large("sb_create_materials"); // the one kernel that holds coefficient rows per building
 
   auto h = std::make_unique<sb_handle>(); // (declared after the device guard: an early return frees it on the device)
   h->device = device;
@@ -1340,10 +1380,51 @@ int sb_create(const sb_plan_desc *plan, const sb_params *params, const sb_obs_la
   SB_CHECK(d.reg ? setup_reg(h.get(), plan, r, k) : setup_lds(h.get(), plan, q, k));
   SB_CHECK(setup_obs_tables(h.get(), params, obs, acts));
   SB_CHECK(setup_state(h.get(), plan));
+  if (sd) SB_CHECK(setup_materials(h.get(), plan, sd));
   setup_debug(h.get(), k);
   SB_CHECK(prepare_and_reset(h.get()));
   *out = h.release();
   return SB_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sb_plan_info(const sb_plan_desc *plan, int32_t n_obs, int32_t n_buildings, sb_launch_info *out) {
+  const Knobs k;
+  if (!out) return fail(SB_ERR_INVALID, "sb_plan_info: null argument");
+  int rc = check_plan(plan);
+  if (rc != SB_OK) return rc;
+  RegPlan r;
+  const LdsPlan q = plan_lds(plan);
+  rc = choose_kernel(plan, q, k, r);
+  if (rc != SB_OK) return rc;
+  fill_launch_info(plan, r, q, n_obs, capped_cus(256, k), std::max(n_buildings, 1), out);
+  return SB_OK;
+}
+
+int sb_plan_info_materials(const sb_plan_desc *plan, int32_t n_obs, int32_t n_buildings, sb_launch_info *out) {
+  const Knobs k;
+  if (!out) return fail(SB_ERR_INVALID, "sb_plan_info_materials: null argument");
+  const int rc = check_plan(plan);
+  if (rc != SB_OK) return rc;
+  const RegPlan r; // (kernel = SB_KERNEL_LDS: the one kernel of such a handle)
+  const LdsPlan q = plan_lds(plan, true);
+  if (!q.fits) return materials_too_large("sb_plan_info_materials");
+  fill_launch_info(plan, r, q, n_obs, capped_cus(256, k), std::max(n_buildings, 1), out);
+  return SB_OK;
+}
+
+int sb_create(const sb_plan_desc *plan, const sb_params *params, const sb_obs_layout *obs,
+              int32_t n_buildings, int32_t device, sb_handle **out) {
+  return create_handle(plan, nullptr, params, obs, n_buildings, device, out);
+}
+
+int sb_create_materials(const sb_plan_desc *plan, const sb_struct_desc *desc, const sb_params *params,
+                        const sb_obs_layout *obs, int32_t n_buildings, int32_t device, sb_handle **out) {
+  if (!desc) return fail(SB_ERR_INVALID, "sb_create_materials: null argument");
+  return create_handle(plan, desc, params, obs, n_buildings, device, out);
 }
 
 int sb_create_jacobi(const sb_plan_desc *plan, const sb_jacobi_desc *jac, const sb_params *params,

@@ -277,6 +277,10 @@ __device__ __forceinline__ double sweep(const Dev &a, double *E, const double *g
 
 extern __shared__ __attribute__((aligned(16))) double lds[];
 
+// PERB (sb_create_materials): every building has coefficient rows of its own (Dev::ctab_b).  The [5][ts] table then is not
+// the workgroup's but the wavefront's (off_wtab inside its region), reloaded for every building it draws, next to gtab;
+// the sweeps run unchanged on that pointer.  PERB = false is the kernel as it always was.
+template <bool PERB>
 __global__ void __launch_bounds__(256) k_sweep_lds(Dev a) {
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
@@ -284,9 +288,11 @@ __global__ void __launch_bounds__(256) k_sweep_lds(Dev a) {
   const int wave = blockIdx.x * wpb + wib;
   const int nwaves = gridDim.x * wpb;
   // LDS: [tab: 5*ts | zone_off] then per wave [guard | E: NL | guard | gtab: ts | zscr: 3*Z | zmode]
-  double *tab = lds;
-  int *zoffL = (int *)(lds + 5 * a.ts); // [Z+1] zone_off, shared
-  double *mine = lds + 5 * a.ts + ((a.Z + 2) >> 1) + (size_t)wib * a.lds_wave_doubles;
+  // PERB: [zone_off] then per wave [guard | E: NL | guard | gtab: ts | zscr: 3*Z | zmode | tab: 5*ts]
+  const int shared_tab = PERB ? 0 : 5 * a.ts;
+  int *zoffL = (int *)(lds + shared_tab); // [Z+1] zone_off, shared
+  double *mine = lds + shared_tab + ((a.Z + 2) >> 1) + (size_t)wib * a.lds_wave_doubles;
+  double *tab = PERB ? mine + a.off_wtab : lds;
   double *E = mine + kGuard; // [guard | E: NL | guard]: the guards stay zero (finite) forever
   for (int i = lane; i < kGuard; i += 64) {
     mine[i] = 0.0;
@@ -294,10 +300,11 @@ __global__ void __launch_bounds__(256) k_sweep_lds(Dev a) {
   }
   double *gtab = mine + a.off_agtab;
   double *zscr = mine + a.off_zscr; // [Z..2Z): post-update zone sums
-  for (int i = threadIdx.x; i < 5 * a.ts; i += blockDim.x) {
-    const int j = i / a.ts, c = i - j * a.ts;
-    tab[i] = c < a.ncls ? a.ctab[c * 8 + j] : 0.0; // columns 0..4 of class_coef: bU bD bL bR ap
-  }
+  if (!PERB)
+    for (int i = threadIdx.x; i < 5 * a.ts; i += blockDim.x) {
+      const int j = i / a.ts, c = i - j * a.ts;
+      tab[i] = c < a.ncls ? a.ctab[c * 8 + j] : 0.0; // columns 0..4 of class_coef: bU bD bL bR ap
+    }
   for (int i = threadIdx.x; i <= a.Z; i += blockDim.x) zoffL[i] = a.zone_off[i];
   __syncthreads();
 
@@ -309,6 +316,14 @@ __global__ void __launch_bounds__(256) k_sweep_lds(Dev a) {
     SB_STAMP(0);
     double *T = a.temp + (size_t)b * a.Np + kPad; // T[-kPad..-1] and T[N..N+kPad) are zero
     for (int c = lane; c < a.ts; c += 64) gtab[c] = a.gtabg[(size_t)b * a.ts + c];
+    if (PERB) { // the building's own bU bD bL bR ap; the wave_barrier below orders it, like gtab, before the first sweep
+      const double *cb = a.ctab_b + (size_t)b * (a.ncls + 1) * 8;
+      for (int c = lane; c < a.ts; c += 64) {
+        const bool in = c < a.ncls;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) tab[j * a.ts + c] = in ? cb[c * 8 + j] : 0.0;
+      }
+    }
     SB_STAMP(1);
     // grid -> LDS.  Even W: one flat copy by LDS-DMA (global_load_lds_dwordx4: 1 KiB per
     // wave instruction, no VGPR round trip, every piece in flight at once).
@@ -421,13 +436,15 @@ __global__ void __launch_bounds__(256) k_sweep_lds(Dev a) {
 
 } // namespace
 
-int prepare_sweep_lds(size_t lds_bytes) {
-  return (int)hipFuncSetAttribute((const void *)k_sweep_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_bytes);
+// (Dev::ctab_b: the handle has coefficient rows per building -> the PERB instantiation)
+int prepare_sweep_lds(const Dev &d, size_t lds_bytes) {
+  const void *k = d.ctab_b ? (const void *)k_sweep_lds<true> : (const void *)k_sweep_lds<false>;
+  return (int)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
 }
 
 int launch_sweep_lds(const Dev &d, int workgroups, int waves_per_wg, size_t lds_bytes, hipStream_t stream) {
-  hipLaunchKernelGGL(k_sweep_lds, dim3(workgroups), dim3(64 * waves_per_wg), lds_bytes, stream, d);
+  if (d.ctab_b) hipLaunchKernelGGL(k_sweep_lds<true>, dim3(workgroups), dim3(64 * waves_per_wg), lds_bytes, stream, d);
+  else hipLaunchKernelGGL(k_sweep_lds<false>, dim3(workgroups), dim3(64 * waves_per_wg), lds_bytes, stream, d);
   return (int)hipGetLastError();
 }
 

@@ -332,12 +332,22 @@ class BatchedSimulator:
                observation_normalization: Optional[Mapping[str, Tuple[float, float]]] = None,
                zone_names: Optional[Sequence[str]] = None, orientation: str = "auto",
                histogram_parameters: Optional[Sequence[Tuple[str, Sequence[float]]]] = None,
-               normalize_reduce: bool = False, solver: str = "gauss_seidel"):
+               normalize_reduce: bool = False, solver: str = "gauss_seidel",
+               building_materials: Optional[host_inputs.BuildingMaterials] = None):
     """``solver``: "gauss_seidel" -- SimulatorFlexibleGeometries' float64 sweep (simulator.py:278-371), the library's
     own kernels; "jacobi_fp32" -- TFSimulator's float32 Jacobi update (tf_simulator.py:502-853), the solver of SB1's
-    shipped sim_config.gin, on k_sweep_jacobi (grid in the caller's orientation only; no snapshots, no convection)."""
+    shipped sim_config.gin, on k_sweep_jacobi (grid in the caller's orientation only; no snapshots, no convection).
+    ``building_materials``: a ``host_inputs.BuildingMaterials`` makes a handle whose buildings have materials and a
+    convection coefficient of their own (sb_create_materials: structural classes, k_sweep_lds with a coefficient table
+    per building; ``set_building_materials`` changes the rows later).  None, the default, is the handle without."""
     if solver not in SOLVERS:
       raise ValueError(f"solver must be one of {SOLVERS}")
+    if building_materials is not None:
+      if not isinstance(building_materials, host_inputs.BuildingMaterials):
+        raise ValueError("building_materials must be a host_inputs.BuildingMaterials (or None)")
+      if solver == "jacobi_fp32":
+        raise ValueError("building_materials is not implemented for solver='jacobi_fp32' (its float32 class table is one "
+                         "per batch); use solver='gauss_seidel'")
     if solver == "jacobi_fp32" and orientation not in ("auto", "rows"):
       raise ValueError("solver='jacobi_fp32' keeps the caller's orientation (transposing would move TFSimulator's "
                        "swapped horizontal neighbours to the other axis): orientation must be 'auto' or 'rows'")
@@ -350,6 +360,8 @@ class BatchedSimulator:
     self._occ_attached = self._conv_attached = None   # the arguments of the device generators (SimState fingerprint)
     self._building_params = None   # set_building_params: the per-building table in force (None: the config's values)
     self._reward_function = None   # set_reward_function: None -- the default regret function of the SimConfig
+    self._materials_handle = building_materials is not None   # sb_create_materials made the handle
+    self._building_materials = None   # set_building_materials: the rows in force (None: the plan's own values)
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -393,6 +405,29 @@ class BatchedSimulator:
     if solver == "jacobi_fp32":
       self.transposed = False
       self.compiled, keep, pd_, jd = self._describe_jacobi(plan, config.time_step_sec, h_conv)
+    elif self._materials_handle:
+      # always k_sweep_lds: the orientation with fewer wavefront steps per sweep (rows on a tie, as below) among those
+      # whose grid, with the coefficient table per wavefront, fits in LDS (sb_plan_info_materials).
+      # The slots are numbered once, in the caller's orientation: a table's [B, M] columns mean plan.material_slots()
+      # whichever orientation the device runs (the transposed plan's own raster order can differ)
+      slot_ids, self._slot_table = plan.material_slots()
+      building_materials.check_plan(self.B, len(self._slot_table))
+      plan_info = _ffi.materials_entry("sb_plan_info_materials")
+      chosen = None
+      for tr in sorted({"rows": [False], "columns": [True], "auto": [False, True]}[orientation],
+                       key=lambda tr: FloorPlan.sweep_steps(*(plan.shape[::-1] if tr else plan.shape))):
+        cand = self._describe_structural(plan.transposed() if tr else plan, config.time_step_sec, h_conv,
+                                         (slot_ids.T if tr else slot_ids, self._slot_table))
+        rc = plan_info(C.byref(cand[2]), self.O, self.B, C.byref(_ffi.LaunchInfo()))
+        if rc == 0:
+          chosen = (tr, cand)
+          break
+        if rc != -4:   # (SB_ERR_TOO_LARGE: the other orientation may fit)
+          _ffi.check(rc, "sb_plan_info_materials")
+      if chosen is None:
+        raise ValueError("building_materials needs k_sweep_lds, which cannot hold this floor plan: "
+                         + (self._lib.sb_last_error() or b"").decode())
+      self.transposed, (self.compiled, keep, pd_, sd_) = chosen
     else:
       cands = {"rows": [False], "columns": [True], "auto": [False, True]}[orientation]
       best = None
@@ -433,6 +468,9 @@ class BatchedSimulator:
       if solver == "jacobi_fp32":
         _ffi.check(_ffi.jacobi_entry("sb_create_jacobi")(C.byref(pd_), C.byref(jd), C.byref(params), C.byref(ol), self.B,
                                                          self.device, C.byref(h)), "sb_create_jacobi")
+      elif self._materials_handle:
+        _ffi.check(_ffi.materials_entry("sb_create_materials")(C.byref(pd_), C.byref(sd_), C.byref(params), C.byref(ol),
+                                                               self.B, self.device, C.byref(h)), "sb_create_materials")
       else:
         _ffi.check(self._lib.sb_create(C.byref(pd_), C.byref(params), C.byref(ol), self.B, self.device,
                                        C.byref(h)), "sb_create")
@@ -442,6 +480,23 @@ class BatchedSimulator:
     _ffi.check(self._lib.sb_get_launch_info(self._h, C.byref(info)), "sb_get_launch_info")
     self.launch_info = {f[0]: getattr(info, f[0]) for f in _ffi.LaunchInfo._fields_}
     self.sweep_events = None   # a list: step() appends (start, end) HIP events of every sweep-kernel launch (bench.py)
+    if building_materials is not None:
+      self.set_building_materials(building_materials)
+
+  @staticmethod
+  def _describe_structural(plan: FloorPlan, dt: float, h_conv: float, slots):
+    """FloorPlan.compile_structural's tables (material slots numbered by ``slots``) as sb_create_materials' arguments."""
+    sp = plan.compile_structural(dt, slots)
+    keep = dict(cls=np.ascontiguousarray(sp.cell_class), coef=np.ascontiguousarray(sp.class_coef(h_conv=h_conv)),
+                czone=np.ascontiguousarray(sp.class_zone), zoff=np.ascontiguousarray(sp.zone_off),
+                zcells=np.ascontiguousarray(sp.zone_cells), cdesc=np.ascontiguousarray(sp.class_desc),
+                cdiff=np.ascontiguousarray(sp.class_diffuser), slots=np.ascontiguousarray(sp.slot_table))
+    pd_ = _ffi.PlanDesc(sp.H, sp.W, sp.Z, sp.n_classes, keep["cls"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                        keep["coef"].ctypes.data_as(_ffi._dp), keep["czone"].ctypes.data_as(_ffi._ip),
+                        keep["zoff"].ctypes.data_as(_ffi._ip), keep["zcells"].ctypes.data_as(_ffi._ip))
+    sd = _ffi.StructDesc(sp.n_slots, 0, keep["cdesc"].ctypes.data_as(_ffi._ip), keep["cdiff"].ctypes.data_as(_ffi._dp),
+                         keep["slots"].ctypes.data_as(_ffi._dp), float(h_conv), sp.dx, sp.dx ** 2, sp.zh)
+    return sp, keep, pd_, sd
 
   @staticmethod
   def _describe_jacobi(plan: FloorPlan, dt: float, h_conv: float):
@@ -606,6 +661,49 @@ class BatchedSimulator:
     """The parameters every building runs with: SimConfig field name -> float64 [B] ([B, 2] for the windows)."""
     return host_inputs.effective_building_params(self._building_params, self.config, self.B)
 
+  # ---- per-building materials (sb_set_building_materials) ----
+  def set_building_materials(self, materials: Optional[host_inputs.BuildingMaterials]) -> None:
+    """Per-building conductivity, heat capacity and density of the plan's material slots and convection coefficient
+    (``host_inputs.BuildingMaterials``; None: every building back to the plan's own values), on a simulator created with
+    ``building_materials``.  The device computes every building's coefficient rows (k_class_coef) on the current stream
+    and the call synchronises with it; not while that stream is being captured into a graph.  Configuration of the
+    building's slot, as ``set_building_params``: snapshots do not carry it, a forked building keeps its own row, and
+    it applies from the next step."""
+    if not self._materials_handle:
+      raise ValueError("set_building_materials needs a simulator created with building_materials=... (its floor plan is "
+                       "compiled into structural classes and runs on k_sweep_lds)")
+    fn = _ffi.materials_entry("sb_set_building_materials")
+    if materials is None:
+      with torch.cuda.device(self.device):
+        _ffi.check(fn(self._h, 0, None, None, self._stream()), "sb_set_building_materials")
+      self._building_materials = None
+      return
+    if not isinstance(materials, host_inputs.BuildingMaterials):
+      raise ValueError("set_building_materials needs a host_inputs.BuildingMaterials (or None)")
+    M = len(self._slot_table)
+    materials.check_plan(self.B, M)
+    fields, values = materials.c_table(M)
+    with torch.cuda.device(self.device):
+      rc = fn(self._h, int(fields.shape[0]), fields.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p),
+              self._stream())
+    if rc == -1:   # SB_ERR_INVALID
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_set_building_materials")
+    self._building_materials = materials
+
+  def building_materials(self) -> Dict[str, np.ndarray]:
+    """The materials every building runs with: conductivity / heat_capacity / density float64 [B, M] by material slot
+    (``FloorPlan.material_slots()``), convection_coefficient [B]."""
+    table = self._slot_table if self._materials_handle else self.plan.material_slots()[1]
+    return host_inputs.effective_building_materials(self._building_materials, table, self._h_conv, self.B)
+
+  def building_coef(self) -> torch.Tensor:
+    """sb_get_building_coef: every building's coefficient rows in force, float64 [B, n_classes, 8] (bU bD bL bR ap gc sc
+    pad; classes of ``self.compiled``, the device's orientation)."""
+    if not self._materials_handle:
+      raise ValueError("building_coef needs a simulator created with building_materials=...")
+    return self._get(_ffi.materials_entry("sb_get_building_coef"), (self.B, self.compiled.n_classes, 8), torch.float64)
+
   # ---- the reward function (sb_set_reward_function) ----
   def set_reward_function(self, reward_function: Optional[host_inputs.SetpointEnergyCarbonReward]) -> None:
     """The reward every building's step returns from the next step on: a ``host_inputs.SetpointEnergyCarbonReward``
@@ -638,18 +736,24 @@ class BatchedSimulator:
     default, the reward function (its kind and constants: the reward a restored batch replays).  Not the layout, the
     orientation or the sweep kernel: a snapshot moves between them."""
     if self._fingerprint is None:
-      cp = self.plan.compile(self.config.time_step_sec, self._h_conv)
+      if self._materials_handle:   # the structural tables (caller's orientation): the coefficients are the rows', not the plan's
+        sp = self.plan.compile_structural(self.config.time_step_sec)
+        tables = (sp.cell_class, sp.class_desc, sp.class_diffuser, sp.class_zone, sp.zone_off, sp.zone_cells)
+      else:
+        cp = self.plan.compile(self.config.time_step_sec, self._h_conv)
+        tables = (cp.cell_class, cp.class_coef, cp.class_zone, cp.zone_off, cp.zone_cells)
       prm = self.config.to_params()
       vals = []
       for name, ctype in _ffi.PARAM_FIELDS:
         v = getattr(prm, name)
         vals.append(repr([v[i] for i in range(prm.n_actions)]) if name.startswith("act_") else repr(v))
       params_hash = hashlib.sha256(repr(vals).encode()).hexdigest()
-      self._fingerprint = ((self.H, self.W, self.Z),
-                           _sha(cp.cell_class, cp.class_coef, cp.class_zone, cp.zone_off, cp.zone_cells), params_hash)
+      self._fingerprint = ((self.H, self.W, self.Z), _sha(*tables), params_hash)
     fp = self._fingerprint + (self._occ_attached, self._conv_attached)
     if self._reward_function is not None:   # (the default adds nothing: checkpoints from before the option still load)
       fp += (("reward_function",) + self._reward_function.as_tuple(),)
+    if self._materials_handle:   # (a table is configuration, not state: the marker says which class map the state means)
+      fp += (("building_materials",),)
     return fp
 
   def save_state(self, rows: Optional[torch.Tensor] = None) -> SimState:
@@ -805,10 +909,13 @@ class BatchedEnvironment:
                observation_histogram_parameters: Optional[Sequence[Tuple[str, Sequence[float]]]] = None,
                normalize_reduce: bool = False, convection_simulator=None, solver: str = "gauss_seidel",
                building_params: Optional[host_inputs.BuildingParams] = None,
-               reward_function: Optional[host_inputs.SetpointEnergyCarbonReward] = None):
+               reward_function: Optional[host_inputs.SetpointEnergyCarbonReward] = None,
+               building_materials: Optional[host_inputs.BuildingMaterials] = None):
     """``solver``: the finite-difference solver (BatchedSimulator): "gauss_seidel" (default) or "jacobi_fp32"
     (TFSimulator, SB1's shipped configuration; no convection_simulator, snapshot, restore or fork).
     ``building_params``: per-building plant, setpoint and reward parameters (``set_building_params``).
+    ``building_materials``: per-building materials and convection coefficient (``set_building_materials``); such an
+    environment runs on k_sweep_lds, not with solver="jacobi_fp32", and its floor plan must fit that kernel.
     ``reward_function``: None -- the reference's SetpointEnergyCarbonRegretFunction with the SimConfig's arguments;
     a ``host_inputs.SetpointEnergyCarbonReward`` -- its SetpointEnergyCarbonRewardFunction (``set_reward_function``)."""
     if discount_factor <= 0 or discount_factor > 1:
@@ -830,7 +937,7 @@ class BatchedEnvironment:
     self.sim = BatchedSimulator(plan, self.config, n_buildings, h_conv, device,
                                 observation_normalization,
                                 histogram_parameters=observation_histogram_parameters,
-                                normalize_reduce=normalize_reduce, solver=solver)
+                                normalize_reduce=normalize_reduce, solver=solver, building_materials=building_materials)
     self.batch_size = self.sim.B
     if building_params is not None:
       self.sim.set_building_params(building_params)
@@ -1023,6 +1130,14 @@ class BatchedEnvironment:
   def building_params(self) -> Dict[str, np.ndarray]:
     return self.sim.building_params()
 
+  def set_building_materials(self, materials: Optional[host_inputs.BuildingMaterials]) -> None:
+    """BatchedSimulator.set_building_materials between steps (an environment created with ``building_materials``): the
+    new rows apply from the next step; None returns every building to the plan's own values."""
+    self.sim.set_building_materials(materials)
+
+  def building_materials(self) -> Dict[str, np.ndarray]:
+    return self.sim.building_materials()
+
   def set_reward_function(self, reward_function: Optional[host_inputs.SetpointEnergyCarbonReward]) -> None:
     """BatchedSimulator.set_reward_function: the reward of the steps from now on (None: the default regret function)."""
     self.sim.set_reward_function(reward_function)
@@ -1148,8 +1263,12 @@ class MixedBatchedEnvironment:
   global (class-major) order."""
 
   def __init__(self, classes: Sequence[Tuple[FloorPlan, int]], device: int = 0, rank: int = 0, world: int = 1,
-               building_params: Optional[host_inputs.BuildingParams] = None, reward_function=None, **env_kwargs):
-    """``building_params``: one row per GLOBAL building of the mixed batch (``sum(class_totals)`` rows, class-major);
+               building_params: Optional[host_inputs.BuildingParams] = None, reward_function=None,
+               building_materials: Optional[Sequence[Optional[host_inputs.BuildingMaterials]]] = None, **env_kwargs):
+    """``building_materials``: a list / tuple with one ``host_inputs.BuildingMaterials`` or None per class (material
+    slots are a floor plan's own, so a table belongs to one class); a class's table has one row per building of the
+    class over every rank (``class_totals[k]`` rows), and this rank takes its share (``class_ranges[k]``).
+    ``building_params``: one row per GLOBAL building of the mixed batch (``sum(class_totals)`` rows, class-major);
     each class on this rank takes its buildings' rows (``distributed.class_global_rows``), whatever the sharding.
     ``reward_function``: one for every class (None: the default regret function), or a list / tuple with one per
     class (None entries: the default for that class)."""
@@ -1170,6 +1289,7 @@ class MixedBatchedEnvironment:
     classes = [(plan, hi - lo_) for (plan, _), (lo_, hi) in zip(classes, self.class_ranges)]
     self.global_rows = _sd.class_global_rows(self.class_totals, self.rank, self.world)
     self._check_building_params(building_params)
+    self._check_building_materials(building_materials)
     rewards = self._per_class_rewards(reward_function, len(classes))
     lo = 0
     for k, (plan, n) in enumerate(classes):
@@ -1192,6 +1312,8 @@ class MixedBatchedEnvironment:
       if building_params is not None:
         kw["building_params"] = building_params.rows(*self.global_rows[k])
       kw["reward_function"] = rewards[k]
+      if building_materials is not None and building_materials[k] is not None:
+        kw["building_materials"] = building_materials[k].rows(*self.class_ranges[k])
       with torch.cuda.stream(stream):
         env = BatchedEnvironment(plan, int(n), device=self.device, **kw)
       self.envs.append(env)
@@ -1247,6 +1369,29 @@ class MixedBatchedEnvironment:
     None clears every class's table."""
     self._check_building_params(params)
     self._on_streams(lambda k, env: env.set_building_params(None if params is None else params.rows(*self.global_rows[k])))
+
+  def _check_building_materials(self, materials) -> None:
+    if materials is None:
+      return
+    if not isinstance(materials, (list, tuple)) or len(materials) != len(self.class_totals):
+      raise ValueError(f"building_materials: a list with one BuildingMaterials or None per class ({len(self.class_totals)})")
+    for k, (bm, total) in enumerate(zip(materials, self.class_totals)):
+      if bm is not None and (not isinstance(bm, host_inputs.BuildingMaterials) or bm.n_buildings != total):
+        raise ValueError(f"building_materials[{k}] needs one row per building of class {k} over every rank ({total})")
+
+  def set_building_materials(self, materials) -> None:
+    """Per-building materials per class (as the constructor's ``building_materials``) from the next step on; a None
+    entry returns that class to its plan's own values -- or leaves it alone if it was created without a table."""
+    self._check_building_materials(materials)
+    if materials is None:
+      materials = [None] * len(self.envs)
+
+    def apply(k, env):
+      if env.sim._materials_handle:
+        env.set_building_materials(None if materials[k] is None else materials[k].rows(*self.class_ranges[k]))
+      elif materials[k] is not None:
+        raise ValueError(f"class {k} was created without building_materials")
+    self._on_streams(apply)
 
   @staticmethod
   def _per_class_rewards(reward_function, n_classes: int) -> list:

@@ -171,6 +171,77 @@ class CompiledPlan:
 
 
 @dataclasses.dataclass
+class StructuralPlan:
+  """Device-ready tables of one floor plan whose coefficients are computed per building (FloorPlan.compile_structural):
+  CompiledPlan's class map and zones, and per class a descriptor instead of coefficients."""
+  H: int
+  W: int
+  Z: int
+  n_classes: int
+  n_slots: int                # M: distinct materials of the plan
+  cell_class: np.ndarray      # [H*W] uint8, row-major
+  class_desc: np.ndarray      # [n_classes, 4] int32: material slot, neighbour count, present mask, half-factor mask
+  class_diffuser: np.ndarray  # [n_classes] float64 diffuser weight (0: none)
+  class_zone: np.ndarray      # [n_classes] int32: zone whose q feeds sc, or -1
+  zone_off: np.ndarray        # [Z+1] int32
+  zone_cells: np.ndarray      # [sum] int32
+  slot_table: np.ndarray      # [M, 3] float64 the plan's own (conductivity, heat_capacity, density) per slot
+  dt: float
+  dx: float                   # cv_size_cm / 100
+  zh: float                   # floor_height_cm / 100
+
+  def class_coef(self, conductivity=None, heat_capacity=None, density=None, h_conv: float = 0.0) -> np.ndarray:
+    """structural_class_coef of this plan; a material left out is the plan's own."""
+    t = self.slot_table
+    return structural_class_coef(self, t[:, 0] if conductivity is None else conductivity,
+                                 t[:, 1] if heat_capacity is None else heat_capacity,
+                                 t[:, 2] if density is None else density, h_conv, self.dt, self.dx, self.zh)
+
+
+def structural_class_coef(desc, k, c, rho, h_conv: float, dt: float, dx: float, zh: float) -> np.ndarray:
+  """[n_classes, 8] class_coef (bU bD bL bR ap gc sc pad) of a StructuralPlan's classes for the materials k[M], c[M],
+  rho[M] (conductivity, heat capacity, density per slot) and convection coefficient h_conv: FloorPlan.compile's
+  arithmetic, operation for operation, so that ``structural_class_coef(...)[cell_class]`` equals ``compile``'s
+  ``class_coef[cell_class]`` on the plan with those materials bit for bit.  The device's k_class_coef (runtime.hip)
+  is the same sequence again."""
+  dt, dx, zh, h_conv = float(dt), float(dx), float(zh), float(h_conv)
+  dx2 = dx ** 2
+  out = np.zeros((desc.n_classes, 8), dtype=np.float64)
+  for i in range(desc.n_classes):
+    slot, n, pmask, hmask = (int(v) for v in desc.class_desc[i])
+    kk, rr, cc = float(k[slot]), float(rho[slot]), float(c[slot])
+    b = [0.0, 0.0, 0.0, 0.0]
+    ap = gc = sc = 0.0
+    if n <= 1:
+      gc = 1.0
+    elif n == 2:
+      t0 = rr * dx2 * cc / dt / 2.0
+      den = 2.0 * kk + 2.0 * h_conv * dx + t0
+      for j in range(4):
+        if pmask >> j & 1:
+          b[j] = kk / den
+      ap, gc = t0 / den, 2.0 * h_conv * dx / den
+    elif n == 3:
+      t0 = rr * dx2 / 2 * cc / dt
+      den = 2.0 * kk + h_conv * dx + t0
+      for j in range(4):
+        if pmask >> j & 1:
+          b[j] = kk * (0.5 if hmask >> j & 1 else 1.0) / den
+      ap, gc = t0 / den, h_conv * dx / den
+    else:
+      alpha = kk / rr / cc
+      t0 = dx2 / dt / alpha
+      den = 4.0 + t0
+      b = [1.0 / den] * 4
+      ap = t0 / den
+      dw = float(desc.class_diffuser[i])
+      if dw > 0.0:
+        sc = dw / kk / zh / den
+    out[i, :7] = [b[0], b[1], b[2], b[3], ap, gc, sc]
+  return out
+
+
+@dataclasses.dataclass
 class FloorPlan:
   """Post-preprocessing description of one building geometry."""
   conductivity: np.ndarray    # [H, W] float64
@@ -328,6 +399,77 @@ class FloorPlan:
         zone_off=zone_off,
         zone_cells=(np.concatenate(zlists) if zlists else np.zeros(0)).astype(np.int32),
         dt=float(dt), h_conv=float(h_conv))
+
+  # ------------------------------------------------------------------ structural classes (per-building materials)
+  def material_slots(self) -> Tuple[np.ndarray, np.ndarray]:
+    """(ids [H, W] uint8, table [M, 3]): the distinct (conductivity, heat_capacity, density) triples of the grids in
+    order of first raster occurrence, and every cell's index into them.  ``table[ids]`` gives the three grids back."""
+    H, W = self.shape
+    triples = np.stack([self.conductivity, self.heat_capacity, self.density], axis=2).reshape(H * W, 3)
+    uniq, first, inverse = np.unique(triples, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")            # sorted-unique index -> raster-first order
+    if len(order) > 255:
+      raise ValueError(f"floor plan has {len(order)} distinct materials; a material slot is one byte")
+    rank = np.empty(len(order), dtype=np.int64)
+    rank[order] = np.arange(len(order))
+    return rank[inverse.reshape(-1)].astype(np.uint8).reshape(H, W), np.ascontiguousarray(uniq[order], dtype=np.float64)
+
+  def compile_structural(self, dt: float, slots: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> "StructuralPlan":
+    """``compile`` without the material values: classes keyed by what a cell IS -- its material slot
+    (``material_slots``), neighbour count, which neighbours it has, which of them take the edge formula's half factor
+    (the neighbour has < 4 neighbours, simulator.py:180-183), its diffuser weight and zone -- so that one class map
+    serves every choice of materials and convection coefficient (``structural_class_coef`` gives the coefficients).
+    Only what the cell's formula reads enters the key: an ambient cell's slot, a corner's half factors and an interior
+    cell's masks do not.  ``slots``: the (ids [H, W], table [M, 3]) to number the materials by instead of this plan's own
+    ``material_slots()`` -- raster order changes under ``transposed()``, so whoever compiles the transposed plan for a
+    table whose columns follow the original plan passes ``(ids.T, table)`` of the original."""
+    H, W = self.shape
+    present, count = self.neighbor_masks()
+    if slots is None:
+      ids, table = self.material_slots()
+    else:
+      ids, table = np.asarray(slots[0]), np.ascontiguousarray(slots[1], dtype=np.float64)
+      if ids.shape != (H, W) or table.ndim != 2 or table.shape[1] != 3 or not 0 < len(table) <= 255 or \
+          ids.dtype.kind not in "iu" or ids.min() < 0 or ids.max() >= len(table) or \
+          not np.array_equal(table[ids], np.stack([self.conductivity, self.heat_capacity, self.density], axis=2)):
+        raise ValueError("slots must be (ids [H, W], table [M, 3]) with table[ids] equal to this plan's material grids")
+    ncount = np.full((H, W, 4), 4, dtype=np.int32)
+    ncount[1:, :, 0] = count[:-1, :]
+    ncount[:-1, :, 1] = count[1:, :]
+    ncount[:, 1:, 2] = count[:, :-1]
+    ncount[:, :-1, 3] = count[:, 1:]
+    keys, desc, weights, zones = {}, [], [], []
+    cell_class = np.zeros(H * W, dtype=np.int64)
+    for x in range(H):
+      for y in range(W):
+        n = int(count[x, y])
+        slot = pmask = hmask = 0
+        dw, zone = 0.0, -1
+        if n >= 2:
+          slot = int(ids[x, y])
+          pmask = sum(1 << j for j in range(4) if present[x, y, j])
+        if n == 3:
+          hmask = sum(1 << j for j in range(4) if present[x, y, j] and ncount[x, y, j] < 4)
+        if n >= 4 and float(self.diffusers[x, y]) > 0.0 and self.zone_label[x, y] >= 0:
+          dw, zone = float(self.diffusers[x, y]), int(self.zone_label[x, y])
+        key = (slot, n, pmask, hmask, dw, zone)
+        if key not in keys:
+          keys[key] = len(desc)
+          desc.append([slot, n, pmask, hmask])
+          weights.append(dw)
+          zones.append(zone)
+        cell_class[x * W + y] = keys[key]
+    if len(desc) > 255:
+      raise ValueError(f"floor plan needs {len(desc)} cell classes; the device format holds 255")
+    zlists = self.zone_cell_lists()
+    zone_off = np.zeros(len(zlists) + 1, dtype=np.int32)
+    zone_off[1:] = np.cumsum([len(z) for z in zlists])
+    return StructuralPlan(
+        H=H, W=W, Z=len(zlists), n_classes=len(desc), n_slots=len(table), cell_class=cell_class.astype(np.uint8),
+        class_desc=np.asarray(desc, dtype=np.int32).reshape(-1, 4), class_diffuser=np.asarray(weights, dtype=np.float64),
+        class_zone=np.asarray(zones, np.int32), zone_off=zone_off,
+        zone_cells=(np.concatenate(zlists) if zlists else np.zeros(0)).astype(np.int32),
+        slot_table=table, dt=float(dt), dx=self.cv_size_cm / 100.0, zh=self.floor_height_cm / 100.0)
 
   def compile_jacobi(self, dt: float, h_conv: float) -> "JacobiPlan":
     """Folds TFSimulator's per-CV tensors (jacobi_cv_tensors, bitwise what the reference computes in float32) into a

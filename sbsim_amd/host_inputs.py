@@ -706,3 +706,98 @@ def effective_building_params(params: Optional[BuildingParams], config, n_buildi
       v = np.asarray(getattr(config, name), dtype=np.float64)
       out[name] = np.broadcast_to(v, (n_buildings,) + v.shape).copy()
   return out
+
+
+_MATERIAL_KINDS = ("conductivity", "heat_capacity", "density")   # sb_material_kind, in order
+
+
+class BuildingMaterials:
+  """Per-building envelope physics of one batch (sb_set_building_materials): the conductivity, heat capacity and density
+  of each of the floor plan's M material slots (``FloorPlan.material_slots()``: the plan's distinct materials in raster
+  order -- for a ``from_file_input`` plan the exterior wall, the interior wall and the air, in the order the plan meets
+  them), float64 [B, M] each, and the outside convection coefficient, float64 [B].  What is left out keeps the plan's own
+  value (the ``h_conv`` of the weather controller for the convection coefficient) for every building.
+
+      ids, table = plan.material_slots()
+      bm = BuildingMaterials(conductivity=table[:, 0] * np.random.uniform(0.5, 2.0, size=(B, len(table))),
+                             convection_coefficient=np.random.uniform(5.0, 50.0, size=B))
+      env = BatchedEnvironment(plan, B, building_materials=bm)
+
+  Raises ValueError, naming the building, for a wrong shape, a value that is not finite, a material value <= 0 or a
+  negative convection coefficient."""
+
+  def __init__(self, conductivity=None, heat_capacity=None, density=None, convection_coefficient=None):
+    given = dict(conductivity=conductivity, heat_capacity=heat_capacity, density=density,
+                 convection_coefficient=convection_coefficient)
+    if all(v is None for v in given.values()):
+      raise ValueError("BuildingMaterials needs at least one field (pass None instead of a table to clear one)")
+    self.fields: Dict[str, np.ndarray] = {}
+    self.n_buildings = None
+    self.n_slots = None   # M; None when only the convection coefficient is given
+    for name, arr in given.items():
+      if arr is None:
+        continue
+      a = np.array(arr, dtype=np.float64)
+      material = name in _MATERIAL_KINDS
+      if a.ndim != (2 if material else 1) or 0 in a.shape:
+        raise ValueError(f"{name} must have shape [B" + (", M]" if material else "]") + f", got {a.shape}")
+      if self.n_buildings is None:
+        self.n_buildings = int(a.shape[0])
+      elif a.shape[0] != self.n_buildings:
+        raise ValueError(f"{name} has {a.shape[0]} rows, the other fields {self.n_buildings}: one row per building")
+      if material:
+        if self.n_slots is None:
+          self.n_slots = int(a.shape[1])
+        elif a.shape[1] != self.n_slots:
+          raise ValueError(f"{name} has {a.shape[1]} material slots, the other fields {self.n_slots}")
+      bad = np.nonzero(~np.isfinite(a).reshape(a.shape[0], -1).all(axis=1))[0]
+      if bad.size:
+        raise ValueError(f"building {int(bad[0])}: {name} is not finite")
+      ok = (a > 0.0) if material else (a >= 0.0)
+      if not ok.all():
+        b = int(np.argmin(ok.reshape(a.shape[0], -1).all(axis=1)))
+        raise ValueError(f"building {b}: {name} must " + ("be positive" if material else "not be negative"))
+      a.setflags(write=False)
+      self.fields[name] = a
+
+  def rows(self, lo: int, hi: int) -> "BuildingMaterials":
+    """Buildings lo .. hi-1 (a class's or a rank's share of a larger batch)."""
+    if not 0 <= lo < hi <= self.n_buildings:
+      raise ValueError(f"rows [{lo}, {hi}) outside the table's {self.n_buildings} buildings")
+    return BuildingMaterials(**{k: v[lo:hi] for k, v in self.fields.items()})
+
+  def check_plan(self, n_buildings: int, n_slots: int) -> None:
+    if self.n_buildings != n_buildings:
+      raise ValueError(f"BuildingMaterials has {self.n_buildings} rows, the simulator {n_buildings} buildings")
+    if self.n_slots is not None and self.n_slots != n_slots:
+      raise ValueError(f"BuildingMaterials has {self.n_slots} material slots, the floor plan {n_slots} "
+                       "(FloorPlan.material_slots())")
+
+  def c_table(self, n_slots: int) -> Tuple[np.ndarray, np.ndarray]:
+    """sb_set_building_materials' arguments for a plan of n_slots slots: the named fields (kind * M + slot; 3 M: the
+    convection coefficient; int32 [n]) and their rows ([n][B])."""
+    fields, rows = [], []
+    for name, a in self.fields.items():
+      if name == "convection_coefficient":
+        fields.append(3 * n_slots)
+        rows.append(a)
+      else:
+        for s in range(n_slots):
+          fields.append(_MATERIAL_KINDS.index(name) * n_slots + s)
+          rows.append(a[:, s])
+    return np.asarray(fields, dtype=np.int32), np.ascontiguousarray(np.stack(rows))
+
+
+def effective_building_materials(materials: Optional[BuildingMaterials], slot_table: np.ndarray, h_conv: float,
+                                 n_buildings: int) -> Dict[str, np.ndarray]:
+  """The materials every building runs with: ``materials``' rows where it has the field, the plan's own slot table
+  ([M, 3]) and convection coefficient elsewhere.  conductivity / heat_capacity / density [B, M],
+  convection_coefficient [B]."""
+  out = {}
+  for j, name in enumerate(_MATERIAL_KINDS):
+    out[name] = np.broadcast_to(np.asarray(slot_table, dtype=np.float64)[:, j], (n_buildings, len(slot_table))).copy()
+  out["convection_coefficient"] = np.full(n_buildings, float(h_conv))
+  if materials is not None:
+    for name, a in materials.fields.items():
+      out[name] = a.copy()
+  return out
