@@ -616,6 +616,63 @@ int sb_set_building_materials(sb_handle *h, int32_t n_fields, const int32_t *fie
 /* The coefficient rows in force: DEVICE [B][n_classes][8] (bU bD bL bR ap gc sc pad), stream-ordered. */
 int sb_get_building_coef(sb_handle *h, double *out_dev, void *stream);
 
+/* A calendar per building (no reference counterpart in one object: the reference builds one Environment, with its own
+ * start_timestamp, per building -- environment.py:427-439, 1202-1209).  The host tabulates everything a step derives
+ * from an instant, one row per instant of the lattice t_r = start + r * dt, and gives every building an offset into
+ * it: building b lives at row offset[b] + pos, where pos is the batch's common position (sb_clock_seek).  k_pre,
+ * k_post, k_observe and k_occupancy then read the building's rows instead of sb_step_in's scalars; the sweep kernels
+ * see nothing of it (they take T_ambient per building already).  Fields of a row (doubles; the fp32 features are
+ * stored as the doubles of the same value), all functions of the row's instant t: */
+typedef enum sb_clock_field {
+  SB_CLK_T_AMB = 0,      /* weather.get_current_temp(t) of a weather shared by the batch            -> t_amb_now / t_amb_next */
+  SB_CLK_WEATHER_F,      /* the per-building sinusoid's factor 0.5 * (sin(rad(t)) + 1)               -> weather_f_now / _next */
+  SB_CLK_WEATHER_T,      /* the per-building replay's query time, seconds on the trace's clock       -> weather_t_now / _next */
+  SB_CLK_COMFORT,        /* schedule.is_comfort_mode(t), 0 / 1                        -> comfort_now / comfort_prev / comfort_next */
+  SB_CLK_AUX0,           /* the SB_NUM_AUX auxiliary features observed at t (SB_CLK_AUX0 + i)        -> aux[i] */
+  SB_CLK_OCCUPANCY = SB_CLK_AUX0 + SB_NUM_AUX, /* average_zone_occupancy over [t, t + dt], all zones -> occupancy */
+  SB_CLK_E_PRICE, SB_CLK_E_CARBON, SB_CLK_G_PRICE, SB_CLK_G_CARBON, /* the rates of a reward that starts at t -> e_* / g_* */
+  SB_CLK_OCC_HOUR, SB_CLK_OCC_WORKDAY,     /* sb_occupancy_peek's local hour and working-day flag at t ... */
+  SB_CLK_OCC_HOUR5, SB_CLK_OCC_WORKDAY5,   /* ... and at t - 5 min (SimulatorBuilding.num_occupants' query) */
+  SB_CLOCK_FIELDS        /* 20 */
+} sb_clock_field;
+/* rows_host: HOST [n_rows][n_fields] (n_fields must be SB_CLOCK_FIELDS), offsets_host: HOST [B] int32 rows; both are
+ * copied to the device (synchronously; a table attached earlier is replaced once the device is idle).  SB_ERR_INVALID:
+ * a null argument, another n_fields, n_rows < 2, a negative offset or one past n_rows - 2 (the message names the
+ * building), a row value that is not finite (the message names the row and the field); SB_ERR_TOO_LARGE: n_rows above
+ * 2^22.  The offsets configure the building's SLOT, as sb_set_building_params' rows do: snapshots do not carry them,
+ * and a building that takes another's state keeps its own. */
+#define SB_CLOCK_MAX_ROWS (1 << 22)
+int sb_clock_attach(sb_handle *h, const double *rows_host, int32_t n_rows, int32_t n_fields, const int32_t *offsets_host);
+/* A host value of the handle, no device work: the position of the next sb_step*, sb_observe* and sb_occupancy_peek.
+ * A step at pos reads, for building b, row offset[b] + pos as "now" (t), row offset[b] + pos + 1 as "next" (t + dt) and
+ * row offset[b] + prev_pos as the previous thermostat update (prev_pos = -1: none, comfort_prev = -1); an observation
+ * reads row offset[b] + pos.  SB_ERR_INVALID: no clock attached, pos < 0, prev_pos < -1, or max(offset) + pos past
+ * n_rows - 2 (max(offset) + prev_pos past n_rows - 1).
+ * With a clock attached these fields of sb_step_in are IGNORED and the rows used instead:
+ *   t_amb_now, t_amb_next            row now / next, SB_CLK_T_AMB (t_amb_dev, which is per building already, still overrides)
+ *   weather_f_now, weather_f_next    row now / next, SB_CLK_WEATHER_F (weather_lohi_dev stays the buildings' pairs)
+ *   weather_t_now, weather_t_next    row now / next, SB_CLK_WEATHER_T (weather_times_dev, weather_tempf_dev, weather_n and
+ *                                    weather_offset_dev stay: the building's offset adds to its row's query time)
+ *   comfort_now, comfort_next        row now / next, SB_CLK_COMFORT
+ *   comfort_prev                     row prev, SB_CLK_COMFORT, or -1 (reject_dev still keeps it per building on the device)
+ *   aux[i]                           row next, SB_CLK_AUX0 + i (num_occupants_dev still overrides aux[6])
+ *   occupancy                        row next, SB_CLK_OCCUPANCY (occupancy_dev / occupancy_bz_dev still override)
+ *   e_price, e_carbon, g_price, g_carbon   row next, SB_CLK_E_PRICE .. SB_CLK_G_CARBON
+ * Every other field (the pointers, has_action, actions_native, occupancy_norm) keeps its meaning.  sb_observe /
+ * sb_observe_occupancy ignore aux and t_amb likewise (row pos: SB_CLK_AUX0 + i, SB_CLK_T_AMB; t_amb_dev overrides);
+ * sb_observe_step_in adds the per-building weather forms.  sb_occupancy_peek ignores its hour and working-day flag and
+ * reads its two arguments as: local_hour -- 0: the row at pos (the observation after a reset), 1: the row at pos + 1 (a
+ * step's two queries); is_work_day -- non-zero: the row's SB_CLK_OCC_HOUR / _WORKDAY (the reward's query at t), 0: its
+ * SB_CLK_OCC_HOUR5 / _WORKDAY5 (num_occupants' query at t - 5 min).  sb_step* on a handle whose clock was never sought
+ * is SB_ERR_INVALID.  sb_tap_pre / sb_tap_post take their sb_step_in as it is, clock or not. */
+int sb_clock_seek(sb_handle *h, int32_t pos, int32_t prev_pos);
+/* Drops the clock once the device is idle: the handle runs on sb_step_in's scalars again, exactly as before. */
+int sb_clock_detach(sb_handle *h);
+/* sb_observe_occupancy with its inputs in an sb_step_in: aux, num_occupants_dev, occupancy_norm, and the ambient
+ * temperature at t by the weather block of a step's "now" half (t_amb_now, t_amb_dev[2 b], weather_lohi_dev with
+ * weather_f_now, the replay trace with weather_t_now) -- with a clock, each building's own row at pos. */
+int sb_observe_step_in(sb_handle *h, const sb_step_in *in, float *obs_dev, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

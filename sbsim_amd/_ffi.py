@@ -131,6 +131,12 @@ class RewardConfig(C.Structure):   # sb_reward_config
               ("carbon_cost_factor", C.c_double), ("normalizer_shift", C.c_double), ("normalizer_scale", C.c_double)]
 
 
+# enum sb_clock_field: the fields of one row of sb_clock_attach's table, in order
+CLOCK_FIELDS = ("t_amb", "weather_f", "weather_t", "comfort") + tuple(f"aux{i}" for i in range(SB_NUM_AUX)) + (
+    "occupancy", "e_price", "e_carbon", "g_price", "g_carbon", "occ_hour", "occ_workday", "occ_hour5", "occ_workday5")
+SB_CLOCK_FIELDS = len(CLOCK_FIELDS)   # 20
+SB_CLOCK_MAX_ROWS = 1 << 22
+
 SB_JACOBI_COEFS = 16   # floats per class row of sb_jacobi_desc.class_f32
 
 
@@ -158,12 +164,13 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_pb_zone_info", "sb_pb_variable_info", "sb_record_append", "sb_tap_pre", "sb_tap_post",
            "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi", "sb_set_building_params",
            "sb_set_reward_function", "sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials",
-           "sb_get_building_coef")
+           "sb_get_building_coef", "sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
 BUILDING_PARAM_ENTRIES = ("sb_set_building_params",)
 REWARD_ENTRIES = ("sb_set_reward_function",)
+CLOCK_ENTRIES = ("sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in")
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -255,6 +262,11 @@ def load():
     L.sb_plan_info_materials.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.c_int32, C.POINTER(LaunchInfo)]
     L.sb_set_building_materials.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.sb_get_building_coef.argtypes = [vp, vp, vp]
+  if all(hasattr(L, name) for name in CLOCK_ENTRIES):
+    L.sb_clock_attach.argtypes = [vp, vp, C.c_int32, C.c_int32, vp]
+    L.sb_clock_seek.argtypes = [vp, C.c_int32, C.c_int32]
+    L.sb_clock_detach.argtypes = [vp]
+    L.sb_observe_step_in.argtypes = [vp, C.POINTER(StepIn), vp, vp]
   _lib = L
   return L
 
@@ -286,6 +298,12 @@ def reward_entry(name: str):
 def materials_entry(name: str):
   """The per-building-materials entry `name` (sb_create_materials, sb_plan_info_materials, sb_set_building_materials,
   sb_get_building_coef): see entry()."""
+  return entry(name)
+
+
+def clock_entry(name: str):
+  """The per-building-calendar entry `name` (sb_clock_attach, sb_clock_seek, sb_clock_detach, sb_observe_step_in): see
+  entry()."""
   return entry(name)
 
 

@@ -32,20 +32,28 @@ struct OccArgs {
   long long first_building;
   uint32_t query;
   float *count, *total;
+  // sb_clock_attach: hour and workday per building, from its row at clk.pos + delta -- the row's t pair (SB_CLK_OCC_HOUR) or
+  // its t - 5 min pair (SB_CLK_OCC_HOUR5), `field` says which
+  ClockView clk;
+  int delta, field;
 };
 
 // ZoneOccupant.peek (randomized_arrival_departure_occupancy.py:138-160) for every occupant of
 // every zone of one building per thread.  Uniform of occupant i: word i & 3 of the Philox block
 // with counter (building lo, building hi, zone, query * 8 + (i >> 2)), u = (x >> 8) / 2^24.
+template <bool CLK> // a calendar per building: a kernel per value (sb_device.h, clocked)
 __global__ void k_occupancy(OccArgs o) {
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < o.B; b += gridDim.x * blockDim.x) {
     const unsigned long long gb = (unsigned long long)(o.first_building + b);
+    const int crow = clock_row<CLK>(o.clk, b) + o.delta;
+    const int hour = CLK ? (int)clocked<CLK>(o.clk, crow, o.field, 0.0) : o.hour;
+    const bool workday = CLK ? clocked<CLK>(o.clk, crow, o.field + 1, 0.0) != 0.0 : o.workday != 0;
     float tot = 0.0f;
     for (int z = 0; z < o.Z; ++z) {
       uint32_t st = o.state[(size_t)b * o.Z + z];
-      if (!o.workday) st = 0;
+      if (!workday) st = 0;
       else {
-        const bool arr_open = !(o.hour < o.e_arr || o.hour > o.l_arr), dep_open = !(o.hour < o.e_dep);
+        const bool arr_open = !(hour < o.e_arr || hour > o.l_arr), dep_open = !(hour < o.e_dep);
         if (arr_open || dep_open)
           for (int blk = 0; blk * 4 < o.n_occ; ++blk) {
             uint32_t c[4] = {(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)z, o.query * 8u + (uint32_t)blk};
@@ -451,9 +459,17 @@ int sb_occupancy_peek(sb_handle *h, int32_t local_hour, int32_t is_work_day, flo
   if (!h) return fail(SB_ERR_INVALID, "sb_occupancy_peek: null handle");
   if (!h->occ_attached) return fail(SB_ERR_INVALID, "sb_occupancy_peek: sb_occupancy_attach first");
   if (local_hour < 0 || local_hour > 23) return fail(SB_ERR_INVALID, "sb_occupancy_peek: hour must be 0..23");
+  OccArgs o;
+  o.clk = ClockView{}; o.delta = 0; o.field = SB_CLK_OCC_HOUR;
+  if (h->clock_rows.p) { // a calendar per building: the two arguments choose the row and its pair (sbsim_amd.h, sb_clock_seek)
+    if (h->clock_pos < 0) return fail(SB_ERR_INVALID, "sb_occupancy_peek: the handle has a clock that was never sought (sb_clock_seek)");
+    if (local_hour > 1) return fail(SB_ERR_INVALID, "sb_occupancy_peek: with a clock the hour argument is the row, 0 or 1");
+    o.clk = ClockView{h->clock_rows.p, h->clock_offs.p, h->clock_pos, h->clock_prev, h->clock_n_rows};
+    o.delta = local_hour;
+    o.field = is_work_day ? SB_CLK_OCC_HOUR : SB_CLK_OCC_HOUR5;
+  }
   SB_ON_DEVICE(h->device);
   const sb_occupancy_config &c = h->occ;
-  OccArgs o;
   o.state = h->occ_state.p; o.B = h->d.B; o.Z = h->d.Z; o.n_occ = c.zone_assignment;
   o.hour = local_hour; o.workday = is_work_day != 0;
   o.e_arr = c.earliest_arrival_hour; o.l_arr = c.latest_arrival_hour; o.e_dep = c.earliest_departure_hour;
@@ -463,7 +479,8 @@ int sb_occupancy_peek(sb_handle *h, int32_t local_hour, int32_t is_work_day, flo
   o.seed = c.seed; o.first_building = c.first_building; o.query = h->occ_queries++;
   o.count = count_dev; o.total = total_dev;
   const int blocks = std::max(1, std::min((o.B + 63) / 64, 4096));
-  hipLaunchKernelGGL(k_occupancy, dim3(blocks), dim3(64), 0, (hipStream_t)stream, o);
+  if (o.clk.rows) hipLaunchKernelGGL(k_occupancy<true>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, o);
+  else hipLaunchKernelGGL(k_occupancy<false>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, o);
   SB_HIP(hipGetLastError());
   return SB_OK;
 }

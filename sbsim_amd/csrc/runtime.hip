@@ -96,14 +96,16 @@ __global__ void k_reset(Dev a, double initial_temp, const double *temps, int fir
   }
 }
 
-__global__ void k_observe(Dev a, float *obs, float aux0, float aux1, float aux2, float aux3,
-                          float aux4, float aux5, float aux6, double t_amb, const double *t_amb_b,
-                          const float *num_occupants, double occ_norm) {
-  const float aux[SB_NUM_AUX] = {aux0, aux1, aux2, aux3, aux4, aux5, aux6};
+// in: the observation's inputs as a step's "now" half (aux, num_occupants_dev, occupancy_norm, the weather at t);
+// t_amb_b: sb_observe's [B] ambient temperatures (override); clk: the building's own row at the position sought
+template <bool CLK> // a calendar per building (sb_clock_attach): a kernel per value, see sb_device.h clocked()
+__global__ void k_observe(Dev a, ClockView clk, sb_step_in in, const double *t_amb_b, float *obs) {
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) {
     double *S = a.scal + (size_t)b * kNScal;
     observe_boiler(a, S, b);
-    write_obs(a, b, obs, aux, t_amb_b ? t_amb_b[b] : t_amb, S, num_occupants, occ_norm);
+    const int crow = clock_row<CLK>(clk, b);
+    write_obs<CLK>(a, b, obs, in.aux, t_amb_b ? t_amb_b[b] : ambient_temp<CLK>(in, clk, crow, b, false), S, in.num_occupants_dev,
+              in.occupancy_norm, clk, crow);
   }
 }
 
@@ -307,7 +309,7 @@ __global__ void k_copy_temps_jacobi(const float *grid, size_t n, double *out) {
 // order through DPP row broadcasts.  k_post: one thread per building (the row shape was measured slower: sb_device.h).
 // only >= 0: that building alone (the known-answer taps).
 constexpr int kRowsPerBlock = 16; // buildings per workgroup of 256 threads
-template <bool MAT> // the building's own coefficient rows (sb_create_materials): a kernel per value, see pre_building
+template <bool MAT, bool CLK> // the building's own coefficient rows (sb_create_materials), its own calendar (sb_clock_attach): a kernel per value, see pre_building
 __global__ void __launch_bounds__(16 * kRowsPerBlock) k_pre(Dev a, StepArgs s, int only) {
   if (blockIdx.x == 0 && threadIdx.x == 0) { // the sweep kernel's draw counter; k_sweep_roll: the redo list's counters
     *a.next_b = 0;
@@ -315,25 +317,29 @@ __global__ void __launch_bounds__(16 * kRowsPerBlock) k_pre(Dev a, StepArgs s, i
   }
   const int i = threadIdx.x & 15, r = threadIdx.x >> 4;
   if (only >= 0) {
-    if (blockIdx.x == 0 && r == 0) pre_building<MAT>(a, s, only, i);
+    if (blockIdx.x == 0 && r == 0) pre_building<MAT, CLK>(a, s, only, i);
     return;
   }
-  for (int b = blockIdx.x * kRowsPerBlock + r; b < a.B; b += gridDim.x * kRowsPerBlock) pre_building<MAT>(a, s, b, i);
+  for (int b = blockIdx.x * kRowsPerBlock + r; b < a.B; b += gridDim.x * kRowsPerBlock) pre_building<MAT, CLK>(a, s, b, i);
 }
 
 // k_pre of the handle (sb_create_materials: the variant that reads the building's own gc and sc); only >= 0: that building alone
 void launch_pre(const sb_handle *h, const StepArgs &s, dim3 grid, hipStream_t stream, int only) {
-  if (h->d.ctab_b) hipLaunchKernelGGL(k_pre<true>, grid, dim3(16 * kRowsPerBlock), 0, stream, h->d, s, only);
-  else hipLaunchKernelGGL(k_pre<false>, grid, dim3(16 * kRowsPerBlock), 0, stream, h->d, s, only);
+  const dim3 block(16 * kRowsPerBlock);
+  if (s.clk.rows) {
+    if (h->d.ctab_b) hipLaunchKernelGGL((k_pre<true, true>), grid, block, 0, stream, h->d, s, only);
+    else hipLaunchKernelGGL((k_pre<false, true>), grid, block, 0, stream, h->d, s, only);
+  } else if (h->d.ctab_b) hipLaunchKernelGGL((k_pre<true, false>), grid, block, 0, stream, h->d, s, only);
+  else hipLaunchKernelGGL((k_pre<false, false>), grid, block, 0, stream, h->d, s, only);
 }
 
-template <int KIND> // the reward function (sb_reward_kind): a kernel per kind, see post_building
+template <int KIND, bool CLK> // the reward function (sb_reward_kind), a calendar per building: a kernel per value, see post_building
 __global__ void __launch_bounds__(64) k_post(Dev a, StepArgs s, sb_reward_config rc, int only) { // one thread per building: see sb_device.h
   if (only >= 0) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) post_building<KIND>(a, s, rc, only);
+    if (blockIdx.x == 0 && threadIdx.x == 0) post_building<KIND, CLK>(a, s, rc, only);
     return;
   }
-  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) post_building<KIND>(a, s, rc, b);
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) post_building<KIND, CLK>(a, s, rc, b);
 }
 
 // sb_create_materials: every building's coefficient rows from its own materials and convection coefficient.  One thread
@@ -386,10 +392,12 @@ __global__ void __launch_bounds__(256) k_class_coef(const int4 *desc, const doub
 
 // k_post of the handle's reward function (sb_set_reward_function); only >= 0: that building alone
 void launch_post(const sb_handle *h, const StepArgs &s, dim3 grid, hipStream_t stream, int only) {
-  if (h->reward.kind == SB_REWARD_SETPOINT_ENERGY_CARBON)
-    hipLaunchKernelGGL(k_post<SB_REWARD_SETPOINT_ENERGY_CARBON>, grid, dim3(64), 0, stream, h->d, s, h->reward, only);
-  else
-    hipLaunchKernelGGL(k_post<SB_REWARD_REGRET>, grid, dim3(64), 0, stream, h->d, s, h->reward, only);
+  const bool dollars = h->reward.kind == SB_REWARD_SETPOINT_ENERGY_CARBON;
+  if (s.clk.rows) {
+    if (dollars) hipLaunchKernelGGL((k_post<SB_REWARD_SETPOINT_ENERGY_CARBON, true>), grid, dim3(64), 0, stream, h->d, s, h->reward, only);
+    else hipLaunchKernelGGL((k_post<SB_REWARD_REGRET, true>), grid, dim3(64), 0, stream, h->d, s, h->reward, only);
+  } else if (dollars) hipLaunchKernelGGL((k_post<SB_REWARD_SETPOINT_ENERGY_CARBON, false>), grid, dim3(64), 0, stream, h->d, s, h->reward, only);
+  else hipLaunchKernelGGL((k_post<SB_REWARD_REGRET, false>), grid, dim3(64), 0, stream, h->d, s, h->reward, only);
 }
 
 } // namespace
@@ -499,16 +507,40 @@ int sb_set_temps(sb_handle *h, const double *temps_dev, void *stream) {
   return SB_OK;
 }
 
+// The handle's clock as the kernels take it (sb_clock_attach / sb_clock_seek); rows == NULL without one.
+static int clock_view(const sb_handle *h, const char *who, ClockView *out) {
+  *out = ClockView{};
+  if (!h->clock_rows.p) return SB_OK;
+  if (h->clock_pos < 0) return fail(SB_ERR_INVALID, std::string(who) + ": the handle has a clock that was never sought (sb_clock_seek)");
+  *out = ClockView{h->clock_rows.p, h->clock_offs.p, h->clock_pos, h->clock_prev, h->clock_n_rows};
+  return SB_OK;
+}
+
+static int launch_observe(sb_handle *h, const sb_step_in &in, const double *t_amb_b, float *obs_dev, void *stream) {
+  ClockView clk;
+  SB_CHECK(clock_view(h, "sb_observe", &clk));
+  SB_ON_DEVICE(h->device);
+  const int blocks = std::max(1, std::min((h->d.B + 63) / 64, 4096));
+  if (clk.rows) hipLaunchKernelGGL(k_observe<true>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->d, clk, in, t_amb_b, obs_dev);
+  else hipLaunchKernelGGL(k_observe<false>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->d, clk, in, t_amb_b, obs_dev);
+  SB_HIP(hipGetLastError());
+  return SB_OK;
+}
+
 int sb_observe_occupancy(sb_handle *h, const float aux[SB_NUM_AUX], double t_amb, const double *t_amb_dev,
                          const float *num_occupants_dev, double occupancy_norm, float *obs_dev, void *stream) {
   if (!h || !aux || !obs_dev) return fail(SB_ERR_INVALID, "sb_observe: null argument");
-  SB_ON_DEVICE(h->device);
-  const int blocks = std::max(1, std::min((h->d.B + 63) / 64, 4096));
-  hipLaunchKernelGGL(k_observe, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->d, obs_dev, aux[0],
-                     aux[1], aux[2], aux[3], aux[4], aux[5], aux[6], t_amb, t_amb_dev, num_occupants_dev,
-                     occupancy_norm);
-  SB_HIP(hipGetLastError());
-  return SB_OK;
+  sb_step_in in{};
+  in.t_amb_now = t_amb;
+  in.num_occupants_dev = num_occupants_dev;
+  in.occupancy_norm = occupancy_norm;
+  std::copy_n(aux, SB_NUM_AUX, in.aux);
+  return launch_observe(h, in, t_amb_dev, obs_dev, stream);
+}
+
+int sb_observe_step_in(sb_handle *h, const sb_step_in *in, float *obs_dev, void *stream) {
+  if (!h || !in || !obs_dev) return fail(SB_ERR_INVALID, "sb_observe_step_in: null argument");
+  return launch_observe(h, *in, nullptr, obs_dev, stream);
 }
 
 int sb_observe(sb_handle *h, const float aux[SB_NUM_AUX], double t_amb, const double *t_amb_dev,
@@ -520,9 +552,10 @@ int sb_step_phases(sb_handle *h, const float *actions_dev, const sb_step_in *in,
                    float *reward_dev, float *info_dev, void *stream, int32_t phases) {
   if (!h || !in || !reward_dev) return fail(SB_ERR_INVALID, "sb_step: null argument");
   if (in->has_action && !actions_dev) return fail(SB_ERR_INVALID, "sb_step: has_action set but actions_dev is NULL");
-  SB_ON_DEVICE(h->device);
   StepArgs s;
   s.actions = actions_dev; s.obs = obs_dev; s.reward = reward_dev; s.info = info_dev; s.in = *in;
+  SB_CHECK(clock_view(h, "sb_step", &s.clk));
+  SB_ON_DEVICE(h->device);
   const Dev &d = h->d;
   const int blocks = std::max(1, std::min((d.B + kRowsPerBlock - 1) / kRowsPerBlock, h->cus * 32)); // a 16-lane row per building
   if (phases & SB_PHASE_PRE) {
@@ -789,6 +822,74 @@ int sb_get_building_coef(sb_handle *h, double *out_dev, void *stream) {
   SB_HIP(hipMemcpy2DAsync(out_dev, row, h->ctab_b.p, row + 8 * sizeof(double), row, (size_t)h->d.B, hipMemcpyDeviceToDevice,
                           (hipStream_t)stream));
   return SB_OK;
+}
+
+/* ---- a calendar per building ---- */
+static const char *const kClockFieldNames[SB_CLOCK_FIELDS] = {
+    "t_amb", "weather_f", "weather_t", "comfort", "aux[0]", "aux[1]", "aux[2]", "aux[3]", "aux[4]", "aux[5]", "aux[6]",
+    "occupancy", "e_price", "e_carbon", "g_price", "g_carbon", "occ_hour", "occ_workday", "occ_hour5", "occ_workday5"};
+
+static int drop_clock(sb_handle *h) { // the kernels in flight read the table: it goes once the device is idle
+  if (!h->clock_rows.p && !h->clock_offs.p) return SB_OK;
+  SB_HIP(hipDeviceSynchronize());
+  if (h->clock_rows.p) SB_HIP(hipFree(h->clock_rows.p));
+  h->clock_rows.p = nullptr;
+  if (h->clock_offs.p) SB_HIP(hipFree(h->clock_offs.p));
+  h->clock_offs.p = nullptr;
+  h->clock_n_rows = h->clock_max_off = 0;
+  h->clock_pos = h->clock_prev = -1;
+  return SB_OK;
+}
+
+int sb_clock_attach(sb_handle *h, const double *rows_host, int32_t n_rows, int32_t n_fields, const int32_t *offsets_host) {
+  if (!h || !rows_host || !offsets_host) return fail(SB_ERR_INVALID, "sb_clock_attach: null argument");
+  if (n_fields != SB_CLOCK_FIELDS)
+    return fail(SB_ERR_INVALID, "sb_clock_attach: n_fields is " + std::to_string(n_fields) + ", this library's rows have " +
+                                    std::to_string((int)SB_CLOCK_FIELDS) + " fields (sb_clock_field)");
+  if (n_rows > SB_CLOCK_MAX_ROWS) return fail(SB_ERR_TOO_LARGE, "sb_clock_attach: more than 2^22 rows");
+  if (n_rows < 2) return fail(SB_ERR_INVALID, "sb_clock_attach: a step reads two rows: n_rows must be at least 2");
+  const int B = h->d.B;
+  int max_off = 0;
+  for (int b = 0; b < B; ++b) {
+    if (offsets_host[b] < 0)
+      return fail(SB_ERR_INVALID, "sb_clock_attach: building " + std::to_string(b) + ": negative offset " + std::to_string(offsets_host[b]));
+    if (offsets_host[b] > n_rows - 2)
+      return fail(SB_ERR_INVALID, "sb_clock_attach: building " + std::to_string(b) + ": offset " + std::to_string(offsets_host[b]) +
+                                      " leaves no two rows of the table's " + std::to_string(n_rows));
+    max_off = std::max(max_off, (int)offsets_host[b]);
+  }
+  for (size_t i = 0; i < (size_t)n_rows * SB_CLOCK_FIELDS; ++i)
+    if (!std::isfinite(rows_host[i]))
+      return fail(SB_ERR_INVALID, "sb_clock_attach: row " + std::to_string(i / SB_CLOCK_FIELDS) + ": " +
+                                      kClockFieldNames[i % SB_CLOCK_FIELDS] + " is not finite");
+  SB_ON_DEVICE(h->device);
+  SB_CHECK(drop_clock(h));
+  SB_CHECK(upload(h->clock_rows, rows_host, (size_t)n_rows * SB_CLOCK_FIELDS));
+  SB_CHECK(upload(h->clock_offs, offsets_host, (size_t)B));
+  h->clock_n_rows = n_rows;
+  h->clock_max_off = max_off;
+  return SB_OK;
+}
+
+int sb_clock_seek(sb_handle *h, int32_t pos, int32_t prev_pos) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_clock_seek: null handle");
+  if (!h->clock_rows.p) return fail(SB_ERR_INVALID, "sb_clock_seek: sb_clock_attach first");
+  if (pos < 0 || prev_pos < -1) return fail(SB_ERR_INVALID, "sb_clock_seek: pos must be >= 0 and prev_pos >= -1");
+  // (64-bit sums: the rows a kernel reads stay inside the table whatever the arguments)
+  if ((long long)h->clock_max_off + pos > (long long)h->clock_n_rows - 2 ||
+      (long long)h->clock_max_off + prev_pos > (long long)h->clock_n_rows - 1)
+    return fail(SB_ERR_INVALID, "sb_clock_seek: position " + std::to_string(pos) + " (previous " + std::to_string(prev_pos) +
+                                    ") plus the largest offset " + std::to_string(h->clock_max_off) + " runs past the table's " +
+                                    std::to_string(h->clock_n_rows) + " rows");
+  h->clock_pos = pos;
+  h->clock_prev = prev_pos;
+  return SB_OK;
+}
+
+int sb_clock_detach(sb_handle *h) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_clock_detach: null handle");
+  SB_ON_DEVICE(h->device);
+  return drop_clock(h);
 }
 
 /* ---- the reward function ---- */

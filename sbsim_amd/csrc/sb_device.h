@@ -208,10 +208,38 @@ __device__ __forceinline__ double bparam(const Dev &a, int k, int b) {
   return a.bp ? a.bp[(size_t)k * a.B + b] : param_field(a.p, k);
 }
 
+// sb_clock_attach: a calendar per building.  rows: [n_rows][SB_CLOCK_FIELDS] what a step derives from an instant, one row
+// per instant of the lattice; offs: [B] every building's offset into it; pos / prev: the batch's position and that of the
+// previous thermostat update (-1: none), both sb_clock_seek's.  rows == NULL: no clock.  A kernel argument of k_pre, k_post,
+// k_observe and k_occupancy alone (StepArgs, not Dev: no sweep kernel carries it).
+struct ClockView {
+  const double *rows;
+  const int *offs;
+  int pos, prev, n_rows;
+};
+
+// CLK: the kernel was launched for a handle with a clock (c.rows != NULL).  A kernel per value, as k_pre per MAT and k_post
+// per reward kind: the test is made once, at launch, and a handle without a clock launches the code it always has -- the
+// helpers below fold to sb_step_in's scalar, so every result is today's, bit for bit, in the registers it had.
+// Building b's row "now" (its rows "next" and "previous": + 1, + c.prev - c.pos); 0 without a clock.
+template <bool CLK>
+__device__ __forceinline__ int clock_row(const ClockView &c, int b) {
+  if constexpr (CLK) return c.offs[b] + c.pos;
+  else return 0;
+}
+// A time-dependent input of a step: field `field` (sb_clock_field) of row `row` when there is a clock, else sb_step_in's
+// scalar.  Every such input of k_pre, k_post, k_observe and k_occupancy is read through this.
+template <bool CLK>
+__device__ __forceinline__ double clocked(const ClockView &c, int row, int field, double scalar) {
+  if constexpr (CLK) return c.rows[(size_t)row * SB_CLOCK_FIELDS + field];
+  else return scalar;
+}
+
 struct StepArgs {
   const float *actions;
   float *obs, *reward, *info;
   sb_step_in in;
+  ClockView clk;
 };
 
 // Host launchers (one per translation unit that defines a sweep kernel).
@@ -376,8 +404,10 @@ __device__ __forceinline__ void put_obs_n(const Dev &a, float *row, int n, const
 }
 
 // The air handler's and the boiler's fields, the histograms' normalisation, the auxiliary features (write_obs's second half).
+// clk, crow: the building's row of the auxiliary features when there is a clock (else `aux`).
+template <bool CLK>
 __device__ inline void write_obs_plant(const Dev &a, float *row, const float *aux, double t_amb_obs, const double *S,
-                                       const float *num_occupants, double occ_norm, int b) {
+                                       const float *num_occupants, double occ_norm, int b, const ClockView &clk, int crow) {
   const int n_ahu = a.p.ahu_has_weather ? 9 : 8;
   const double flow = S[2];
   const double ahu_dp = bparam(a, SB_BP_AHU_DP, b), ahu_max_flow = bparam(a, SB_BP_AHU_MAX_FLOW, b);
@@ -419,7 +449,7 @@ __device__ inline void write_obs_plant(const Dev &a, float *row, const float *au
       for (int j = 0; j < n; ++j) tot += (double)h[j];
       for (int j = 0; j < n; ++j) h[j] = (float)((double)h[j] / tot);
     }
-  for (int i = 0; i < SB_NUM_AUX; ++i) row[a.col_aux + i] = aux[i];
+  for (int i = 0; i < SB_NUM_AUX; ++i) row[a.col_aux + i] = (float)clocked<CLK>(clk, crow, SB_CLK_AUX0 + i, aux[i]); // (fp32 values both)
   if (num_occupants) // environment.py:951-955 with the building's own int(num_occupants)
     row[a.col_aux + SB_NUM_AUX - 1] = (float)(((double)(int)num_occupants[b] - occ_norm) / (occ_norm + 1.0));
 }
@@ -427,8 +457,10 @@ __device__ inline void write_obs_plant(const Dev &a, float *row, const float *au
 // One building's observation row, written by one thread.  S: the building's scalar state
 // (kNScalOut doubles).  Device columns in sorted (device, field) order (air_handler.py:66-95 /
 // boiler.py:69-79).
+template <bool CLK>
 __device__ inline void write_obs(const Dev &a, int b, float *obs, const float *aux, double t_amb_obs,
-                                 const double *S, const float *num_occupants = nullptr, double occ_norm = 0.0) {
+                                 const double *S, const float *num_occupants, double occ_norm, const ClockView &clk,
+                                 int crow) {
   float *row = obs + (size_t)b * a.O;
   for (int k = 0; k < a.n_hist; ++k)
     for (int j = a.hist_off[k]; j < a.hist_off[k + 1]; ++j) row[a.hist_col[k] + j - a.hist_off[k]] = 0.0f;
@@ -446,7 +478,7 @@ __device__ inline void write_obs(const Dev &a, int b, float *obs, const float *a
     }
     put_obs_n<12>(a, row, 3 * (a.Z - z0 < 4 ? a.Z - z0 : 4), src, val);
   }
-  write_obs_plant(a, row, aux, t_amb_obs, S, num_occupants, occ_norm, b);
+  write_obs_plant<CLK>(a, row, aux, t_amb_obs, S, num_occupants, occ_norm, b, clk, crow);
 }
 
 // ---------------------------------------------------------------- the step around the sweep
@@ -505,6 +537,24 @@ __device__ inline double replay_weather_kelvin(const double *xp, const double *f
   return __dadd_rn(__dmul_rn(f - 32.0, 5.0) / 9.0, 273.15);
 }
 
+// Building b's ambient temperature at a step's t (next == false) or t + dt: sb_step_in's three weather forms, their
+// time-dependent halves -- the replay's query time, the sinusoid's factor, the shared temperature -- read through the
+// clock (crow: the building's row of that instant).  k_pre's two calls and k_observe's one.
+template <bool CLK>
+__device__ __forceinline__ double ambient_temp(const sb_step_in &in, const ClockView &clk, int crow, int b, bool next) {
+  if (in.weather_times_dev) {
+    const double off = in.weather_offset_dev ? in.weather_offset_dev[b] : 0.0;
+    const double t = clocked<CLK>(clk, crow, SB_CLK_WEATHER_T, next ? in.weather_t_next : in.weather_t_now);
+    return replay_weather_kelvin(in.weather_times_dev, in.weather_tempf_dev, in.weather_n, t + off);
+  }
+  if (in.weather_lohi_dev) { // weather_controller.py:119-121, per building; no fma: the reference's two roundings
+    const double lo = in.weather_lohi_dev[2 * b], hi = in.weather_lohi_dev[2 * b + 1];
+    return __dadd_rn(__dmul_rn(clocked<CLK>(clk, crow, SB_CLK_WEATHER_F, next ? in.weather_f_next : in.weather_f_now), hi - lo), lo);
+  }
+  if (in.t_amb_dev) return in.t_amb_dev[2 * b + (next ? 1 : 0)];
+  return clocked<CLK>(clk, crow, SB_CLK_T_AMB, next ? in.t_amb_next : in.t_amb_now);
+}
+
 // Lane k of the calling lane's 16-lane DPP row broadcast to the row (row_newbcast:k).
 template <int K>
 __device__ __forceinline__ double row_bcast(double x) {
@@ -530,25 +580,18 @@ __device__ __forceinline__ void row_each(int n, double x0, double x1, double x2,
 // i: the lane's index in its row; every lane of the row runs the per-building (uniform) part -- same addresses, one transaction.
 // MAT (sb_create_materials): gc and sc come from the building's own coefficient rows (Dev::ctab_b); a kernel per value, as
 // k_post per reward kind -- a handle without such rows launches the code it always has.
-template <bool MAT>
+template <bool MAT, bool CLK>
 __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int i) {
   const sb_params &p = a.p;
   const sb_step_in &in = s.in;
   const double *S = a.scal + (size_t)b * kNScal;
   const size_t zb = (size_t)b * a.Z;
   Bld v;
-  if (in.weather_times_dev) {
-    const double off = in.weather_offset_dev ? in.weather_offset_dev[b] : 0.0;
-    v.t_now = replay_weather_kelvin(in.weather_times_dev, in.weather_tempf_dev, in.weather_n, in.weather_t_now + off);
-    v.t_next = replay_weather_kelvin(in.weather_times_dev, in.weather_tempf_dev, in.weather_n, in.weather_t_next + off);
-  } else if (in.weather_lohi_dev) { // weather_controller.py:119-121, per building; no fma: the reference's two roundings
-    const double lo = in.weather_lohi_dev[2 * b], hi = in.weather_lohi_dev[2 * b + 1];
-    v.t_now = __dadd_rn(__dmul_rn(in.weather_f_now, hi - lo), lo);
-    v.t_next = __dadd_rn(__dmul_rn(in.weather_f_next, hi - lo), lo);
-  } else {
-    v.t_now = in.t_amb_dev ? in.t_amb_dev[2 * b] : in.t_amb_now;
-    v.t_next = in.t_amb_dev ? in.t_amb_dev[2 * b + 1] : in.t_amb_next;
-  }
+  // the building's own calendar (sb_clock_attach): its row "now"; the 16 lanes of the row read one address
+  const int crow = clock_row<CLK>(s.clk, b);
+  v.t_now = ambient_temp<CLK>(in, s.clk, crow, b, false);
+  v.t_next = ambient_temp<CLK>(in, s.clk, crow + 1, b, true);
+  const int comfort_now = (int)clocked<CLK>(s.clk, crow, SB_CLK_COMFORT, (double)in.comfort_now);
   v.heat_sp = S[0]; v.cool_sp = S[1]; v.blr_sp = S[4];
   const double recirc = S[11], S8 = S[8], S9 = S[9], S10 = S[10], S18 = S[18];
   double age = S[19];
@@ -594,14 +637,16 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
     }
     gt[c] = gg;
   }
-  const double hsp = in.comfort_now ? bparam(a, SB_BP_COMFORT_LO, b) : bparam(a, SB_BP_ECO_LO, b);
-  const double csp = in.comfort_now ? bparam(a, SB_BP_COMFORT_HI, b) : bparam(a, SB_BP_ECO_HI, b);
+  const double hsp = comfort_now ? bparam(a, SB_BP_COMFORT_LO, b) : bparam(a, SB_BP_ECO_LO, b);
+  const double csp = comfort_now ? bparam(a, SB_BP_COMFORT_HI, b) : bparam(a, SB_BP_ECO_HI, b);
   const double vav_max_air_flow = bparam(a, SB_BP_VAV_MAX_AIR_FLOW, b);
   const double vav_max_water_flow = bparam(a, SB_BP_VAV_MAX_WATER_FLOW, b);
   const double ahu_max_flow = bparam(a, SB_BP_AHU_MAX_FLOW, b);
   // Thermostat._previous_timestamp (thermostat.py:88): the host's value, or the building's own when
   // buildings can skip thermostat updates (scal[18]: -1 none, else is_comfort_mode of the last update)
-  const int comfort_prev = in.reject_dev ? (int)S18 : in.comfort_prev;
+  const int comfort_prev = in.reject_dev ? (int)S18
+                           : CLK && s.clk.prev < 0 ? -1
+                           : (int)clocked<CLK>(s.clk, crow + s.clk.prev - s.clk.pos, SB_CLK_COMFORT, (double)in.comfort_prev);
   double ahu_flow = 0.0, blr_flow = 0.0, num = 0.0, den = 0.0;
   int ahu_count = 0, blr_count = 0;
   for (int z0 = 0; z0 < a.Z; z0 += 16) { // sixteen zones at a time, a lane each; then their demand in zone order
@@ -613,7 +658,7 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
     int mode = mraw & kModeMask;            // thermostat.py:114-148
     bool valve_open = (mraw & kValveBit) != 0;
     if (!rejected) {
-      if (in.comfort_now) mode = default_control(mode, tz, hsp, csp);
+      if (comfort_now) mode = default_control(mode, tz, hsp, csp);
       else if (comfort_prev == 1) mode = 3;
       else if (!(mode == 3 && tz > hsp)) mode = default_control(mode, tz, hsp, csp);
       valve_open = mode == 1;               // vav.py:229-243: update_settings writes damper and valve
@@ -668,7 +713,7 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
     if (boiler_action || !none) v.duration = age * p.dt;
   }
   v.action_age = age;
-  v.comfort_seen = rejected ? (int)S18 : in.comfort_now;
+  v.comfort_seen = rejected ? (int)S18 : comfort_now;
   const double heating_rate = bparam(a, SB_BP_BLR_HEATING_RATE, b), cooling_rate = bparam(a, SB_BP_BLR_COOLING_RATE, b);
   if (cooling_rate > 0.0 && heating_rate > 0.0) {
     const double begin = v.tank;
@@ -689,7 +734,7 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
 // k_post, one thread per building.  reward_info (simulator.py:457-576) + the reward function KIND (sb_reward_kind: a
 // template parameter, one k_post per kind chosen at launch -- the default kernel carries nothing of the other reward)
 // on fp32 proto fields, scalar state, observation row, from the sweep kernel's zone sums / grid sum.
-template <int KIND>
+template <int KIND, bool CLK>
 __device__ inline void post_building(const Dev &a, const StepArgs &s, const sb_reward_config &rc, int b) {
   const sb_params &p = a.p;
   const sb_step_in &in = s.in;
@@ -699,8 +744,11 @@ __device__ inline void post_building(const Dev &a, const StepArgs &s, const sb_r
   const double recirc2 = a.gsum[b] / (double)a.N;
   const int n_sweeps = a.nsw[b] & 0xffff, converged = a.nsw[b] >> 16;
   // the building's own parameters (bparam) are read where they are used: one coalesced load per field and wavefront
-  const double hsp2 = (double)(float)(in.comfort_next ? bparam(a, SB_BP_COMFORT_LO, b) : bparam(a, SB_BP_ECO_LO, b));
-  const double csp2 = (double)(float)(in.comfort_next ? bparam(a, SB_BP_COMFORT_HI, b) : bparam(a, SB_BP_ECO_HI, b));
+  // the building's own calendar (sb_clock_attach): its row "next" (t + dt), each field read where it is used, like bparam
+  const int cnext = clock_row<CLK>(s.clk, b) + 1;
+  const int comfort_next = (int)clocked<CLK>(s.clk, cnext, SB_CLK_COMFORT, (double)in.comfort_next);
+  const double hsp2 = (double)(float)(comfort_next ? bparam(a, SB_BP_COMFORT_LO, b) : bparam(a, SB_BP_ECO_LO, b));
+  const double csp2 = (double)(float)(comfort_next ? bparam(a, SB_BP_COMFORT_HI, b) : bparam(a, SB_BP_ECO_HI, b));
   double cumulative = 0.0, total_occ = 0.0;
   for (int z0 = 0; z0 < a.Z; z0 += 8) { // eight zones' inputs first (as in pre_building), then their arithmetic in zone order
    double zs8[8], oc8[8];
@@ -711,7 +759,8 @@ __device__ inline void post_building(const Dev &a, const StepArgs &s, const sb_r
      zs8[k] = a.zsum[zb + zz];
      zn8[k] = a.zone_off[zz + 1] - a.zone_off[zz];
      oc8[k] = in.occupancy_bz_dev ? (double)in.occupancy_bz_dev[zb + zz]
-                                  : (double)(float)(in.occupancy_dev ? in.occupancy_dev[zz] : in.occupancy);
+                                  : (double)(float)(in.occupancy_dev ? in.occupancy_dev[zz]
+                                                                     : clocked<CLK>(s.clk, cnext, SB_CLK_OCCUPANCY, in.occupancy));
    }
 #pragma unroll
    for (int k = 0; k < 8; ++k) {
@@ -769,7 +818,7 @@ __device__ inline void post_building(const Dev &a, const StepArgs &s, const sb_r
       I[4] = (float)n_sweeps; I[5] = (float)converged; I[6] = (float)v.t_sa; I[7] = (float)reward;
       resp(I);
     }
-    if (s.obs) write_obs(a, b, s.obs, in.aux, v.t_next, S, in.num_occupants_dev, in.occupancy_norm);
+    if (s.obs) write_obs<CLK>(a, b, s.obs, in.aux, v.t_next, S, in.num_occupants_dev, in.occupancy_norm, s.clk, cnext);
   };
 
   if constexpr (KIND == SB_REWARD_SETPOINT_ENERGY_CARBON) {
@@ -780,8 +829,10 @@ __device__ inline void post_building(const Dev &a, const StepArgs &s, const sb_r
     // :128-132).  response.carbon_cost is read back from its proto float field for the reward (:177, :183).
     const double elec = ((double)blower + fabs((double)ac)) + (double)pump;
     const double gas_rate = (double)gas < 0.0 ? 0.0 : (double)gas;
-    const double ce = in.e_price * fabs(elec) * p.dt, ke = in.e_carbon * fabs(elec) * p.dt;
-    const double cg = in.g_price * (gas_rate * p.dt), kg = in.g_carbon * (gas_rate * p.dt);
+    const double e_price = clocked<CLK>(s.clk, cnext, SB_CLK_E_PRICE, in.e_price), e_carbon = clocked<CLK>(s.clk, cnext, SB_CLK_E_CARBON, in.e_carbon);
+    const double g_price = clocked<CLK>(s.clk, cnext, SB_CLK_G_PRICE, in.g_price), g_carbon = clocked<CLK>(s.clk, cnext, SB_CLK_G_CARBON, in.g_carbon);
+    const double ce = e_price * fabs(elec) * p.dt, ke = e_carbon * fabs(elec) * p.dt;
+    const double cg = g_price * (gas_rate * p.dt), kg = g_carbon * (gas_rate * p.dt);
     const double carbon = ke + kg;
     const float carbon_cost = (float)(carbon * rc.carbon_cost_factor);
     const double raw = cumulative - rc.energy_cost_weight * (ce + cg) - rc.carbon_cost_weight * (double)carbon_cost;
@@ -803,10 +854,12 @@ __device__ inline void post_building(const Dev &a, const StepArgs &s, const sb_r
     const double elec = ((double)blower + fabs((double)ac)) + (double)pump;
     const double cap_e = fmin(elec, max_elec);
     const double cap_g = fmax(fmin((double)gas, max_gas), 0.0);
-    const double ce = in.e_price * fabs(cap_e) * p.dt, ce_max = in.e_price * fabs(max_elec) * p.dt;
-    const double ke = in.e_carbon * fabs(cap_e) * p.dt, ke_max = in.e_carbon * fabs(max_elec) * p.dt;
-    const double cg = in.g_price * (cap_g * p.dt), cg_max = in.g_price * (max_gas * p.dt);
-    const double kg = in.g_carbon * (cap_g * p.dt), kg_max = in.g_carbon * (max_gas * p.dt);
+    const double e_price = clocked<CLK>(s.clk, cnext, SB_CLK_E_PRICE, in.e_price), e_carbon = clocked<CLK>(s.clk, cnext, SB_CLK_E_CARBON, in.e_carbon);
+    const double g_price = clocked<CLK>(s.clk, cnext, SB_CLK_G_PRICE, in.g_price), g_carbon = clocked<CLK>(s.clk, cnext, SB_CLK_G_CARBON, in.g_carbon);
+    const double ce = e_price * fabs(cap_e) * p.dt, ce_max = e_price * fabs(max_elec) * p.dt;
+    const double ke = e_carbon * fabs(cap_e) * p.dt, ke_max = e_carbon * fabs(max_elec) * p.dt;
+    const double cg = g_price * (cap_g * p.dt), cg_max = g_price * (max_gas * p.dt);
+    const double kg = g_carbon * (cap_g * p.dt), kg_max = g_carbon * (max_gas * p.dt);
     const double nec = (ce + cg) / (ce_max + cg_max);
     const double nce = (ke + kg) / (ke_max + kg_max);
     const double reward =

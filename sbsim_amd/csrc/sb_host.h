@@ -191,6 +191,11 @@ struct sb_handle {
   sb_occupancy_config occ{};
   uint32_t occ_queries = 0;
   bool occ_attached = false;
+  // sb_clock_attach / sb_clock_seek: the table of instants, the buildings' offsets, the position of the next step
+  DevBuf<double> clock_rows;        // [clock_n_rows][SB_CLOCK_FIELDS]; NULL: no clock
+  DevBuf<int> clock_offs;           // [B]
+  int clock_n_rows = 0, clock_max_off = 0;
+  int clock_pos = -1, clock_prev = -1; // pos < 0: never sought
   // sb_create_materials: the structural classes' descriptors, the buildings' values and their coefficient rows
   bool materials = false;
   int mat_slots = 0;                // M

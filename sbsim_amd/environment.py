@@ -362,6 +362,7 @@ class BatchedSimulator:
     self._reward_function = None   # set_reward_function: None -- the default regret function of the SimConfig
     self._materials_handle = building_materials is not None   # sb_create_materials made the handle
     self._building_materials = None   # set_building_materials: the rows in force (None: the plan's own values)
+    self._clock_offsets = None   # clock_attach: the buildings' offsets into the timeline (None: one clock for the batch)
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -593,6 +594,43 @@ class BatchedSimulator:
         self._h, int(local_hour), int(bool(is_work_day)), C.c_void_p(count.data_ptr()) if count is not None else None,
         C.c_void_p(total.data_ptr()) if total is not None else None, self._stream()), "sb_occupancy_peek")
 
+  # ---- a calendar per building (sb_clock_attach / sb_clock_seek) ----
+  def clock_attach(self, rows: np.ndarray, offsets: np.ndarray) -> None:
+    """sb_clock_attach: ``rows`` float64 [n_rows, SB_CLOCK_FIELDS] (``host_inputs.Timeline.rows``), ``offsets`` int32 [B].
+    The library copies both; ``clock_seek`` before the first step, observation or occupancy query.  Configuration of the
+    buildings' slots, as ``set_building_params``: snapshots do not carry it, a forked building keeps its slot's offset."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    if rows.ndim != 2 or offsets.shape != (self.B,):
+      raise ValueError(f"clock_attach needs rows [n_rows, {_ffi.SB_CLOCK_FIELDS}] and offsets [{self.B}]")
+    with torch.cuda.device(self.device):
+      rc = _ffi.clock_entry("sb_clock_attach")(self._h, rows.ctypes.data_as(C.c_void_p), int(rows.shape[0]),
+                                               int(rows.shape[1]), offsets.ctypes.data_as(C.c_void_p))
+    if rc in (-1, -4):   # SB_ERR_INVALID, SB_ERR_TOO_LARGE
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_clock_attach")
+    self._clock_offsets = offsets.copy()
+
+  def clock_seek(self, pos: int, prev_pos: int = -1) -> None:
+    """sb_clock_seek: the position of the next step, observation and occupancy query (a host value: no device work);
+    prev_pos: the position of the previous thermostat update, -1 for none."""
+    rc = _ffi.clock_entry("sb_clock_seek")(self._h, int(pos), int(prev_pos))
+    if rc == -1:
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_clock_seek")
+
+  def clock_detach(self) -> None:
+    with torch.cuda.device(self.device):
+      _ffi.check(_ffi.clock_entry("sb_clock_detach")(self._h), "sb_clock_detach")
+    self._clock_offsets = None
+
+  def observe_step_in(self, step_in: _ffi.StepIn, out: torch.Tensor) -> torch.Tensor:
+    """sb_observe_step_in: the observation with its inputs in a StepIn (the weather forms per building; with a clock,
+    every building's own row)."""
+    _ffi.check(_ffi.clock_entry("sb_observe_step_in")(self._h, C.byref(step_in), C.c_void_p(out.data_ptr()), self._stream()),
+               "sb_observe_step_in")
+    return out
+
   def observe(self, aux: Sequence[float], t_amb, out: Optional[torch.Tensor] = None,
               num_occupants: Optional[torch.Tensor] = None, occupancy_norm: float = 0.0) -> torch.Tensor:
     """t_amb: one ambient temperature, or a float64 [B] device tensor (per-building weather).
@@ -754,6 +792,8 @@ class BatchedSimulator:
       fp += (("reward_function",) + self._reward_function.as_tuple(),)
     if self._materials_handle:   # (a table is configuration, not state: the marker says which class map the state means)
       fp += (("building_materials",),)
+    if self._clock_offsets is not None:   # (the offsets stay with the slots; a snapshot restores where they are the same)
+      fp += (("clock", _sha(self._clock_offsets)),)
     return fp
 
   def save_state(self, rows: Optional[torch.Tensor] = None) -> SimState:
@@ -910,8 +950,12 @@ class BatchedEnvironment:
                normalize_reduce: bool = False, convection_simulator=None, solver: str = "gauss_seidel",
                building_params: Optional[host_inputs.BuildingParams] = None,
                reward_function: Optional[host_inputs.SetpointEnergyCarbonReward] = None,
-               building_materials: Optional[host_inputs.BuildingMaterials] = None):
-    """``solver``: the finite-difference solver (BatchedSimulator): "gauss_seidel" (default) or "jacobi_fp32"
+               building_materials: Optional[host_inputs.BuildingMaterials] = None, start_offsets=None):
+    """``start_offsets``: None -- every building lives at ``start_timestamp + step * step_interval``; an integer array
+    [B] of whole step intervals (>= 0) -- building b lives at ``start_timestamp + (start_offsets[b] + step) *
+    step_interval``: its own calendar (time features, setpoint schedule, tariffs, occupancy, weather) on the batch's one
+    episode clock (``current_simulation_timestamps()``).
+    ``solver``: the finite-difference solver (BatchedSimulator): "gauss_seidel" (default) or "jacobi_fp32"
     (TFSimulator, SB1's shipped configuration; no convection_simulator, snapshot, restore or fork).
     ``building_params``: per-building plant, setpoint and reward parameters (``set_building_params``).
     ``building_materials``: per-building materials and convection coefficient (``set_building_materials``); such an
@@ -966,6 +1010,13 @@ class BatchedEnvironment:
     self._step_interval = dt.timedelta(seconds=self.config.time_step_sec)
     # environment.py:427-435
     self._num_timesteps_in_episode = int(dt.timedelta(days=num_days_in_episode) / self._step_interval)
+    self.start_offsets = self.timeline = self._cursor = None
+    if start_offsets is not None:   # a calendar per building: the table of instants, built once, and the offsets into it
+      self.start_offsets = host_inputs.check_start_offsets(start_offsets, self.batch_size)
+      self.timeline = host_inputs.Timeline(self._models(), self._start_timestamp, self.start_offsets,
+                                           self._num_timesteps_in_episode)
+      self.sim.clock_attach(self.timeline.rows, self.start_offsets)
+      self._cursor = host_inputs.ClockCursor()
     self._action_spec = ArraySpec((self.sim.n_actions,), np.dtype(np.float32), "action", -1.0, 1.0)
     self._observation_spec = ArraySpec((self.sim.O,), np.dtype(np.float32), "observation")
     self.field_names = self.sim.field_names
@@ -1006,68 +1057,77 @@ class BatchedEnvironment:
   def info(self) -> Optional[torch.Tensor]:
     return self._info
 
+  def current_simulation_timestamps(self) -> List[dt.datetime]:
+    """Every building's own instant: ``current_simulation_timestamp`` (the batch's base clock) moved by the building's
+    start offset; without ``start_offsets``, the base clock B times."""
+    if self.start_offsets is None:
+      return [self._now] * self.batch_size
+    return [self._now + int(o) * self._step_interval for o in self.start_offsets]
+
   # ---- host-side step inputs ----
+  def _models(self) -> host_inputs.StepModels:
+    """The host models in force (``restore`` may have replaced a stateful one) as the step-input functions take them."""
+    return host_inputs.StepModels(self.weather, self.schedule, self.occupancy, self.electricity, self.gas,
+                                  self._step_interval, tuple(self.sim.zone_names[:self.sim.Z]), self._occ_norm)
+
   def _aux(self, ts: dt.datetime):
     """environment.py:916-956 auxiliary features at the observation time."""
-    hod = host_inputs.get_radian_time(ts, hour_of_day=True)
-    dow = host_inputs.get_radian_time(ts, hour_of_day=False)
-    n_occ = 0.0   # simulator_building.py:305-315
     if self._occ_total is not None:   # per building, on the device: overrides aux[6]
       t5 = ts - dt.timedelta(minutes=5)
-      self.sim.occupancy_peek(self.occupancy.local(t5).hour, self.occupancy.is_work_day(t5), None, self._occ_total)
-    elif isinstance(self.occupancy, host_inputs.StepFunctionOccupancy):
-      v = self.occupancy.average_zone_occupancy("", ts - dt.timedelta(minutes=5), ts)   # stateless, the same for
-      for _ in range(self.sim.Z):                                                        # every zone: one query,
-        n_occ += v                                                                       # the reference's sum
-    else:
-      for z in range(self.sim.Z):
-        n_occ += self.occupancy.average_zone_occupancy(self.sim.zone_names[z], ts - dt.timedelta(minutes=5), ts)
-    n_occ = int(n_occ)
-    return [np.float32(np.cos(hod)), np.float32(np.sin(hod)), np.float32(np.cos(dow)),
-            np.float32(np.sin(dow)), np.float32(self.schedule.is_comfort_mode(ts)),
-            np.float32(self.schedule.is_comfort_mode(ts + dt.timedelta(minutes=60))),
-            np.float32((n_occ - self._occ_norm) / (self._occ_norm + 1))]
+      self.sim.occupancy_peek(*host_inputs.occupancy_clock(self.occupancy, t5), None, self._occ_total)
+    return host_inputs.aux_features(self._models(), ts)
 
-  def make_step_in(self, ts: dt.datetime, has_action: bool = True) -> _ffi.StepIn:
-    nxt = ts + self._step_interval
-    si = _ffi.StepIn()
+  def _device_inputs(self, si: _ffi.StepIn) -> None:
+    """The fields of a StepIn that do not depend on the instant: the per-building weather's device tables."""
     if self._weather_replay is not None:   # per-building replay weather, interpolated on the device
       tt, tf, off = self._weather_replay
       si.weather_times_dev, si.weather_tempf_dev, si.weather_offset_dev = tt.data_ptr(), tf.data_ptr(), off.data_ptr()
       si.weather_n = int(tt.shape[0])
-      si.weather_t_now, si.weather_t_next = self.weather.query_time(ts), self.weather.query_time(nxt)
     elif isinstance(self.weather, host_inputs.BatchedSinusoidWeather):   # per-building weather, on the device
       si.weather_lohi_dev = self._weather_lohi.data_ptr()
-      si.weather_f_now, si.weather_f_next = self.weather.factor(ts), self.weather.factor(nxt)
-    else:
-      si.t_amb_now = self.weather.get_current_temp(ts)
-      si.t_amb_next = self.weather.get_current_temp(nxt)
-    si.comfort_now = int(self.schedule.is_comfort_mode(ts))
-    si.comfort_prev = (-1 if self._prev_thermostat_ts is None
-                       else int(self.schedule.is_comfort_mode(self._prev_thermostat_ts)))
-    si.comfort_next = int(self.schedule.is_comfort_mode(nxt))
+
+  def make_step_in(self, ts: dt.datetime, has_action: bool = True) -> _ffi.StepIn:
+    """The step's host-resolved inputs at ``ts`` (sb_step_in): ``host_inputs.step_inputs``, built from the functions a
+    ``Timeline`` row is built from, and the device occupancy's two queries."""
+    nxt = ts + self._step_interval
+    si = _ffi.StepIn()
+    self._device_inputs(si)
+    d = host_inputs.step_inputs(self._models(), ts, self._prev_thermostat_ts)
+    for name in host_inputs.STEP_INPUT_SCALARS:
+      setattr(si, name, d[name])
     si.has_action = int(has_action)
+    for i, v in enumerate(d["aux"]):
+      si.aux[i] = float(v)
     # the reference asks the occupancy model in this order (environment.py:1310-1330):
     # _get_observation (num_occupants), then _get_reward (reward_info) -- it matters for the
     # randomized model, whose every query advances the occupants
-    for i, v in enumerate(self._aux(nxt)):
-      si.aux[i] = float(v)
     if self._occ_count is not None:
-      self.sim.occupancy_peek(self.occupancy.local(nxt).hour, self.occupancy.is_work_day(nxt), self._occ_count, None)
+      self.sim.occupancy_peek(*host_inputs.occupancy_clock(self.occupancy, nxt - dt.timedelta(minutes=5)), None, self._occ_total)
+      self.sim.occupancy_peek(*host_inputs.occupancy_clock(self.occupancy, nxt), self._occ_count, None)
       si.occupancy_bz_dev = self._occ_count.data_ptr()
       si.num_occupants_dev = self._occ_total.data_ptr()
       si.occupancy_norm = self._occ_norm
-    elif isinstance(self.occupancy, host_inputs.RandomizedArrivalDepartureOccupancy):
-      occ = [self.occupancy.average_zone_occupancy(self.sim.zone_names[z], nxt, nxt + self._step_interval)
-             for z in range(self.sim.Z)]   # one shared instance: per-zone values, same for every building
-      self._occ_zone = torch.tensor(occ, dtype=torch.float64, device=self.sim.tdev)
+    elif isinstance(d["occupancy"], list):   # one shared randomized instance: per-zone values, same for every building
+      self._occ_zone = torch.tensor(d["occupancy"], dtype=torch.float64, device=self.sim.tdev)
       si.occupancy_dev = self._occ_zone.data_ptr()
     else:
-      si.occupancy = self.occupancy.average_zone_occupancy("", nxt, nxt + self._step_interval)
-    self._occ_host = occ if si.occupancy_dev else si.occupancy   # what the step's RewardInfo holds (episode_writer.py)
-    start_utc = host_inputs.reward_start_time_utc(nxt)
-    si.e_price, si.e_carbon = self.electricity.rates(start_utc)
-    si.g_price, si.g_carbon = self.gas.rates(start_utc)
+      si.occupancy = d["occupancy"]
+    self._occ_host = d["occupancy"]   # what the step's RewardInfo holds (episode_writer.py)
+    return si
+
+  def _clock_step_in(self, has_action: bool = True) -> _ffi.StepIn:
+    """A step's StepIn under a calendar per building: what does not depend on the instant; the library reads the rest from
+    every building's own rows at the position sought.  The device occupancy is asked in make_step_in's order."""
+    si = _ffi.StepIn()
+    self._device_inputs(si)
+    si.has_action = int(has_action)
+    self.sim.clock_seek(*self._cursor.seek_args())
+    if self._occ_count is not None:
+      self.sim.occupancy_peek(1, 0, None, self._occ_total)   # the next row's t - 5 min pair: num_occupants' query
+      self.sim.occupancy_peek(1, 1, self._occ_count, None)   # ... its t pair: the reward's query
+      si.occupancy_bz_dev = self._occ_count.data_ptr()
+      si.num_occupants_dev = self._occ_total.data_ptr()
+      si.occupancy_norm = self._occ_norm
     return si
 
   # ---- PyEnvironment API ----
@@ -1079,11 +1139,21 @@ class BatchedEnvironment:
     self._episode_count += 1
     self._step_count = 0
     self._needs_reset = False
-    if isinstance(self.weather, (host_inputs.BatchedSinusoidWeather, host_inputs.BatchedReplayWeather)):
-      t_amb = torch.tensor(self.weather.temps(self._now), dtype=torch.float64, device=self.sim.tdev)
+    if self._cursor is not None:   # every building's observation at its own instant: the rows at position 0
+      self._cursor.reset()
+      self.sim.clock_seek(*self._cursor.seek_args())
+      si = _ffi.StepIn()
+      self._device_inputs(si)
+      if self._occ_total is not None:
+        self.sim.occupancy_peek(0, 0, None, self._occ_total)   # this row's t - 5 min pair
+        si.num_occupants_dev, si.occupancy_norm = self._occ_total.data_ptr(), self._occ_norm
+      self.sim.observe_step_in(si, self._obs)
     else:
-      t_amb = self.weather.get_current_temp(self._now)
-    self.sim.observe(self._aux(self._now), t_amb, self._obs, self._occ_total, self._occ_norm)
+      if isinstance(self.weather, (host_inputs.BatchedSinusoidWeather, host_inputs.BatchedReplayWeather)):
+        t_amb = torch.tensor(self.weather.temps(self._now), dtype=torch.float64, device=self.sim.tdev)
+      else:
+        t_amb = self.weather.get_current_temp(self._now)
+      self.sim.observe(self._aux(self._now), t_amb, self._obs, self._occ_total, self._occ_norm)
     first = torch.full((self.batch_size,), STEP_FIRST, dtype=torch.int32, device=self.sim.tdev)
     return TimeStep(first, self._zero, torch.ones_like(self._discount), self._obs)
 
@@ -1097,7 +1167,7 @@ class BatchedEnvironment:
     overwrites them (clone what you keep across steps)."""
     if self._needs_reset or self._episode_ended:
       return self.reset()
-    si = self.make_step_in(self._now)
+    si = self.make_step_in(self._now) if self._cursor is None else self._clock_step_in()
     if rejected is not None:
       if tuple(rejected.shape) != (self.batch_size,) or rejected.device != self.sim.tdev:
         raise ValueError(f"rejected must be a [{self.batch_size}] tensor on {self.sim.tdev}")
@@ -1112,6 +1182,8 @@ class BatchedEnvironment:
     self.sim.step(action, si, self._obs, self._reward, self._info)
     self._prev_thermostat_ts = self._now
     self._now = self._now + self._step_interval
+    if self._cursor is not None:
+      self._cursor.advance()
     self._episode_ended = self._step_count >= self._num_timesteps_in_episode   # :1366-1368
     dev = self.sim.tdev
     if self._episode_ended:
@@ -1196,6 +1268,9 @@ class BatchedEnvironment:
       setattr(self, k, v)
     for k, v in models.items():
       setattr(self, k, v)
+    if self._cursor is not None:   # the restored clock, as positions on the timeline (the next step re-seeks)
+      at = lambda t: None if t is None else int(round((t - self._start_timestamp) / self._step_interval))
+      self._cursor = host_inputs.ClockCursor(at(self._now), at(self._prev_thermostat_ts))
     if snap.rejected is not None:
       self._rejected = snap.rejected.clone()
     elif getattr(self, "_rejected", None) is not None:

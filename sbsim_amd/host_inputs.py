@@ -15,7 +15,7 @@ from __future__ import annotations
 import csv
 import datetime as dt
 import math
-from typing import Dict, Iterable, Mapping, Optional, Sequence, Set, Tuple
+from typing import Dict, Iterable, List, Mapping, NamedTuple, Optional, Sequence, Set, Tuple
 from zoneinfo import ZoneInfo
 
 import numpy as np
@@ -567,6 +567,215 @@ def get_radian_time(ts, hour_of_day: bool) -> float:
   else:
     frac = float(ts.weekday()) / 7.0
   return 2.0 * np.pi * frac
+
+
+# --------------------------------------------------------------------------- what a step derives from an instant
+class StepModels(NamedTuple):
+  """The host models one environment resolves its step inputs with, and the three constants that go with them."""
+  weather: object
+  schedule: SetpointSchedule
+  occupancy: object
+  electricity: ElectricityEnergyCost
+  gas: NaturalGasEnergyCost
+  step_interval: dt.timedelta
+  zone_names: Tuple[str, ...]
+  occupancy_norm: float
+
+
+def weather_inputs(weather, ts) -> Tuple[float, float, float]:
+  """(t_amb, weather_f, weather_t) of sb_step_in at ``ts``: the form the weather model uses, 0.0 for the other two."""
+  if isinstance(weather, BatchedReplayWeather):
+    return 0.0, 0.0, weather.query_time(ts)
+  if isinstance(weather, BatchedSinusoidWeather):
+    return 0.0, weather.factor(ts), 0.0
+  return weather.get_current_temp(ts), 0.0, 0.0
+
+
+def host_num_occupants(m: StepModels, ts) -> float:
+  """SimulatorBuilding.num_occupants at ``ts`` (simulator_building.py:305-315) of a host occupancy model: the sum over
+  the zones of its ``[ts - 5 min, ts]`` query.  0 for the device generator, whose buildings have their own."""
+  t5 = ts - dt.timedelta(minutes=5)
+  n_occ = 0.0
+  if isinstance(m.occupancy, BatchedRandomizedArrivalDepartureOccupancy):
+    pass
+  elif isinstance(m.occupancy, StepFunctionOccupancy):
+    v = m.occupancy.average_zone_occupancy("", t5, ts)   # stateless, the same for every zone: one query,
+    for _ in m.zone_names:                                 # the reference's sum
+      n_occ += v
+  else:
+    for z in m.zone_names:
+      n_occ += m.occupancy.average_zone_occupancy(z, t5, ts)
+  return n_occ
+
+
+def aux_features(m: StepModels, ts) -> list:
+  """environment.py:916-956: the SB_NUM_AUX auxiliary features of an observation at ``ts``, float32."""
+  hod = get_radian_time(ts, hour_of_day=True)
+  dow = get_radian_time(ts, hour_of_day=False)
+  n_occ = int(host_num_occupants(m, ts))
+  return [np.float32(np.cos(hod)), np.float32(np.sin(hod)), np.float32(np.cos(dow)),
+          np.float32(np.sin(dow)), np.float32(m.schedule.is_comfort_mode(ts)),
+          np.float32(m.schedule.is_comfort_mode(ts + dt.timedelta(minutes=60))),
+          np.float32((n_occ - m.occupancy_norm) / (m.occupancy_norm + 1))]
+
+
+def reward_occupancy(m: StepModels, ts):
+  """average_zone_occupancy over [ts, ts + dt] as the reward's RewardInfo holds it: one value for every zone; a list per
+  zone for a shared RandomizedArrivalDepartureOccupancy; 0.0 for the device generator (its buildings have their own)."""
+  if isinstance(m.occupancy, BatchedRandomizedArrivalDepartureOccupancy):
+    return 0.0
+  if isinstance(m.occupancy, RandomizedArrivalDepartureOccupancy):
+    return [m.occupancy.average_zone_occupancy(z, ts, ts + m.step_interval) for z in m.zone_names]
+  return m.occupancy.average_zone_occupancy("", ts, ts + m.step_interval)
+
+
+def reward_rates(m: StepModels, ts) -> Tuple[float, float, float, float]:
+  """(e_price, e_carbon, g_price, g_carbon) of a reward whose interval starts at ``ts``."""
+  start_utc = reward_start_time_utc(ts)
+  return m.electricity.rates(start_utc) + m.gas.rates(start_utc)
+
+
+def occupancy_clock(occupancy, ts) -> Tuple[int, int]:
+  """sb_occupancy_peek's (local hour, working day) at ``ts``; (0, 0) for a model that is not the device generator."""
+  if not isinstance(occupancy, BatchedRandomizedArrivalDepartureOccupancy):
+    return 0, 0
+  return occupancy.local(ts).hour, int(occupancy.is_work_day(ts))
+
+
+# sb_step_in's time-dependent scalars, as step_inputs names them
+STEP_INPUT_SCALARS = ("t_amb_now", "t_amb_next", "weather_f_now", "weather_f_next", "weather_t_now", "weather_t_next",
+                      "comfort_now", "comfort_prev", "comfort_next", "e_price", "e_carbon", "g_price", "g_carbon")
+
+
+def step_inputs(m: StepModels, ts, prev_thermostat_ts=None) -> Dict[str, object]:
+  """Everything ``BatchedEnvironment.make_step_in`` derives from the step's instant ``ts`` (and the instant of the
+  previous thermostat update, None: none): STEP_INPUT_SCALARS, ``aux`` (the observation's features at ts + dt) and
+  ``occupancy`` (the reward's, over [ts + dt, ts + 2 dt]: one value, or a list per zone for a shared randomized model).
+  The occupancy model is asked in the reference's order (environment.py:1310-1330): the observation's num_occupants, then
+  the reward's query -- it matters for the randomized model, whose every query advances the occupants."""
+  nxt = ts + m.step_interval
+  d: Dict[str, object] = {}
+  d["t_amb_now"], d["weather_f_now"], d["weather_t_now"] = weather_inputs(m.weather, ts)
+  d["t_amb_next"], d["weather_f_next"], d["weather_t_next"] = weather_inputs(m.weather, nxt)
+  d["comfort_now"] = int(m.schedule.is_comfort_mode(ts))
+  d["comfort_prev"] = -1 if prev_thermostat_ts is None else int(m.schedule.is_comfort_mode(prev_thermostat_ts))
+  d["comfort_next"] = int(m.schedule.is_comfort_mode(nxt))
+  d["aux"] = aux_features(m, nxt)
+  d["occupancy"] = reward_occupancy(m, nxt)
+  d["e_price"], d["e_carbon"], d["g_price"], d["g_carbon"] = reward_rates(m, nxt)
+  return d
+
+
+# --------------------------------------------------------------------------- a calendar per building
+# enum sb_clock_field (include/sbsim_amd.h): the fields of a Timeline row, in order
+CLOCK_FIELDS = ("t_amb", "weather_f", "weather_t", "comfort", "aux0", "aux1", "aux2", "aux3", "aux4", "aux5", "aux6",
+                "occupancy", "e_price", "e_carbon", "g_price", "g_carbon", "occ_hour", "occ_workday", "occ_hour5",
+                "occ_workday5")
+
+
+def instant_row(m: StepModels, ts) -> List[float]:
+  """One Timeline row: everything ``BatchedEnvironment.make_step_in``, ``_aux`` and ``reset`` derive from the instant
+  ``ts``, by the functions they call themselves -- as "now" (weather, comfort), as "next" (the auxiliary features, the
+  reward's occupancy and rates) or as the previous thermostat update (comfort)."""
+  occupancy = reward_occupancy(m, ts)   # (a Timeline refuses the shared randomized model: one value)
+  return [*weather_inputs(m.weather, ts), float(int(m.schedule.is_comfort_mode(ts))), *(float(v) for v in aux_features(m, ts)),
+          float(occupancy), *reward_rates(m, ts), *occupancy_clock(m.occupancy, ts),
+          *occupancy_clock(m.occupancy, ts - dt.timedelta(minutes=5))]
+
+
+def check_start_offsets(start_offsets, n_buildings: int) -> np.ndarray:
+  """``BatchedEnvironment(start_offsets=...)`` as int32 [B]: whole step intervals, >= 0.  ValueError otherwise, naming
+  the building."""
+  a = np.asarray(start_offsets)
+  if a.shape != (int(n_buildings),):
+    raise ValueError(f"start_offsets must have shape [{int(n_buildings)}] (one offset per building), got {a.shape}")
+  if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+    raise ValueError(f"start_offsets must be integers (whole step intervals), got dtype {a.dtype}")
+  if (a < 0).any():
+    bad = int(np.argmax(a < 0))
+    raise ValueError(f"start_offsets: building {bad}: negative offset {a[bad]}")
+  if (a > (1 << 22)).any():
+    bad = int(np.argmax(a > (1 << 22)))
+    raise ValueError(f"start_offsets: building {bad}: offset {a[bad]} is beyond the 2^22 rows a timeline may have")
+  return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class Timeline:
+  """The calendar of a batch whose buildings start at different times (``BatchedEnvironment(start_offsets=...)``): one
+  ``instant_row`` per instant ``t_r = start_timestamp + r * step_interval`` for ``r = 0 .. max(offsets) +
+  steps_per_episode + 1``, float64 ``rows [n_rows, len(CLOCK_FIELDS)]`` (sb_clock_attach's table).  Building b lives at
+  row ``offsets[b] + position``; an episode of N transitions steps at positions 0 .. N (the last is the terminal step)
+  and reads one row beyond.
+
+  ValueError: a shared host-side ``RandomizedArrivalDepartureOccupancy`` (one stateful instance that answers for one
+  instant per query; ``BatchedRandomizedArrivalDepartureOccupancy``, the device generator, is the supported form), and a
+  replay weather whose trace ends before the latest building's episode does -- the message names that building."""
+
+  def __init__(self, models: StepModels, start_timestamp, offsets, steps_per_episode: int):
+    m = models
+    self.offsets = check_start_offsets(offsets, len(np.atleast_1d(np.asarray(offsets))))
+    self.start = as_datetime(start_timestamp)
+    self.step_interval = m.step_interval
+    self.n_rows = int(self.offsets.max()) + int(steps_per_episode) + 2
+    if self.n_rows > (1 << 22):
+      raise ValueError(f"start_offsets: the timeline would have {self.n_rows} rows, more than 2^22")
+    if (isinstance(m.occupancy, RandomizedArrivalDepartureOccupancy)
+        and not isinstance(m.occupancy, BatchedRandomizedArrivalDepartureOccupancy)):
+      raise ValueError("start_offsets: a host-side RandomizedArrivalDepartureOccupancy is one stateful instance queried at "
+                       "one instant per step; use BatchedRandomizedArrivalDepartureOccupancy (the device generator)")
+    if isinstance(m.weather, ReplayWeatherController):
+      self._check_trace(m.weather)
+    self.rows = np.array([instant_row(m, self.instant(r)) for r in range(self.n_rows)], dtype=np.float64)
+    self.rows.setflags(write=False)
+
+  def instant(self, row: int) -> dt.datetime:
+    return self.start + row * self.step_interval
+
+  def _check_trace(self, weather) -> None:
+    """Every building's last query (the row after its terminal step, plus its own replay offset) inside the trace."""
+    if self.start.tzinfo is None:
+      raise TypeError("ReplayWeatherController needs a tz-aware timestamp (reference: tz_convert)")
+    shift = getattr(weather, "offsets_sec", None)
+    if shift is not None and shift.shape != self.offsets.shape:
+      raise ValueError("BatchedReplayWeather needs one offset per building")
+    last_row = self.offsets.astype(np.int64) + (self.n_rows - 1 - int(self.offsets.max()))
+    last = self.start.timestamp() + last_row * self.step_interval.total_seconds() + (0.0 if shift is None else shift)
+    first = self.start.timestamp() + self.offsets * self.step_interval.total_seconds() + (0.0 if shift is None else shift)
+    t_min, t_max = float(weather._times.min()), float(weather._times.max())
+    if (last > t_max).any():
+      b = int(np.argmax(last))
+      raise ValueError(f"start_offsets: building {b}: its episode ends at "
+                       f"{dt.datetime.fromtimestamp(float(last[b]), tz=UTC)}, after the weather trace's last time stamp "
+                       f"{dt.datetime.fromtimestamp(t_max, tz=UTC)}")
+    if (first < t_min).any():
+      b = int(np.argmin(first))
+      raise ValueError(f"start_offsets: building {b}: its episode starts before the weather trace's first time stamp")
+
+
+class ClockCursor:
+  """Which Timeline rows a batch reads: ``pos``, the position of the next step (0 after a ``reset``), and ``prev``, the
+  position of the last step taken -- the previous thermostat update, which survives ``reset`` as
+  ``Thermostat._previous_timestamp`` does (thermostat.py:66-69) and is None only before the first step ever."""
+
+  def __init__(self, pos: int = 0, prev: Optional[int] = None):
+    self.pos, self.prev = int(pos), (None if prev is None else int(prev))
+
+  def reset(self) -> None:
+    self.pos = 0
+
+  def advance(self) -> None:
+    """One step taken at ``pos``."""
+    self.prev = self.pos
+    self.pos += 1
+
+  def rows(self, offsets) -> Dict[str, Optional[np.ndarray]]:
+    """Per building: the rows a step at ``pos`` reads as now, next and the previous thermostat update (None: none)."""
+    o = np.asarray(offsets, dtype=np.int64)
+    return dict(now=o + self.pos, next=o + self.pos + 1, prev=None if self.prev is None else o + self.prev)
+
+  def seek_args(self) -> Tuple[int, int]:
+    """sb_clock_seek's (pos, prev_pos)."""
+    return self.pos, (-1 if self.prev is None else self.prev)
 
 
 # --------------------------------------------------------------------------- per-building plant parameters
