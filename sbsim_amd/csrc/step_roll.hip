@@ -40,6 +40,10 @@
 //   * the next building's small inputs and class bytes are asked for BEFORE its rows (memory operations return in order);
 //   * A = ap*Tprev + g has no pass of its own: a slot's A is formed during the ramp-up of the first sweep, a few slots ahead
 //     of the step that reads it (struct APass), so the ramp-up starts on the first rows while the last are in flight;
+//   * the ramp-up's 63 half-empty steps have a step of their own (step_ramp: no seam value under lane 63, no collect in
+//     lane 63, no inline-asm result read by the next instruction), and the A values a pair asks for are formed behind the
+//     NEXT pair's one wait (struct APrev): the block from a building's top to its first period is 1,822 instructions
+//     (was 2,185 -- more than a whole 96-step period; profiles/roll_ramp_resource_usage.txt);
 //   * the tail rows' scan multiplies by STATIC factors (the multiplicative halves of its composed maps are products of bL:
 //     the planner runs that half once, sweep_common.h tail_pass_static): a level is two DPP moves and one FMA;
 //   * the stopping decision of the library's kernel is taken on high words throughout (rows, tail cells, ring): one 32-bit
@@ -195,7 +199,8 @@ __device__ __forceinline__ void track(Acc &acc, double d) {
 template <int NR, int S, bool EXACT, bool FREE = false>
 __device__ __forceinline__ void step(double (&e)[NR], double (&bk)[kWin], d2 ud, d2 lr, double A,
                                      double sm, Acc &acc) {
-  static_assert(!FREE || (!EXACT && S >= kWin), "free periods: the library's kernel, after the ramp-up");
+  static_assert(S >= kWin, "the ramp-up has a step of its own: step_ramp");
+  static_assert(!FREE || !EXACT, "free periods: the library's kernel");
   constexpr int r = S % NR, rm = (S + NR - 1) % NR, rp = (S + 1) % NR;
   const double Dn = wave_shift1<0x130, true>(e[rp], sm);
   // the chain starts in a register of its own (early clobber): accumulated in place in A's
@@ -212,12 +217,7 @@ __device__ __forceinline__ void step(double (&e)[NR], double (&bk)[kWin], d2 ud,
     sr = wave_shift1<0x138, true>(sr, U);
   }
 #endif
-  if constexpr (S < kWin) {
-    const double sel = lanes_upto<S>() ? nv : e[r];
-    if constexpr (EXACT) acc.cur = fmax(acc.cur, fabs(sel - e[r]));
-    else track(acc, sel - e[r]);
-    e[r] = sel;
-  } else if constexpr (S < NR) {
+  if constexpr (S < NR) {
     if constexpr (EXACT) acc.cur = fmax(acc.cur, fabs(nv - e[r]));
     else if constexpr (!FREE) track(acc, nv - e[r]);
     e[r] = nv;
@@ -242,6 +242,40 @@ __device__ __forceinline__ void step(double (&e)[NR], double (&bk)[kWin], d2 ud,
     // here, not after the window: e[J] and bk[J] both survive the window
     asm volatile("" : "+v"(acc.cur), "+v"(acc.neg));
   }
+}
+
+// A step of the ramp-up (S < 63: lanes > S have not started; the select drops their result).  The same four products in
+// the same order as step<>, without what a half-empty wavefront does not need:
+//   * lane 63 has not started, so its lower neighbour is never used: the Dn move fills lane 63 with 0 (bound_ctrl) instead
+//     of keeping a seam value -- no destination pair to pre-load (two v_mov_b32 per step);
+//   * lane 63 collects nothing: the travelling maximum that entered lane 0 at step 0 reaches lane 63 at step 63; until
+//     then lane 63's `tr` is a maximum of zeros (0 shifted into lane 0, |sel - e| = 0 in the lanes that have not
+//     started) and `fin` stays 0 with or without the v_max_f32 -- the first collect that can see anything is step 64's;
+//   * the chain's first FMA is the compiler's: the result goes through the select anyway, so accumulating in place in the
+//     ds_read_b128 tuple of A costs no copy here (step<>'s reason for the early-clobber asm), and no instruction reads an
+//     inline-asm result right behind it.  The hazard recogniser wants one wait state between an inline asm and a VALU
+//     instruction that reads its result, and counts NO inline asm as a wait state (it may be empty): the asm v_fma_f64
+//     with its v_fmac behind it, or with only the s_bfm_b64 of lanes_upto between them, was an s_nop per step;
+//   * for the same reason `started` -- lanes_upto<S>(), an inline asm -- is formed by the caller, well before the select.
+template <int NR, int S, bool EXACT>
+__device__ __forceinline__ void step_ramp(double (&e)[NR], d2 ud, d2 lr, double A, Acc &acc, bool started) {
+  static_assert(S < kWin, "ramp-up steps only");
+  constexpr int r = S % NR, rm = (S + NR - 1) % NR, rp = (S + 1) % NR;
+  const double Dn = wave_shift1<0x130, false>(e[rp], 0.0);
+  double t = fma(ud.y, Dn, A);
+  t = fma(lr.y, e[rp], t);
+  const double U = wave_shift1<0x13c, false>(e[rm], 0.0); // wave_ror:1, as in step<>
+  t = fma(lr.x, e[rm], t);
+  const double nv = fma(ud.x, U, t);
+  const double sel = started ? nv : e[r];
+  if constexpr (EXACT) {
+    acc.cur = fmax(acc.cur, fabs(sel - e[r]));
+  } else {
+#ifndef SB_EXP_NOTRACK
+    asm("v_max_f32_dpp %0, %0, |%1| wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(acc.tr) : "v"(__double2hiint(sel - e[r])));
+#endif
+  }
+  e[r] = sel;
 }
 
 // A = ap * Tprev + g, slot by slot (slot j goes to position (j + 1) mod NR of the lane's rotated row: LDS, or a register
@@ -293,37 +327,61 @@ constexpr int kDepth = SB_DEPTH;          // pairs between the LDS reads of a st
 constexpr int kBufs = kDepth + 1;         // NR / 2 pairs per period: kBufs must divide that (checked per instantiation in k_sweep_roll)
 constexpr int pair_buf(int S) { return ((S - 1) / 2) % kBufs; }
 
+// The table values (ap, g) of the three slots that a pair of the ramp-up asked for (APass::fetch).  The FMAs and the LDS
+// writes that form A from them (APass::put) belong to the NEXT pair, behind that pair's one wait -- which covers them:
+// LDS answers in order, and the pair's last coefficient read was issued after the three table reads.  (Formed at the end
+// of their own pair, each of the three FMAs waited for its own ds_read2_b64: three more s_waitcnt per pair.)
+struct APrev {
+  d2 v[3];
+};
+
 template <int NR, int S, int S1, bool WRAP, bool EXACT, bool APASS, bool FREE, int NAR>
 __device__ __forceinline__ void roll_pairs(double (&e)[NR], double (&bk)[kWin], double (&Areg)[NAR],
-                                           PairBuf (&pb)[kBufs], Ctx<NR> &x, Acc &acc, const APass<NR, NAR> &ap) {
+                                           PairBuf (&pb)[kBufs], Ctx<NR> &x, Acc &acc, const APass<NR, NAR> &ap,
+                                           const APrev pv = APrev{}) {
   if constexpr (S < S1) {
+    static_assert(!APASS || S1 <= kWin, "the A pass belongs to the ramp-up");
     constexpr bool wrapped = WRAP && S + 2 * kDepth >= S1;
     constexpr int N = wrapped ? S + 2 * kDepth - NR : S + 2 * kDepth;
     PairBuf &cur = pb[pair_buf(S)], &nxt = pb[pair_buf(N)];
 #if SB_ONE_WAIT // one s_waitcnt per pair: every LDS value of the pair is asked for here, before the next pair's reads are issued
-    asm volatile("" ::"v"(cur.ud0.x), "v"(cur.A.x), "v"(cur.sm.x), "v"(cur.ud1.x), "v"(cur.lr1.x));
+    if constexpr (S < kWin) asm volatile("" ::"v"(cur.ud0.x), "v"(cur.A.x), "v"(cur.ud1.x), "v"(cur.lr1.x)); // (the ramp-up reads no seam values)
+    else asm volatile("" ::"v"(cur.ud0.x), "v"(cur.A.x), "v"(cur.sm.x), "v"(cur.ud1.x), "v"(cur.lr1.x));
     __builtin_amdgcn_sched_barrier(0);
 #endif
     load_first<NR, N, !wrapped>(nxt, x, Areg);
-    // the ramp-up forms A of three more slots per pair (APass): the table reads here, the values after the pair's steps
-    constexpr int j0 = kA0 + 3 * ((S - 1) / 2);
-    static_assert(!APASS || (S % 2 == 1 && j0 >= S + 2 * kDepth + 2), "a slot's A is written before the pair that reads it ahead");
-    d2 pa0 = d2{0.0, 0.0}, pa1 = d2{0.0, 0.0}, pa2 = d2{0.0, 0.0};
-    if constexpr (APASS && j0 < NR) pa0 = ap.template fetch<j0 < NR ? j0 : 0>();
-    if constexpr (APASS && j0 + 1 < NR) pa1 = ap.template fetch<j0 + 1 < NR ? j0 + 1 : 0>();
-    if constexpr (APASS && j0 + 2 < NR) pa2 = ap.template fetch<j0 + 2 < NR ? j0 + 2 : 0>();
+    // The ramp-up forms A of three more slots per pair (APass).  Pair S asks for the table values of the slots j0 .. j0 + 2
+    // and forms A of the slots jp .. jp + 2 that the pair before it asked for (struct APrev) -- here, behind the pair's one
+    // wait.  load_first above has read A of the slots S + 2 kDepth and S + 2 kDepth + 1: every slot below jp is written by
+    // then (the prologue's kA0, the earlier pairs'), and slot jp is first worked on at step jp.
+    constexpr int j0 = kA0 + 3 * ((S - 1) / 2), jp = j0 - 3;
+    static_assert(!APASS || (S % 2 == 1 && jp >= S + 2 * kDepth + 2), "a slot's A is written before the pair that reads it ahead");
+    static_assert(!APASS || jp >= S + 2, "a slot still holds Tprev when its A is formed");
+    static_assert(!APASS || S + 2 < S1 || j0 >= NR, "the ramp-up's last pair asks for no slot: no pair would form its A");
+    if constexpr (APASS && S > 1) {
+      if constexpr (jp < NR) ap.template put<jp < NR ? jp : 0>(pv.v[0], e[jp < NR ? jp : 0]);
+      if constexpr (jp + 1 < NR) ap.template put<jp + 1 < NR ? jp + 1 : 0>(pv.v[1], e[jp + 1 < NR ? jp + 1 : 0]);
+      if constexpr (jp + 2 < NR) ap.template put<jp + 2 < NR ? jp + 2 : 0>(pv.v[2], e[jp + 2 < NR ? jp + 2 : 0]);
+    }
+    // the ramp-up's two lane masks, formed HERE: an s_bfm_b64 right in front of the v_cndmask that reads it costs an s_nop
+    // (step_ramp), and the scheduler sinks it there if it can -- not across the barrier below
+    bool m0 = false, m1 = false;
+    if constexpr (S < kWin) m0 = lanes_upto<S < kWin ? S : 0>();
+    if constexpr (S + 1 < kWin) m1 = lanes_upto<S + 1 < kWin ? S + 1 : 0>();
+    APrev pa{{d2{0.0, 0.0}, d2{0.0, 0.0}, d2{0.0, 0.0}}};
+    if constexpr (APASS && j0 < NR) pa.v[0] = ap.template fetch<j0 < NR ? j0 : 0>();
+    if constexpr (APASS && j0 + 1 < NR) pa.v[1] = ap.template fetch<j0 + 1 < NR ? j0 + 1 : 0>();
+    if constexpr (APASS && j0 + 2 < NR) pa.v[2] = ap.template fetch<j0 + 2 < NR ? j0 + 2 : 0>();
     __builtin_amdgcn_sched_barrier(0);
-    step<NR, S, EXACT, FREE>(e, bk, cur.ud0, cur.lr0, cur.A.x, cur.sm.x, acc);
+    if constexpr (S < kWin) step_ramp<NR, S, EXACT>(e, cur.ud0, cur.lr0, cur.A.x, acc, m0);
+    else step<NR, S, EXACT, FREE>(e, bk, cur.ud0, cur.lr0, cur.A.x, cur.sm.x, acc);
     __builtin_amdgcn_sched_barrier(0);
     load_second<NR, N + 1>(nxt, x);
     __builtin_amdgcn_sched_barrier(0);
-    step<NR, S + 1, EXACT, FREE>(e, bk, cur.ud1, cur.lr1, cur.A.y, cur.sm.y, acc);
+    if constexpr (S + 1 < kWin) step_ramp<NR, S + 1, EXACT>(e, cur.ud1, cur.lr1, cur.A.y, acc, m1);
+    else step<NR, S + 1, EXACT, FREE>(e, bk, cur.ud1, cur.lr1, cur.A.y, cur.sm.y, acc);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (APASS && j0 < NR) ap.template put<j0 < NR ? j0 : 0>(pa0, e[j0 < NR ? j0 : 0]);
-    if constexpr (APASS && j0 + 1 < NR) ap.template put<j0 + 1 < NR ? j0 + 1 : 0>(pa1, e[j0 + 1 < NR ? j0 + 1 : 0]);
-    if constexpr (APASS && j0 + 2 < NR) ap.template put<j0 + 2 < NR ? j0 + 2 : 0>(pa2, e[j0 + 2 < NR ? j0 + 2 : 0]);
-    if constexpr (APASS) __builtin_amdgcn_sched_barrier(0);
-    roll_pairs<NR, S + 2, S1, WRAP, EXACT, APASS, FREE>(e, bk, Areg, pb, x, acc, ap);
+    roll_pairs<NR, S + 2, S1, WRAP, EXACT, APASS, FREE>(e, bk, Areg, pb, x, acc, ap, pa);
   }
 }
 
@@ -559,7 +617,7 @@ __global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_e
     const APass<NR, kNAR> ap{amapw, (unsigned)(size_t)(__attribute__((address_space(3))) double *)tapg, A + (size_t)R * kAS,
                              A + 64 * kAS + (size_t)R * (kNL - kAS), Areg};
     {
-      static_assert(kA0 == 8 && kA0 + 3 * ((kWin - 1) / 2) >= NR, "the ramp-up's pairs reach the last slot");
+      static_assert(kA0 == 8 && kA0 + 3 * ((kWin - 3) / 2) >= NR, "the ramp-up's pairs but the last one reach the last slot");
       const d2 g0 = ap.template fetch<0>(), g1 = ap.template fetch<1>(), g2 = ap.template fetch<2>(), g3 = ap.template fetch<3>(),
                g4 = ap.template fetch<4>(), g5 = ap.template fetch<5>(), g6 = ap.template fetch<6>(), g7 = ap.template fetch<7>();
       __builtin_amdgcn_sched_barrier(0);
@@ -589,7 +647,7 @@ __global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_e
           load_second<NR, 4>(pb[pair_buf(3)], x);
         }
         static_assert(kDepth <= 2, "initial fill of the pair buffers");
-        step<NR, 0, EXACT>(e, bk, ud, lr, x.Arow[1], 0.0, acc);
+        step_ramp<NR, 0, EXACT>(e, ud, lr, x.Arow[1], acc, lanes_upto<0>());
       }
       __builtin_amdgcn_sched_barrier(0);
       roll_pairs<NR, 1, kWin, false, EXACT, true, false>(e, bk, Areg, pb, x, acc, ap); // ramp-up (+ A of the slots from kA0 on); reads ahead for the first pairs of the period
