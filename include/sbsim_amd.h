@@ -676,6 +676,11 @@ int sb_observe_step_in(sb_handle *h, const sb_step_in *in, float *obs_dev, void 
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);
+/* Developer aid (host only, for tests): the status sb_plan_info would return for the plan (per_building_tables != 0:
+ * sb_plan_info_materials) and, in *out, a 64-bit FNV-1a hash of everything the planner hands the chosen sweep kernel:
+ * the kernel and its variant, every launch scalar, every table (lengths and raw bytes, doubles by bit pattern) and the
+ * LDS-grid kernel's geometry.  *out is 0 on a refusal.  Equal digests: the kernels see the same bytes. */
+int sb_debug_plan_digest(const sb_plan_desc *plan, int32_t per_building_tables, uint64_t *out);
 
 #ifdef __cplusplus
 }

@@ -164,13 +164,15 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_pb_zone_info", "sb_pb_variable_info", "sb_record_append", "sb_tap_pre", "sb_tap_post",
            "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi", "sb_set_building_params",
            "sb_set_reward_function", "sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials",
-           "sb_get_building_coef", "sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in")
+           "sb_get_building_coef", "sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in",
+           "sb_debug_plan_digest")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
 BUILDING_PARAM_ENTRIES = ("sb_set_building_params",)
 REWARD_ENTRIES = ("sb_set_reward_function",)
 CLOCK_ENTRIES = ("sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in")
+PLAN_DIGEST_ENTRIES = ("sb_debug_plan_digest",)
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -267,6 +269,8 @@ def load():
     L.sb_clock_seek.argtypes = [vp, C.c_int32, C.c_int32]
     L.sb_clock_detach.argtypes = [vp]
     L.sb_observe_step_in.argtypes = [vp, C.POINTER(StepIn), vp, vp]
+  if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
+    L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
   return L
 

@@ -9,8 +9,6 @@ using namespace sb;
 
 namespace {
 
-constexpr int kLdsCap = 160 * 1024;
-
 // ---------------------------------------------------------------- randomized occupancy
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten
 // rounds of two 32x32 -> 64 multiplies on a 128-bit counter under a 64-bit key.

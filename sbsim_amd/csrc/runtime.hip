@@ -1,6 +1,6 @@
 // runtime.hip -- the step runtime behind the C ABI (include/sbsim_amd.h): the state kernels (reset, observe, copies,
 // k_pre / k_post around the sweep), the dispatch to the sweep kernel sb_create chose, and every entry point but
-// sb_plan_info / sb_create (sbsim_hip.hip).
+// sb_plan_info / sb_create (sbsim_hip.hip; the planner behind them: planner.cpp).
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (fma only where written).
 #include <hip/hip_runtime.h>

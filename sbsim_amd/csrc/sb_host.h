@@ -1,5 +1,6 @@
-// sb_host.h -- what the host-side translation units (sbsim_hip.hip: the planner and sb_create; runtime.hip: the step
-// runtime; generators.hip) share: error reporting, device buffers, the handle behind the C ABI, the sweep-kernel dispatch.
+// sb_host.h -- what the host-side translation units that use HIP (sbsim_hip.hip: sb_create; runtime.hip: the step
+// runtime; generators.hip) share: HIP error reporting, device buffers, the handle behind the C ABI, the sweep-kernel
+// dispatch.  (The planner is HIP-free: planner.h, with sb_error.h's fail().)
 #ifndef SBSIM_AMD_SB_HOST_H_
 #define SBSIM_AMD_SB_HOST_H_
 #include <hip/hip_runtime.h>
@@ -8,22 +9,13 @@
 #include <string>
 #include <vector>
 
+#include "planner.h"
 #include "sb_device.h"
-
-// The experimental sweep kernels (step_stream_ms.hip, step_stream.hip's k_sweep_stream_roll: exact, tested, slower than what
-// they were meant to replace) are in the library only when it is built with SBSIM_BUILD_EXPERIMENTAL=1 (-DSB_EXPERIMENTAL,
-// sbsim_amd/build.py); the default build answers for step_stream_ms.hip's entry points (sbsim_hip.hip) and never plans them.
-#ifdef SB_EXPERIMENTAL
-constexpr bool kExperimental = true;
-#else
-constexpr bool kExperimental = false;
-#endif
 
 // step_stream.hip's overlapped-sweeps kernel (declared here: sb_device.h is part of the traffic profile's source hash)
 namespace sb {
 int launch_sweep_stream_roll(const Dev &d, double *abuf, double *ebuf, int waves, hipStream_t stream);
 int prepare_sweep_stream_roll(const Dev &d, int waves);
-int sweep_stream_roll_xchg_extra_doubles();
 } // namespace sb
 
 // step_jacobi.hip: k_sweep_jacobi (SB_KERNEL_JACOBI), TFSimulator's float32 Jacobi update, both grids in LDS;
@@ -66,32 +58,12 @@ int sweep_jacobi_g_blocks_per_cu();
 int launch_sweep_jacobi_g(const Dev &d, const JacArgs &j, int workgroups, hipStream_t stream);
 } // namespace sb
 
-// SB_KERNEL_STREAM's variants (= Dev::stream_ms): k_sweep_stream; the experimental k_sweep_stream_ms, k_sweep_stream_roll
-enum { kStreamPlain = 0, kStreamMs = 1, kStreamRoll = 2 };
-
-namespace sb {
-namespace host {
-inline thread_local std::string g_err; // sb_last_error()
-} // namespace host
-} // namespace sb
-
-inline int fail(int code, const std::string &msg) {
-  sb::host::g_err = msg;
-  return code;
-}
-
 #define SB_HIP(call)                                                                     \
   do {                                                                                   \
     hipError_t e_ = (call);                                                              \
     if (e_ != hipSuccess)                                                                \
       return fail(SB_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));        \
   } while (0)
-#define SB_CHECK(call)                                                                   \
-  do {                                                                                   \
-    const int rc_ = (call);                                                              \
-    if (rc_ != SB_OK) return rc_;                                                        \
-  } while (0)
-
 // Entry points run on the handle's device and leave the calling thread's current device as
 // they found it (a handle on device 1 must not redirect the caller's later torch allocations).
 struct DeviceGuard {

@@ -1,4 +1,4 @@
-// step_band.hip -- mode 5, one row per lane on two to four wavefronts per building: what the planner asks and the
+// step_band.hip -- mode 5, one row per lane on two to four wavefronts per building: the
 // dispatch to the instantiations, which live in one translation unit per slot count (step_band_68.hip ..
 // step_band_96.hip <- step_band_impl.h) so that they compile in parallel.
 #include "sb_device.h"
@@ -34,17 +34,6 @@ int dispatch(const Dev &d, hipStream_t stream, bool prepare) {
 }
 } // namespace
 
-bool sweep_band_supported(int NR) {
-  for (int s : kSlotCounts)
-    if (s == NR) return true;
-  return false;
-}
-int sweep_band_max_waves() { return kWMax; }
-int sweep_band_lds_slots(int NR) { return lds_slots(NR); }
-int sweep_band_seam_doubles(int NR, int W) { return (2 * W + 2) * seam_region(NR) + W * (64 + NR + 8); }
-int sweep_band_sync_doubles(int W) { return 32 * W + 2 * W * kHist + 8; }
-int sweep_band_decision_lag(int NR, int W) { (void)NR; return W; } // periods until a sweep's max|delta| is known for certain
-int sweep_band_set_table() { return kSets; }
 int prepare_sweep_band(const Dev &d) { return dispatch(d, nullptr, true); }
 int launch_sweep_band(const Dev &d, hipStream_t stream) { return dispatch(d, stream, false); }
 

@@ -1,4 +1,4 @@
-// step_band_cfg.h -- what step_band.hip (the planner's interface) and step_band_impl.h (the kernel) agree on.
+// step_band_cfg.h -- what the planner (planner.cpp, plan_band), step_band.hip and step_band_impl.h (the kernel) agree on.
 #pragma once
 
 namespace sb {
@@ -19,6 +19,9 @@ constexpr int kWMax = 4;   // wavefronts per building: one per SIMD
 constexpr int lds_slots(int NR) { return 66; }
 constexpr int seam_region(int NR) { return NR + 72; }                    // doubles per seam row: 64 finite ones in front (steps < 63)
 constexpr int kSlotCounts[] = {68, 72, 76, 80, 84, 88, 92, 96};                  // the instantiations (step_band_NN.hip)
+// LDS doubles of the seam rows and the publish scratch; of the progress counters and the published max|delta| parts (W wavefronts)
+constexpr int seam_doubles(int NR, int W) { return (2 * W + 2) * seam_region(NR) + W * (64 + NR + 8); }
+constexpr int sync_doubles(int W) { return 32 * W + 2 * W * kHist + 8; }
 
 } // namespace band
 } // namespace sb

@@ -8,12 +8,14 @@
 // cross-check of the others in the GPU tests).
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (fma only where written).
+#include "step_lds_cfg.h"
 #include "sweep_common.h"
 
 namespace sb {
 namespace {
 
 using namespace sweep;
+using lds::kGuard;
 
 __device__ __forceinline__ int lds_index(const Dev &a, int gidx) {
   if (a.pitch == a.W) return gidx;
@@ -110,7 +112,6 @@ __device__ double sweep_generic(const Dev &a, double *E, const double *gtab, con
 //     only the LDS store and the max-delta update are masked (per-slot lane masks in SGPRs).
 // Requires S >= W + 8 (one row segment per chunk) and, when H > 64, S - 63 > 16 (the seam
 // row is written at least 17 steps before lane 0 prefetches it).
-constexpr int kGuard = 16; // finite guard doubles before and after E in LDS
 
 struct StageG {
   double P[kChunk];

@@ -29,33 +29,19 @@
 //
 // HBM state of a building: [NR][RS] float64, slot-major (one coalesced 8*RS-byte row per
 // register), pad cells 0.
+#include "step_reg_cfg.h"
 #include "sweep_common.h"
 
 namespace sb {
 namespace {
 
 using namespace sweep;
+using namespace reg; // kPair, lds_slots, waves_per_simd, table_stride, kSeamPad
 
-constexpr int kPair = 2; // template parameter P: 1 = one wavefront per building, kPair = two
-
-// Slots of A = ap*Tprev + g kept in LDS; the remaining NR - lds_slots live in registers
-// (AGPRs).  96-slot plans on one wavefront: 71 of 96 slots in LDS make a building fit a
-// quarter of a CU's LDS, so all four SIMDs own a building instead of three.
-// The 96-slot two-wavefront variant (up to 128 x 96 cells) keeps 89 slots in LDS: two buildings
-// per CU (it runs one wavefront per SIMD: 192 registers of grid + the rest do not fit twice).
-constexpr int lds_slots(int NR, int P) {
-  return (NR == 96 && P != kPair) ? 71 : ((NR == 96 && P == kPair) ? 89 : NR);
-}
-constexpr int waves_per_simd(int NR, int P) { return (P == kPair && NR <= 66) ? 2 : 1; }
 #ifndef SB_LOOK
 #define SB_LOOK 2
 #endif
 constexpr int kLook = SB_LOOK; // steps between the LDS reads of a step and its arithmetic
-// Coefficient-table stride: classes + the pad class <= stride.  The class maps hold
-// class * (256 / stride) in a byte; times stride / 32 that is the class's byte offset into a
-// table column (stride 32: the byte IS the offset, one SDWA add per step).
-constexpr int table_stride(int NR, int P) { return (NR == 96 && P == 2) ? 64 : 32; }
-constexpr int kSeamPad = 8;
 
 struct Co { double bU, bD, bL, bR, A, smU, smD; };
 struct Pipe {
@@ -465,9 +451,8 @@ void launch_variant(const Dev &d, int workgroups, hipStream_t stream) {
                      (size_t)d.lds_reg_bytes, stream, d);
 }
 
-#define SB_VARIANT(NR, P) {NR, P, (const void *)k_sweep_reg<NR, P>, launch_variant<NR, P>}
-const Variant kVariants[] = {SB_VARIANT(32, 1), SB_VARIANT(66, 1), SB_VARIANT(66, 2), SB_VARIANT(96, 1),
-                            SB_VARIANT(96, 2)}; // tail rows, overlapped sweeps: k_sweep_roll (step_roll.hip)
+#define SB_VARIANT(NR, P) {NR, P, (const void *)k_sweep_reg<NR, P>, launch_variant<NR, P>},
+const Variant kVariants[] = {SB_REG_VARIANTS(SB_VARIANT)}; // (step_reg_cfg.h: the list the planner chooses from)
 #undef SB_VARIANT
 
 const Variant *find_variant(int NR, int P) {
@@ -477,11 +462,6 @@ const Variant *find_variant(int NR, int P) {
 }
 
 } // namespace
-
-bool sweep_reg_supported(int NR, int P) { return find_variant(NR, P) != nullptr; }
-int sweep_reg_table_stride(int NR, int P) { return table_stride(NR, P); }
-int sweep_reg_lds_slots(int NR, int P) { return lds_slots(NR, P); }
-int sweep_reg_waves_per_simd(int NR, int P) { return waves_per_simd(NR, P); }
 
 int prepare_sweep_reg(const Dev &d) {
   const Variant *v = find_variant(d.NR, d.P);

@@ -52,12 +52,14 @@
 //   * no kernel-lifetime per-lane pointers or converted constants (each one the register allocator parks in scratch costs a
 //     scratch reload = a wait for every load in flight): per-lane addresses are formed where they are used (opaque()).
 // Policy loop (two sweeps per step): 3.73e8 -> 4.45e8 zone-updates/s; the driver's window: frac 0.199 -> 0.208.
+#include "step_roll_cfg.h"
 #include "sweep_common.h"
 
 namespace sb {
 namespace {
 
 using namespace sweep;
+using namespace roll; // lds_slots, a_stride, kWaves, tail_row, tail_mul_doubles
 
 #ifndef SB_ONE_WAIT
 #define SB_ONE_WAIT 1
@@ -65,17 +67,6 @@ using namespace sweep;
 constexpr int kWin = 63;      // steps of a period in which the lanes are in two different sweeps
 constexpr int kTS = 32;       // entries of the per-class tables (ap, g) and of the coefficient-set table
 constexpr int kSeamPad = 8;
-
-// Slots of A = ap*Tprev + g kept in LDS (the rest: registers).  72 of 96: a building needs 38.2 KB of
-// LDS, so four buildings -- one per SIMD -- and the shared tables (7 KB) fill a CU's 160 KB.  Rows of
-// 70 slots (the stride is 2 mod 4 doubles: rows are 16-byte aligned and 16 lanes' ds_read_b128 cover
-// all banks) and a second array [64][2] with slots 70, 71 (a stride of 72 would be four-way conflicted,
-// 74 does not fit).  NR = 72, 80, 88: the same 70 + 2 slots in LDS (NR - 72 in registers); NR = 64: all of them,
-// rows of 66.
-constexpr int lds_slots(int NR) { return NR >= 72 ? 72 : ((NR / 2) % 2 ? NR : NR + 2); }
-constexpr int a_stride(int NR) { return NR >= 72 ? 70 : ((NR / 2) % 2 ? NR : NR + 2); }
-constexpr int kWaves = 4;     // wavefronts = buildings per workgroup
-constexpr int tail_row(int NR) { return NR + 4; } // tail rows in LDS: column c at [2 + c], zero guards around
 
 struct PairBuf { // LDS values of two consecutive steps
   d2 ud0, lr0, ud1, lr1; // (bU, bD), (bL, bR)
@@ -831,13 +822,6 @@ __global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_e
 }
 
 } // namespace
-
-bool sweep_roll_supported(int NR) { return NR == 64 || NR == 72 || NR == 80 || NR == 88 || NR == 96; }
-int sweep_roll_lds_slots(int NR) { return lds_slots(NR); }
-int sweep_roll_a_stride(int NR) { return a_stride(NR); }
-int sweep_roll_seam_doubles(int NR, int T) { (void)T; return tail_row(NR); } // the first tail row, by column
-int sweep_roll_waves() { return kWaves; }
-int sweep_roll_tail_mul_doubles(int NR, int T) { return tail_mul_doubles(NR, T); } // the tail scan's static multipliers (shared by the workgroup)
 
 int sweep_roll_redo_workgroups() { return 8; } // the exact kernel's launch on the redo list (a handful of buildings per step at most)
 

@@ -19,27 +19,24 @@
 // steps of loads in flight, so what counts is wavefronts per CU (round 5: 128 registers per lane -- 132-144 B of them spilled
 // -- for four wavefronts per SIMD and a zone-sum scratch of 8 instead of 16 columns so that three workgroups of a
 // 299 x 401 plan share a CU instead of two: 1.0e11 -> 1.35e11 cell-sweeps/s at 3,072 buildings).
+#include "step_stream_cfg.h"
 #include "sweep_common.h"
 
 namespace sb {
 namespace {
 
 using namespace sweep;
+using namespace stream; // kSets, kZC
 
-constexpr int kSets = 32;   // entries of the coefficient-set table (at LDS address 0)
 // (developer knobs of tools/build_variant.sh: prefetch depth, zone-sum columns, wavefronts per SIMD asked of the compiler)
 #ifndef SB_STREAM_PF
 #define SB_STREAM_PF 8
-#endif
-#ifndef SB_STREAM_ZC
-#define SB_STREAM_ZC 9
 #endif
 #ifndef SB_STREAM_WPE
 #define SB_STREAM_WPE 4
 #endif
 constexpr int kSpinMax = 1 << 24; // a wait that long is a protocol error: trap instead of hanging the GPU (overlapped sweeps)
 constexpr int kPF = SB_STREAM_PF; // steps between a global load and its use
-constexpr int kZC = SB_STREAM_ZC; // columns of the zone-sum scratch per zone (16 lane columns + 1: odd stride)
 
 extern __shared__ __attribute__((aligned(16))) double lds[];
 
@@ -465,15 +462,10 @@ int dispatch(const Dev &d, double *abuf, int waves, hipStream_t stream, bool pre
 
 } // namespace
 
-int sweep_stream_set_table() { return kSets; }
-int sweep_stream_zone_columns() { return kZC; }
-
 #ifdef SB_EXPERIMENTAL
-int sweep_stream_roll_xchg_extra_doubles() { return 16; } // the odd sweeps' max |delta| parts behind the publish scratch
 int prepare_sweep_stream_roll(const Dev &d, int waves) { return dispatch_roll(d, nullptr, nullptr, waves, nullptr, true); }
 int launch_sweep_stream_roll(const Dev &d, double *abuf, double *ebuf, int waves, hipStream_t stream) { return dispatch_roll(d, abuf, ebuf, waves, stream, false); }
-#else // the planner never asks for it (sbsim_hip.hip: kExperimental)
-int sweep_stream_roll_xchg_extra_doubles() { return 0; }
+#else // the planner never asks for it (planner.h: kExperimental)
 int prepare_sweep_stream_roll(const Dev &, int) { return (int)hipErrorNotSupported; }
 int launch_sweep_stream_roll(const Dev &, double *, double *, int, hipStream_t) { return (int)hipErrorNotSupported; }
 #endif

@@ -25,21 +25,19 @@
 // one, the pass is run again from the same input with j + 1 sweeps -- the iterates and the sweep count are always
 // those of the plain schedule; how many sweeps a pass carries (the decay of max |delta| extrapolated to the
 // threshold, like step_two.hip / step_band.hip) only decides the speed.
+#include "step_stream_ms_cfg.h"
 #include "sweep_common.h"
 
 namespace sb {
 namespace {
 
 using namespace sweep;
+using namespace stream_ms; // kS
 
-constexpr int kSets = 32;   // entries of the coefficient-set table (at LDS address 0)
+constexpr int kSets = stream::kSets;
 constexpr int kPF = 8;      // steps between sweep 0's global loads and their use
 constexpr int kQF = 4;      // ... the later sweeps' (A, class word): L1 / L2 hits
-constexpr int kZC = 9;      // columns of the zone-sum scratch per zone (8 lane columns + 1: odd stride) -- step_stream.hip's (the planner asks it)
-#ifndef SB_STREAM_S
-#define SB_STREAM_S 4
-#endif
-constexpr int kS = SB_STREAM_S; // sweeps per pass, at most
+constexpr int kZC = stream::kZC; // columns of the zone-sum scratch per zone: step_stream.hip's
 
 // (the compiler must not fold `word & 0xffff` into the load that fills the read-ahead ring: it then waits for the load at once)
 __device__ __forceinline__ unsigned used_now(unsigned v) {
@@ -370,12 +368,6 @@ int dispatch(const Dev &d, double *abuf, double *ebuf, int waves, hipStream_t st
 }
 
 } // namespace
-
-static_assert(kZC == 9, "sweep_stream_zone_columns() of step_stream.hip");
-int sweep_stream_ms_sweeps() { return kS; }
-// LDS doubles of the seam rows (kS sweeps + the input grid's) and of the exchange area, W wavefronts, NS slots
-int sweep_stream_ms_seam_doubles(int NS, int W) { return (kS + 1) * W * (NS + 8); }
-int sweep_stream_ms_xchg_doubles(int W) { return 16 + kS * 16 + 64 * W; }
 
 int prepare_sweep_stream_ms(const Dev &d, int waves) { return dispatch(d, nullptr, nullptr, waves, nullptr, true); }
 int launch_sweep_stream_ms(const Dev &d, double *abuf, double *ebuf, int waves, hipStream_t stream) {

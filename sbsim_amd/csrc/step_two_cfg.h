@@ -1,4 +1,4 @@
-// step_two_cfg.h -- what step_two.hip (the planner's interface) and step_two_impl.h (the kernel) agree on.
+// step_two_cfg.h -- what the planner (planner.cpp, plan_two), step_two.hip and step_two_impl.h (the kernel) agree on.
 #pragma once
 
 namespace sb {
@@ -7,6 +7,7 @@ namespace two {
 constexpr int kSets = 32;  // entries of the coefficient-set table (at LDS address 0)
 // Slots of A kept in LDS, by level (step_two_impl.h): level 0: two buildings per CU, 1: three, 2: four.
 constexpr int kLevels = 3;
+constexpr int kSlotCounts[] = {64, 76, 80};              // the instantiations (step_two_NN.hip)
 constexpr int lds_slots(int NR, int level) {
   return NR <= 64 ? (level == 0 ? 64 : level == 1 ? 46 : 34)
          : NR <= 76 ? (level == 0 ? 72 : level == 1 ? 46 : 34) : (level == 0 ? 74 : level == 1 ? 56 : 42);

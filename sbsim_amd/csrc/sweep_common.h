@@ -136,7 +136,7 @@ __device__ __forceinline__ double tail_pass(int T, bool active, double *tE0c, do
 // keeps the previous level's shifted value -- finite, times 0.
 // LDS layout of the table (shared by the workgroup), n = NR / 2 lanes own tail columns, l' = lane - (64 - n):
 //   [t < T][d2 (A1, A2)][n] [d2 (A3, A4)][n]   then   [d2 (A5 of row 0, A5 of row 1)][n]
-constexpr int tail_mul_doubles(int NR, int T) { return T > 0 ? (4 * T + 2) * (NR / 2) : 0; }
+// (tail_mul_doubles of them: step_roll_cfg.h)
 
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ void scan_level(double &q, double A, double &qs) {

@@ -1,7 +1,7 @@
 """Irregular, mixed-material floor plans for the sweep kernels (test utility, no GPU).
 
 Every plan the other parity tests use is `rectangular_floor_plan`: equal rooms, one material per wall kind, a one-CV
-exterior ring.  Much of the planner (sbsim_hip.hip: plan_two's two-coefficient check, the tail rows' coefficient sets,
+exterior ring.  Much of the planner (planner.cpp: plan_two's two-coefficient check, the tail rows' coefficient sets,
 the zone-free tail rows of plan_band / k_sweep_roll, the class-table strides) only does something once a plan stops
 being that.  The builders here draw file-format plans (exterior space / wall / interior) with notches, courtyards,
 passages and wall stubs, pass them through `FloorPlan.from_file_input` (wall kinds and diffusers follow the

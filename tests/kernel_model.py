@@ -210,7 +210,7 @@ class FastSweepModel:
 
 
 # ----------------------------------------------------------------------------------------
-# Model of the register-resident sweeps and of their launch planning (plan_reg in sbsim_hip.hip):
+# Model of the register-resident sweeps and of their launch planning (plan_reg / plan_roll in planner.cpp):
 # trim box, cyclic-skewed slots, DPP neighbours, lane predicates; k_sweep_reg's one-wavefront
 # mode (mode 1) and its two-wavefront seam protocol with the chunk lag and 2-step-early seam
 # reads (mode 2) (sbsim_amd/csrc/step_reg.hip); k_sweep_roll's tail-row recurrence (mode 3) and

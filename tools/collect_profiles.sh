@@ -37,7 +37,7 @@ for line in open(out + "/bench_under_rocprof.json"):
         bench = json.loads(line)
 li = bench.get("config", {}).get("launch", {})
 Z, O = bench.get("config", {}).get("zones", 9), 46
-# sb_launch_info.state_bytes_per_env_step = 16*state_doubles + per-zone/scalar/obs bytes (sbsim_hip.hip)
+# sb_launch_info.state_bytes_per_env_step = 16*state_doubles + per-zone/scalar/obs bytes (planner.cpp)
 state_bytes = (li.get("state_bytes_per_env_step", 0) - ((8 * 4 + 4 * 2) * Z + 16 * 16 + 8 + 4 * O + 4)) // 2
 kern = "k_sweep"
 # the sweep kernel's real name, from the counter rows themselves
