@@ -673,6 +673,56 @@ int sb_clock_detach(sb_handle *h);
  * weather_f_now, the replay trace with weather_t_now) -- with a clock, each building's own row at pos. */
 int sb_observe_step_in(sb_handle *h, const sb_step_in *in, float *obs_dev, void *stream);
 
+/* Episodes per building (the reference builds one Environment per building and resets each on its own,
+ * environment.py:1165-1212): part of a batch is reset on the device while the rest runs on.
+ *
+ * For every building b with mask_host[b] != 0: exactly what sb_reset does to building b (grid from temps_dev[b] or
+ * initial_temp -- temps_dev is the full [B][H*W] array, only masked rows are read --, zone means, VAV state, the mode
+ * word's thermostat bits kept, scalars, AHU / boiler setpoints from the building's own sb_set_building_params row, the
+ * register layouts' ring extremes; SB_KERNEL_JACOBI: k_reset_jacobi's float32 rounding).  Every other building: not one
+ * bit of its state changes.  restart_pos: with a clock attached, the batch position (sb_clock_seek's pos) of the reset
+ * buildings' next step; from then on building b reads rows offsets[b] + (pos - restart_pos) (+1 for "next").
+ * Ignored without a clock.
+ *
+ * The mask is a HOST array, on purpose: the library keeps a host shadow of every building's restart position and
+ * recomputes from it the bounds sb_clock_seek checks on the host -- the largest effective offset (offsets[b] - the
+ * building's restart position) for "row now + 1 inside the table", and the largest restart position for "pos >= every
+ * building's restart position" -- so that no kernel is launched with a row outside the table.  A seek that would leave
+ * the table for some building, or go below a restart position, is SB_ERR_INVALID; so is an sb_step*, sb_observe* or
+ * sb_occupancy_peek while the clock stands below a restart position (restart_pos may lie ahead of the position sought
+ * last: seek there before the next launch).
+ * The call uploads the mask on `stream`, after the work queued there, and synchronises `stream` before it launches (the
+ * host array may go away on return); SB_ERR_INVALID while the stream is being captured into a graph.
+ * Device side of the calendar: the attached offsets stay; a second [B] array of effective offsets, allocated by
+ * sb_clock_attach, is what the kernels index.  The masked reset writes effective[b] = offsets[b] - restart_pos.
+ * sb_reset (every building) restores effective = offsets with a stream-ordered device copy and clears the shadow: a
+ * handle on which sb_reset_buildings was never called behaves exactly as it always has.
+ * The boiler's action age (the scalar state's last entry) rewinds by the building's OWN steps since its own last reset:
+ * a [B] int array, allocated by the first sb_reset_buildings (which cannot be captured), holds the handle's step count
+ * at each building's last reset; sb_reset subtracts it out and zeroes it (all zero: the arithmetic of a handle that never
+ * saw a partial reset, bit for bit).  The [B] device copy of the mask is allocated by the first call of either entry.
+ * The previous thermostat update: the row offsets[b] + prev_pos means nothing for a building that was just reset alone.
+ * From the first sb_reset_buildings until the next sb_reset, a clocked k_pre takes comfort_prev of EVERY building from its
+ * scalar state (the comfort mode at its last thermostat update, which survives a reset as Thermostat._previous_timestamp
+ * does), as it does under reject_dev; it equals the row lookup whenever no request was rejected.
+ * The device occupancy generator and the convection shuffle are untouched: their state and counters are rewound by no
+ * reset.  A snapshot carries neither the restart positions nor the per-building step counts: sb_state_load is
+ * SB_ERR_INVALID from the first sb_reset_buildings until the next sb_reset.  sb_clock_detach (and a new
+ * sb_clock_attach) drops the restart positions and the comfort_prev rule with the calendar they belonged to.
+ * One stream: the handle has ONE device copy of the mask, so sb_reset_buildings and sb_observe_buildings are to be
+ * called on the stream the handle's other work is queued on -- a call on a second stream could overwrite the mask
+ * under a kernel of the first that is still queued.
+ * SB_ERR_INVALID: a null handle or mask; a call before the first sb_reset; restart_pos < 0 with a clock; a restart that
+ * leaves a masked building without two rows of the table at the position sought (the message names the building).  A
+ * refused call changes nothing.  A mask of all zeros is a no-op that returns SB_OK. */
+int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host /* [B] */, int32_t restart_pos,
+                       double initial_temp, const double *temps_dev, void *stream);
+/* sb_observe_step_in for the buildings with mask_host[b] != 0 only: their rows of obs_dev are written (and their
+ * observe_boiler bookkeeping done); the other buildings' rows and state are untouched.  The mask as above: a HOST array,
+ * uploaded on `stream`, which is synchronised; SB_ERR_INVALID for a null argument or a capturing stream; all zeros: a
+ * no-op. */
+int sb_observe_buildings(sb_handle *h, const uint8_t *mask_host, const sb_step_in *in, float *obs_dev, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

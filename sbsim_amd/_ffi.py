@@ -165,7 +165,7 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi", "sb_set_building_params",
            "sb_set_reward_function", "sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials",
            "sb_get_building_coef", "sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in",
-           "sb_debug_plan_digest")
+           "sb_debug_plan_digest", "sb_reset_buildings", "sb_observe_buildings")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
@@ -173,6 +173,7 @@ BUILDING_PARAM_ENTRIES = ("sb_set_building_params",)
 REWARD_ENTRIES = ("sb_set_reward_function",)
 CLOCK_ENTRIES = ("sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in")
 PLAN_DIGEST_ENTRIES = ("sb_debug_plan_digest",)
+EPISODES_ENTRIES = ("sb_reset_buildings", "sb_observe_buildings")
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -269,6 +270,9 @@ def load():
     L.sb_clock_seek.argtypes = [vp, C.c_int32, C.c_int32]
     L.sb_clock_detach.argtypes = [vp]
     L.sb_observe_step_in.argtypes = [vp, C.POINTER(StepIn), vp, vp]
+  if all(hasattr(L, name) for name in EPISODES_ENTRIES):
+    L.sb_reset_buildings.argtypes = [vp, vp, C.c_int32, C.c_double, vp, vp]
+    L.sb_observe_buildings.argtypes = [vp, vp, C.POINTER(StepIn), vp, vp]
   if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
     L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
@@ -308,6 +312,11 @@ def materials_entry(name: str):
 def clock_entry(name: str):
   """The per-building-calendar entry `name` (sb_clock_attach, sb_clock_seek, sb_clock_detach, sb_observe_step_in): see
   entry()."""
+  return entry(name)
+
+
+def episodes_entry(name: str):
+  """The per-building-episodes entry `name` (sb_reset_buildings, sb_observe_buildings): see entry()."""
   return entry(name)
 
 

@@ -79,8 +79,15 @@ def _device_of(env):
   return getattr(sim, "tdev", torch.device("cpu"))
 
 
+def _refuse_per_building_episodes(env, who: str) -> None:
+  if getattr(env, "per_building_episodes", False):
+    raise ValueError(f"{who} has next-step autoreset semantics: not for an environment with per_building_episodes "
+                     "(same-step autoreset); sbsim_amd.environment.GymVectorEnv is the view that reports it")
+
+
 def tf_agents_environment(env):
   """-> tf_agents PyEnvironment (batched) around ``env``.  ImportError without tf-agents."""
+  _refuse_per_building_episodes(env, "tf_agents_environment")
   from tf_agents.environments import py_environment
   from tf_agents.specs import array_spec
   from tf_agents.trajectories import time_step as ts_lib
@@ -137,6 +144,7 @@ def gymnasium_vector_env(env, time_limit_is_truncation: bool = True):
   that a learner keeps bootstrapping from the last observation.  (The reference's own TF-Agents environment
   ends the episode with discount 0, i.e. as a termination; `time_limit_is_truncation=False` reports it that
   way: `terminated` set, `truncated` False -- round 3's behaviour.)"""
+  _refuse_per_building_episodes(env, "gymnasium_vector_env")
   import gymnasium as gym
 
   a_spec, o_spec = env.action_spec(), env.observation_spec()

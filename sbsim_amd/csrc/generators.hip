@@ -460,9 +460,8 @@ int sb_occupancy_peek(sb_handle *h, int32_t local_hour, int32_t is_work_day, flo
   OccArgs o;
   o.clk = ClockView{}; o.delta = 0; o.field = SB_CLK_OCC_HOUR;
   if (h->clock_rows.p) { // a calendar per building: the two arguments choose the row and its pair (sbsim_amd.h, sb_clock_seek)
-    if (h->clock_pos < 0) return fail(SB_ERR_INVALID, "sb_occupancy_peek: the handle has a clock that was never sought (sb_clock_seek)");
+    SB_CHECK(handle_clock_view(h, "sb_occupancy_peek", &o.clk));
     if (local_hour > 1) return fail(SB_ERR_INVALID, "sb_occupancy_peek: with a clock the hour argument is the row, 0 or 1");
-    o.clk = ClockView{h->clock_rows.p, h->clock_offs.p, h->clock_pos, h->clock_prev, h->clock_n_rows};
     o.delta = local_hour;
     o.field = is_work_day ? SB_CLK_OCC_HOUR : SB_CLK_OCC_HOUR5;
   }

@@ -17,13 +17,35 @@ using namespace sb;
 namespace {
 
 // ---------------------------------------------------------------- kernels
+// Episodes per building (sb_reset_buildings): which buildings a reset kernel resets, and what it keeps per building.
+struct EpisodeArgs {
+  const uint8_t *mask; // [B] the buildings to reset (mask[b] != 0); NULL: every building (sb_reset)
+  int *ep_start;       // [B] the handle's steps_since_reset at the building's own last reset; NULL: never allocated, all 0
+  int *eff;            // [B] a masked reset writes the building's effective clock offset; NULL: no clock
+  const int *offs0;    // [B] the attached offsets
+  int restart_pos;     // the batch position of the masked buildings' next step
+};
+__device__ __forceinline__ bool skips(const uint8_t *mask, int b) { return mask && !mask[b]; }
+
+// The end of a building's reset (lane 0 of its wavefront), shared by k_reset and k_reset_jacobi: Thermostat._previous_timestamp
+// and SmartDevice._action_timestamp are construction state, Simulator.reset() leaves them alone (thermostat.py:66-69,
+// smart_device.py:71-72) ... but the clock rewinds under them: the boiler's age of its last action goes negative, by the
+// building's own steps since its own last reset (ep_start all 0: by steps_since_reset, the batch's).
+__device__ __forceinline__ void reset_episode(double *S, const EpisodeArgs &ep, int b, int first, int steps_since_reset) {
+  if (first) { S[18] = -1.0; S[19] = kAgeNone; }
+  else if (!age_is_none(S[19])) S[19] -= (double)(steps_since_reset - (ep.ep_start ? ep.ep_start[b] : 0));
+  if (ep.ep_start) ep.ep_start[b] = ep.mask ? steps_since_reset : 0;
+  if (ep.mask && ep.eff) ep.eff[b] = ep.offs0[b] - ep.restart_pos;
+}
+
 // Simulator.reset(): grid (either state layout), zone means, device scalars.
 // temps_only (sb_set_temps): the grid inside the building and the zone means follow `temps`; every device state stays.
-__global__ void k_reset(Dev a, double initial_temp, const double *temps, int first, int steps_since_reset, int temps_only) {
+__global__ void k_reset(Dev a, EpisodeArgs ep, double initial_temp, const double *temps, int first, int steps_since_reset, int temps_only) {
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int nwaves = gridDim.x * (blockDim.x >> 6);
   for (int b = wave; b < a.B; b += nwaves) {
+    if (skips(ep.mask, b)) continue; // (b is the wavefront's: uniform)
     double s = 0.0, rlo = INFINITY, rhi = -INFINITY;
     if (a.reg) {
       double *T = a.temp + (size_t)b * a.state_doubles;
@@ -87,20 +109,18 @@ __global__ void k_reset(Dev a, double initial_temp, const double *temps, int fir
       S[12] = S[13] = S[14] = S[15] = 0.0;
       S[16] = a.reg && a.n_ring > 0 ? rlo : 0.0; // extremes of the exterior-space ring (register path)
       S[17] = a.reg && a.n_ring > 0 ? rhi : 0.0;
-      // Thermostat._previous_timestamp and SmartDevice._action_timestamp are construction state:
-      // Simulator.reset() leaves them alone (thermostat.py:66-69, smart_device.py:71-72)
-      // ... but the clock rewinds under them: the boiler's age of its last action goes negative
-      if (first) { S[18] = -1.0; S[19] = kAgeNone; }
-      else if (!age_is_none(S[19])) S[19] -= (double)steps_since_reset;
+      reset_episode(S, ep, b, first, steps_since_reset);
     }
   }
 }
 
 // in: the observation's inputs as a step's "now" half (aux, num_occupants_dev, occupancy_norm, the weather at t);
-// t_amb_b: sb_observe's [B] ambient temperatures (override); clk: the building's own row at the position sought
+// t_amb_b: sb_observe's [B] ambient temperatures (override); clk: the building's own row at the position sought;
+// mask (sb_observe_buildings): the buildings to observe, NULL: every building
 template <bool CLK> // a calendar per building (sb_clock_attach): a kernel per value, see sb_device.h clocked()
-__global__ void k_observe(Dev a, ClockView clk, sb_step_in in, const double *t_amb_b, float *obs) {
+__global__ void k_observe(Dev a, ClockView clk, sb_step_in in, const double *t_amb_b, float *obs, const uint8_t *mask) {
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) {
+    if (skips(mask, b)) continue;
     double *S = a.scal + (size_t)b * kNScal;
     observe_boiler(a, S, b);
     const int crow = clock_row<CLK>(clk, b);
@@ -258,11 +278,12 @@ __global__ void __launch_bounds__(kStateThreads) k_state(Dev a, sb_state_view v,
 // SB_KERNEL_JACOBI: Simulator.reset() on the float32 grid.  The grid is stored rounded to float32 (as the reference's first
 // FD update reads it); the zone means and the grid mean the first step reads are the float64 values, as the reference's
 // are.  The scalars as k_reset sets them.  One wavefront per building.
-__global__ void k_reset_jacobi(Dev a, float *grid, double initial_temp, const double *temps, int first, int steps_since_reset) {
+__global__ void k_reset_jacobi(Dev a, EpisodeArgs ep, float *grid, double initial_temp, const double *temps, int first, int steps_since_reset) {
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int nwaves = gridDim.x * (blockDim.x >> 6);
   for (int b = wave; b < a.B; b += nwaves) {
+    if (skips(ep.mask, b)) continue;
     double s = 0.0;
     for (int g = lane; g < a.N; g += 64) {
       const double v = temps ? temps[(size_t)b * a.N + g] : initial_temp;
@@ -293,8 +314,7 @@ __global__ void k_reset_jacobi(Dev a, float *grid, double initial_temp, const do
       S[11] = s / (double)a.N;
       S[12] = S[13] = S[14] = S[15] = 0.0;
       S[16] = S[17] = 0.0; // (the register path's ring extremes: no ring here)
-      if (first) { S[18] = -1.0; S[19] = kAgeNone; }
-      else if (!age_is_none(S[19])) S[19] -= (double)steps_since_reset;
+      reset_episode(S, ep, b, first, steps_since_reset);
     }
   }
 }
@@ -477,21 +497,98 @@ int sb_get_launch_info(const sb_handle *h, sb_launch_info *out) {
   return SB_OK;
 }
 
-int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *stream) {
-  if (!h) return fail(SB_ERR_INVALID, "sb_reset: null handle");
-  SB_ON_DEVICE(h->device);
+// The reset kernel of the handle's state layout on the buildings of `ep` (sb_reset: every building; sb_reset_buildings: its mask).
+static void launch_reset(sb_handle *h, const EpisodeArgs &ep, double initial_temp, const double *temps_dev, hipStream_t stream) {
   const int wpb = 4;
   const int blocks = std::min((h->d.B + wpb - 1) / wpb, 4096);
   if (h->kernel == SB_KERNEL_JACOBI)
-    hipLaunchKernelGGL(k_reset_jacobi, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream, h->d, h->jgrid.p,
+    hipLaunchKernelGGL(k_reset_jacobi, dim3(blocks), dim3(64 * wpb), 0, stream, h->d, ep, h->jgrid.p,
                        initial_temp, temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset);
   else
-    hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream, h->d, initial_temp,
+    hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(64 * wpb), 0, stream, h->d, ep, initial_temp,
                        temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset, 0);
+}
+
+// The bounds sb_clock_seek checks, from the host shadow of the restart positions.
+static void episode_bounds(sb_handle *h) {
+  int max_eff = INT32_MIN, max_restart = 0;
+  for (size_t b = 0; b < h->h_clock_offs.size(); ++b) {
+    const int r = h->restart_pos.empty() ? 0 : h->restart_pos[b];
+    max_eff = std::max(max_eff, h->h_clock_offs[b] - r);
+    max_restart = std::max(max_restart, r);
+  }
+  h->clock_max_off = h->h_clock_offs.empty() ? 0 : max_eff;
+  h->max_restart = max_restart;
+}
+
+int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *stream) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_reset: null handle");
+  SB_ON_DEVICE(h->device);
+  launch_reset(h, EpisodeArgs{nullptr, h->ep_start.p, nullptr, nullptr, 0}, initial_temp, temps_dev, (hipStream_t)stream);
   h->was_reset = true;
   h->steps_since_reset = 0;
   h->counters_zeroed_on = (void *)(uintptr_t)1; // (whatever came before a reset is no promise about the draw counters)
   SB_HIP(hipGetLastError());
+  h->ep_dirty = false; // (the kernel above zeroes ep_start)
+  if (!h->restart_pos.empty() || h->own_prev) { // episodes per building: every building back on the attached calendar
+    if (h->clock_eff.p)
+      SB_HIP(hipMemcpyAsync(h->clock_eff.p, h->clock_offs.p, (size_t)h->d.B * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    h->restart_pos.clear();
+    h->own_prev = false;
+    episode_bounds(h);
+  }
+  return SB_OK;
+}
+
+// sb_reset_buildings / sb_observe_buildings: the mask on the device, after the work queued on `stream` (the copy reads
+// host memory that may go away with the call: the stream is drained before it returns).
+static int upload_mask(sb_handle *h, const uint8_t *mask_host, const char *who, hipStream_t stream) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  SB_HIP(hipStreamIsCapturing(stream, &cap));
+  if (cap != hipStreamCaptureStatusNone)
+    return fail(SB_ERR_INVALID, std::string(who) + ": not while the stream is being captured into a graph");
+  const size_t B = (size_t)h->d.B;
+  if (!h->ep_mask.p) SB_HIP(hipMalloc((void **)&h->ep_mask.p, B));
+  SB_HIP(hipMemcpyAsync(h->ep_mask.p, mask_host, B, hipMemcpyHostToDevice, stream));
+  SB_HIP(hipStreamSynchronize(stream));
+  return SB_OK;
+}
+
+int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host, int32_t restart_pos, double initial_temp,
+                       const double *temps_dev, void *stream) {
+  if (!h || !mask_host) return fail(SB_ERR_INVALID, "sb_reset_buildings: null argument");
+  if (!h->was_reset) return fail(SB_ERR_INVALID, "sb_reset_buildings: sb_reset first");
+  const int B = h->d.B;
+  const bool clk = h->clock_rows.p != nullptr;
+  if (!clk) restart_pos = 0; // (ignored without a clock)
+  if (restart_pos < 0) return fail(SB_ERR_INVALID, "sb_reset_buildings: restart_pos must be >= 0");
+  bool any = false;
+  for (int b = 0; b < B; ++b) {
+    if (!mask_host[b]) continue;
+    any = true;
+    // the rows of the building's next launch: at the position sought now, or at restart_pos once the caller has sought
+    // there (sb_clock_seek refuses a position below it)
+    if (!clk) continue;
+    const long long now = (long long)h->h_clock_offs[b] + std::max(0LL, (long long)h->clock_pos - restart_pos);
+    if (now > (long long)h->clock_n_rows - 2)
+      return fail(SB_ERR_INVALID, "sb_reset_buildings: building " + std::to_string(b) + ": restarting at position " +
+                                      std::to_string(restart_pos) + " with the clock at " + std::to_string(h->clock_pos) +
+                                      " leaves no two rows of the table's " + std::to_string(h->clock_n_rows));
+  }
+  if (!any) return SB_OK;
+  SB_ON_DEVICE(h->device);
+  SB_CHECK(upload_mask(h, mask_host, "sb_reset_buildings", (hipStream_t)stream));
+  if (!h->ep_start.p) SB_CHECK(alloc_zero(h->ep_start, (size_t)B));
+  launch_reset(h, EpisodeArgs{h->ep_mask.p, h->ep_start.p, clk ? h->clock_eff.p : nullptr, h->clock_offs.p, restart_pos},
+               initial_temp, temps_dev, (hipStream_t)stream);
+  SB_HIP(hipGetLastError());
+  h->own_prev = h->ep_dirty = true;
+  if (clk) {
+    if (h->restart_pos.empty()) h->restart_pos.assign((size_t)B, 0);
+    for (int b = 0; b < B; ++b)
+      if (mask_host[b]) h->restart_pos[b] = restart_pos;
+    episode_bounds(h);
+  }
   return SB_OK;
 }
 
@@ -502,29 +599,33 @@ int sb_set_temps(sb_handle *h, const double *temps_dev, void *stream) {
   SB_ON_DEVICE(h->device);
   const int wpb = 4;
   const int blocks = std::min((h->d.B + wpb - 1) / wpb, 4096);
-  hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream, h->d, 0.0, temps_dev, 0, 0, 1);
+  hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream, h->d, EpisodeArgs{}, 0.0, temps_dev, 0, 0, 1);
   SB_HIP(hipGetLastError());
   return SB_OK;
 }
 
 // The handle's clock as the kernels take it (sb_clock_attach / sb_clock_seek); rows == NULL without one.
-static int clock_view(const sb_handle *h, const char *who, ClockView *out) {
-  *out = ClockView{};
-  if (!h->clock_rows.p) return SB_OK;
-  if (h->clock_pos < 0) return fail(SB_ERR_INVALID, std::string(who) + ": the handle has a clock that was never sought (sb_clock_seek)");
-  *out = ClockView{h->clock_rows.p, h->clock_offs.p, h->clock_pos, h->clock_prev, h->clock_n_rows};
+static int launch_observe(sb_handle *h, const sb_step_in &in, const double *t_amb_b, float *obs_dev, void *stream,
+                          const uint8_t *mask_host = nullptr) {
+  ClockView clk;
+  SB_CHECK(handle_clock_view(h, mask_host ? "sb_observe_buildings" : "sb_observe", &clk));
+  SB_ON_DEVICE(h->device);
+  const uint8_t *mask = nullptr;
+  if (mask_host) {
+    if (!std::any_of(mask_host, mask_host + h->d.B, [](uint8_t m) { return m != 0; })) return SB_OK;
+    SB_CHECK(upload_mask(h, mask_host, "sb_observe_buildings", (hipStream_t)stream));
+    mask = h->ep_mask.p;
+  }
+  const int blocks = std::max(1, std::min((h->d.B + 63) / 64, 4096));
+  if (clk.rows) hipLaunchKernelGGL(k_observe<true>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->d, clk, in, t_amb_b, obs_dev, mask);
+  else hipLaunchKernelGGL(k_observe<false>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->d, clk, in, t_amb_b, obs_dev, mask);
+  SB_HIP(hipGetLastError());
   return SB_OK;
 }
 
-static int launch_observe(sb_handle *h, const sb_step_in &in, const double *t_amb_b, float *obs_dev, void *stream) {
-  ClockView clk;
-  SB_CHECK(clock_view(h, "sb_observe", &clk));
-  SB_ON_DEVICE(h->device);
-  const int blocks = std::max(1, std::min((h->d.B + 63) / 64, 4096));
-  if (clk.rows) hipLaunchKernelGGL(k_observe<true>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->d, clk, in, t_amb_b, obs_dev);
-  else hipLaunchKernelGGL(k_observe<false>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, h->d, clk, in, t_amb_b, obs_dev);
-  SB_HIP(hipGetLastError());
-  return SB_OK;
+int sb_observe_buildings(sb_handle *h, const uint8_t *mask_host, const sb_step_in *in, float *obs_dev, void *stream) {
+  if (!h || !mask_host || !in || !obs_dev) return fail(SB_ERR_INVALID, "sb_observe_buildings: null argument");
+  return launch_observe(h, *in, nullptr, obs_dev, stream, mask_host);
 }
 
 int sb_observe_occupancy(sb_handle *h, const float aux[SB_NUM_AUX], double t_amb, const double *t_amb_dev,
@@ -554,7 +655,7 @@ int sb_step_phases(sb_handle *h, const float *actions_dev, const sb_step_in *in,
   if (in->has_action && !actions_dev) return fail(SB_ERR_INVALID, "sb_step: has_action set but actions_dev is NULL");
   StepArgs s;
   s.actions = actions_dev; s.obs = obs_dev; s.reward = reward_dev; s.info = info_dev; s.in = *in;
-  SB_CHECK(clock_view(h, "sb_step", &s.clk));
+  SB_CHECK(handle_clock_view(h, "sb_step", &s.clk));
   SB_ON_DEVICE(h->device);
   const Dev &d = h->d;
   const int blocks = std::max(1, std::min((d.B + kRowsPerBlock - 1) / kRowsPerBlock, h->cus * 32)); // a 16-lane row per building
@@ -674,6 +775,9 @@ int sb_state_load(sb_handle *h, const int32_t *pick_dev, const sb_state_view *vi
   SB_CHECK(check_state_view(h, view, "sb_state_load"));
   if (!pick_dev && view->n != h->d.B) return fail(SB_ERR_INVALID, "sb_state_load: without pick_dev, view->n must be the batch size");
   if (clock_in && clock_in->steps_since_reset < 0) return fail(SB_ERR_INVALID, "sb_state_load: negative steps_since_reset");
+  if (h->ep_dirty || h->own_prev) // the snapshot carries neither the buildings' restart positions nor their own step counts
+    return fail(SB_ERR_INVALID, "sb_state_load: buildings were reset by themselves (sb_reset_buildings) since the last sb_reset: "
+                                "their episode positions are not in a snapshot; sb_reset first");
   SB_ON_DEVICE(h->device);
   launch_state(h, false, pick_dev, 0, view, transposed, (hipStream_t)stream);
   SB_HIP(hipGetLastError());
@@ -830,12 +934,18 @@ static const char *const kClockFieldNames[SB_CLOCK_FIELDS] = {
     "occupancy", "e_price", "e_carbon", "g_price", "g_carbon", "occ_hour", "occ_workday", "occ_hour5", "occ_workday5"};
 
 static int drop_clock(sb_handle *h) { // the kernels in flight read the table: it goes once the device is idle
-  if (!h->clock_rows.p && !h->clock_offs.p) return SB_OK;
+  if (!h->clock_rows.p && !h->clock_offs.p && !h->clock_eff.p) return SB_OK;
   SB_HIP(hipDeviceSynchronize());
   if (h->clock_rows.p) SB_HIP(hipFree(h->clock_rows.p));
   h->clock_rows.p = nullptr;
   if (h->clock_offs.p) SB_HIP(hipFree(h->clock_offs.p));
   h->clock_offs.p = nullptr;
+  if (h->clock_eff.p) SB_HIP(hipFree(h->clock_eff.p));
+  h->clock_eff.p = nullptr;
+  h->h_clock_offs.clear();
+  h->restart_pos.clear(); // a clock attached later starts from its own offsets and reads its own previous row
+  h->own_prev = false;
+  h->max_restart = 0;
   h->clock_n_rows = h->clock_max_off = 0;
   h->clock_pos = h->clock_prev = -1;
   return SB_OK;
@@ -866,6 +976,8 @@ int sb_clock_attach(sb_handle *h, const double *rows_host, int32_t n_rows, int32
   SB_CHECK(drop_clock(h));
   SB_CHECK(upload(h->clock_rows, rows_host, (size_t)n_rows * SB_CLOCK_FIELDS));
   SB_CHECK(upload(h->clock_offs, offsets_host, (size_t)B));
+  SB_CHECK(upload(h->clock_eff, offsets_host, (size_t)B)); // every building on its attached offset until sb_reset_buildings
+  h->h_clock_offs.assign(offsets_host, offsets_host + B);
   h->clock_n_rows = n_rows;
   h->clock_max_off = max_off;
   return SB_OK;
@@ -881,6 +993,9 @@ int sb_clock_seek(sb_handle *h, int32_t pos, int32_t prev_pos) {
     return fail(SB_ERR_INVALID, "sb_clock_seek: position " + std::to_string(pos) + " (previous " + std::to_string(prev_pos) +
                                     ") plus the largest offset " + std::to_string(h->clock_max_off) + " runs past the table's " +
                                     std::to_string(h->clock_n_rows) + " rows");
+  if (pos < h->max_restart) // (sb_reset_buildings) a building's rows start at its restart position: below it, row < its offset -- or < 0
+    return fail(SB_ERR_INVALID, "sb_clock_seek: position " + std::to_string(pos) + " is below a building's restart position " +
+                                    std::to_string(h->max_restart) + " (sb_reset_buildings)");
   h->clock_pos = pos;
   h->clock_prev = prev_pos;
   return SB_OK;

@@ -211,10 +211,15 @@ __device__ __forceinline__ double bparam(const Dev &a, int k, int b) {
 // per instant of the lattice; offs: [B] every building's offset into it; pos / prev: the batch's position and that of the
 // previous thermostat update (-1: none), both sb_clock_seek's.  rows == NULL: no clock.  A kernel argument of k_pre, k_post,
 // k_observe and k_occupancy alone (StepArgs, not Dev: no sweep kernel carries it).
+// offs are the EFFECTIVE offsets: the attached ones until sb_reset_buildings restarts a building at batch position r, from
+// when its entry is attached offset - r (its rows: attached offset + (pos - r)); sb_reset restores the attached ones.
+// own_prev: some building was reset by itself since the last sb_reset, so the row offs[b] + prev means nothing for it (it
+// can be row -1): k_pre takes every building's previous thermostat update from scal[18], as it does under reject_dev.
 struct ClockView {
   const double *rows;
   const int *offs;
   int pos, prev, n_rows;
+  int own_prev;
 };
 
 // CLK: the kernel was launched for a handle with a clock (c.rows != NULL).  A kernel per value, as k_pre per MAT and k_post
@@ -616,7 +621,9 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
   const double ahu_max_flow = bparam(a, SB_BP_AHU_MAX_FLOW, b);
   // Thermostat._previous_timestamp (thermostat.py:88): the host's value, or the building's own when
   // buildings can skip thermostat updates (scal[18]: -1 none, else is_comfort_mode of the last update)
-  const int comfort_prev = in.reject_dev ? (int)S18
+  // ... or once a building was reset by itself (sb_reset_buildings; ClockView::own_prev): scal[18] survives a reset as
+  // Thermostat._previous_timestamp does, and equals the row lookup whenever no request was rejected
+  const int comfort_prev = in.reject_dev || (CLK && s.clk.own_prev) ? (int)S18
                            : CLK && s.clk.prev < 0 ? -1
                            : (int)clocked<CLK>(s.clk, crow + s.clk.prev - s.clk.pos, SB_CLK_COMFORT, (double)in.comfort_prev);
   double ahu_flow = 0.0, blr_flow = 0.0, num = 0.0, den = 0.0;

@@ -165,9 +165,19 @@ struct sb_handle {
   bool occ_attached = false;
   // sb_clock_attach / sb_clock_seek: the table of instants, the buildings' offsets, the position of the next step
   DevBuf<double> clock_rows;        // [clock_n_rows][SB_CLOCK_FIELDS]; NULL: no clock
-  DevBuf<int> clock_offs;           // [B]
-  int clock_n_rows = 0, clock_max_off = 0;
+  DevBuf<int> clock_offs;           // [B] the attached offsets
+  DevBuf<int> clock_eff;            // [B] the effective offsets (ClockView::offs): attached offset - the building's restart position
+  std::vector<int> h_clock_offs;    // [B] host copy of the attached offsets
+  int clock_n_rows = 0, clock_max_off = 0; // clock_max_off: the largest EFFECTIVE offset (sb_clock_seek's bound)
   int clock_pos = -1, clock_prev = -1; // pos < 0: never sought
+  // sb_reset_buildings: episodes per building.  The host shadow of every building's restart position (empty: all 0), the
+  // largest of them (sb_clock_seek: pos >= it), and whether some building was reset by itself since the last sb_reset
+  std::vector<int> restart_pos;
+  int max_restart = 0;
+  bool own_prev = false;
+  bool ep_dirty = false;            // ep_start may hold non-zero entries: a partial reset since the last sb_reset
+  DevBuf<int> ep_start;             // [B] the handle's steps_since_reset at the building's own last reset (allocated by the first sb_reset_buildings)
+  DevBuf<uint8_t> ep_mask;          // [B] the mask of the call in flight (allocated by the first sb_reset_buildings / sb_observe_buildings)
   // sb_create_materials: the structural classes' descriptors, the buildings' values and their coefficient rows
   bool materials = false;
   int mat_slots = 0;                // M
@@ -184,6 +194,20 @@ struct sb_handle {
   sb::JacArgs jac{};
 };
 
+
+// The handle's clock as the kernels take it (sb_clock_attach / sb_clock_seek); rows == NULL without one.  Refused: a clock
+// never sought, or sought below a building's restart position (sb_reset_buildings: that building's row would lie before
+// its offset, or before the table).
+inline int handle_clock_view(const sb_handle *h, const char *who, sb::ClockView *out) {
+  *out = sb::ClockView{};
+  if (!h->clock_rows.p) return SB_OK;
+  if (h->clock_pos < 0) return fail(SB_ERR_INVALID, std::string(who) + ": the handle has a clock that was never sought (sb_clock_seek)");
+  if (h->clock_pos < h->max_restart)
+    return fail(SB_ERR_INVALID, std::string(who) + ": a building restarts at position " + std::to_string(h->max_restart) +
+                                    " (sb_reset_buildings), the clock is at " + std::to_string(h->clock_pos) + ": sb_clock_seek first");
+  *out = sb::ClockView{h->clock_rows.p, h->clock_eff.p, h->clock_pos, h->clock_prev, h->clock_n_rows, h->own_prev ? 1 : 0};
+  return SB_OK;
+}
 
 // runtime.hip: the one dispatch on sb_handle::kernel -- the sweep kernel's LDS attribute (sb_create), its launch (sb_step)
 int prepare_sweep(const sb_handle *h);

@@ -631,6 +631,62 @@ class BatchedSimulator:
                "sb_observe_step_in")
     return out
 
+  # ---- episodes per building (sb_reset_buildings / sb_observe_buildings) ----
+  def _host_mask(self, mask) -> np.ndarray:
+    """A building mask as the library takes it: uint8 [B] on the host.  bool or uint8, numpy or torch; a device tensor is
+    copied to the host, which synchronises with the device."""
+    if isinstance(mask, torch.Tensor):
+      if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"mask must be bool or uint8, got {mask.dtype}")
+      m = mask.detach().cpu().numpy()
+    else:
+      m = np.asarray(mask)
+      if m.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+        raise ValueError(f"mask must be bool or uint8, got dtype {m.dtype}")
+    if m.shape != (self.B,):
+      raise ValueError(f"mask must have shape [{self.B}] (one flag per building), got {tuple(m.shape)}")
+    return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+  def reset_buildings(self, mask, restart_pos: int = 0, initial_temp: Optional[float] = None,
+                      temps: Optional[torch.Tensor] = None) -> None:
+    """sb_reset_buildings: ``reset`` for the buildings of ``mask`` alone (bool or uint8 [B], numpy or torch -- a device
+    tensor is copied to the host, which synchronises); not one bit of another building's state changes.  ``restart_pos``:
+    with a clock attached, the batch position of the reset buildings' next step (``clock_seek`` there before it).
+    ``temps``: the full [B, H*W] array, of which only the masked rows are read.  The call synchronises with the current
+    stream; not while that stream is being captured.  ValueError: a mask of the wrong shape or dtype (before any
+    launch), and what the library refuses (before the first ``reset``, a negative restart_pos, a restart that leaves a
+    building without two rows of the table)."""
+    fn = _ffi.episodes_entry("sb_reset_buildings")
+    m = self._host_mask(mask)
+    ptr = None
+    if temps is not None:
+      if temps.dtype != torch.float64 or tuple(temps.shape) != (self.B, self.H * self.W) or not temps.is_contiguous():
+        raise ValueError("temps must be a contiguous float64 [B, H*W] tensor")
+      if self.transposed:
+        temps = temps.view(self.B, self.H, self.W).transpose(1, 2).contiguous()
+      ptr = C.c_void_p(temps.data_ptr())
+    t0 = self.config.initial_temp if initial_temp is None else float(initial_temp)
+    with torch.cuda.device(self.device):
+      rc = fn(self._h, m.ctypes.data_as(C.c_void_p), int(restart_pos), t0, ptr, self._stream())
+    if rc == -1:   # SB_ERR_INVALID
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_reset_buildings")
+
+  def observe_buildings(self, mask, step_in: _ffi.StepIn, out: torch.Tensor) -> torch.Tensor:
+    """sb_observe_buildings: ``observe_step_in`` for the buildings of ``mask`` (as ``reset_buildings`` takes it): their
+    rows of ``out`` (float32 [B, O]) are written, every other row and building is left alone."""
+    fn = _ffi.episodes_entry("sb_observe_buildings")
+    m = self._host_mask(mask)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (self.B, self.O)
+        or not out.is_contiguous() or out.device != self.tdev):
+      raise ValueError(f"out must be a contiguous float32 [{self.B}, {self.O}] tensor on {self.tdev}")
+    with torch.cuda.device(self.device):
+      rc = fn(self._h, m.ctypes.data_as(C.c_void_p), C.byref(step_in), C.c_void_p(out.data_ptr()), self._stream())
+    if rc == -1:
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_observe_buildings")
+    return out
+
   def observe(self, aux: Sequence[float], t_amb, out: Optional[torch.Tensor] = None,
               num_occupants: Optional[torch.Tensor] = None, occupancy_norm: float = 0.0) -> torch.Tensor:
     """t_amb: one ambient temperature, or a float64 [B] device tensor (per-building weather).
@@ -950,8 +1006,15 @@ class BatchedEnvironment:
                normalize_reduce: bool = False, convection_simulator=None, solver: str = "gauss_seidel",
                building_params: Optional[host_inputs.BuildingParams] = None,
                reward_function: Optional[host_inputs.SetpointEnergyCarbonReward] = None,
-               building_materials: Optional[host_inputs.BuildingMaterials] = None, start_offsets=None):
-    """``start_offsets``: None -- every building lives at ``start_timestamp + step * step_interval``; an integer array
+               building_materials: Optional[host_inputs.BuildingMaterials] = None, start_offsets=None,
+               per_building_episodes: bool = False, episode_steps=None):
+    """``per_building_episodes`` / ``episode_steps``: episodes per building with same-step autoreset (INTEGRATION.md
+    4k).  ``episode_steps``: an integer array [B], building b's step returns LAST when its own step count has reached
+    ``episode_steps[b]`` (1 .. ``steps_per_episode``); giving it implies the flag, the flag alone gives every building
+    ``steps_per_episode``.  ``step()`` then resets the buildings whose episode just ended on the device and returns
+    their first observation of the new episode (their last one: ``final_observation``); ``reset_buildings(mask)`` ends
+    episodes early.  Both left out (the default): nothing of this is built.
+    ``start_offsets``: None -- every building lives at ``start_timestamp + step * step_interval``; an integer array
     [B] of whole step intervals (>= 0) -- building b lives at ``start_timestamp + (start_offsets[b] + step) *
     step_interval``: its own calendar (time features, setpoint schedule, tariffs, occupancy, weather) on the batch's one
     episode clock (``current_simulation_timestamps()``).
@@ -966,6 +1029,11 @@ class BatchedEnvironment:
       raise ValueError("Discount factor must be in (0,1]")   # environment.py:454-455
     if solver == "jacobi_fp32" and convection_simulator is not None:
       raise ValueError("a convection_simulator is not implemented for solver='jacobi_fp32'")
+    self.per_building_episodes = bool(per_building_episodes) or episode_steps is not None
+    if self.per_building_episodes and isinstance(occupancy, host_inputs.BatchedRandomizedArrivalDepartureOccupancy):
+      raise ValueError("per_building_episodes: BatchedRandomizedArrivalDepartureOccupancy is not supported -- each of its "
+                       "queries advances every building's occupants, so the observation of the buildings that restart "
+                       "would draw for all the others too")
     self.config = config or SimConfig.sb1()
     self.weather = weather or host_inputs.WeatherController(273.0, 283.0, convection_coefficient=100.0)
     self.occupancy = occupancy or host_inputs.StepFunctionOccupancy(
@@ -1017,6 +1085,9 @@ class BatchedEnvironment:
                                            self._num_timesteps_in_episode)
       self.sim.clock_attach(self.timeline.rows, self.start_offsets)
       self._cursor = host_inputs.ClockCursor()
+    self.episode_steps = self.final_observation = None
+    if self.per_building_episodes:
+      self._setup_episodes(episode_steps)
     self._action_spec = ArraySpec((self.sim.n_actions,), np.dtype(np.float32), "action", -1.0, 1.0)
     self._observation_spec = ArraySpec((self.sim.O,), np.dtype(np.float32), "observation")
     self.field_names = self.sim.field_names
@@ -1027,6 +1098,12 @@ class BatchedEnvironment:
                   if collect_info else None)
     self._discount = torch.full((self.batch_size,), self.discount_factor, dtype=torch.float32, device=dev)
     self._zero = torch.zeros((self.batch_size,), dtype=torch.float32, device=dev)
+    if self.per_building_episodes:
+      self.final_observation = torch.zeros_like(self._obs)   # [B, O]: a building's row is written when its episode ends
+      self._step_type = torch.zeros((self.batch_size,), dtype=torch.int32, device=dev)   # per building, kept between calls
+      self._disc = torch.ones((self.batch_size,), dtype=torch.float32, device=dev)
+      # the previous thermostat update stays per building on the device (scal[18]), as after a first rejection
+      self._no_reject = torch.zeros((self.batch_size,), dtype=torch.uint8, device=dev)
     self._episode_ended = False
     self._step_count = 0
     self._episode_count = 0
@@ -1060,9 +1137,18 @@ class BatchedEnvironment:
   def current_simulation_timestamps(self) -> List[dt.datetime]:
     """Every building's own instant: ``current_simulation_timestamp`` (the batch's base clock) moved by the building's
     start offset; without ``start_offsets``, the base clock B times."""
+    if self.per_building_episodes:   # every building's own episode position on its own calendar
+      offs = np.zeros(self.batch_size, dtype=np.int64) if self.start_offsets is None else self.start_offsets
+      return [self._start_timestamp + int(r) * self._step_interval for r in self._cursor.rows(offs)["now"]]
     if self.start_offsets is None:
       return [self._now] * self.batch_size
     return [self._now + int(o) * self._step_interval for o in self.start_offsets]
+
+  def episode_positions(self) -> np.ndarray:
+    """Every building's position in its own episode (the steps it has taken since its last reset), int64 [B]."""
+    if not self.per_building_episodes:
+      return np.full(self.batch_size, int(round((self._now - self._start_timestamp) / self._step_interval)), dtype=np.int64)
+    return self._cursor.positions().astype(np.int64)
 
   # ---- host-side step inputs ----
   def _models(self) -> host_inputs.StepModels:
@@ -1154,6 +1240,11 @@ class BatchedEnvironment:
       else:
         t_amb = self.weather.get_current_temp(self._now)
       self.sim.observe(self._aux(self._now), t_amb, self._obs, self._occ_total, self._occ_norm)
+    if self.per_building_episodes:   # the per-building TimeStep buffers: what reset_buildings() returns for the others
+      self._step_type.fill_(STEP_FIRST)
+      self._reward.zero_()
+      self._disc.fill_(1.0)
+      return TimeStep(self._step_type, self._reward, self._disc, self._obs)
     first = torch.full((self.batch_size,), STEP_FIRST, dtype=torch.int32, device=self.sim.tdev)
     return TimeStep(first, self._zero, torch.ones_like(self._discount), self._obs)
 
@@ -1167,6 +1258,8 @@ class BatchedEnvironment:
     overwrites them (clone what you keep across steps)."""
     if self._needs_reset or self._episode_ended:
       return self.reset()
+    if self.per_building_episodes:
+      return self._step_episodes(action, rejected)
     si = self.make_step_in(self._now) if self._cursor is None else self._clock_step_in()
     if rejected is not None:
       if tuple(rejected.shape) != (self.batch_size,) or rejected.device != self.sim.tdev:
@@ -1192,6 +1285,78 @@ class BatchedEnvironment:
     self._step_count += 1
     mid = torch.full((self.batch_size,), STEP_MID, dtype=torch.int32, device=dev)
     return TimeStep(mid, self._reward, self._discount, self._obs)
+
+  # ---- episodes per building ----
+  def _setup_episodes(self, episode_steps) -> None:
+    """The constructor's part for per_building_episodes: the lengths, the cursor, and a clock in any case (all-zero
+    offsets without start_offsets) -- the library moves a building's rows when it restarts."""
+    self.episode_steps = (np.full(self.batch_size, self._num_timesteps_in_episode, dtype=np.int64) if episode_steps is None
+                          else host_inputs.check_episode_steps(episode_steps, self.batch_size, self._num_timesteps_in_episode))
+    if self.timeline is None:
+      offsets = np.zeros(self.batch_size, dtype=np.int32)
+      self.timeline = host_inputs.Timeline(self._models(), self._start_timestamp, offsets, self._num_timesteps_in_episode)
+      self.sim.clock_attach(self.timeline.rows, offsets)
+    self._cursor = host_inputs.EpisodeCursor(self.batch_size)
+
+  def _restart(self, ended: np.ndarray) -> None:
+    """The buildings of ``ended`` (bool [B]) start a new episode at the next position: reset on the device, their
+    calendars moved, their first observation written into the observation buffer."""
+    self.sim.reset_buildings(ended, restart_pos=self._cursor.pos)
+    self._cursor.restart(ended)
+    self.sim.clock_seek(*self._cursor.seek_args())
+    si = _ffi.StepIn()
+    self._device_inputs(si)
+    self.sim.observe_buildings(ended, si, self._obs)
+
+  def _step_episodes(self, action: torch.Tensor, rejected: Optional[torch.Tensor]) -> TimeStep:
+    """``step`` with episodes per building, same-step autoreset: every building steps; those whose episode just ended
+    leave their last observation in ``final_observation``, are reset, and return the first observation of their new
+    episode with this step's reward, LAST and discount 0."""
+    si = self._clock_step_in()
+    if rejected is not None:
+      if tuple(rejected.shape) != (self.batch_size,) or rejected.device != self.sim.tdev:
+        raise ValueError(f"rejected must be a [{self.batch_size}] tensor on {self.sim.tdev}")
+      self._rejected = rejected.to(torch.uint8).contiguous()
+      si.reject_dev = self._rejected.data_ptr()
+    else:
+      si.reject_dev = self._no_reject.data_ptr()
+    self.sim.step(action, si, self._obs, self._reward, self._info)
+    self._prev_thermostat_ts = self._now
+    self._now = self._now + self._step_interval
+    self._cursor.advance()
+    ended = self._cursor.ended(self.episode_steps)
+    self._step_type.fill_(STEP_MID)
+    self._disc.fill_(self.discount_factor)
+    if ended.any():
+      last = torch.from_numpy(ended).to(self.sim.tdev)
+      self._step_type.masked_fill_(last, STEP_LAST)
+      self._disc.masked_fill_(last, 0.0)
+      self.final_observation.copy_(torch.where(last[:, None], self._obs, self.final_observation))
+      self._restart(ended)
+    return TimeStep(self._step_type, self._reward, self._disc, self._obs)
+
+  def reset_buildings(self, mask) -> TimeStep:
+    """Ends the episodes of the buildings of ``mask`` (bool or uint8 [B], numpy or torch) now, between two steps: they
+    are reset on the device and get FIRST, reward 0, discount 1 and the first observation of their new episode; the
+    other buildings keep the step type, reward, discount and observation of their last step.  ValueError before the
+    first ``reset()`` and on an environment without ``per_building_episodes``."""
+    if not self.per_building_episodes:
+      raise ValueError("reset_buildings needs an environment created with per_building_episodes=True (or episode_steps)")
+    if self._needs_reset:
+      raise ValueError("reset_buildings: reset() first (no building has an episode yet)")
+    m = self.sim._host_mask(mask) != 0
+    if m.any():
+      first = torch.from_numpy(m).to(self.sim.tdev)
+      self._restart(m)
+      self._step_type.masked_fill_(first, STEP_FIRST)
+      self._reward.masked_fill_(first, 0.0)
+      self._disc.masked_fill_(first, 1.0)
+    return TimeStep(self._step_type, self._reward, self._disc, self._obs)
+
+  def _refuse_with_episodes(self, what: str) -> None:
+    if self.per_building_episodes:
+      raise ValueError(f"{what} is not supported with per_building_episodes: the per-building episode positions are not in "
+                       "the snapshot (sb_state_view)")
 
 
   def set_building_params(self, params: Optional[host_inputs.BuildingParams]) -> None:
@@ -1229,6 +1394,7 @@ class BatchedEnvironment:
   def snapshot(self) -> EnvSnapshot:
     """Everything ``restore`` needs to put this environment back where it is now: the simulator state of every
     building, the host clock and episode bookkeeping, stateful host models, the current TimeStep and info."""
+    self._refuse_with_episodes("snapshot()")
     self.sim._refuse_on_jacobi("snapshot()")
     if self._needs_reset:
       raise ValueError("snapshot() needs a current TimeStep: reset() first")
@@ -1254,6 +1420,7 @@ class BatchedEnvironment:
     """Puts the environment back to ``snap`` (of this environment, or of one of the same floor plan, configuration
     and batch size) and returns the TimeStep that was current then.  The simulator's draw counters rewind with it,
     so the device occupancy and convection draw what they drew after the snapshot: a restored batch replays exactly."""
+    self._refuse_with_episodes("restore()")
     self.sim._refuse_on_jacobi("restore()")
     if not isinstance(snap, EnvSnapshot):
       raise ValueError("restore needs an EnvSnapshot")
@@ -1287,6 +1454,7 @@ class BatchedEnvironment:
     observation, reward and info rows follow their buildings.  Random streams: the device occupancy and convection
     draw by (seed, global building, counter), so a forked building keeps its own slot's stream -- forked replicas
     of one building diverge under those stochastic models and stay identical without them."""
+    self._refuse_with_episodes("fork()")
     self.sim._refuse_on_jacobi("fork()")
     if not isinstance(src, torch.Tensor) or src.dtype != torch.int64 or tuple(src.shape) != (self.batch_size,):
       raise ValueError(f"src must be an int64 [{self.batch_size}] tensor")
@@ -1349,6 +1517,8 @@ class MixedBatchedEnvironment:
     class (None entries: the default for that class)."""
     if not classes:
       raise ValueError("MixedBatchedEnvironment needs at least one (floor plan, number of buildings) class")
+    if env_kwargs.get("per_building_episodes") or env_kwargs.get("episode_steps") is not None:
+      raise ValueError("per_building_episodes is not implemented for MixedBatchedEnvironment (its classes step and end together)")
     from . import distributed as _sd
     self.device = int(device)
     self.tdev = torch.device("cuda", self.device)
@@ -1572,6 +1742,11 @@ class GymVectorEnv:
       obs, info = venv.reset()
       obs, reward, terminated, truncated, info = venv.step(actions)      # all [B, ...] tensors in HBM
 
+  Over an environment with ``per_building_episodes`` (same-step autoreset): ``truncated`` / ``terminated`` are per
+  building, the observation of a building whose episode just ended is the first of its next episode,
+  ``info["final_obs"]`` is ``env.final_observation`` (a building's row: the last observation of its episode that ended
+  last) and ``info["autoreset_mode"]`` is ``"same_step"``.  Over any other environment:
+
   Every sub-environment shares the simulator clock, so they end together: the last step of an
   episode (``environment.py:1366-1368``: its time is up) returns ``truncated = True`` for all of
   them (``terminated`` with ``time_limit_is_truncation=False``), and -- gymnasium's "next-step" autoreset mode -- the following ``step`` ignores its
@@ -1596,7 +1771,10 @@ class GymVectorEnv:
     # time_limit_is_truncation=False reports it as a termination, like the reference's discount 0
     last = ts.step_type == STEP_LAST
     terminated, truncated = (torch.zeros_like(last), last) if self.time_limit_is_truncation else (last, torch.zeros_like(last))
-    return ts.observation, ts.reward, terminated, truncated, {"step_type": ts.step_type, "discount": ts.discount}
+    info = {"step_type": ts.step_type, "discount": ts.discount}
+    if getattr(self.env, "per_building_episodes", False):
+      info.update(final_obs=self.env.final_observation, autoreset_mode="same_step")
+    return ts.observation, ts.reward, terminated, truncated, info
 
   def close(self) -> None:
     self.env.close()

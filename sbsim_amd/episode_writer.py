@@ -227,6 +227,9 @@ class BuildingLogger:
     if getattr(env, "start_offsets", None) is not None:
       raise ValueError("BuildingLogger stamps one time on a whole step: not for an environment with start_offsets "
                        "(a calendar per building)")
+    if getattr(env, "per_building_episodes", False):
+      raise ValueError("BuildingLogger stamps one time on a whole step: not for an environment with per_building_episodes "
+                       "(every building at its own position of its own episode)")
     if env.info is None:
       raise ValueError("BuildingLogger needs BatchedEnvironment(collect_info=True)")
     sim = env.sim

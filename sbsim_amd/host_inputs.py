@@ -778,6 +778,71 @@ class ClockCursor:
     return self.pos, (-1 if self.prev is None else self.prev)
 
 
+def check_episode_steps(episode_steps, n_buildings: int, steps_per_episode: int) -> np.ndarray:
+  """``BatchedEnvironment(episode_steps=...)`` as int64 [B]: building b's step returns LAST when its own step count has
+  reached ``episode_steps[b]`` (an episode of ``episode_steps[b] + 1`` steps, as ``steps_per_episode`` counts for the
+  batch); ``1 <= episode_steps[b] <= steps_per_episode``, the length the calendar was built for.  ValueError otherwise,
+  naming the building."""
+  a = np.asarray(episode_steps)
+  if a.shape != (int(n_buildings),):
+    raise ValueError(f"episode_steps must have shape [{int(n_buildings)}] (one length per building), got {a.shape}")
+  if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+    raise ValueError(f"episode_steps must be integers (whole steps), got dtype {a.dtype}")
+  bad = (a < 1) | (a > int(steps_per_episode))
+  if bad.any():
+    b = int(np.argmax(bad))
+    raise ValueError(f"episode_steps: building {b}: {a[b]} is outside 1 .. {int(steps_per_episode)} (steps_per_episode)")
+  return np.ascontiguousarray(a, dtype=np.int64)
+
+
+class EpisodeCursor:
+  """``ClockCursor`` for a batch whose buildings have episodes of their own (``BatchedEnvironment(per_building_episodes=
+  True)``): the batch position ``pos`` of the next step, which only ``reset`` rewinds; ``prev``, the batch position of
+  the last step taken since then (None after a ``reset``: the batch position grows across the buildings' restarts, beyond
+  any row of the restored calendar -- and nothing reads that row in this mode, where every building's previous thermostat
+  update is its own, on the device); and per building the batch position at which its current episode started
+  (``restart_pos``).  Building b's own episode position is ``pos - restart_pos[b]``: the number of steps it has taken in
+  its episode, and the Timeline row it reads next, counted from its start offset."""
+
+  def __init__(self, n_buildings: int, pos: int = 0, prev: Optional[int] = None):
+    self.pos, self.prev = int(pos), (None if prev is None else int(prev))
+    self.restart_pos = np.zeros(int(n_buildings), dtype=np.int64)
+
+  def reset(self) -> None:
+    """Every building at the start of an episode, the batch at position 0, no previous position."""
+    self.pos = 0
+    self.prev = None
+    self.restart_pos[:] = 0
+
+  def advance(self) -> None:
+    """One step taken at ``pos`` by every building."""
+    self.prev = self.pos
+    self.pos += 1
+
+  def positions(self) -> np.ndarray:
+    """Every building's own episode position, int64 [B]."""
+    return self.pos - self.restart_pos
+
+  def rows(self, offsets) -> Dict[str, np.ndarray]:
+    """Per building: the Timeline rows its next step reads as now and next."""
+    now = np.asarray(offsets, dtype=np.int64) + self.positions()
+    return dict(now=now, next=now + 1)
+
+  def ended(self, episode_steps) -> np.ndarray:
+    """bool [B], after ``advance``: the buildings whose step just taken was the last of their episode -- their own step
+    count before it had reached ``episode_steps[b]`` (the batch's rule, environment.py:1366-1368: an episode of
+    ``episode_steps[b]`` transitions plus one terminal step)."""
+    return self.positions() - 1 >= np.asarray(episode_steps, dtype=np.int64)
+
+  def restart(self, mask) -> None:
+    """The buildings of ``mask`` (bool [B]) start a new episode at the batch position of the next step."""
+    self.restart_pos[np.asarray(mask, dtype=bool)] = self.pos
+
+  def seek_args(self) -> Tuple[int, int]:
+    """sb_clock_seek's (pos, prev_pos)."""
+    return self.pos, (-1 if self.prev is None else self.prev)
+
+
 # --------------------------------------------------------------------------- per-building plant parameters
 # SimConfig field -> the sb_params fields it sets (include/sbsim_amd.h sb_building_param), in the enum's order
 BUILDING_PARAM_NAMES: Dict[str, Tuple[str, ...]] = {
