@@ -293,6 +293,18 @@ typedef struct sb_occupancy_config {
 } sb_occupancy_config;
 /* Creates (or re-creates) the handle's occupants, all AWAY, query counter 0. */
 int sb_occupancy_attach(sb_handle *h, const sb_occupancy_config *cfg);
+/* sb_occupancy_attach with one configuration per GROUP of buildings (several calendars in one batch: office hours and
+ * headcount differ between the groups): building b runs cfgs[group_of_building_host[b]] -- its zone_assignment and its
+ * four hours (the event probabilities follow from them and time_step_sec).  Every cfgs[g] passes sb_occupancy_attach's
+ * checks; seed, first_building and time_step_sec must be the same in every group (the draws stay keyed by (seed, global
+ * building, zone, query): a building draws what it would draw on a handle attached with its group's configuration
+ * alone); 1 <= n_groups <= 65,535 and 0 <= group_of_building_host[b] < n_groups.  SB_ERR_INVALID otherwise, the message
+ * naming the group (or the building), and the attachment in force stays as it was.  The group table and the [B] group
+ * index are uploaded once, here (the host arrays may go away on return); sb_occupancy_peek then runs the grouped
+ * instantiation of its kernel, which reads a building's group index and that group's row.  Occupants all AWAY, query
+ * counter 0, as after sb_occupancy_attach -- which, called afterwards, returns the handle to one configuration. */
+int sb_occupancy_attach_groups(sb_handle *h, const sb_occupancy_config *cfgs, int32_t n_groups,
+                               const int32_t *group_of_building_host /* [B] */);
 /* One average_zone_occupancy(zone, start_time, .) for every zone of every building: advances
  * every occupant once and writes the occupants at work -- count_dev [B][Z] fp32 and/or
  * total_dev [B] fp32 (either may be NULL). */

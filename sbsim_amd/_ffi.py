@@ -165,7 +165,7 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi", "sb_set_building_params",
            "sb_set_reward_function", "sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials",
            "sb_get_building_coef", "sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in",
-           "sb_debug_plan_digest", "sb_reset_buildings", "sb_observe_buildings")
+           "sb_debug_plan_digest", "sb_reset_buildings", "sb_observe_buildings", "sb_occupancy_attach_groups")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
@@ -174,6 +174,7 @@ REWARD_ENTRIES = ("sb_set_reward_function",)
 CLOCK_ENTRIES = ("sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in")
 PLAN_DIGEST_ENTRIES = ("sb_debug_plan_digest",)
 EPISODES_ENTRIES = ("sb_reset_buildings", "sb_observe_buildings")
+OCCUPANCY_ENTRIES = ("sb_occupancy_attach_groups",)
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -273,6 +274,8 @@ def load():
   if all(hasattr(L, name) for name in EPISODES_ENTRIES):
     L.sb_reset_buildings.argtypes = [vp, vp, C.c_int32, C.c_double, vp, vp]
     L.sb_observe_buildings.argtypes = [vp, vp, C.POINTER(StepIn), vp, vp]
+  if all(hasattr(L, name) for name in OCCUPANCY_ENTRIES):
+    L.sb_occupancy_attach_groups.argtypes = [vp, C.POINTER(OccupancyConfig), C.c_int32, vp]
   if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
     L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
@@ -312,6 +315,11 @@ def materials_entry(name: str):
 def clock_entry(name: str):
   """The per-building-calendar entry `name` (sb_clock_attach, sb_clock_seek, sb_clock_detach, sb_observe_step_in): see
   entry()."""
+  return entry(name)
+
+
+def occupancy_entry(name: str):
+  """The occupancy-groups entry `name` (sb_occupancy_attach_groups): see entry()."""
   return entry(name)
 
 

@@ -34,34 +34,52 @@ struct OccArgs {
   // its t - 5 min pair (SB_CLK_OCC_HOUR5), `field` says which
   ClockView clk;
   int delta, field;
+  // sb_occupancy_attach_groups (k_occupancy<CLK, true> alone reads these): the groups' rows and every building's group
+  const OccGroup *groups;
+  const uint16_t *group_of; // [B], values below the number of groups (checked on the host before the upload)
 };
+
+// What a building's occupants run with: OccArgs' scalars (one configuration: uniform, scalar registers), or with GRP the
+// row of the building's group -- one coalesced 2-byte load of the group index per building, then the 32-byte row (two
+// 16-byte loads; a table of a few groups stays in L1 / L2).
+template <bool GRP>
+__device__ inline OccGroup occ_config(const OccArgs &o, int b) {
+  if (GRP) return o.groups[o.group_of[b]];
+  return OccGroup{o.e_arr, o.l_arr, o.e_dep, o.n_occ, o.p_arr, o.p_dep};
+}
 
 // ZoneOccupant.peek (randomized_arrival_departure_occupancy.py:138-160) for every occupant of
 // every zone of one building per thread.  Uniform of occupant i: word i & 3 of the Philox block
 // with counter (building lo, building hi, zone, query * 8 + (i >> 2)), u = (x >> 8) / 2^24.
-template <bool CLK> // a calendar per building: a kernel per value (sb_device.h, clocked)
+// CLK: a calendar per building, a kernel per value (sb_device.h, clocked).  GRP: a configuration per group of buildings
+// (sb_occupancy_attach_groups); the counters do not know the group, so a building draws what it draws on a handle
+// attached with its group's configuration alone.
+template <bool CLK, bool GRP>
 __global__ void k_occupancy(OccArgs o) {
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < o.B; b += gridDim.x * blockDim.x) {
     const unsigned long long gb = (unsigned long long)(o.first_building + b);
     const int crow = clock_row<CLK>(o.clk, b) + o.delta;
     const int hour = CLK ? (int)clocked<CLK>(o.clk, crow, o.field, 0.0) : o.hour;
     const bool workday = CLK ? clocked<CLK>(o.clk, crow, o.field + 1, 0.0) != 0.0 : o.workday != 0;
+    const OccGroup g = occ_config<GRP>(o, b);
     float tot = 0.0f;
     for (int z = 0; z < o.Z; ++z) {
       uint32_t st = o.state[(size_t)b * o.Z + z];
+      // (a state word forked in from a larger group, sb_state_load with a pick: the group's own occupants of it)
+      if (GRP) st &= g.n_occ >= 32 ? 0xffffffffu : (1u << g.n_occ) - 1u;
       if (!workday) st = 0;
       else {
-        const bool arr_open = !(hour < o.e_arr || hour > o.l_arr), dep_open = !(hour < o.e_dep);
+        const bool arr_open = !(hour < g.e_arr || hour > g.l_arr), dep_open = !(hour < g.e_dep);
         if (arr_open || dep_open)
-          for (int blk = 0; blk * 4 < o.n_occ; ++blk) {
+          for (int blk = 0; blk * 4 < g.n_occ; ++blk) {
             uint32_t c[4] = {(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)z, o.query * 8u + (uint32_t)blk};
             philox4x32_10(c, (uint32_t)o.seed, (uint32_t)(o.seed >> 32));
-            for (int k = 0; k < 4 && blk * 4 + k < o.n_occ; ++k) {
+            for (int k = 0; k < 4 && blk * 4 + k < g.n_occ; ++k) {
               const int i = blk * 4 + k;
               const double u = (double)(c[k] >> 8) * (1.0 / 16777216.0);
               const bool at_work = (st >> i) & 1u;
-              if (!at_work && arr_open && u < o.p_arr) st |= 1u << i;
-              else if (at_work && dep_open && u < o.p_dep) st &= ~(1u << i);
+              if (!at_work && arr_open && u < g.p_arr) st |= 1u << i;
+              else if (at_work && dep_open && u < g.p_dep) st &= ~(1u << i);
             }
           }
       }
@@ -426,27 +444,90 @@ __global__ void __launch_bounds__(256) k_convect_all(ConvAllArgs o) {
   }
 }
 
+// sb_occupancy_attach's checks of one configuration; `who` starts the message (sb_occupancy_attach_groups: with the group).
+int check_occupancy_config(const sb_occupancy_config &c, const std::string &who) {
+  if (c.zone_assignment < 1 || c.zone_assignment > 32)
+    return fail(SB_ERR_INVALID, who + ": zone_assignment must be 1..32 (one state word per zone)");
+  if (!(c.earliest_arrival_hour < c.latest_arrival_hour && c.latest_arrival_hour < c.earliest_departure_hour &&
+        c.earliest_departure_hour < c.latest_departure_hour))
+    return fail(SB_ERR_INVALID, who + ": hours must be strictly increasing "
+                                      "(randomized_arrival_departure_occupancy.py:68-73)");
+  if (!(c.time_step_sec > 0) || c.first_building < 0)
+    return fail(SB_ERR_INVALID, who + ": time_step_sec must be positive, first_building >= 0");
+  return SB_OK;
+}
+
+// What k_occupancy takes from a configuration.  _get_event_probability (:100-112): 1 / (half the window in time steps)
+OccGroup occ_group_row(const sb_occupancy_config &c) {
+  OccGroup g;
+  g.e_arr = c.earliest_arrival_hour; g.l_arr = c.latest_arrival_hour; g.e_dep = c.earliest_departure_hour;
+  g.n_occ = c.zone_assignment;
+  g.p_arr = 1.0 / ((double)(c.latest_arrival_hour - c.earliest_arrival_hour) * 3600.0 / c.time_step_sec / 2.0);
+  g.p_dep = 1.0 / ((double)(c.latest_departure_hour - c.earliest_departure_hour) * 3600.0 / c.time_step_sec / 2.0);
+  return g;
+}
+
+// The handle's occupants, all AWAY (allocated by the first attachment).
+int occupancy_all_away(sb_handle *h) {
+  if (!h->occ_state.p) return alloc_zero(h->occ_state, (size_t)h->d.B * h->d.Z);
+  SB_HIP(hipMemset(h->occ_state.p, 0, (size_t)h->d.B * h->d.Z * sizeof(uint32_t)));
+  return SB_OK;
+}
+
 } // namespace
 
 extern "C" {
 
 int sb_occupancy_attach(sb_handle *h, const sb_occupancy_config *cfg) {
   if (!h || !cfg) return fail(SB_ERR_INVALID, "sb_occupancy_attach: null argument");
-  if (cfg->zone_assignment < 1 || cfg->zone_assignment > 32)
-    return fail(SB_ERR_INVALID, "sb_occupancy_attach: zone_assignment must be 1..32 (one state word per zone)");
-  if (!(cfg->earliest_arrival_hour < cfg->latest_arrival_hour &&
-        cfg->latest_arrival_hour < cfg->earliest_departure_hour &&
-        cfg->earliest_departure_hour < cfg->latest_departure_hour))
-    return fail(SB_ERR_INVALID, "sb_occupancy_attach: hours must be strictly increasing "
-                                "(randomized_arrival_departure_occupancy.py:68-73)");
-  if (!(cfg->time_step_sec > 0) || cfg->first_building < 0)
-    return fail(SB_ERR_INVALID, "sb_occupancy_attach: time_step_sec must be positive, first_building >= 0");
+  SB_CHECK(check_occupancy_config(*cfg, "sb_occupancy_attach"));
   SB_ON_DEVICE(h->device);
-  if (!h->occ_state.p) {
-    const int rc = alloc_zero(h->occ_state, (size_t)h->d.B * h->d.Z);
-    if (rc != SB_OK) return rc;
-  } else SB_HIP(hipMemset(h->occ_state.p, 0, (size_t)h->d.B * h->d.Z * sizeof(uint32_t)));
+  SB_CHECK(occupancy_all_away(h));
   h->occ = *cfg;
+  h->occ_n_groups = 0; // (one configuration again: sb_occupancy_peek launches the ungrouped kernel; the tables stay allocated)
+  h->occ_queries = 0;
+  h->occ_attached = true;
+  return SB_OK;
+}
+
+int sb_occupancy_attach_groups(sb_handle *h, const sb_occupancy_config *cfgs, int32_t n_groups,
+                               const int32_t *group_of_building_host) {
+  const std::string who = "sb_occupancy_attach_groups";
+  if (!h || !cfgs || !group_of_building_host) return fail(SB_ERR_INVALID, who + ": null argument");
+  if (n_groups < 1 || n_groups > 65535)
+    return fail(SB_ERR_INVALID, who + ": n_groups must be 1..65535 (a building's group index is 16 bits), got " + std::to_string(n_groups));
+  // everything is checked before anything changes: a refused call leaves the attachment in force as it was
+  std::vector<OccGroup> groups((size_t)n_groups);
+  for (int g = 0; g < n_groups; ++g) {
+    const sb_occupancy_config &c = cfgs[g];
+    SB_CHECK(check_occupancy_config(c, who + ": group " + std::to_string(g)));
+    const char *differs = c.seed != cfgs[0].seed ? "seed" : c.first_building != cfgs[0].first_building ? "first_building"
+                          : c.time_step_sec != cfgs[0].time_step_sec ? "time_step_sec" : nullptr;
+    if (differs)
+      return fail(SB_ERR_INVALID, who + ": group " + std::to_string(g) + ": " + differs + " differs from group 0's (the draws are keyed "
+                                  "by seed and global building, one query counter per handle: one value for every group)");
+    groups[(size_t)g] = occ_group_row(c);
+  }
+  const int B = h->d.B;
+  std::vector<uint16_t> group_of((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const int32_t g = group_of_building_host[b];
+    if (g < 0 || g >= n_groups)
+      return fail(SB_ERR_INVALID, who + ": building " + std::to_string(b) + ": group " + std::to_string(g) + " is outside 0.." +
+                                  std::to_string(n_groups - 1));
+    group_of[(size_t)b] = (uint16_t)g;
+  }
+  SB_ON_DEVICE(h->device);
+  // the new tables first, swapped in once both are on the device (hipFree waits for a kernel that still reads the old ones)
+  DevBuf<OccGroup> new_groups;
+  DevBuf<uint16_t> new_group_of;
+  SB_CHECK(upload(new_groups, groups.data(), groups.size()));
+  SB_CHECK(upload(new_group_of, group_of.data(), group_of.size()));
+  SB_CHECK(occupancy_all_away(h));
+  std::swap(h->occ_groups.p, new_groups.p);
+  std::swap(h->occ_group_of.p, new_group_of.p);
+  h->occ = cfgs[0];
+  h->occ_n_groups = n_groups;
   h->occ_queries = 0;
   h->occ_attached = true;
   return SB_OK;
@@ -475,9 +556,14 @@ int sb_occupancy_peek(sb_handle *h, int32_t local_hour, int32_t is_work_day, flo
   o.p_dep = 1.0 / ((double)(c.latest_departure_hour - c.earliest_departure_hour) * 3600.0 / c.time_step_sec / 2.0);
   o.seed = c.seed; o.first_building = c.first_building; o.query = h->occ_queries++;
   o.count = count_dev; o.total = total_dev;
+  const bool grouped = h->occ_n_groups > 0; // sb_occupancy_attach_groups: the scalars above are group 0's and go unread
+  o.groups = grouped ? h->occ_groups.p : nullptr; o.group_of = grouped ? h->occ_group_of.p : nullptr;
   const int blocks = std::max(1, std::min((o.B + 63) / 64, 4096));
-  if (o.clk.rows) hipLaunchKernelGGL(k_occupancy<true>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, o);
-  else hipLaunchKernelGGL(k_occupancy<false>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, o);
+  const dim3 grid(blocks), block(64);
+  if (o.clk.rows && grouped) hipLaunchKernelGGL((k_occupancy<true, true>), grid, block, 0, (hipStream_t)stream, o);
+  else if (o.clk.rows) hipLaunchKernelGGL((k_occupancy<true, false>), grid, block, 0, (hipStream_t)stream, o);
+  else if (grouped) hipLaunchKernelGGL((k_occupancy<false, true>), grid, block, 0, (hipStream_t)stream, o);
+  else hipLaunchKernelGGL((k_occupancy<false, false>), grid, block, 0, (hipStream_t)stream, o);
   SB_HIP(hipGetLastError());
   return SB_OK;
 }

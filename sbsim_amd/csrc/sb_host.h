@@ -112,6 +112,12 @@ struct ConvCell {
   unsigned long long mask; // bit k: offset k of the table leads to a cell of the same room
 };
 
+// One group's row of sb_occupancy_attach_groups' device table (generators.hip, k_occupancy<CLK, true>): what k_occupancy
+// takes from OccArgs' scalars with one configuration.
+struct OccGroup {
+  int e_arr, l_arr, e_dep, n_occ;
+  double p_arr, p_dep;
+};
 
 struct sb_handle {
   sb::Dev d{};
@@ -163,6 +169,11 @@ struct sb_handle {
   sb_occupancy_config occ{};
   uint32_t occ_queries = 0;
   bool occ_attached = false;
+  // sb_occupancy_attach_groups: a configuration per group of buildings (occ then holds group 0's: the shared seed, first
+  // building and time step); occ_n_groups == 0: the one configuration of sb_occupancy_attach
+  DevBuf<OccGroup> occ_groups;      // [occ_n_groups]
+  DevBuf<uint16_t> occ_group_of;    // [B] the building's group
+  int occ_n_groups = 0;
   // sb_clock_attach / sb_clock_seek: the table of instants, the buildings' offsets, the position of the next step
   DevBuf<double> clock_rows;        // [clock_n_rows][SB_CLOCK_FIELDS]; NULL: no clock
   DevBuf<int> clock_offs;           // [B] the attached offsets

@@ -363,6 +363,7 @@ class BatchedSimulator:
     self._materials_handle = building_materials is not None   # sb_create_materials made the handle
     self._building_materials = None   # set_building_materials: the rows in force (None: the plan's own values)
     self._clock_offsets = None   # clock_attach: the buildings' offsets into the timeline (None: one clock for the batch)
+    self._calendars = None   # clock_attach(calendar_of=...): hashes of the concatenated rows and of calendar_of
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -575,6 +576,28 @@ class BatchedSimulator:
     self._occ_attached = (int(zone_assignment), tuple(int(x) for x in hours[:4]), float(time_step_sec),
                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_building))
 
+  def occupancy_attach_groups(self, configs: Sequence, group_of) -> None:
+    """sb_occupancy_attach_groups: ``occupancy_attach`` with one configuration per group of buildings.  ``configs``: per
+    group ``(zone_assignment, hours, time_step_sec, seed, first_building)`` as ``occupancy_attach`` takes them (seed,
+    first_building and time_step_sec the same in every group); ``group_of``: integers [B], building b's group.
+    ValueError for what the library refuses, its message naming the group or the building."""
+    fn = _ffi.occupancy_entry("sb_occupancy_attach_groups")
+    groups = [(int(z), tuple(int(x) for x in hours[:4]), float(step), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first))
+              for z, hours, step, seed, first in configs]
+    g = np.asarray(group_of)
+    if g.shape != (self.B,) or g.dtype == bool or not np.issubdtype(g.dtype, np.integer):
+      raise ValueError(f"group_of must be integers of shape [{self.B}] (one group per building)")
+    g = np.ascontiguousarray(g, dtype=np.int32)
+    cfgs = (_ffi.OccupancyConfig * max(len(groups), 1))(*[
+        _ffi.OccupancyConfig(z, hours[0], hours[1], hours[2], hours[3], step, seed, first)
+        for z, hours, step, seed, first in groups])
+    with torch.cuda.device(self.device):
+      rc = fn(self._h, cfgs, len(groups), g.ctypes.data_as(C.c_void_p))
+    if rc == -1:   # SB_ERR_INVALID
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_occupancy_attach_groups")
+    self._occ_attached = ("groups", tuple(groups), _sha(g))
+
   def convection_attach(self, p: float, distance: int, seed: int, first_building: int = 0) -> None:
     """sb_convection_attach: StochasticConvectionSimulator(p, distance, seed) after every FD update
     (stochastic_convection_simulator.py:62-145), counter-based draws per building."""
@@ -595,10 +618,12 @@ class BatchedSimulator:
         C.c_void_p(total.data_ptr()) if total is not None else None, self._stream()), "sb_occupancy_peek")
 
   # ---- a calendar per building (sb_clock_attach / sb_clock_seek) ----
-  def clock_attach(self, rows: np.ndarray, offsets: np.ndarray) -> None:
+  def clock_attach(self, rows: np.ndarray, offsets: np.ndarray, calendar_of: Optional[np.ndarray] = None) -> None:
     """sb_clock_attach: ``rows`` float64 [n_rows, SB_CLOCK_FIELDS] (``host_inputs.Timeline.rows``), ``offsets`` int32 [B].
     The library copies both; ``clock_seek`` before the first step, observation or occupancy query.  Configuration of the
-    buildings' slots, as ``set_building_params``: snapshots do not carry it, a forked building keeps its slot's offset."""
+    buildings' slots, as ``set_building_params``: snapshots do not carry it, a forked building keeps its slot's offset.
+    ``calendar_of``: the table is a ``host_inputs.CalendarTimeline``'s, several calendars one after the other, and this
+    is its ``calendar_of`` -- the snapshot fingerprint then carries the rows and the buildings' calendars."""
     rows = np.ascontiguousarray(rows, dtype=np.float64)
     offsets = np.ascontiguousarray(offsets, dtype=np.int32)
     if rows.ndim != 2 or offsets.shape != (self.B,):
@@ -610,6 +635,7 @@ class BatchedSimulator:
       raise ValueError((self._lib.sb_last_error() or b"").decode())
     _ffi.check(rc, "sb_clock_attach")
     self._clock_offsets = offsets.copy()
+    self._calendars = None if calendar_of is None else (_sha(rows), _sha(np.ascontiguousarray(calendar_of, dtype=np.int32)))
 
   def clock_seek(self, pos: int, prev_pos: int = -1) -> None:
     """sb_clock_seek: the position of the next step, observation and occupancy query (a host value: no device work);
@@ -622,7 +648,7 @@ class BatchedSimulator:
   def clock_detach(self) -> None:
     with torch.cuda.device(self.device):
       _ffi.check(_ffi.clock_entry("sb_clock_detach")(self._h), "sb_clock_detach")
-    self._clock_offsets = None
+    self._clock_offsets = self._calendars = None
 
   def observe_step_in(self, step_in: _ffi.StepIn, out: torch.Tensor) -> torch.Tensor:
     """sb_observe_step_in: the observation with its inputs in a StepIn (the weather forms per building; with a clock,
@@ -850,6 +876,8 @@ class BatchedSimulator:
       fp += (("building_materials",),)
     if self._clock_offsets is not None:   # (the offsets stay with the slots; a snapshot restores where they are the same)
       fp += (("clock", _sha(self._clock_offsets)),)
+    if self._calendars is not None:   # (only with calendars: checkpoints from before them still load)
+      fp += (("calendars",) + self._calendars,)
     return fp
 
   def save_state(self, rows: Optional[torch.Tensor] = None) -> SimState:
@@ -1007,8 +1035,17 @@ class BatchedEnvironment:
                building_params: Optional[host_inputs.BuildingParams] = None,
                reward_function: Optional[host_inputs.SetpointEnergyCarbonReward] = None,
                building_materials: Optional[host_inputs.BuildingMaterials] = None, start_offsets=None,
-               per_building_episodes: bool = False, episode_steps=None):
-    """``per_building_episodes`` / ``episode_steps``: episodes per building with same-step autoreset (INTEGRATION.md
+               per_building_episodes: bool = False, episode_steps=None,
+               calendars: Optional[Sequence[host_inputs.Calendar]] = None, calendar_of=None):
+    """``calendars`` / ``calendar_of``: several calendars in one batch.  ``calendars``: a list of K
+    ``host_inputs.Calendar`` -- setpoint schedule, occupancy model, tariffs, a shared weather and the start date, each
+    the environment's own where left None; ``calendar_of``: an integer array [B], building b's index into it.  Building
+    b then lives at ``calendars[calendar_of[b]]``'s start ``+ (start_offsets[b] + step) * step_interval`` (zeros without
+    ``start_offsets``) with that calendar's models; ``current_simulation_timestamp`` stays the batch's base clock.
+    Device occupancy generators (``BatchedRandomizedArrivalDepartureOccupancy``) are every calendar's model or none's,
+    with one seed, first_building and time_step_sec.  ValueError before anything is created for what
+    ``host_inputs.check_calendars`` refuses.
+    ``per_building_episodes`` / ``episode_steps``: episodes per building with same-step autoreset (INTEGRATION.md
     4k).  ``episode_steps``: an integer array [B], building b's step returns LAST when its own step count has reached
     ``episode_steps[b]`` (1 .. ``steps_per_episode``); giving it implies the flag, the flag alone gives every building
     ``steps_per_episode``.  ``step()`` then resets the buildings whose episode just ended on the device and returns
@@ -1046,6 +1083,22 @@ class BatchedEnvironment:
     self._start_timestamp = host_inputs.as_datetime(start_timestamp)
     self._occ_norm = float(occupancy_normalization_constant)
     h_conv = self.weather.get_air_convection_coefficient(self._start_timestamp)
+    self.calendars = self.calendar_of = None
+    occupancy_groups = None   # the calendars' device occupancy generators (one per calendar), or None
+    if calendars is not None or calendar_of is not None:
+      if calendars is None:
+        raise ValueError("calendar_of needs calendars: the list of host_inputs.Calendar it indexes")
+      self.calendar_of = host_inputs.check_calendars(calendars, calendar_of, int(n_buildings), self.weather, self.occupancy,
+                                                     self._start_timestamp, self.config.comfort_temp_window,
+                                                     self.config.eco_temp_window)
+      self.calendars = list(calendars)
+      occupancy_groups = host_inputs.device_occupancy_groups(self.calendars, self.occupancy)
+      if occupancy_groups is not None and self.per_building_episodes:
+        raise ValueError("per_building_episodes: BatchedRandomizedArrivalDepartureOccupancy is not supported -- each of its "
+                         "queries advances every building's occupants, so the observation of the buildings that restart "
+                         "would draw for all the others too")
+      if start_offsets is not None:   # (checked here: nothing is created for offsets the timeline would refuse)
+        start_offsets = host_inputs.check_start_offsets(start_offsets, int(n_buildings))
     self.sim = BatchedSimulator(plan, self.config, n_buildings, h_conv, device,
                                 observation_normalization,
                                 histogram_parameters=observation_histogram_parameters,
@@ -1070,16 +1123,27 @@ class BatchedEnvironment:
       c = convection_simulator
       self.sim.convection_attach(c.p, c.distance, c.seed or 0, getattr(c, "first_building", 0))
     self._occ_count = self._occ_total = None
-    if isinstance(self.occupancy, host_inputs.BatchedRandomizedArrivalDepartureOccupancy):
-      o = self.occupancy   # per-building occupants live on the device
-      self.sim.occupancy_attach(o.zone_assignment, o.hours, o.time_step_sec, o.seed or 0, o.first_building)
+    if occupancy_groups is not None or (self.calendars is None and isinstance(
+        self.occupancy, host_inputs.BatchedRandomizedArrivalDepartureOccupancy)):
+      if occupancy_groups is not None:   # a generator per calendar: the building's group is its calendar
+        self.sim.occupancy_attach_groups([(o.zone_assignment, o.hours, o.time_step_sec, o.seed or 0, o.first_building)
+                                          for o in occupancy_groups], self.calendar_of)
+      else:
+        o = self.occupancy   # per-building occupants live on the device
+        self.sim.occupancy_attach(o.zone_assignment, o.hours, o.time_step_sec, o.seed or 0, o.first_building)
       self._occ_count = torch.zeros((self.batch_size, self.sim.Z), dtype=torch.float32, device=self.sim.tdev)
       self._occ_total = torch.zeros((self.batch_size,), dtype=torch.float32, device=self.sim.tdev)
     self._step_interval = dt.timedelta(seconds=self.config.time_step_sec)
     # environment.py:427-435
     self._num_timesteps_in_episode = int(dt.timedelta(days=num_days_in_episode) / self._step_interval)
     self.start_offsets = self.timeline = self._cursor = None
-    if start_offsets is not None:   # a calendar per building: the table of instants, built once, and the offsets into it
+    if self.calendars is not None:   # several calendars: their row tables one after the other, always on the clock path
+      self.timeline = host_inputs.CalendarTimeline(self.calendars, self.calendar_of, self._models(), self._start_timestamp,
+                                                   start_offsets, self._num_timesteps_in_episode)
+      self.start_offsets = self.timeline.start_offsets
+      self.sim.clock_attach(self.timeline.rows, self.timeline.offsets, calendar_of=self.calendar_of)
+      self._cursor = host_inputs.ClockCursor()
+    elif start_offsets is not None:   # a calendar per building: the table of instants, built once, and the offsets into it
       self.start_offsets = host_inputs.check_start_offsets(start_offsets, self.batch_size)
       self.timeline = host_inputs.Timeline(self._models(), self._start_timestamp, self.start_offsets,
                                            self._num_timesteps_in_episode)
@@ -1136,7 +1200,12 @@ class BatchedEnvironment:
 
   def current_simulation_timestamps(self) -> List[dt.datetime]:
     """Every building's own instant: ``current_simulation_timestamp`` (the batch's base clock) moved by the building's
-    start offset; without ``start_offsets``, the base clock B times."""
+    start offset; without ``start_offsets``, the base clock B times.  With ``calendars``: the building's instant on its
+    own calendar (its calendar's start, its start offset, its position)."""
+    if self.calendars is not None:
+      pos = (self._cursor.positions() if self.per_building_episodes
+             else np.full(self.batch_size, int(round((self._now - self._start_timestamp) / self._step_interval))))
+      return [self.timeline.instant(b, int(pos[b])) for b in range(self.batch_size)]
     if self.per_building_episodes:   # every building's own episode position on its own calendar
       offs = np.zeros(self.batch_size, dtype=np.int64) if self.start_offsets is None else self.start_offsets
       return [self._start_timestamp + int(r) * self._step_interval for r in self._cursor.rows(offs)["now"]]
@@ -1289,7 +1358,8 @@ class BatchedEnvironment:
   # ---- episodes per building ----
   def _setup_episodes(self, episode_steps) -> None:
     """The constructor's part for per_building_episodes: the lengths, the cursor, and a clock in any case (all-zero
-    offsets without start_offsets) -- the library moves a building's rows when it restarts."""
+    offsets without start_offsets; with calendars, the CalendarTimeline attached already) -- the library moves a building's
+    rows when it restarts."""
     self.episode_steps = (np.full(self.batch_size, self._num_timesteps_in_episode, dtype=np.int64) if episode_steps is None
                           else host_inputs.check_episode_steps(episode_steps, self.batch_size, self._num_timesteps_in_episode))
     if self.timeline is None:
@@ -1519,6 +1589,9 @@ class MixedBatchedEnvironment:
       raise ValueError("MixedBatchedEnvironment needs at least one (floor plan, number of buildings) class")
     if env_kwargs.get("per_building_episodes") or env_kwargs.get("episode_steps") is not None:
       raise ValueError("per_building_episodes is not implemented for MixedBatchedEnvironment (its classes step and end together)")
+    if env_kwargs.get("calendars") is not None or env_kwargs.get("calendar_of") is not None:
+      raise ValueError("calendars is not implemented for MixedBatchedEnvironment: calendar_of indexes the buildings of one "
+                       "BatchedEnvironment, and the classes of a mixed batch are block-partitioned over classes and ranks")
     from . import distributed as _sd
     self.device = int(device)
     self.tdev = torch.device("cuda", self.device)

@@ -224,6 +224,9 @@ class BuildingLogger:
   def __init__(self, env, output_dir: str, buildings: Sequence[int], zone_ids: Optional[Sequence[str]] = None,
                agent_id: str = "", scenario_id: str = ""):
     import os
+    if getattr(env, "calendars", None) is not None:
+      raise ValueError("BuildingLogger stamps one time on a whole step and logs one set of host models: not for an "
+                       "environment with calendars (every group of buildings on its own calendar)")
     if getattr(env, "start_offsets", None) is not None:
       raise ValueError("BuildingLogger stamps one time on a whole step: not for an environment with start_offsets "
                        "(a calendar per building)")

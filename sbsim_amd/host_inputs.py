@@ -843,6 +843,204 @@ class EpisodeCursor:
     return self.pos, (-1 if self.prev is None else self.prev)
 
 
+# --------------------------------------------------------------------------- several calendars in one batch
+class Calendar:
+  """The exogenous models of one group of buildings (``BatchedEnvironment(calendars=[...], calendar_of=...)``): the
+  setpoint schedule (hours, holidays, time zone), the occupancy model, the two tariffs, a weather shared by the group and
+  the date the group's episode starts on.  Every member left None is the environment's own.
+
+      office = Calendar(schedule=SetpointSchedule(7, 18, comfort, eco, time_zone="Europe/Berlin"),
+                        occupancy=StepFunctionOccupancy(dt.timedelta(hours=8), dt.timedelta(hours=16), 12.0, 0.1),
+                        weather=WeatherController(263.0, 275.0, convection_coefficient=100.0),
+                        start_timestamp=dt.datetime(2023, 1, 9, 5, tzinfo=UTC))
+
+  ``weather`` is a batch-shared form (``WeatherController`` / ``ReplayWeatherController``): the per-building forms
+  (``BatchedSinusoidWeather``, ``BatchedReplayWeather``) have one row per building of the whole batch and stay
+  arguments of the environment.  ValueError otherwise."""
+
+  def __init__(self, schedule: Optional[SetpointSchedule] = None, occupancy=None, electricity_energy_cost=None,
+               natural_gas_energy_cost=None, weather=None, start_timestamp=None):
+    if weather is not None and (isinstance(weather, (BatchedSinusoidWeather, BatchedReplayWeather))
+                                or not isinstance(weather, (WeatherController, ReplayWeatherController))):
+      raise ValueError("a Calendar's weather is shared by its buildings: a WeatherController or a ReplayWeatherController "
+                       f"(the per-building forms are arguments of the environment), got {type(weather).__name__}")
+    if schedule is not None and not isinstance(schedule, SetpointSchedule):
+      raise ValueError(f"a Calendar's schedule is a SetpointSchedule, got {type(schedule).__name__}")
+    self.schedule, self.occupancy, self.weather = schedule, occupancy, weather
+    self.electricity_energy_cost, self.natural_gas_energy_cost = electricity_energy_cost, natural_gas_energy_cost
+    self.start_timestamp = None if start_timestamp is None else as_datetime(start_timestamp)
+
+  def models(self, base: StepModels) -> StepModels:
+    """``base`` with this calendar's members in place of the environment's."""
+    own = lambda mine, theirs: theirs if mine is None else mine
+    return base._replace(weather=own(self.weather, base.weather), schedule=own(self.schedule, base.schedule),
+                         occupancy=own(self.occupancy, base.occupancy),
+                         electricity=own(self.electricity_energy_cost, base.electricity),
+                         gas=own(self.natural_gas_energy_cost, base.gas))
+
+  def start(self, base_start) -> dt.datetime:
+    return as_datetime(base_start) if self.start_timestamp is None else self.start_timestamp
+
+
+def check_calendar_of(calendar_of, n_buildings: int, n_calendars: int) -> np.ndarray:
+  """``BatchedEnvironment(calendar_of=...)`` as int32 [B]: building b's index into ``calendars``, 0 .. K-1, every
+  calendar used by some building.  ValueError otherwise, naming the building or the calendar."""
+  if calendar_of is None:
+    raise ValueError("calendars needs calendar_of: an integer array [B], every building's index into calendars")
+  a = np.asarray(calendar_of)
+  if a.shape != (int(n_buildings),):
+    raise ValueError(f"calendar_of must have shape [{int(n_buildings)}] (one calendar index per building), got {a.shape}")
+  if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+    raise ValueError(f"calendar_of must be integers (indices into calendars), got dtype {a.dtype}")
+  bad = (a < 0) | (a >= int(n_calendars))
+  if bad.any():
+    b = int(np.argmax(bad))
+    raise ValueError(f"calendar_of: building {b}: calendar {a[b]} is outside 0 .. {int(n_calendars) - 1}")
+  unused = np.setdiff1d(np.arange(int(n_calendars)), a)
+  if unused.size:
+    raise ValueError(f"calendars: calendar {int(unused[0])} is used by no building (calendar_of)")
+  return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def device_occupancy_groups(calendars: Sequence[Calendar], occupancy) -> Optional[List]:
+  """The calendars' occupancy models (``occupancy``: the environment's, for a calendar without one) when they are the
+  device generator -- one ``BatchedRandomizedArrivalDepartureOccupancy`` per calendar, sb_occupancy_attach_groups'
+  configurations -- or None when none of them is.  ValueError, naming the calendar, when device and host models are
+  mixed (the device generator's counts override every building's occupancy) or the generators differ in what one handle
+  has once: ``seed``, ``first_building``, ``time_step_sec``."""
+  occ = [occupancy if c.occupancy is None else c.occupancy for c in calendars]
+  dev = [isinstance(o, BatchedRandomizedArrivalDepartureOccupancy) for o in occ]
+  if not any(dev):
+    return None
+  if not all(dev):
+    k = dev.index(False)
+    raise ValueError(f"calendars: calendar {k} has a host-side occupancy model ({type(occ[k]).__name__}), calendar "
+                     f"{dev.index(True)} the device generator: BatchedRandomizedArrivalDepartureOccupancy overrides every "
+                     "building's occupancy, so it is every calendar's model or none's")
+  for k, o in enumerate(occ):
+    for name in ("seed", "first_building", "time_step_sec"):
+      if (getattr(o, name) or 0) != (getattr(occ[0], name) or 0):
+        raise ValueError(f"calendars: calendar {k} (occupancy group {k}): {name} = {getattr(o, name)!r} differs from "
+                         f"calendar 0's {getattr(occ[0], name)!r}: the device generator has one {name} per handle")
+  return occ
+
+
+def check_calendars(calendars: Sequence[Calendar], calendar_of, n_buildings: int, weather, occupancy, start_timestamp,
+                    comfort_temp_window, eco_temp_window) -> np.ndarray:
+  """What ``BatchedEnvironment(calendars=...)`` refuses before it creates anything; ``weather``, ``occupancy``,
+  ``start_timestamp`` and the two windows are the environment's own (the windows: its SimConfig's).  Returns
+  ``calendar_of`` as int32 [B].  ValueError, naming the calendar: a member of ``calendars`` that is no ``Calendar``; a
+  schedule whose temperature windows are not the SimConfig's (the windows are per-building parameter rows:
+  ``building_params``); a weather next to a per-building weather of the environment, or whose convection coefficient at
+  the calendar's start is not the environment's (one coefficient table per handle: ``building_materials``); and
+  ``device_occupancy_groups``' refusals."""
+  calendars = list(calendars) if isinstance(calendars, (list, tuple)) else None
+  if not calendars or not all(isinstance(c, Calendar) for c in calendars):
+    raise ValueError("calendars must be a non-empty list of host_inputs.Calendar")
+  cal_of = check_calendar_of(calendar_of, n_buildings, len(calendars))
+  h_conv = weather.get_air_convection_coefficient(as_datetime(start_timestamp))
+  for k, c in enumerate(calendars):
+    if c.schedule is not None:
+      for name, want in (("comfort_temp_window", comfort_temp_window), ("eco_temp_window", eco_temp_window)):
+        got = tuple(float(v) for v in getattr(c.schedule, name))
+        if got != tuple(float(v) for v in want):
+          raise ValueError(f"calendars: calendar {k}: its schedule's {name} {got} is not the SimConfig's "
+                           f"{tuple(float(v) for v in want)}: the windows are per-building parameters, set them with "
+                           "building_params (BuildingParams)")
+    if c.weather is not None:
+      if isinstance(weather, (BatchedSinusoidWeather, BatchedReplayWeather)):
+        raise ValueError(f"calendars: calendar {k} carries a weather, but the environment's {type(weather).__name__} "
+                         "already gives every building its own")
+      got = c.weather.get_air_convection_coefficient(c.start(start_timestamp))
+      if got != h_conv:
+        raise ValueError(f"calendars: calendar {k}: its weather's convection coefficient {got} is not the environment's "
+                         f"{h_conv}: the coefficient tables are one per handle, give buildings their own with "
+                         "building_materials (BuildingMaterials)")
+  device_occupancy_groups(calendars, occupancy)
+  return cal_of
+
+
+class CalendarTimeline:
+  """``Timeline`` for a batch whose buildings live on K calendars: for calendar k the rows ``Timeline`` builds --
+  ``instant_row(calendars[k].models(models), t)`` at ``t = start_k + r * step_interval``, ``start_k`` the calendar's own
+  start or ``start_timestamp`` -- for ``r = 0 .. max(start_offsets of its buildings) + steps_per_episode + 1``, the K
+  segments one after the other in ``rows [n_rows, len(CLOCK_FIELDS)]`` (sb_clock_attach's table).  ``base[k]`` is the
+  first row of calendar k's segment; building b lives at row ``offsets[b] + position`` with ``offsets[b] =
+  base[calendar_of[b]] + start_offsets[b]`` (int32 [B]), at the instant ``instant(b, position)``.
+
+  ValueError, naming the global building and its calendar: ``Timeline``'s refusals per calendar (a host-side
+  ``RandomizedArrivalDepartureOccupancy``, a replay weather whose trace does not hold a building's episode, more than
+  2^22 rows in the concatenated table), a wrong ``calendar_of`` and a calendar no building uses."""
+
+  def __init__(self, calendars: Sequence[Calendar], calendar_of, models: StepModels, start_timestamp, start_offsets,
+               steps_per_episode: int):
+    self.calendars = list(calendars)
+    n_buildings = len(np.atleast_1d(np.asarray(calendar_of if start_offsets is None else start_offsets)))
+    self.calendar_of = check_calendar_of(calendar_of, n_buildings, len(self.calendars))
+    self.start_offsets = check_start_offsets(np.zeros(n_buildings, dtype=np.int32) if start_offsets is None
+                                             else start_offsets, n_buildings)
+    self.step_interval = models.step_interval
+    self.models = [c.models(models) for c in self.calendars]
+    self.starts = [c.start(start_timestamp) for c in self.calendars]
+    steps = int(steps_per_episode)
+    # Segment k has max(start_offsets of its buildings) + steps + 2 rows.  sb_clock_seek's bound -- largest offset + pos <=
+    # n_rows - 2 -- therefore holds up to pos = steps for the concatenation as it does for one Timeline: every calendar
+    # has a building, so the largest offset is base[K-1] + (the last segment's largest start offset), and the last
+    # segment is sized for exactly that one: n_rows = base[K-1] + that offset + steps + 2.
+    members = [np.nonzero(self.calendar_of == k)[0] for k in range(len(self.calendars))]
+    sizes = np.array([int(self.start_offsets[idx].max()) + steps + 2 for idx in members], dtype=np.int64)
+    self.base = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    self.n_rows = int(sizes.sum())
+    if self.n_rows > (1 << 22):
+      k = int(np.argmax(np.cumsum(sizes) > (1 << 22)))
+      raise ValueError(f"calendars: the concatenated timeline would have {self.n_rows} rows, more than 2^22 (reached in "
+                       f"calendar {k}, whose building {int(members[k][np.argmax(self.start_offsets[members[k]])])} starts "
+                       f"at offset {int(self.start_offsets[members[k]].max())})")
+    segments = []
+    for k, (m, idx) in enumerate(zip(self.models, members)):
+      if (isinstance(m.occupancy, RandomizedArrivalDepartureOccupancy)
+          and not isinstance(m.occupancy, BatchedRandomizedArrivalDepartureOccupancy)):
+        raise ValueError(f"calendars: calendar {k} (building {int(idx[0])}): a host-side RandomizedArrivalDepartureOccupancy "
+                         "is one stateful instance queried at one instant per step; use "
+                         "BatchedRandomizedArrivalDepartureOccupancy (the device generator)")
+      if isinstance(m.weather, ReplayWeatherController):
+        self._check_trace(k, m.weather, idx, int(sizes[k]))
+      segments.append(np.array([instant_row(m, self.starts[k] + r * self.step_interval) for r in range(int(sizes[k]))],
+                               dtype=np.float64).reshape(int(sizes[k]), len(CLOCK_FIELDS)))
+    self.rows = np.concatenate(segments, axis=0)
+    self.rows.setflags(write=False)
+    self.offsets = np.ascontiguousarray(self.base[self.calendar_of] + self.start_offsets, dtype=np.int32)
+
+  def instant(self, building: int, position: int = 0) -> dt.datetime:
+    """Building ``building``'s instant at ``position`` of its episode, on its own calendar."""
+    k = int(self.calendar_of[building])
+    return self.starts[k] + (int(self.start_offsets[building]) + int(position)) * self.step_interval
+
+  def _check_trace(self, k: int, weather, idx: np.ndarray, n_rows: int) -> None:
+    """Timeline._check_trace for calendar k's buildings ``idx`` (global indices) on its segment of ``n_rows`` rows."""
+    start = self.starts[k]
+    if start.tzinfo is None:
+      raise TypeError("ReplayWeatherController needs a tz-aware timestamp (reference: tz_convert)")
+    shift = getattr(weather, "offsets_sec", None)
+    if shift is not None and shift.shape != self.calendar_of.shape:
+      raise ValueError("BatchedReplayWeather needs one offset per building")
+    shift = 0.0 if shift is None else shift[idx]
+    offs = self.start_offsets[idx].astype(np.int64)
+    step = self.step_interval.total_seconds()
+    last = start.timestamp() + (offs + (n_rows - 1 - int(offs.max()))) * step + shift
+    first = start.timestamp() + offs * step + shift
+    t_min, t_max = float(weather._times.min()), float(weather._times.max())
+    if (last > t_max).any():
+      b = int(idx[np.argmax(last)])
+      raise ValueError(f"calendars: building {b} (calendar {k}): its episode ends at "
+                       f"{dt.datetime.fromtimestamp(float(last.max()), tz=UTC)}, after the weather trace's last time stamp "
+                       f"{dt.datetime.fromtimestamp(t_max, tz=UTC)}")
+    if (first < t_min).any():
+      b = int(idx[np.argmin(first)])
+      raise ValueError(f"calendars: building {b} (calendar {k}): its episode starts before the weather trace's first "
+                       "time stamp")
+
+
 # --------------------------------------------------------------------------- per-building plant parameters
 # SimConfig field -> the sb_params fields it sets (include/sbsim_amd.h sb_building_param), in the enum's order
 BUILDING_PARAM_NAMES: Dict[str, Tuple[str, ...]] = {
