@@ -735,6 +735,47 @@ int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host /* [B] */, int32_t
  * no-op. */
 int sb_observe_buildings(sb_handle *h, const uint8_t *mask_host, const sb_step_in *in, float *obs_dev, void *stream);
 
+/* Spatial outputs from the device state: per-zone {min, max, mean} of the air CVs (Building.get_zone_temp_stats,
+ * simulator/building.py:564-577, 845-861) and a pooled temperature map (the grid the reference hands to VisualLogger /
+ * BuildingRenderer every step, reduced on the device).  One kernel, k_spatial (spatial.hip), reads a building's state
+ * once -- in whatever layout the handle keeps it: register slots with an exterior ring, the padded LDS grid, a
+ * transposed plan, the Jacobi solver's float32 grid -- through index tables built on the host (spatial_plan.cpp) and
+ * writes the few kilobytes per building the caller asked for.
+ *
+ * Values read: building.temp exactly as sb_get_temps reports it, in the caller's orientation (on register layouts an
+ * exterior-space CV is its ring value, or scal[16] when scal[16] == scal[17]; a Jacobi handle's float32 values are
+ * widened to double).
+ * Zone statistics: over the cells of the plan descriptor's zone_cells (the reference's room_dict).
+ * Pooled map: tile (i, j) covers rows [i*pool_h, min((i+1)*pool_h, H)) and columns [j*pool_w, min((j+1)*pool_w, W)) of the
+ * caller's [H, W] grid; its value is the mean over EVERY CV of the tile (walls and exterior space included), accumulated
+ * in float64, divided by the tile's cell count in float64, stored as float32.
+ *
+ * SUMMATION ORDER (fixed; defined on the caller's raster order, never on the state layout: the same temperatures give
+ * the same bits on every kernel's layout, either orientation, with or without a pick, from run to run; no atomics):
+ *   wave order of a list x[0..n):  lane l of 64 starts from +0.0 and adds x[l], x[l+64], x[l+128], ... in sequence; then
+ *       for o = 32, 16, 8, 4, 2, 1:  s[l] <- s[l] + s[l xor o]  (every lane at once: all 64 end with the same bits).
+ *       min and max run the same way from +inf / -inf.
+ *   zone z: wave order of its cells in ascending flat index g = y*W + x of the CALLER's grid (zone_cells' own order
+ *       for the plans sbsim_amd/floorplan.py compiles); mean = sum / (double)n.
+ *   tile of at most 64 cells (pool_h*pool_w <= 64): +0.0, then its cells added row-major in sequence by one lane.
+ *   tile of more cells (pool_h*pool_w > 64): wave order of the tile's cells listed row-major.
+ *   (The rule looks at pool_h*pool_w, not at a ragged tile's own count.) */
+/* host only: the map's shape for a pool size (ceil division); pool_h, pool_w >= 1 */
+int sb_spatial_shape(int32_t H, int32_t W, int32_t pool_h, int32_t pool_w, int32_t *map_h, int32_t *map_w);
+/* Builds and uploads the index tables.  pool_h = pool_w = 0: zone statistics only.  transposed: as in
+ * sb_convection_attach (the handle runs the caller's grid transposed; tiles, cell order and the map are the caller's).
+ * Attaching again replaces the tables once the device is idle.  Not state: snapshots do not carry it.
+ * SB_ERR_INVALID: a null handle, a negative pool, only one of the two pool sizes zero. */
+int sb_spatial_attach(sb_handle *h, int32_t pool_h, int32_t pool_w, int32_t transposed);
+/* ONE launch, stream-ordered, no allocation, no synchronisation (capturable, like sb_state_save).  Row r is building
+ * pick_dev[r] (DEVICE [n] int32); pick_dev NULL means row r is building r and n == B.  A pick outside [0, B) leaves
+ * its row untouched.
+ *   zone_stats_dev: DEVICE [n][Z][3] double {min, max, mean}, or NULL.
+ *   map_dev: DEVICE [n][map_h][map_w] float, or NULL.
+ * SB_ERR_INVALID: a null handle, n <= 0 (without pick_dev: n != B), both outputs NULL, a map requested with no pool
+ * attached, a call before sb_reset, a call before sb_spatial_attach. */
+int sb_spatial(sb_handle *h, const int32_t *pick_dev, int32_t n, double *zone_stats_dev, float *map_dev, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

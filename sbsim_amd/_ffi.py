@@ -165,7 +165,8 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_state_save", "sb_state_load", "sb_create_jacobi", "sb_tap_jacobi", "sb_set_building_params",
            "sb_set_reward_function", "sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials",
            "sb_get_building_coef", "sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in",
-           "sb_debug_plan_digest", "sb_reset_buildings", "sb_observe_buildings", "sb_occupancy_attach_groups")
+           "sb_debug_plan_digest", "sb_reset_buildings", "sb_observe_buildings", "sb_occupancy_attach_groups",
+           "sb_spatial_shape", "sb_spatial_attach", "sb_spatial")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
@@ -175,6 +176,7 @@ CLOCK_ENTRIES = ("sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_obse
 PLAN_DIGEST_ENTRIES = ("sb_debug_plan_digest",)
 EPISODES_ENTRIES = ("sb_reset_buildings", "sb_observe_buildings")
 OCCUPANCY_ENTRIES = ("sb_occupancy_attach_groups",)
+SPATIAL_ENTRIES = ("sb_spatial_shape", "sb_spatial_attach", "sb_spatial")
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -276,6 +278,10 @@ def load():
     L.sb_observe_buildings.argtypes = [vp, vp, C.POINTER(StepIn), vp, vp]
   if all(hasattr(L, name) for name in OCCUPANCY_ENTRIES):
     L.sb_occupancy_attach_groups.argtypes = [vp, C.POINTER(OccupancyConfig), C.c_int32, vp]
+  if all(hasattr(L, name) for name in SPATIAL_ENTRIES):
+    L.sb_spatial_shape.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.sb_spatial_attach.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.sb_spatial.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
   if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
     L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
@@ -325,6 +331,11 @@ def occupancy_entry(name: str):
 
 def episodes_entry(name: str):
   """The per-building-episodes entry `name` (sb_reset_buildings, sb_observe_buildings): see entry()."""
+  return entry(name)
+
+
+def spatial_entry(name: str):
+  """The spatial-outputs entry `name` (sb_spatial_shape, sb_spatial_attach, sb_spatial): see entry()."""
   return entry(name)
 
 

@@ -198,6 +198,12 @@ struct sb_handle {
   DevBuf<double> mat_diff;          // [ncls] diffuser weight
   DevBuf<double> mat_tab;           // [3 M + 1][B] the values in force
   DevBuf<double> ctab_b;            // [B][ncls + 1][8] (Dev::ctab_b)
+  // sb_spatial_attach (spatial.hip): k_spatial's index tables (spatial.h) on the device, and the scalars that go with them
+  bool sp_attached = false;
+  int sp_map_h = 0, sp_map_w = 0, sp_tile_len = 0, sp_tile_wave = 0; // map_h == 0: zone statistics only
+  int sp_state_len = 0;             // elements of a building's state (the source indices' first range)
+  int sp_stage_bytes = 0;           // > 0: the state is staged in this much LDS per workgroup; 0: gathered from global memory
+  DevBuf<int> sp_tile_src, sp_tile_off, sp_tile_cnt, sp_zone_off, sp_zone_src;
   // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
   DevBuf<float> jgrid, jtab, jscratch; // (jscratch: k_sweep_jacobi_g's per-workgroup grids)
   DevBuf<double> jrden;

@@ -29,6 +29,7 @@ import dataclasses
 import datetime as dt
 import hashlib
 import math
+import operator
 import os
 import pickle
 from typing import Dict, List, Mapping, Optional, Sequence, Tuple
@@ -364,6 +365,7 @@ class BatchedSimulator:
     self._building_materials = None   # set_building_materials: the rows in force (None: the plan's own values)
     self._clock_offsets = None   # clock_attach: the buildings' offsets into the timeline (None: one clock for the batch)
     self._calendars = None   # clock_attach(calendar_of=...): hashes of the concatenated rows and of calendar_of
+    self._spatial = (False, None)   # spatial_attach: (attached, the map's shape or None); configuration, not state
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -981,6 +983,85 @@ class BatchedSimulator:
   def zone_power(self) -> torch.Tensor:
     return self._get(self._lib.sb_get_zone_power, (self.B, self.Z), torch.float64)
 
+  # ---- spatial outputs (sb_spatial_attach / sb_spatial) ----
+  def spatial_attach(self, pool: Optional[Tuple[int, int]] = None) -> None:
+    """sb_spatial_attach: builds the index tables of ``zone_temp_stats`` / ``temperature_map`` / ``spatial``.
+    ``pool``: (pool_h, pool_w) of the pooled map on the caller's [H, W] grid; None: zone statistics only.  Attaching again
+    replaces the tables.  Not state: it enters neither ``state_fingerprint()`` nor a ``SimState``."""
+    attach = _ffi.spatial_entry("sb_spatial_attach")
+    if pool is None:
+      ph = pw = 0
+      shape = None
+    else:
+      try:
+        ph, pw = (operator.index(x) for x in pool)
+      except (TypeError, ValueError):
+        raise ValueError("pool must be (pool_h, pool_w), two integers >= 1, or None") from None
+      if ph < 1 or pw < 1 or ph >= 1 << 31 or pw >= 1 << 31:
+        raise ValueError("pool must be (pool_h, pool_w), two integers >= 1, or None")
+      mh, mw = C.c_int32(), C.c_int32()
+      _ffi.check(_ffi.spatial_entry("sb_spatial_shape")(self.H, self.W, ph, pw, C.byref(mh), C.byref(mw)), "sb_spatial_shape")
+      shape = (mh.value, mw.value)
+    with torch.cuda.device(self.device):
+      _ffi.check(attach(self._h, ph, pw, int(self.transposed)), "sb_spatial_attach")
+    self._spatial = (True, shape)
+
+  @property
+  def map_shape(self) -> Optional[Tuple[int, int]]:
+    """(map_h, map_w) of ``temperature_map`` as attached, or None (no pool, or nothing attached)."""
+    return self._spatial[1]
+
+  def spatial(self, rows: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None,
+              map_out: Optional[torch.Tensor] = None, stats: bool = True, map: Optional[bool] = None):  # pylint: disable=redefined-builtin
+    """sb_spatial: ONE launch on the current stream.  Returns (zone statistics [n, Z, 3] float64 {min, max, mean},
+    pooled map [n, map_h, map_w] float32); row i is building rows[i] (int32 / int64 [n] on the device), or building i
+    (``rows`` None, n == B).  ``stats`` / ``map`` False leave that output out (None in its place); ``map`` defaults to
+    "a pool is attached".  ``stats_out`` / ``map_out``: the tensors to write (contiguous, of that shape and dtype, on
+    the device); rows of a repeated pick are written more than once, with the same values.  ValueError before any launch
+    for rows of the wrong dtype, shape, device or range, for outputs that do not fit, and for a map without a pool."""
+    fn = _ffi.spatial_entry("sb_spatial")
+    attached, shape = self._spatial
+    if not attached:
+      raise ValueError("spatial outputs need spatial_attach() first")
+    if map is None:
+      map = shape is not None or map_out is not None
+    if map and shape is None:
+      raise ValueError("temperature_map needs a pool size: spatial_attach(pool=(pool_h, pool_w))")
+    if not stats and not map:
+      raise ValueError("spatial: nothing asked for (stats and map both off)")
+    pick, n = None, self.B
+    if rows is not None:
+      pick = self._check_index(rows, None, 0, self.B, "rows")
+      n = int(pick.shape[0])
+    outs = []
+    for want, out, shp, dtype, what in ((stats, stats_out, (n, self.Z, 3), torch.float64, "stats_out"),
+                                        (map, map_out, (n,) + (shape or (0, 0)), torch.float32, "map_out")):
+      if not want:
+        if out is not None:
+          raise ValueError(f"{what} given, but that output is off")
+        outs.append(None)
+        continue
+      if out is None:
+        out = torch.empty(shp, dtype=dtype, device=self.tdev)
+      elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != shp or out.dtype != dtype or out.device != self.tdev
+            or not out.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous {dtype} {shp} tensor on {self.tdev}")
+      outs.append(out)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    rc = fn(self._h, ptr(pick), n, ptr(outs[0]), ptr(outs[1]), self._stream())
+    if rc == -1:   # SB_ERR_INVALID (before sb_reset, ...)
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_spatial")
+    return outs[0], outs[1]
+
+  def zone_temp_stats(self, rows: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Building.get_zone_temp_stats for every zone (building.py:564-577): [n, Z, 3] float64 {min, max, mean}."""
+    return self.spatial(rows, stats_out=out, stats=True, map=False)[0]
+
+  def temperature_map(self, rows: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The grid pooled by the attached (pool_h, pool_w): [n, map_h, map_w] float32 tile means."""
+    return self.spatial(rows, map_out=out, stats=False, map=True)[1]
+
 
 @dataclasses.dataclass
 class EnvSnapshot:
@@ -1036,8 +1117,13 @@ class BatchedEnvironment:
                reward_function: Optional[host_inputs.SetpointEnergyCarbonReward] = None,
                building_materials: Optional[host_inputs.BuildingMaterials] = None, start_offsets=None,
                per_building_episodes: bool = False, episode_steps=None,
-               calendars: Optional[Sequence[host_inputs.Calendar]] = None, calendar_of=None):
-    """``calendars`` / ``calendar_of``: several calendars in one batch.  ``calendars``: a list of K
+               calendars: Optional[Sequence[host_inputs.Calendar]] = None, calendar_of=None,
+               spatial: Optional[host_inputs.SpatialOutputs] = None):
+    """``spatial``: a ``host_inputs.SpatialOutputs`` -- ``temperature_map`` and / or ``zone_temp_stats`` of the state
+    the returned observation describes, refreshed with one launch per call; with
+    ``per_building_episodes`` also ``final_temperature_map`` / ``final_zone_temp_stats``, written like
+    ``final_observation``.  None (the default): the attributes are None and nothing is built or launched.
+    ``calendars`` / ``calendar_of``: several calendars in one batch.  ``calendars``: a list of K
     ``host_inputs.Calendar`` -- setpoint schedule, occupancy model, tariffs, a shared weather and the start date, each
     the environment's own where left None; ``calendar_of``: an integer array [B], building b's index into it.  Building
     b then lives at ``calendars[calendar_of[b]]``'s start ``+ (start_offsets[b] + step) * step_interval`` (zeros without
@@ -1168,6 +1254,10 @@ class BatchedEnvironment:
       self._disc = torch.ones((self.batch_size,), dtype=torch.float32, device=dev)
       # the previous thermostat update stays per building on the device (scal[18]), as after a first rejection
       self._no_reject = torch.zeros((self.batch_size,), dtype=torch.uint8, device=dev)
+    self.spatial = None
+    self.temperature_map = self.zone_temp_stats = self.final_temperature_map = self.final_zone_temp_stats = None
+    if spatial is not None:
+      self._setup_spatial(spatial)
     self._episode_ended = False
     self._step_count = 0
     self._episode_count = 0
@@ -1309,6 +1399,7 @@ class BatchedEnvironment:
       else:
         t_amb = self.weather.get_current_temp(self._now)
       self.sim.observe(self._aux(self._now), t_amb, self._obs, self._occ_total, self._occ_norm)
+    self._refresh_spatial()
     if self.per_building_episodes:   # the per-building TimeStep buffers: what reset_buildings() returns for the others
       self._step_type.fill_(STEP_FIRST)
       self._reward.zero_()
@@ -1342,6 +1433,7 @@ class BatchedEnvironment:
         self._no_reject = torch.zeros((self.batch_size,), dtype=torch.uint8, device=self.sim.tdev)
       si.reject_dev = self._no_reject.data_ptr()
     self.sim.step(action, si, self._obs, self._reward, self._info)
+    self._refresh_spatial()
     self._prev_thermostat_ts = self._now
     self._now = self._now + self._step_interval
     if self._cursor is not None:
@@ -1402,7 +1494,9 @@ class BatchedEnvironment:
       self._step_type.masked_fill_(last, STEP_LAST)
       self._disc.masked_fill_(last, 0.0)
       self.final_observation.copy_(torch.where(last[:, None], self._obs, self.final_observation))
+      self._final_spatial(last)
       self._restart(ended)
+    self._refresh_spatial()
     return TimeStep(self._step_type, self._reward, self._disc, self._obs)
 
   def reset_buildings(self, mask) -> TimeStep:
@@ -1418,6 +1512,7 @@ class BatchedEnvironment:
     if m.any():
       first = torch.from_numpy(m).to(self.sim.tdev)
       self._restart(m)
+      self._refresh_spatial()
       self._step_type.masked_fill_(first, STEP_FIRST)
       self._reward.masked_fill_(first, 0.0)
       self._disc.masked_fill_(first, 1.0)
@@ -1516,6 +1611,7 @@ class BatchedEnvironment:
     self._reward.copy_(snap.reward)
     if self._info is not None:
       self._info.copy_(snap.info)
+    self._refresh_spatial()   # (not in the snapshot: recomputed from the restored state)
     return self._timestep()
 
   def fork(self, src: torch.Tensor) -> None:
@@ -1539,6 +1635,40 @@ class BatchedEnvironment:
     self._reward.copy_(self._reward[src])
     if self._info is not None:
       self._info.copy_(self._info[src])
+    self._refresh_spatial()
+
+  # ---- spatial outputs ----
+  def _setup_spatial(self, spatial: host_inputs.SpatialOutputs) -> None:
+    """The constructor's part for ``spatial``: the index tables on the device and the output tensors."""
+    if not isinstance(spatial, host_inputs.SpatialOutputs):
+      raise ValueError("spatial must be a host_inputs.SpatialOutputs (or None)")
+    self.sim.spatial_attach(spatial.pool)
+    self.spatial = spatial
+    dev, B = self.sim.tdev, self.batch_size
+    if spatial.pool is not None:
+      self.temperature_map = torch.zeros((B,) + self.sim.map_shape, dtype=torch.float32, device=dev)
+    if spatial.zone_stats:
+      self.zone_temp_stats = torch.zeros((B, self.sim.Z, 3), dtype=torch.float64, device=dev)
+    if self.per_building_episodes:   # [B, ...]: a building's row is written when its episode ends, as final_observation's
+      self.final_temperature_map = None if self.temperature_map is None else torch.zeros_like(self.temperature_map)
+      self.final_zone_temp_stats = None if self.zone_temp_stats is None else torch.zeros_like(self.zone_temp_stats)
+
+  def _refresh_spatial(self) -> None:
+    """One sb_spatial launch on the current stream: the outputs of the state the current observation describes."""
+    if self.spatial is not None:
+      self.sim.spatial(None, stats_out=self.zone_temp_stats, map_out=self.temperature_map,
+                       stats=self.zone_temp_stats is not None, map=self.temperature_map is not None)
+
+  def _final_spatial(self, last: torch.Tensor) -> None:
+    """Before the buildings of ``last`` (bool [B] on the device) are reset: one picked launch, their rows of final_*."""
+    if self.spatial is None:
+      return
+    rows = torch.nonzero(last).reshape(-1)
+    stats, tmap = self.sim.spatial(rows, stats=self.zone_temp_stats is not None, map=self.temperature_map is not None)
+    if stats is not None:
+      self.final_zone_temp_stats.index_copy_(0, rows, stats)
+    if tmap is not None:
+      self.final_temperature_map.index_copy_(0, rows, tmap)
 
   def close(self) -> None:
     self.sim.close()
@@ -1620,6 +1750,10 @@ class MixedBatchedEnvironment:
         if len(kw["solver"]) != len(classes):
           raise ValueError(f"solver: one per class ({len(classes)}), or one for all")
         kw["solver"] = kw["solver"][k]
+      if isinstance(kw.get("spatial"), (list, tuple)):   # one SpatialOutputs (or None) per class
+        if len(kw["spatial"]) != len(classes):
+          raise ValueError(f"spatial: one per class ({len(classes)}), or one for all")
+        kw["spatial"] = kw["spatial"][k]
       for key in ("convection_simulator", "occupancy"):
         gen = kw.get(key)
         if gen is not None and hasattr(gen, "first_building"):
@@ -1675,6 +1809,18 @@ class MixedBatchedEnvironment:
   @property
   def current_simulation_timestamp(self) -> dt.datetime:
     return self.envs[0].current_simulation_timestamp
+
+  @property
+  def temperature_maps(self) -> List[Optional[torch.Tensor]]:
+    """Every class's ``BatchedEnvironment.temperature_map`` ([B_k, map_h_k, map_w_k] float32, or None), computed on the
+    class's stream by the last ``reset`` / ``step`` / ``restore`` / ``fork`` (``spatial``: one for all classes, or one per
+    class)."""
+    return [e.temperature_map for e in self.envs]
+
+  @property
+  def zone_temp_stats(self) -> List[Optional[torch.Tensor]]:
+    """Every class's ``BatchedEnvironment.zone_temp_stats`` ([B_k, Z_k, 3] float64, or None)."""
+    return [e.zone_temp_stats for e in self.envs]
 
   def _check_building_params(self, params: Optional[host_inputs.BuildingParams]) -> None:
     total = sum(self.class_totals)

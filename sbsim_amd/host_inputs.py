@@ -553,6 +553,42 @@ class SetpointEnergyCarbonReward:
     return "SetpointEnergyCarbonReward(%r, %r, %r, %r, %r)" % self.as_tuple()[1:]
 
 
+class SpatialOutputs:
+  """What ``BatchedEnvironment(..., spatial=SpatialOutputs(...))`` keeps beside the observation, refreshed with one
+  launch by every ``reset()`` / ``step()`` / ``reset_buildings()`` / ``restore()`` / ``fork()``:
+
+  ``pool``: None -- no map; ``(pool_h, pool_w)``, two integers >= 1 -- ``env.temperature_map`` [B, map_h, map_w] float32,
+  the mean of every ``pool_h x pool_w`` tile of the [H, W] grid (the last row / column of tiles may be ragged).
+  ``zone_stats``: ``env.zone_temp_stats`` [B, Z, 3] float64 {min, max, mean} over each zone's air control volumes
+  (Building.get_zone_temp_stats, building.py:564-577).
+  ValueError for a pool that is not two integers >= 1, and when neither output is asked for."""
+
+  def __init__(self, pool: Optional[Sequence[int]] = None, zone_stats: bool = True):
+    if pool is not None:
+      try:
+        ok = not any(isinstance(x, (bool, np.bool_)) for x in pool)
+        pool = tuple(x.__index__() for x in pool)   # (integers only: a float pool is refused, not truncated)
+        ok = ok and len(pool) == 2 and all(1 <= x < 1 << 31 for x in pool)
+      except (TypeError, ValueError, AttributeError):
+        ok = False
+      if not ok:
+        raise ValueError("pool must be (pool_h, pool_w), two integers >= 1, or None")
+    if not isinstance(zone_stats, (bool, np.bool_)):
+      raise ValueError("zone_stats must be a bool")
+    if pool is None and not zone_stats:
+      raise ValueError("SpatialOutputs with neither a pool nor zone_stats asks for nothing")
+    self.pool, self.zone_stats = pool, bool(zone_stats)
+
+  def __eq__(self, other) -> bool:
+    return isinstance(other, SpatialOutputs) and (self.pool, self.zone_stats) == (other.pool, other.zone_stats)
+
+  def __hash__(self) -> int:
+    return hash((self.pool, self.zone_stats))
+
+  def __repr__(self) -> str:
+    return f"SpatialOutputs(pool={self.pool!r}, zone_stats={self.zone_stats!r})"
+
+
 def reward_start_time_utc(ts: dt.datetime) -> dt.datetime:
   """conversion_utils.py:39-59: the reward sees pandas_to_proto -> proto_to_pandas, i.e. UTC."""
   return dt.datetime.fromtimestamp(int(epoch_seconds(ts)), tz=UTC)
