@@ -862,15 +862,20 @@ def _need_experimental_kernels(variant, monkeypatch):
 
 def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatch, expect_steps=None,
                                iteration_limit=None, expect_kernel=None, B=6, T=14, expect_waves=None,
-                               init=None, acts=None, cfg=None, env=None, buildings=None, on_launch=None):
+                               init=None, acts=None, cfg=None, env=None, buildings=None, on_launch=None,
+                               golden=None, on_step=None, force_path=True):
   """Every building against its oracle twin at every step.  `file_plan` may be a FloorPlan; `init` [B, H*W], `acts`
   [T, B, 2] and `cfg` replace the seeded initial grids, actions and SimConfig.sb1(); `env` sets developer switches;
-  `buildings` names the buildings that get a twin (default: every one); `on_launch` is called with the launch_info.
+  `buildings` names the buildings that get a twin (default: every one); `on_launch` is called with the launch_info;
+  `golden` replaces the step-input rows of h2_sb1_r9_random.npz; `on_step(sim, t, obs, outs)` is called after every
+  step's own checks with the observation rows (numpy) and the twins' results of the step ({building: dict});
+  `force_path=False` leaves the choice between the LDS-grid and the streaming kernel to the library (`path` is then
+  only what the launch must report).
   Returns the info rows and the grids after every step."""
   _need_gpu()
   for k, v in dict(env or {}).items():
     monkeypatch.setenv(k, v)
-  g = load("h2_sb1_r9_random.npz")
+  g = load("h2_sb1_r9_random.npz") if golden is None else golden
   plan = file_plan if isinstance(file_plan, FloorPlan) else FloorPlan.from_file_input(file_plan, Materials.sb1(), 10.0, 300.0)
   H, W = plan.shape
   rs = np.random.RandomState(11)
@@ -885,9 +890,9 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
   if orientation == "generic":
     monkeypatch.setenv("SBSIM_FORCE_GENERIC_SWEEP", "1")
     orientation = "rows"
-  if path == 0:
+  if path == 0 and force_path:
     monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
-  if path == 2 and H * W < 100000:
+  if path == 2 and H * W < 100000 and force_path:
     monkeypatch.setenv("SBSIM_FORCE_STREAM_PATH", "1")   # small plans reach the streaming kernel only when told to
   sim = BatchedSimulator(plan, cfg, B, float(g["h_conv"]), orientation=orientation)
   assert sim.Z == n_zones and sim.launch_info["path"] == path
@@ -915,6 +920,7 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
     r = rew.cpu().numpy()
     infos.append(i)
     grids.append(sim.temps().cpu().numpy())
+    outs = {}
     for b in checked:
       a = acts[t, b]
       native = [np.float32((float(a[0]) + 1.0) / 2.0 * (lo[1] - lo[0]) + lo[0]),
@@ -932,6 +938,9 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
       ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
       assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b)
       assert abs(float(r[b]) - o["reward"]) < 2e-6, (t, b)
+      outs[b] = o
+    if on_step is not None:
+      on_step(sim, t, obs.cpu().numpy(), outs)
   grid = sim.temps().cpu().numpy()
   for b in checked:
     assert np.abs(grid[b] - twins[b].grid()).max() < T_TOL, b

@@ -82,7 +82,7 @@ def oracle_twin(plan, cfg, init_flat) -> orc.OracleBuilding:
       vav_max_air_flow=c.vav_max_air_flow_rate, vav_max_water_flow=c.vav_reheat_max_water_flow_rate,
       ahu_recirc=c.ahu_recirculation, ahu_heat_sp=c.ahu_heating_air_temp_setpoint,
       ahu_cool_sp=c.ahu_cooling_air_temp_setpoint, ahu_dp=c.ahu_fan_differential_pressure,
-      ahu_eff=c.ahu_fan_efficiency, blr_setpoint=c.boiler_reheat_water_setpoint,
+      ahu_eff=c.ahu_fan_efficiency, ahu_max_flow=c.ahu_max_air_flow_rate, blr_setpoint=c.boiler_reheat_water_setpoint,
       blr_head=c.boiler_water_pump_differential_head, blr_pump_eff=c.boiler_water_pump_efficiency,
       comfort_lo=c.comfort_temp_window[0], comfort_hi=c.comfort_temp_window[1],
       eco_lo=c.eco_temp_window[0], eco_hi=c.eco_temp_window[1],
