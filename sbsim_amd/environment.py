@@ -1617,9 +1617,11 @@ class BatchedEnvironment:
   def fork(self, src: torch.Tensor) -> None:
     """Building b takes building src[b]'s current state (src: int64 [B] on the device; repeats and aliasing allowed):
     one save of the distinct source buildings and one load with a pick.  The clock does not move; the current
-    observation, reward and info rows follow their buildings.  Random streams: the device occupancy and convection
-    draw by (seed, global building, counter), so a forked building keeps its own slot's stream -- forked replicas
-    of one building diverge under those stochastic models and stay identical without them."""
+    observation, reward and info rows follow their buildings.  With ``start_offsets`` or ``calendars`` the thermostats'
+    previous update is the source building's, like the rest of its state, not the row of the slot's calendar.  Random
+    streams: the device occupancy and convection draw by (seed, global building, counter), so a forked building keeps
+    its own slot's stream -- forked replicas of one building diverge under those stochastic models and stay identical
+    without them."""
     self._refuse_with_episodes("fork()")
     self.sim._refuse_on_jacobi("fork()")
     if not isinstance(src, torch.Tensor) or src.dtype != torch.int64 or tuple(src.shape) != (self.batch_size,):
@@ -1631,6 +1633,11 @@ class BatchedEnvironment:
     uniq, inv = torch.unique(src, return_inverse=True)
     state = self.sim.save_state(rows=uniq)
     self.sim.load_state(state, pick=inv, clock=False)
+    if self._cursor is not None and getattr(self, "_rejected", None) is None:
+      # The previous thermostat update is state (scal[18], Thermostat._previous_timestamp): a forked building's is its
+      # source's, which the row of its own slot's calendar does not know.  From here on k_pre reads scal[18], as after a
+      # first rejection -- a step after a fork must not depend on whether `rejected` was ever passed.
+      self._rejected = torch.zeros((self.batch_size,), dtype=torch.uint8, device=self.sim.tdev)
     self._obs.copy_(self._obs[src])
     self._reward.copy_(self._reward[src])
     if self._info is not None:
