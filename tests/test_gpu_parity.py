@@ -863,14 +863,17 @@ def _need_experimental_kernels(variant, monkeypatch):
 def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatch, expect_steps=None,
                                iteration_limit=None, expect_kernel=None, B=6, T=14, expect_waves=None,
                                init=None, acts=None, cfg=None, env=None, buildings=None, on_launch=None,
-                               golden=None, on_step=None, force_path=True):
+                               golden=None, on_step=None, force_path=True, h_conv=None, step_sec=300.0,
+                               on_end=None):
   """Every building against its oracle twin at every step.  `file_plan` may be a FloorPlan; `init` [B, H*W], `acts`
   [T, B, 2] and `cfg` replace the seeded initial grids, actions and SimConfig.sb1(); `env` sets developer switches;
   `buildings` names the buildings that get a twin (default: every one); `on_launch` is called with the launch_info;
   `golden` replaces the step-input rows of h2_sb1_r9_random.npz; `on_step(sim, t, obs, outs)` is called after every
   step's own checks with the observation rows (numpy) and the twins' results of the step ({building: dict});
   `force_path=False` leaves the choice between the LDS-grid and the streaming kernel to the library (`path` is then
-  only what the launch must report).
+  only what the launch must report); `h_conv` replaces the rows' convection coefficient and `step_sec` the 300 s between
+  the twins' timestamps (a cfg of another time_step_sec); `on_end(grid, twins)` is called with the final grids
+  [B, H, W] and the twins ({building: OracleBuilding}) before the final grids are compared.
   Returns the info rows and the grids after every step."""
   _need_gpu()
   for k, v in dict(env or {}).items():
@@ -894,7 +897,8 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
     monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
   if path == 2 and H * W < 100000 and force_path:
     monkeypatch.setenv("SBSIM_FORCE_STREAM_PATH", "1")   # small plans reach the streaming kernel only when told to
-  sim = BatchedSimulator(plan, cfg, B, float(g["h_conv"]), orientation=orientation)
+  h_conv = float(g["h_conv"]) if h_conv is None else float(h_conv)
+  sim = BatchedSimulator(plan, cfg, B, h_conv, orientation=orientation)
   assert sim.Z == n_zones and sim.launch_info["path"] == path
   if expect_steps is not None:
     assert sim.launch_info["sweep_steps"] == expect_steps   # the two-rows kernel with two tail rows
@@ -926,7 +930,7 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
       native = [np.float32((float(a[0]) + 1.0) / 2.0 * (lo[1] - lo[0]) + lo[0]),
                 np.float32((float(a[1]) + 1.0) / 2.0 * (hi[1] - hi[0]) + hi[0])]
       o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
+          now_ts=step_sec * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=h_conv,
           t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
           comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
           occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]),
@@ -942,6 +946,8 @@ def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatc
     if on_step is not None:
       on_step(sim, t, obs.cpu().numpy(), outs)
   grid = sim.temps().cpu().numpy()
+  if on_end is not None:
+    on_end(grid, twins)
   for b in checked:
     assert np.abs(grid[b] - twins[b].grid()).max() < T_TOL, b
   sim.close()
