@@ -211,7 +211,7 @@ def oracle(case: Case, first_building: Optional[int] = None) -> ConvectionOracle
 
 @functools.lru_cache(maxsize=None)
 def _expected(name: str) -> Tuple[np.ndarray, ...]:
-  case = CASES[name]
+  case = _cases()[name]
   o = oracle(case)
   g = input_grids(floor_plan(case), case.B)
   out = []
@@ -247,47 +247,7 @@ def plan_info(case: Case) -> dict:
 
 
 # ---------------------------------------------------------------- the table
-CASES: Dict[str, Case] = {}
-
 SETTINGS = (("d5", 1.0, 5), ("d20", 0.7, 20), ("d1000", 0.5, -1), ("all", 1.0, -1))
-
-
-def _add(name: str, group: str, plan, p: float, distance: int, hits: str, **kw) -> None:
-  assert name not in CASES
-  fp = _plan(plan)
-  br = branches(fp, p, distance)
-  if "q" not in kw:
-    kw["q"] = None if br == (ALL,) else natural_q(fp)
-  CASES[name] = Case(name, group, plan, p, distance, br, hits, **kw)
-
-
-# a. hand-over: every workgroup DEPTH buildings deep, the last round partly empty
-_add("handover-d5", "handover", TINY, 1.0, 5, "early draw, val/oth hand-over, head[] re-arm: every cell starts a swap",
-     B=B_HANDOVER, cus=1, seed=11)
-_add("handover-d5-p0.5", "handover", TINY, 0.5, 5, "the same with cells that start no swap (word 0)", B=B_HANDOVER, cus=1, seed=12)
-_add("handover-d20", "handover", TINY, 0.7, 20, "the wide draw issued early for the next building", B=B_HANDOVER, cus=1, seed=13)
-_add("handover-all", "handover", TINY, 1.0, -1, "k_convect_all's b += gridDim.x loop", B=B_HANDOVER, cus=1, seed=14)
-
-# c. every Q
-for _q in range(1, 9):
-  _add(f"q{_q}-forced", "q", "q256", 0.75, 5, f"k_convect<{_q}> on rooms of 256, 77, 15 and 2 cells", q=_q, force_q=True,
-       seed=20 + _q)
-_add("q1-256cells", "q", "q256", 1.0, 5, "256 cells: the last size of k_convect<1>, four full wavefronts", seed=31)
-_add("q2-257cells", "q", "q257", 1.0, 5, "257 cells: the first size of k_convect<2>, 192 lanes", seed=32)
-_add("q3-600cells", "q", "sizes", 1.0, 5, "600 cells on k_convect<3>, the other zones far smaller", seed=33)
-_add("q4-600cells", "q", "sizes", 0.75, 20, "600 cells on 192 lanes (k_convect<4>): the last q partly filled", q=4, force_q=True,
-     seed=34)
-_add("q8-2047cells", "q", "one2047", 1.0, 5, "2047 cells: the 11-bit rank, other | next << 16 and the partner table at their limits",
-     B=2, seed=35)
-_add("q8-2047cells-rank", "q", "one2047", 0.5, -1, "2047 cells drawn by rank (by_rank[] and list indices up to 2046)", B=2, seed=36)
-_add("all-2047cells", "q", "one2047", 1.0, -1, "k_convect_all with all eight cells per lane in use", B=2, seed=37)
-
-# d. room shapes
-for _plan_name, _what in (("sizes", "rooms of 600, 64, 65, 1, 2 and 3 cells"),
-                          ("shapes", "an L, a corridor, closets of the corridor's zone"),
-                          ("quirks", "a zone of two rooms, a one-cell zone, an unzoned corridor")):
-  for _tag, _p, _d in SETTINGS:
-    _add(f"{_plan_name}-{_tag}", "shapes", _plan_name, _p, _d, _what, seed=40 + len(CASES))
 
 # e. layouts: (plan, orientation, env, (kernel, path, waves))
 LAYOUTS = (
@@ -303,23 +263,76 @@ LAYOUTS = (
     ("lds-rows", "R9", "rows", (), (hc.LDS, 0, 1)),
     ("lds-columns", "R9", "columns", (), (hc.LDS, 0, 1)),
 )
-for _name, _spec, _orient, _env, _pin in LAYOUTS:
-  _add(f"{_name}-d5", "layout", _spec, 1.0, 5, f"ConvCell.sidx of {_name}", B=2, orientation=_orient, env=_env, pin=_pin,
-       seed=70 + len(CASES))
-  _add(f"{_name}-d20", "layout", _spec, 0.7, 20, f"the wide window on {_name}", B=2, orientation=_orient, env=_env, pin=_pin,
-       seed=70 + len(CASES))
-_add("pair-d1000", "layout", ((2, 5), (30, 12)), 0.5, -1, "the by-rank branch with the handle transposed (W0 = H)", B=2,
-     orientation="columns", env=hc.PAIR_ENV, pin=(hc.REG_PAIR, 1, 2), seed=90)
-_add("lds-columns-all", "layout", "R9", 1.0, -1, "k_convect_all with the handle transposed", B=2, orientation="columns",
-     pin=(hc.LDS, 0, 1), seed=91)
 
-# f. call number and first_building
-_add("calls3-d5", "calls", TINY, 0.5, 5, "calls 0, 1, 2 of the table path", calls=3, seed=101)
-_add("calls3-d20", "calls", TINY, 0.7, 20, "calls 0, 1, 2 of a wide window", calls=3, seed=102)
-_add("calls3-all", "calls", TINY, 1.0, -1, "calls 0, 1, 2 of the whole-room shuffle", calls=3, seed=103)
-_add("first-max-d5", "calls", TINY, 1.0, 5, "first_building + B = 2^32 exactly", B=5, first_building=2 ** 32 - 5, seed=104)
-_add("first-max-all", "calls", TINY, 1.0, -1, "first_building + B = 2^32 exactly (Philox counter)", B=5,
-     first_building=2 ** 32 - 5, seed=105)
+
+@functools.lru_cache(maxsize=None)
+def _cases() -> Dict[str, Case]:
+  """The table.  A case's branches and its q come from its plan, and preprocessing a plan loads the library: the table is
+  built when it is first asked for (`CASES`, below), not when this module is imported."""
+  cases: Dict[str, Case] = {}
+
+  def _add(name: str, group: str, plan, p: float, distance: int, hits: str, **kw) -> None:
+    assert name not in cases
+    fp = _plan(plan)
+    br = branches(fp, p, distance)
+    if "q" not in kw:
+      kw["q"] = None if br == (ALL,) else natural_q(fp)
+    cases[name] = Case(name, group, plan, p, distance, br, hits, **kw)
+
+  # a. hand-over: every workgroup DEPTH buildings deep, the last round partly empty
+  _add("handover-d5", "handover", TINY, 1.0, 5, "early draw, val/oth hand-over, head[] re-arm: every cell starts a swap",
+       B=B_HANDOVER, cus=1, seed=11)
+  _add("handover-d5-p0.5", "handover", TINY, 0.5, 5, "the same with cells that start no swap (word 0)", B=B_HANDOVER, cus=1, seed=12)
+  _add("handover-d20", "handover", TINY, 0.7, 20, "the wide draw issued early for the next building", B=B_HANDOVER, cus=1, seed=13)
+  _add("handover-all", "handover", TINY, 1.0, -1, "k_convect_all's b += gridDim.x loop", B=B_HANDOVER, cus=1, seed=14)
+
+  # c. every Q
+  for _q in range(1, 9):
+    _add(f"q{_q}-forced", "q", "q256", 0.75, 5, f"k_convect<{_q}> on rooms of 256, 77, 15 and 2 cells", q=_q, force_q=True,
+         seed=20 + _q)
+  _add("q1-256cells", "q", "q256", 1.0, 5, "256 cells: the last size of k_convect<1>, four full wavefronts", seed=31)
+  _add("q2-257cells", "q", "q257", 1.0, 5, "257 cells: the first size of k_convect<2>, 192 lanes", seed=32)
+  _add("q3-600cells", "q", "sizes", 1.0, 5, "600 cells on k_convect<3>, the other zones far smaller", seed=33)
+  _add("q4-600cells", "q", "sizes", 0.75, 20, "600 cells on 192 lanes (k_convect<4>): the last q partly filled", q=4, force_q=True,
+       seed=34)
+  _add("q8-2047cells", "q", "one2047", 1.0, 5, "2047 cells: the 11-bit rank, other | next << 16 and the partner table at their limits",
+       B=2, seed=35)
+  _add("q8-2047cells-rank", "q", "one2047", 0.5, -1, "2047 cells drawn by rank (by_rank[] and list indices up to 2046)", B=2, seed=36)
+  _add("all-2047cells", "q", "one2047", 1.0, -1, "k_convect_all with all eight cells per lane in use", B=2, seed=37)
+
+  # d. room shapes
+  for _plan_name, _what in (("sizes", "rooms of 600, 64, 65, 1, 2 and 3 cells"),
+                            ("shapes", "an L, a corridor, closets of the corridor's zone"),
+                            ("quirks", "a zone of two rooms, a one-cell zone, an unzoned corridor")):
+    for _tag, _p, _d in SETTINGS:
+      _add(f"{_plan_name}-{_tag}", "shapes", _plan_name, _p, _d, _what, seed=40 + len(cases))
+
+  # e. layouts
+  for _name, _spec, _orient, _env, _pin in LAYOUTS:
+    _add(f"{_name}-d5", "layout", _spec, 1.0, 5, f"ConvCell.sidx of {_name}", B=2, orientation=_orient, env=_env, pin=_pin,
+         seed=70 + len(cases))
+    _add(f"{_name}-d20", "layout", _spec, 0.7, 20, f"the wide window on {_name}", B=2, orientation=_orient, env=_env, pin=_pin,
+         seed=70 + len(cases))
+  _add("pair-d1000", "layout", ((2, 5), (30, 12)), 0.5, -1, "the by-rank branch with the handle transposed (W0 = H)", B=2,
+       orientation="columns", env=hc.PAIR_ENV, pin=(hc.REG_PAIR, 1, 2), seed=90)
+  _add("lds-columns-all", "layout", "R9", 1.0, -1, "k_convect_all with the handle transposed", B=2, orientation="columns",
+       pin=(hc.LDS, 0, 1), seed=91)
+
+  # f. call number and first_building
+  _add("calls3-d5", "calls", TINY, 0.5, 5, "calls 0, 1, 2 of the table path", calls=3, seed=101)
+  _add("calls3-d20", "calls", TINY, 0.7, 20, "calls 0, 1, 2 of a wide window", calls=3, seed=102)
+  _add("calls3-all", "calls", TINY, 1.0, -1, "calls 0, 1, 2 of the whole-room shuffle", calls=3, seed=103)
+  _add("first-max-d5", "calls", TINY, 1.0, 5, "first_building + B = 2^32 exactly", B=5, first_building=2 ** 32 - 5, seed=104)
+  _add("first-max-all", "calls", TINY, 1.0, -1, "first_building + B = 2^32 exactly (Philox counter)", B=5,
+       first_building=2 ** 32 - 5, seed=105)
+  return cases
+
+
+def __getattr__(name):
+  if name == "CASES":
+    return _cases()
+  raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
 
 # refusals (tests/test_convection_cases_gpu.py): a 2048-cell room at attach; a forced Q too small for the largest room at launch
 REFUSED_ROOM = "one2048"

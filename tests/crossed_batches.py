@@ -10,7 +10,7 @@ the CPU oracle, which knows nothing about batches, clock tables or offsets.
 A twin takes every input of a step from the public methods of its own host models at its own time stamp (the calls
 `BatchedEnvironment.make_step_in` makes for a plain environment: `host_inputs.step_inputs`), its physics from
 `oracle.OracleBuilding` on a plan with its own materials and an `OracleParams` of its own row, its device occupants from
-`DeviceOccupancyOracle`, the dollars reward from `tests/test_reward_function_cpu.restate` and its observation row from the
+`DeviceOccupancyOracle`, the dollars reward from `tests/reward_cases.restate` and its observation row from the
 reference's chain (native value -> float32 -> (x - mean) / sigma in float64 -> float32; `oracle/hist_oracle.py` where a
 reducer is configured).  It never reads a `CalendarTimeline` row, a `ClockView` offset or a tensor of the environment.
 
@@ -33,10 +33,10 @@ from oracle.occupancy_oracle import DeviceOccupancyOracle
 from sbsim_amd import host_inputs
 from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
 from tests import calendar_cases as cc
-from tests.test_building_materials_cpu import substituted
-from tests.test_building_params_gpu import _c_row as c_row, _random_params as random_params
-from tests.test_reward_function_cpu import restate
-from tests.test_state_snapshot import _copy_twin
+from tests.materials_cases import substituted
+from tests.params_cases import c_row, random_params
+from tests.reward_cases import restate
+from tests.twins import copy_twin, native_value, oracle_plan_of
 
 UTC = dt.timezone.utc
 DT = dt.timedelta(seconds=300)
@@ -159,12 +159,6 @@ def covered_pairs() -> set:
 
 
 # ---------------------------------------------------------------- the observation row, restated
-def native_action(lo_hi: Tuple[float, float], a) -> np.float32:
-  """bounded_action_normalizer.py:73-98, then the proto's float field."""
-  lo, hi = lo_hi
-  return np.float32((float(a) + 1.0) / 2.0 * (hi - lo) + lo)
-
-
 _TEMPERATURE_FIELDS = ("zone_air_temperature_sensor", "supply_water_temperature_sensor", "outside_air_temperature_sensor")
 
 
@@ -248,8 +242,7 @@ class Twin:
                models: host_inputs.StepModels, episode_steps: int, discount: float, reward_function, layout: ObsLayout,
                action_names: Sequence[str], action_zones: Sequence[int], action_ranges, init_grid: np.ndarray,
                initial_temp: float, occupants: Optional[DeviceOccupancyOracle]):
-    self.oplan = orc.OraclePlan(plan.conductivity, plan.density, plan.heat_capacity, plan.exterior_space,
-                                plan.zone_cell_lists(), plan.diffusers, plan.cv_size_cm, plan.floor_height_cm)
+    self.oplan = oracle_plan_of(plan)
     self.params, self.h_conv, self.start, self.models = params, float(h_conv), start, models
     self.episode_steps, self.discount, self.reward_function, self.layout = int(episode_steps), float(discount), reward_function, layout
     self.action_names, self.action_zones, self.action_ranges = tuple(action_names), tuple(action_zones), tuple(action_ranges)
@@ -329,7 +322,7 @@ class Twin:
       occupancy = np.full(self.oplan.Z, float(d["occupancy"]))
     kw, cmd = {}, np.full(self.oplan.Z, np.nan)
     for col, name in enumerate(self.action_names):
-      v = native_action(self.action_ranges[col], action_row[col])
+      v = native_value(action_row[col], *self.action_ranges[col])
       if name == "supply_water_setpoint":
         blr = v
       elif name == "supply_air_heating_temperature_setpoint":
@@ -394,7 +387,7 @@ class Twin:
     """fork / restore: the other building's state into this slot -- the thermostats' previous update among it, which is
     an instant of the other building's calendar; the slot's configuration (parameters, materials, calendar, start, random
     stream) stays."""
-    _copy_twin(self.ob, other.ob)
+    copy_twin(self.ob, other.ob)
     self.ob.reset_temps, self.first_episode = None, False
     self.pos = other.pos
     self.prev_update, self.prev_schedule = other.prev_update, other.prev_schedule   # state: the other building's

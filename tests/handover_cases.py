@@ -29,6 +29,7 @@ import numpy as np
 
 from tests import irregular_plans as ip
 from tests import threshold_cases as tc
+from tests.twins import oracle_twin, step_kwargs
 
 LDS, REG, REG_PAIR, ROLL, TWO, BAND, STREAM, JACOBI = 0, 1, 2, 3, 4, 5, 6, 7   # sb_sweep_kernel (include/sbsim_amd.h)
 SWITCH = "SBSIM_DEBUG_CUS"
@@ -126,7 +127,7 @@ class _Env:
 
 
 def case_env(case: Case) -> Dict[str, str]:
-  """The case's switches, with what tests/test_gpu_parity.py's _check_plan_against_oracle sets for its path."""
+  """The case's switches, with what tests/parity.py's check_plan_against_oracle sets for its path."""
   env = dict(case.env)
   if case.orientation == "generic":
     env["SBSIM_FORCE_GENERIC_SWEEP"] = "1"
@@ -170,12 +171,12 @@ def oracle_rollout(case: Case, buildings: Optional[List[int]] = None, B: Optiona
   fp, cfg = floor_plan(case), config(case)
   init, acts, _ = case_batch(case, B)
   bs = list(range(init.shape[0])) if buildings is None else list(buildings)
-  twins = [tc.oracle_twin(fp, cfg, init[b]) for b in bs]
+  twins = [oracle_twin(fp, cfg, init[b]) for b in bs]
   n = np.zeros((case.T, len(bs)), dtype=np.int64)
   conv = np.zeros((case.T, len(bs)), dtype=np.int64)
   for t in range(case.T):
     for k, b in enumerate(bs):
-      o = twins[k].step(**tc.oracle_step_kwargs(g, t, cfg, acts[t, b]))
+      o = twins[k].step(**step_kwargs(g, tc.TT0 + t, t, cfg, acts[t, b]))
       n[t, k], conv[t, k] = o["n_sweeps"], o["converged"]
   return n, conv
 

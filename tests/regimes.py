@@ -37,6 +37,8 @@ import numpy as np
 from sbsim_amd.floorplan import FloorPlan, Material, Materials
 from tests import handover_cases as hc
 from tests import threshold_cases as tc
+from tests.materials_cases import substituted
+from tests.twins import oracle_twin, step_kwargs
 
 B, T = 5, 6
 GOLDEN = "regimes.npz"
@@ -213,7 +215,7 @@ def plan(c: KernelCase, regime: Regime) -> FloorPlan:
 
 
 def case_env(c: KernelCase) -> Dict[str, str]:
-  """The case's switches with what _check_plan_against_oracle sets for the case's own path and orientation."""
+  """The case's switches with what tests/parity.py's check_plan_against_oracle sets for the case's own path and orientation."""
   fp = sb1_plan(c)
   env = dict(c.env)
   if c.orientation == "generic":
@@ -265,20 +267,13 @@ def plan_info_and_digest(c: KernelCase, regime: Regime, n_buildings: int = B) ->
 
 # ---------------------------------------------------------------- the batches and their oracle twins
 def batch(n_cells: int, regime: Regime, n_buildings: int = B, n_steps: int = T) -> Tuple[np.ndarray, np.ndarray]:
-  """(initial grids [B, n_cells], actions [T, B, 2]): _check_plan_against_oracle's own draw (a rough grid around an offset per
+  """(initial grids [B, n_cells], actions [T, B, 2]): check_plan_against_oracle's own draw (a rough grid around an offset per
   building, clipped to 285 .. 305 K) with the regime's seed and widths."""
   rs = np.random.RandomState(regime.seed)
   init = np.clip(294.0 + regime.spread * rs.randn(n_buildings, 1) + regime.noise * rs.randn(n_buildings, n_cells),
                  285.0, 305.0)
   acts = rs.uniform(-1, 1, size=(n_steps, n_buildings, 2)).astype(np.float32)
   return init, acts
-
-
-def step_kwargs(g, t: int, cfg, regime: Regime, a) -> dict:
-  """OracleBuilding.step's arguments at step t: tests/threshold_cases.py's rows with the regime's h_conv and clock."""
-  kw = tc.oracle_step_kwargs(g, t, cfg, a)
-  kw.update(now_ts=regime.time_step_sec * t, h_conv=regime.h_conv)
-  return kw
 
 
 _ROLLOUTS: Dict[Tuple[object, str], list] = {}
@@ -294,8 +289,9 @@ def oracle_rollout(c: KernelCase, regime: Regime) -> list:
     fp = plan(c, regime)
     cfg = case_config(c, regime)
     init, acts = batch(fp.shape[0] * fp.shape[1], regime)
-    twins = [tc.oracle_twin(fp, cfg, init[b]) for b in range(B)]
-    _ROLLOUTS[key] = [[twins[b].step(**step_kwargs(g, t, cfg, regime, acts[t, b]), trace=True) for b in range(B)]
+    twins = [oracle_twin(fp, cfg, init[b]) for b in range(B)]
+    _ROLLOUTS[key] = [[twins[b].step(**step_kwargs(g, tc.TT0 + t, t, cfg, acts[t, b], h_conv=regime.h_conv,
+                                                              step_sec=regime.time_step_sec), trace=True) for b in range(B)]
                       for t in range(T)]
   return _ROLLOUTS[key]
 
@@ -329,14 +325,7 @@ def mixed_batch():
 
 
 def mixed_twins(fp, cfg, ids, mats, init) -> list:
-  from tests.test_building_materials_cpu import substituted
-  return [tc.oracle_twin(substituted(fp, ids, mats[b]), cfg, init[b]) for b in range(len(mats))]
-
-
-def mixed_step_kwargs(g, t: int, cfg, h_conv: float, a) -> dict:
-  kw = tc.oracle_step_kwargs(g, t, cfg, a)
-  kw.update(h_conv=float(h_conv))
-  return kw
+  return [oracle_twin(substituted(fp, ids, mats[b]), cfg, init[b]) for b in range(len(mats))]
 
 
 def golden_inputs(regime: Regime, shape: Tuple[int, int]) -> np.ndarray:

@@ -7,6 +7,7 @@ import re
 import pytest
 
 from sbsim_amd import _ffi, build
+from tests.twins import plan_info
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -47,18 +48,6 @@ def test_struct_layouts_match_header():
                    C.sizeof(_ffi.StepIn), C.sizeof(_ffi.LaunchInfo)]
 
 
-def _plan_info(fp, n_obs=46, n_buildings=1024):
-  import numpy as np
-  cp = fp.compile(300.0, 12.0)
-  keep = [np.ascontiguousarray(x) for x in (cp.cell_class, cp.class_coef, cp.class_zone, cp.zone_off, cp.zone_cells)]
-  desc = _ffi.PlanDesc(cp.H, cp.W, cp.Z, cp.n_classes, keep[0].ctypes.data_as(C.POINTER(C.c_uint8)),
-                       keep[1].ctypes.data_as(_ffi._dp), keep[2].ctypes.data_as(_ffi._ip),
-                       keep[3].ctypes.data_as(_ffi._ip), keep[4].ctypes.data_as(_ffi._ip))
-  info = _ffi.LaunchInfo()
-  rc = _ffi.load().sb_plan_info(C.byref(desc), n_obs, n_buildings, C.byref(info))
-  return rc, {f[0]: getattr(info, f[0]) for f in _ffi.LaunchInfo._fields_}
-
-
 def test_plan_info_picks_the_step_kernel_without_a_gpu():
   """Host-only launch planning (sb_plan_info): R9 (68x98, 66x96 inside the exterior ring) runs
   on the register path either way -- lanes = rows: one wavefront owns rows 0..63 and the two
@@ -68,10 +57,10 @@ def test_plan_info_picks_the_step_kernel_without_a_gpu():
   tail row; a small plan uses one wavefront per building."""
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
   r9 = FloorPlan.from_file_input(rectangular_floor_plan((3, 3), (20, 30)), Materials.sb1(), 10.0, 300.0)
-  rc, rows = _plan_info(r9)
+  rc, rows = plan_info(r9)
   assert rc == 0 and rows["path"] == 1 and rows["waves_per_building"] == 1 and rows["kernel"] == 3   # k_sweep_roll
   assert rows["waves_per_workgroup"] == 4 and rows["workgroups"] == 256 and rows["lds_bytes_per_workgroup"] <= 160 * 1024
-  rc, cols = _plan_info(r9.transposed())
+  rc, cols = plan_info(r9.transposed())
   assert rc == 0 and cols["path"] == 1 and cols["waves_per_building"] == 1 and cols["kernel"] == 4   # k_sweep_two
   # step_two.hip: 66 columns -> 76 slots; a rectangular plan's cells are two-coefficient cells, so the rows are
   # shifted by one (a pad row above row 0): 96 rows -> 49 lanes; most of A streams from L2: four buildings per CU
@@ -79,27 +68,27 @@ def test_plan_info_picks_the_step_kernel_without_a_gpu():
   assert 4 * ((cols["lds_bytes_per_workgroup"] + 1279) // 1280 * 1280) <= 160 * 1024
   assert cols["algorithmic_bytes_per_env_step"] == 53764
   sb1 = FloorPlan.from_file_input(rectangular_floor_plan((14, 9), (8, 7)), Materials.sb1(), 10.0, 300.0)
-  rc, big = _plan_info(sb1)
+  rc, big = plan_info(sb1)
   assert rc == 0 and big["path"] == 1 and big["waves_per_building"] == 1 and big["kernel"] == 4
   assert big["sweep_steps"] == 76 + 64 - 1 + 8         # 129 x 75 inside the ring: rows -1 .. 126 on 64 lanes + two tail rows
   assert 4 * ((big["lds_bytes_per_workgroup"] + 1279) // 1280 * 1280) <= 160 * 1024
   small = FloorPlan.from_file_input(rectangular_floor_plan((1, 2), (6, 8)), Materials.sb1(), 10.0, 300.0)
-  rc, one = _plan_info(small)
+  rc, one = plan_info(small)
   assert rc == 0 and one["path"] == 1 and one["waves_per_building"] == 1 and one["kernel"] == 1
   # a plan of <= 64 rows whose k_sweep_reg sweep (NR + rows - 1 steps) is at least as long as k_sweep_roll's 96-step
   # period runs on k_sweep_roll without tail rows (round 4): 45 x 96 inside the ring
   wide = FloorPlan.from_file_input(rectangular_floor_plan((2, 3), (20, 30)), Materials.sb1(), 10.0, 300.0)
-  rc, wr = _plan_info(wide)
+  rc, wr = plan_info(wide)
   assert rc == 0 and wr["kernel"] == 3 and wr["waves_per_workgroup"] == 4 and wr["sweep_steps"] == 96
   # ... and plans of <= 64 columns on its 64-slot instantiation: 47 x 48 (k_sweep_reg: 66 + 46 steps per sweep)
   narrow = FloorPlan.from_file_input(rectangular_floor_plan((4, 5), (10, 8)), Materials.sb1(), 10.0, 300.0)
-  rc, nr = _plan_info(narrow, n_obs=3 * 20 + 19)
+  rc, nr = plan_info(narrow, n_obs=3 * 20 + 19)
   assert rc == 0 and nr["kernel"] == 3 and nr["waves_per_workgroup"] == 4 and nr["sweep_steps"] == 64
   assert nr["lds_bytes_per_workgroup"] <= 160 * 1024   # four buildings per workgroup, one workgroup per CU
   # 65..80 columns: the 80-slot instantiation (72 of its A slots in LDS, like the 96-slot one); 65 x 78: + one tail row
   for shape, steps in (((20, 24), 80), ((30, 24), 84)):
     mid = FloorPlan.from_file_input(rectangular_floor_plan((2, 3), shape), Materials.sb1(), 10.0, 300.0)
-    rc, mr = _plan_info(mid)
+    rc, mr = plan_info(mid)
     assert rc == 0 and mr["kernel"] == 3 and mr["sweep_steps"] == steps and mr["lds_bytes_per_workgroup"] <= 160 * 1024
 
 
@@ -113,26 +102,26 @@ def test_plan_info_for_plans_beyond_one_cu_and_the_opt_in_kernel(monkeypatch):
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
   big = FloorPlan.from_file_input(rectangular_floor_plan((14, 9), (20, 43)), Materials.sb1(), 10.0, 300.0)
   assert big.shape == (299, 401)
-  rc, info = _plan_info(big, n_obs=397, n_buildings=4096)
+  rc, info = plan_info(big, n_obs=397, n_buildings=4096)
   assert rc == 0 and info["path"] == 2 and info["kernel"] == 6 and info["waves_per_building"] == 5
   assert info["sweep_steps"] == 64 * 4 + 400 + 63
   assert 3 * ((info["lds_bytes_per_workgroup"] + 1279) // 1280 * 1280) <= 160 * 1024
   assert info["workgroups"] == 768 and info["algorithmic_bytes_per_env_step"] == 8 * 299 * 401 + 24 * 126 + 8 + 4 * 397 + 44
   tall = FloorPlan.from_file_input(rectangular_floor_plan((1, 1), (1119, 20)), Materials.sb1(), 10.0, 300.0)   # 1,125 x 26
-  rc, t_rows = _plan_info(tall, n_obs=22)
+  rc, t_rows = plan_info(tall, n_obs=22)
   assert rc == -4 and b"1,024 rows" in _ffi.load().sb_last_error()      # SB_ERR_TOO_LARGE in this orientation ...
-  rc, t_cols = _plan_info(tall.transposed(), n_obs=22)
+  rc, t_cols = plan_info(tall.transposed(), n_obs=22)
   assert rc == 0 and t_cols["kernel"] == 6 and t_cols["waves_per_building"] == 1   # ... 24 rows x 1,123 columns in the other
   huge = FloorPlan.from_file_input(rectangular_floor_plan((1, 1), (514, 1094)), Materials.sb1(), 10.0, 300.0)  # 520 x 1,100
-  rc, _ = _plan_info(huge, n_obs=22)
+  rc, _ = plan_info(huge, n_obs=22)
   assert rc == -4 and b"seam rows" in _ffi.load().sb_last_error()        # nine wavefronts x 1,100 columns of seam rows: > 160 KiB
-  rc, _ = _plan_info(huge.transposed(), n_obs=22)
+  rc, _ = plan_info(huge.transposed(), n_obs=22)
   assert rc == -4 and b"1,024 rows" in _ffi.load().sb_last_error()
   sb2 = FloorPlan.from_file_input(rectangular_floor_plan((8, 5), (12, 14)), Materials.sb1(), 10.0, 300.0)
-  rc, two = _plan_info(sb2, n_obs=3 * 40 + 19)
+  rc, two = plan_info(sb2, n_obs=3 * 40 + 19)
   assert rc == 0 and two["kernel"] == 4
   monkeypatch.setenv("SBSIM_BAND_PATH", "1")
-  rc, band = _plan_info(sb2, n_obs=3 * 40 + 19)
+  rc, band = plan_info(sb2, n_obs=3 * 40 + 19)
   assert rc == 0 and band["kernel"] == 5 and band["waves_per_building"] == 2 and band["sweep_steps"] == 80
   assert 2 * ((band["lds_bytes_per_workgroup"] + 1279) // 1280 * 1280) <= 160 * 1024
 
@@ -144,26 +133,26 @@ def test_plan_info_for_plans_of_131_to_258_rows(monkeypatch):
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
   mk = lambda rooms, shape: FloorPlan.from_file_input(rectangular_floor_plan(rooms, shape), Materials.sb1(), 10.0, 300.0)
   p4 = mk((10, 4), (19, 20))          # 205 x 89: 203 x 87 inside the ring
-  rc, i4 = _plan_info(p4, n_obs=3 * 40 + 19, n_buildings=4096)
+  rc, i4 = plan_info(p4, n_obs=3 * 40 + 19, n_buildings=4096)
   assert rc == 0 and i4["path"] == 1 and i4["kernel"] == 5 and i4["waves_per_building"] == 4 == i4["waves_per_workgroup"]
   assert i4["sweep_steps"] == 88 and i4["workgroups"] == 256 and i4["lds_bytes_per_workgroup"] <= 160 * 1024   # 87 columns: 88 slots
-  rc, i3 = _plan_info(mk((10, 4), (18, 20)), n_obs=3 * 40 + 19)   # 193 x 87: three wavefronts + ONE tail row
+  rc, i3 = plan_info(mk((10, 4), (18, 20)), n_obs=3 * 40 + 19)   # 193 x 87: three wavefronts + ONE tail row
   assert rc == 0 and i3["kernel"] == 5 and i3["waves_per_building"] == 3 and i3["sweep_steps"] == 88 + 4
-  rc, i96 = _plan_info(mk((10, 4), (19, 22)), n_obs=3 * 40 + 19)  # 203 x 95: the widest instantiation
+  rc, i96 = plan_info(mk((10, 4), (19, 22)), n_obs=3 * 40 + 19)  # 203 x 95: the widest instantiation
   assert rc == 0 and i96["kernel"] == 5 and i96["waves_per_building"] == 4 and i96["sweep_steps"] == 96
   assert i96["lds_bytes_per_workgroup"] <= 160 * 1024
-  rc, i3b = _plan_info(mk((9, 4), (16, 17)), n_obs=3 * 36 + 19)   # 156 x 75: 76 slots
+  rc, i3b = plan_info(mk((9, 4), (16, 17)), n_obs=3 * 36 + 19)   # 156 x 75: 76 slots
   assert rc == 0 and i3b["kernel"] == 5 and i3b["waves_per_building"] == 3 and i3b["sweep_steps"] == 76
-  rc, it = _plan_info(p4.transposed(), n_obs=3 * 40 + 19)         # lanes = the file's columns: 87 rows x 203 columns
+  rc, it = plan_info(p4.transposed(), n_obs=3 * 40 + 19)         # lanes = the file's columns: 87 rows x 203 columns
   assert rc == 0 and it["kernel"] != 5
-  rc, wide = _plan_info(mk((6, 6), (24, 24)), n_obs=3 * 36 + 19)  # 153 x 153 inside the ring: too wide either way
+  rc, wide = plan_info(mk((6, 6), (24, 24)), n_obs=3 * 36 + 19)  # 153 x 153 inside the ring: too wide either way
   assert rc == 0 and wide["kernel"] != 5
-  rc, w2 = _plan_info(mk((6, 4), (17, 21)), n_obs=3 * 24 + 19, n_buildings=4096)   # 111 x 91: too wide for step_two.hip -> two wavefronts, 92 slots
+  rc, w2 = plan_info(mk((6, 4), (17, 21)), n_obs=3 * 24 + 19, n_buildings=4096)   # 111 x 91: too wide for step_two.hip -> two wavefronts, 92 slots
   assert rc == 0 and w2["kernel"] == 5 and w2["waves_per_building"] == 2 and w2["sweep_steps"] == 92 and w2["workgroups"] == 512
   monkeypatch.setenv("SBSIM_NO_BAND_PATH", "1")
-  rc, w2off = _plan_info(mk((6, 4), (17, 21)), n_obs=3 * 24 + 19)
+  rc, w2off = plan_info(mk((6, 4), (17, 21)), n_obs=3 * 24 + 19)
   assert rc == 0 and w2off["kernel"] == 2
-  rc, off = _plan_info(p4, n_obs=3 * 40 + 19)
+  rc, off = plan_info(p4, n_obs=3 * 40 + 19)
   assert rc == 0 and off["kernel"] == 0 and off["waves_per_building"] == 1
 
 
@@ -216,13 +205,13 @@ def test_plan_info_narrowest_instantiations(monkeypatch):
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
   mk = lambda rooms, shape: FloorPlan.from_file_input(rectangular_floor_plan(rooms, shape), Materials.sb1(), 10.0, 300.0)
   plan = mk((8, 5), (12, 10))
-  rc, a = _plan_info(plan, n_obs=3 * 40 + 19)
+  rc, a = plan_info(plan, n_obs=3 * 40 + 19)
   assert rc == 0 and a["kernel"] == 4 and a["lds_bytes_per_workgroup"] <= 160 * 1024
   monkeypatch.setenv("SBSIM_NO_TWO_64", "1")
-  rc, b = _plan_info(plan, n_obs=3 * 40 + 19)
+  rc, b = plan_info(plan, n_obs=3 * 40 + 19)
   monkeypatch.delenv("SBSIM_NO_TWO_64")
   assert rc == 0 and b["kernel"] == 4 and b["sweep_steps"] == a["sweep_steps"] + 12   # 76 - 64 slots
-  rc, c = _plan_info(mk((9, 4), (16, 15)), n_obs=3 * 36 + 19)
+  rc, c = plan_info(mk((9, 4), (16, 15)), n_obs=3 * 36 + 19)
   assert rc == 0 and c["kernel"] == 5 and c["waves_per_building"] == 3 and c["sweep_steps"] == 68
-  rc, d = _plan_info(mk((12, 3), (20, 22)), n_obs=3 * 36 + 19)
+  rc, d = plan_info(mk((12, 3), (20, 22)), n_obs=3 * 36 + 19)
   assert rc == 0 and d["kernel"] == 5 and d["waves_per_building"] == 4 and d["sweep_steps"] in (72, 76)   # 255 rows: + a tail row's 4 steps when it has one

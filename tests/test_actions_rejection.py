@@ -12,6 +12,8 @@ import pytest
 
 from oracle import oracle as orc
 from tests.golden_util import load, oracle_params, oracle_plan
+from tests.twins import (T_TOL, native_value, oracle_params_of, oracle_plan_of, plan_from_npz, rates_match, step_in,
+                         step_kwargs)
 
 
 def _ulp32(a, b):
@@ -60,7 +62,7 @@ def test_hip_action_set_and_rejections_against_reference_golden(path, monkeypatc
     pytest.skip("no GPU")
   from sbsim_amd import _ffi
   from sbsim_amd.environment import ACTION_REJECTION_REWARD, BatchedSimulator, SimConfig, observation_field_names
-  from tests.test_gpu_parity import T_TOL, _plan, _step_in
+  from tests.parity import step_buffers
   if path == "lds":
     monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
   g = load("h2_sb1_r9_actions.npz")
@@ -69,12 +71,10 @@ def test_hip_action_set_and_rejections_against_reference_golden(path, monkeypatc
   cfg.action_zones = tuple(int(z) for z in g["action_zone"])
   cfg.action_ranges = tuple((float(lo), float(hi)) for lo, hi in g["action_ranges"])
   B = 6
-  sim = BatchedSimulator(_plan(load("plan_r9_sb1.npz")), cfg, B, float(g["h_conv"]))
+  sim = BatchedSimulator(plan_from_npz(load("plan_r9_sb1.npz")), cfg, B, float(g["h_conv"]))
   assert sim.n_actions == 4 and sim.launch_info["path"] == (1 if path == "reg" else 0)
   sim.reset()
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  obs, rew, info = step_buffers(sim)
   col_aux = observation_field_names([str(z) for z in g["zone_names"]], True)[4]
   T = len(g["n_sweeps"])
   # buildings 0..3 follow the golden (its rejections included); 4 and 5 are never rejected and
@@ -83,7 +83,7 @@ def test_hip_action_set_and_rejections_against_reference_golden(path, monkeypatc
     act = torch.tensor(np.tile(g["actions_norm"][t], (B, 1)), dtype=torch.float32, device="cuda")
     rej = torch.zeros((B,), dtype=torch.uint8, device="cuda")
     rej[:4] = int(g["rejected"][t])
-    si = _step_in(g, t)
+    si = step_in(g, t)
     si.reject_dev = rej.data_ptr()
     sim.step(act, si, obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
@@ -91,7 +91,7 @@ def test_hip_action_set_and_rejections_against_reference_golden(path, monkeypatc
     assert (i[:4, 4] == g["n_sweeps"][t]).all(), (t, i[:, 4], g["n_sweeps"][t])
     assert np.abs(zt[:4] - g["zone_temp_post"][t]).max() < T_TOL, t
     assert np.array_equal(sim.modes().cpu().numpy()[:4], np.tile(g["mode"][t], (4, 1))), t
-    assert np.allclose(i[:4, :4], g["rates"][t].astype(np.float64), rtol=2e-6, atol=1e-6), t
+    assert rates_match(i[:4, :4], g["rates"][t].astype(np.float64)), t
     r = rew.cpu().numpy().astype(np.float64)
     if g["action_accepted"][t]:
       assert np.abs(r[:4] - float(g["reward"][t])).max() < 1e-6, t
@@ -121,10 +121,9 @@ def test_hip_simulator_building_replays_the_reference_rollout():
     pytest.skip("no GPU")
   import datetime as dt
   from sbsim_amd import building_adapter as ba
-  from tests.test_gpu_parity import _plan
   g = load("h2_sb1_r9_random.npz")
   start = dt.datetime.fromisoformat(str(g["start_timestamp"]))
-  b = ba.HipSimulatorBuilding(_plan(load("plan_r9_sb1.npz")), start_timestamp=start, holiday_calendar=None)
+  b = ba.HipSimulatorBuilding(plan_from_npz(load("plan_r9_sb1.npz")), start_timestamp=start, holiday_calendar=None)
   assert b.time_step_sec == 300.0 and b.current_timestamp == start and len(b.zones) == 9 and len(b.devices) == 11
   req = b.observation_request_for_all_fields()
   names = [f"{r.device_id}/{r.measurement_name}" for r in req.single_observation_requests]
@@ -153,7 +152,7 @@ def test_hip_simulator_building_replays_the_reference_rollout():
     ah, bl = ri.air_handler_reward_infos["air_handler_id"], ri.boiler_reward_infos["boiler_id"]
     rates = [ah.blower_electrical_energy_rate, ah.air_conditioning_electrical_energy_rate,
              bl.natural_gas_heating_energy_rate, bl.pump_electrical_energy_rate]
-    assert np.allclose(rates, g["rates"][t].astype(np.float64), rtol=2e-6, atol=1e-6), t
+    assert rates_match(rates, g["rates"][t].astype(np.float64)), t
     assert abs(b.last_reward - float(g["reward"][t])) < 1e-6, t
     assert b.num_occupants == int(g["num_occupants"][t]), t
   # an unknown device, a field that is not settable, a damper command the handle does not drive
@@ -180,13 +179,12 @@ def test_hip_simulator_building_rejections_and_damper_commands():
   import datetime as dt
   from sbsim_amd import building_adapter as ba
   from sbsim_amd.environment import SimConfig
-  from tests.test_gpu_parity import T_TOL, _plan
   g = load("h2_sb1_r9_actions.npz")
   cfg = SimConfig.sb1()
   cfg.action_names = tuple(str(n) for n in g["action_names"])
   cfg.action_zones = tuple(int(z) for z in g["action_zone"])
   cfg.action_ranges = tuple((float(lo), float(hi)) for lo, hi in g["action_ranges"])
-  b = ba.HipSimulatorBuilding(_plan(load("plan_r9_sb1.npz")), config=cfg, holiday_calendar=None,
+  b = ba.HipSimulatorBuilding(plan_from_npz(load("plan_r9_sb1.npz")), config=cfg, holiday_calendar=None,
                               start_timestamp=dt.datetime.fromisoformat(str(g["start_timestamp"])))
   vav = b.devices[2 + int(g["action_zone"][3])].device_id
   for t in range(len(g["n_sweeps"])):
@@ -269,7 +267,7 @@ def test_action_vector_as_wide_as_the_building_has_setpoints():
   from sbsim_amd import _ffi
   from sbsim_amd.environment import ACTION_REJECTION_REWARD, BatchedSimulator, SimConfig
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
-  from tests.test_gpu_parity import T_TOL, _step_in
+  from tests.parity import step_buffers
   plan = FloorPlan.from_file_input(rectangular_floor_plan((14, 9), (8, 7)), Materials.sb1(), 10.0, 300.0)
   Z = len(plan.zone_cell_lists())
   assert Z == 126
@@ -287,29 +285,15 @@ def test_action_vector_as_wide_as_the_building_has_setpoints():
   H, W = plan.shape
   init = np.clip(294.0 + rs.randn(B, 1) + np.zeros((B, H * W)), 285.0, 305.0)
   sim.reset(temps=torch.tensor(init, dtype=torch.float64, device="cuda"))
-  oplan = orc.OraclePlan(plan.conductivity, plan.density, plan.heat_capacity, plan.exterior_space,
-                         plan.zone_cell_lists(), plan.diffusers, plan.cv_size_cm, plan.floor_height_cm)
-  c = cfg
-  oprm = orc.OracleParams(
-      dt=c.time_step_sec, conv_threshold=c.convergence_threshold, iter_limit=c.iteration_limit,
-      vav_max_air_flow=c.vav_max_air_flow_rate, vav_max_water_flow=c.vav_reheat_max_water_flow_rate,
-      ahu_recirc=c.ahu_recirculation, ahu_heat_sp=c.ahu_heating_air_temp_setpoint,
-      ahu_cool_sp=c.ahu_cooling_air_temp_setpoint, ahu_dp=c.ahu_fan_differential_pressure,
-      ahu_eff=c.ahu_fan_efficiency, blr_setpoint=c.boiler_reheat_water_setpoint,
-      blr_head=c.boiler_water_pump_differential_head, blr_pump_eff=c.boiler_water_pump_efficiency,
-      comfort_lo=c.comfort_temp_window[0], comfort_hi=c.comfort_temp_window[1],
-      eco_lo=c.eco_temp_window[0], eco_hi=c.eco_temp_window[1],
-      blr_heating_rate=c.boiler_heating_rate, blr_cooling_rate=c.boiler_cooling_rate, ahu_has_weather=1)
+  oplan, oprm = oracle_plan_of(plan), oracle_params_of(cfg)
   twins = [orc.OracleBuilding(oplan, oprm, 0.0, reset_temps=init[b]) for b in range(B)]
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  obs, rew, info = step_buffers(sim)
   n_rejected = 0
   for t in range(T):
     norm = rs.uniform(-1, 1, size=(B, 3 + Z)).astype(np.float32)
     native = np.empty((B, 3 + Z), dtype=np.float32)
-    for i, (lo, hi) in enumerate(cfg.action_ranges):   # bounded_action_normalizer.py:93-98, then the proto's float
-      native[:, i] = ((norm[:, i].astype(np.float64) + 1.0) / 2.0 * (hi - lo) + lo).astype(np.float32)
+    for i, (lo, hi) in enumerate(cfg.action_ranges):
+      native[:, i] = [native_value(a, lo, hi) for a in norm[:, i]]
     keep = rs.rand(B, 3 + Z) < 0.3                      # the request does not mention these fields
     keep[:, :2] = False                                 # (the twins' interface always carries the two SB1 setpoints)
     if t % 2 == 0:                                      # every other step in native units with left-out columns
@@ -317,7 +301,7 @@ def test_action_vector_as_wide_as_the_building_has_setpoints():
       act[keep] = _ffi.SB_ACTION_KEEP
     else:
       act, keep = norm, np.zeros_like(keep)
-    si = _step_in(g, t + 100)
+    si = step_in(g, t + 100)
     si.actions_native = int(t % 2 == 0)
     sim.step(torch.tensor(act, device="cuda"), si, obs, rew, info)
     i_ = info.cpu().numpy().astype(np.float64)
@@ -328,14 +312,8 @@ def test_action_vector_as_wide_as_the_building_has_setpoints():
       for col in range(3, 3 + Z):
         if not keep[b, col]:
           cmd[cfg.action_zones[col]] = float(native[b, col])
-      tt = t + 100
-      o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
-          t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]), e_carbon=float(g["e_carbon"][tt]),
-          g_price=float(g["g_price"][tt]), g_carbon=float(g["g_carbon"][tt]),
-          action=[native[b, 0], native[b, 1]], cool_sp=None if keep[b, 2] else float(native[b, 2]), damper_cmd=cmd)
+      o = twins[b].step(**step_kwargs(g, t + 100, t, cfg, norm[b, :2]),   # (the first two columns: native[b, :2])
+                        cool_sp=None if keep[b, 2] else float(native[b, 2]), damper_cmd=cmd)
       assert i_[b, 4] == o["n_sweeps"], (t, b, i_[b, 4], o["n_sweeps"])
       assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
       assert np.allclose(dm[b], o["q_zone"], rtol=1e-12, atol=1e-9), (t, b)     # every zone's VAV power: every damper landed

@@ -170,8 +170,8 @@ def test_batched_environment_meets_the_time_step_contract():
     pytest.skip("no GPU")
   from sbsim_amd.environment import BatchedEnvironment
   from tests.golden_util import load
-  from tests.test_gpu_parity import _plan
-  env = BatchedEnvironment(_plan(load("plan_r9_sb1.npz")), 8, num_days_in_episode=6 * 300 / 86400.0, holiday_calendar=None)
+  from tests.twins import plan_from_npz
+  env = BatchedEnvironment(plan_from_npz(load("plan_r9_sb1.npz")), 8, num_days_in_episode=6 * 300 / 86400.0, holiday_calendar=None)
   out = adapters.validate_batched_environment(env, episodes=3)
   assert out["episodes"] == 3 and out["steps"] == 3 * 7 + 2
   env.close()

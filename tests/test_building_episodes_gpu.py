@@ -20,7 +20,8 @@ from sbsim_amd.environment import (STEP_FIRST, STEP_LAST, STEP_MID, BatchedEnvir
 from sbsim_amd.host_inputs import BuildingMaterials, BuildingParams  # noqa: E402
 from tests import handover_cases as hc  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_gpu_parity import T_TOL, _plan  # noqa: E402
+from tests.parity import need_gpu  # noqa: E402
+from tests.twins import RATE_ATOL, RATE_RTOL, T_TOL, plan_from_npz  # noqa: E402
 
 B, N = 7, 12
 DT = dt.timedelta(seconds=300)
@@ -34,13 +35,8 @@ START_SWITCH = dt.datetime(2023, 7, 6, 12, 30, 0)
 REG, LDS, REG_PAIR, ROLL, BAND, STREAM, JACOBI = 1, 0, 2, 3, 5, 6, 7   # sb_sweep_kernel
 
 
-def _need_gpu():
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
-
-
 def _small():
-  return _plan(load("plan_small_test.npz"))
+  return plan_from_npz(load("plan_small_test.npz"))
 
 
 def _params():
@@ -64,7 +60,7 @@ LAYOUTS = {
     "small-stream": (_small, (("SBSIM_FORCE_STREAM_PATH", "1"),), {}, STREAM, None, False),
     "small-jacobi": (_small, (), dict(solver="jacobi_fp32"), JACOBI, 0, True),
     "small-jacobi-global": (_small, (("SBSIM_FORCE_JACOBI_GLOBAL", "1"),), dict(solver="jacobi_fp32"), JACOBI, 2, True),
-    "r9-roll": (lambda: _plan(load("plan_r9_sb1.npz")), (), {}, ROLL, None, True),
+    "r9-roll": (lambda: plan_from_npz(load("plan_r9_sb1.npz")), (), {}, ROLL, None, True),
     "pair-68x65": (lambda: hc.floor_plan(hc.CASES["pair-68x65"]),
                    hc.CASES["pair-68x65"].env + (("SBSIM_ORIENTATION", "columns"),), {}, REG_PAIR, None, True),
     "band3-193x87": (lambda: hc.floor_plan(hc.CASES["band3-193x87"]), hc.CASES["band3-193x87"].env, {}, BAND, None, True),
@@ -107,7 +103,7 @@ def _assert_rows(got, want, rows, bitwise, what):
     elif k in ("temps", "zone_temps"):
       assert torch.allclose(g, w, rtol=0.0, atol=T_TOL), f"{what}: {k} differs by {(g - w).abs().max().item()}"
     else:
-      assert torch.allclose(g.double(), w.double(), rtol=2e-6, atol=1e-6), f"{what}: {k} differs"
+      assert torch.allclose(g.double(), w.double(), rtol=RATE_RTOL, atol=RATE_ATOL), f"{what}: {k} differs"
 
 
 def _actions(n, seed=3):
@@ -127,7 +123,7 @@ def test_partial_reset_is_a_global_reset_for_the_masked_and_nothing_for_the_rest
   rule the boiler's action age rewinds by the building's own 11 steps against C's 6, so the duration its reset
   observation stamps is -10 dt against -5 dt (asserted).  D is the building with A's unmasked buildings' history, and
   the comparison with it is bitwise in every field."""
-  _need_gpu()
+  need_gpu()
   bitwise = LAYOUTS[layout][5]
   a, c, d = _make(layout, monkeypatch, 3, start_offsets=[OFFSETS] * 3, building_params=[_params()] * 3,
                   per_building_episodes=[True, False, False])
@@ -186,7 +182,7 @@ def test_per_building_lengths_against_plain_twins(monkeypatch):
   Then reset(): by then the batch position (30) lies far beyond the calendar's max(offsets) + N + 2 rows, which a
   restored calendar must not be asked about.  Every building starts over like its twin after the twin's reset(), at the
   reset and for two steps (the shortest episode's MID steps), in every getter."""
-  _need_gpu()
+  need_gpu()
   steps = np.array([2, 3, 5, 2, 7, 12, 3])
   offs = np.array([0, 3, 6, 9, 12, 1, 4])
   a, = _make("small", monkeypatch, 1, start=START_SWITCH, start_offsets=[offs], episode_steps=[steps],
@@ -258,7 +254,7 @@ def _state(sim, obs):
 def test_masked_entries_leave_the_other_buildings_alone(layout, monkeypatch):
   """sb_observe_buildings and sb_reset_buildings: every state getter's output and the observation buffer before and
   after, the unmasked rows bitwise; an all-zero mask changes nothing at all."""
-  _need_gpu()
+  need_gpu()
   a, = _make(layout, monkeypatch, 1, start_offsets=[OFFSETS], per_building_episodes=[True])
   acts = _actions(4, seed=5)
   ts = a.reset()
@@ -292,7 +288,7 @@ def test_masked_entries_leave_the_other_buildings_alone(layout, monkeypatch):
 def test_feature_off_and_on_without_an_early_end_agree(monkeypatch):
   """The default environment and one with per_building_episodes=True (no start_offsets: the all-zero calendar) agree
   bitwise on everything 8 steps return."""
-  _need_gpu()
+  need_gpu()
   off, on = _make("small", monkeypatch, 2, building_params=[_params()] * 2, per_building_episodes=[False, True])
   assert off._cursor is None and off.final_observation is None and not off.per_building_episodes
   assert on.episode_steps.tolist() == [N] * B
@@ -313,7 +309,7 @@ def test_feature_off_and_on_without_an_early_end_agree(monkeypatch):
 
 
 def test_python_refusals(monkeypatch):
-  _need_gpu()
+  need_gpu()
   plan = _small()
   occ = host_inputs.BatchedRandomizedArrivalDepartureOccupancy(3, 7, 9, 16, 18, 300, seed=5, holiday_calendar=None)
   with pytest.raises(ValueError, match="advances every building's occupants"):
@@ -357,7 +353,7 @@ def test_python_refusals(monkeypatch):
 def test_c_refusals_leave_the_handle_unchanged(monkeypatch):
   """Every refusal of the two entries and of sb_clock_seek is SB_ERR_INVALID, decided on the host; afterwards the handle
   steps like an untouched twin."""
-  _need_gpu()
+  need_gpu()
   lib = _ffi.load()
   reset_b, observe_b = _ffi.episodes_entry("sb_reset_buildings"), _ffi.episodes_entry("sb_observe_buildings")
   err = lambda: lib.sb_last_error().decode()
@@ -447,7 +443,7 @@ def test_c_refusals_leave_the_handle_unchanged(monkeypatch):
 
 
 def test_gym_view(monkeypatch):
-  _need_gpu()
+  need_gpu()
   steps = np.array([2, 3, 5, 2, 7, 12, 3])
   a, plain = _make("small", monkeypatch, 2, episode_steps=[steps, None])
   va, vp = GymVectorEnv(a), GymVectorEnv(plain)

@@ -17,9 +17,9 @@ from sbsim_amd.environment import BatchedEnvironment, BatchedSimulator, MixedBat
 from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan, structural_class_coef  # noqa: E402
 from sbsim_amd.host_inputs import BuildingMaterials  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_building_materials_cpu import random_sets, substituted, the_plan  # noqa: E402
-from tests.test_gpu_parity import T_TOL, _need_gpu, _step_in  # noqa: E402
-from tests.threshold_cases import native_action, oracle_twin  # noqa: E402
+from tests.materials_cases import random_sets, substituted, the_plan  # noqa: E402
+from tests.parity import need_gpu, step_buffers  # noqa: E402
+from tests.twins import T_TOL, assert_step_matches, oracle_twin, step_in, step_kwargs  # noqa: E402
 
 SB1 = SimConfig.sb1()
 MANY = "roll66-48sets"   # irregular plan with more than 32 structural classes: the ts = 128 sweep body
@@ -27,7 +27,7 @@ LDS = 0                  # sb_sweep_kernel
 
 
 def _table(plan, B, seed):
-  """B random rows around the plan's own materials (tests/test_building_materials_cpu.py, random_sets)."""
+  """B random rows around the plan's own materials (tests/materials_cases.py, random_sets)."""
   ids, table = plan.material_slots()
   sets, hs = random_sets(table, B, seed)
   bm = BuildingMaterials(conductivity=sets[:, :, 0], heat_capacity=sets[:, :, 1], density=sets[:, :, 2],
@@ -53,19 +53,13 @@ def _two_sets(plan, B):
                            convection_coefficient=hs)
 
 
-def _bufs(sim):
-  B = sim.B
-  return (torch.zeros((B, sim.O), dtype=torch.float32, device="cuda"), torch.zeros((B,), dtype=torch.float32, device="cuda"),
-          torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda"))
-
-
 FOURTH = "r9-fourth-material"   # the plan and its transpose meet the materials in different orders (columns: transposed)
 
 
 @pytest.mark.parametrize("name,orientation", [("plan_small_test", "auto"), ("plan_weird_test", "auto"), (MANY, "auto"),
                                               (FOURTH, "columns"), (FOURTH, "rows")])
 def test_coefficient_tap_is_bitwise_the_numpy_restatement(name, orientation):
-  _need_gpu()
+  need_gpu()
   plan = the_plan(name)
   B = 7
   ids, sets, hs, bm = _table(plan, B, seed=31)
@@ -95,7 +89,7 @@ def test_coefficient_tap_is_bitwise_the_numpy_restatement(name, orientation):
 @pytest.mark.parametrize("name,orientation", [("plan_small_test", "auto"), ("plan_weird_test", "auto"), (MANY, "auto"),
                                               ("plan_r9_test", "auto"), (FOURTH, "columns")])
 def test_every_building_against_a_default_handle_and_an_oracle_twin(name, orientation, monkeypatch):
-  _need_gpu()
+  need_gpu()
   g = load("h2_sb1_r9_random.npz")
   plan = the_plan(name)
   H, W = plan.shape
@@ -116,32 +110,23 @@ def test_every_building_against_a_default_handle_and_an_oracle_twin(name, orient
     s = BatchedSimulator(pb, SB1, 1, float(hs[b]), orientation="columns" if sim.transposed else "rows")
     assert s.launch_info["kernel"] == LDS and s.transposed == sim.transposed
     s.reset(temps=torch.tensor(init[b:b + 1], dtype=torch.float64, device="cuda"))
-    singles.append((s,) + _bufs(s))
+    singles.append((s,) + step_buffers(s))
     twins.append(oracle_twin(pb, SB1, init[b]))
-  obs, rew, info = _bufs(sim)
+  obs, rew, info = step_buffers(sim)
   for t in range(T):
     tt = 100 + t
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, tt), obs, rew, info)
+    sim.step(torch.tensor(acts[t], device="cuda"), step_in(g, tt), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     zt, grid = sim.zone_temps().cpu().numpy(), sim.temps().cpu().numpy()
     for b, (s, o1, r1, i1) in enumerate(singles):
-      s.step(torch.tensor(acts[t, b:b + 1], device="cuda"), _step_in(g, tt), o1, r1, i1)
+      s.step(torch.tensor(acts[t, b:b + 1], device="cuda"), step_in(g, tt), o1, r1, i1)
       assert i[b, 4] == float(i1[0, 4]), (t, b, i[b, 4], float(i1[0, 4]))   # sweep counts
       z1, g1 = s.zone_temps().cpu().numpy()[0], s.temps().cpu().numpy()[0]
       assert np.abs(zt[b] - z1).max() < T_TOL and np.abs(grid[b] - g1).max() < T_TOL, (t, b)
       assert np.array_equal(zt[b], z1) and np.array_equal(grid[b], g1), (t, b)
       assert torch.equal(obs[b], o1[0]) and torch.equal(rew[b], r1[0]) and torch.equal(info[b], i1[0]), (t, b)
-      o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(hs[b]),
-          t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]), e_carbon=float(g["e_carbon"][tt]),
-          g_price=float(g["g_price"][tt]), g_carbon=float(g["g_carbon"][tt]), action=native_action(SB1, acts[t, b]),
-          observe=True)
-      assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
-      assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
-      ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
-      assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b, i[b, :4], ref)
+      o = twins[b].step(**step_kwargs(g, tt, t, SB1, acts[t, b], h_conv=hs[b]))
+      assert_step_matches(i[b], zt[b], float(rew[b]), o, (t, b))
       assert abs(float(rew[b]) - o["reward"]) < 1e-6, (t, b)
   final = sim.temps().cpu().numpy()
   for b in range(B):
@@ -179,7 +164,7 @@ def _r9():
 
 @pytest.mark.parametrize("name", ["r9", "plan_small_test"])
 def test_the_plans_own_values_are_bitwise_a_default_handle_on_k_sweep_lds(name, monkeypatch):
-  _need_gpu()
+  need_gpu()
   plan = _r9() if name == "r9" else the_plan(name)
   B, T = 8, 12
   acts = _acts(T, B, 51)
@@ -199,7 +184,7 @@ def test_the_plans_own_values_are_bitwise_a_default_handle_on_k_sweep_lds(name, 
 
 
 def test_hand_over_between_buildings_reloads_the_wavefronts_table():
-  _need_gpu()
+  need_gpu()
   plan = the_plan("plan_small_test")
   # enough buildings for every wavefront of a full launch to draw a second and a third one
   cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -228,7 +213,7 @@ def test_hand_over_between_buildings_reloads_the_wavefronts_table():
 
 
 def test_a_new_table_applies_from_the_next_step():
-  _need_gpu()
+  need_gpu()
   plan = the_plan("plan_small_test")
   B = 6
   acts = _acts(8, B, 71)
@@ -260,7 +245,7 @@ def test_snapshots_and_stochastic_models_on_a_materials_handle():
   """snapshot / restore / fork, the convection shuffle, device occupancy, BuildingParams and the dollar reward see the
   LDS state layout and the k_pre / k_post hand-over only -- none of them reads a coefficient table -- so they work on a
   materials handle unchanged."""
-  _need_gpu()
+  need_gpu()
   plan = _r9()
   B = 6
   acts = _acts(10, B, 81)
@@ -290,7 +275,7 @@ def test_snapshots_and_stochastic_models_on_a_materials_handle():
 
 
 def test_refusals():
-  _need_gpu()
+  need_gpu()
   plan = the_plan("plan_small_test")
   B = 4
   own = _own(plan, B, 12.0)
@@ -357,7 +342,7 @@ def test_refusals():
 
 @pytest.mark.parametrize("rank,world", [(0, 1), (0, 2), (1, 2)])
 def test_mixed_batch_does_not_depend_on_the_sharding(rank, world):
-  _need_gpu()
+  need_gpu()
   plans = [the_plan("plan_small_test"), FloorPlan.from_file_input(rectangular_floor_plan((2, 3), (9, 10)), Materials.sb1(), 10.0, 300.0)]
   totals = [6, 5]
   _, _, _, bm0 = _table(plans[0], totals[0], seed=91)

@@ -13,49 +13,16 @@ from sbsim_amd import _ffi  # noqa: E402
 from sbsim_amd.environment import BatchedEnvironment, BatchedSimulator, MixedBatchedEnvironment, SimConfig  # noqa: E402
 from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan  # noqa: E402
 from sbsim_amd.host_inputs import BUILDING_PARAM_NAMES, BuildingParams  # noqa: E402
-from tests.golden_util import load  # noqa: E402
+from tests.golden_util import load, oracle_params, oracle_plan  # noqa: E402
+from tests.params_cases import c_row, random_params  # noqa: E402
+from tests.parity import need_gpu, step_buffers  # noqa: E402
+from tests.twins import T_TOL, oracle_rates, plan_from_npz, rates_match, step_in, step_kwargs  # noqa: E402
 
 SB1 = SimConfig.sb1()
-# temperatures move by kelvins around SB1's, everything else by a factor in [0.7, 1.3]
-_TEMPS_K = {"ahu_heating_air_temp_setpoint": 4.0, "ahu_cooling_air_temp_setpoint": 4.0,
-            "boiler_reheat_water_setpoint": 10.0}
-
-
-def _need_gpu():
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
 
 
 def _r9():
   return FloorPlan.from_file_input(rectangular_floor_plan((3, 3), (20, 30)), Materials.sb1(), 10.0, 300.0)
-
-
-def _random_params(B, seed, keep_default=(0,)) -> BuildingParams:
-  """Every per-building field of every building drawn around SB1 (buildings in keep_default: SB1's own values), the
-  windows and the air handler's setpoint order kept valid."""
-  rs = np.random.RandomState(seed)
-  out = {}
-  for name in BUILDING_PARAM_NAMES:
-    v = np.asarray(getattr(SB1, name), dtype=np.float64)
-    if name in _TEMPS_K:
-      a = v + rs.uniform(-_TEMPS_K[name], _TEMPS_K[name], size=B)
-    elif v.ndim == 1:   # a window: its lower end +- 2 K, its width * [0.7, 1.3]
-      lo = v[0] + rs.uniform(-2.0, 2.0, size=B)
-      a = np.stack([lo, lo + (v[1] - v[0]) * rs.uniform(0.7, 1.3, size=B)], axis=1)
-    else:
-      a = v * rs.uniform(0.7, 1.3, size=B)
-    a[list(keep_default)] = v
-    out[name] = a
-  return BuildingParams(out)
-
-
-def _c_row(bp: BuildingParams, b: int) -> dict:
-  """Building b's parameters by sb_params field name (the oracle's OracleParams names)."""
-  row = {}
-  for name, a in bp.fields.items():
-    for j, f in enumerate(BUILDING_PARAM_NAMES[name]):
-      row[f] = float(a[b] if a.ndim == 1 else a[b, j])
-  return row
 
 
 def _col(sim, suffix):
@@ -64,10 +31,8 @@ def _col(sim, suffix):
 
 @pytest.mark.parametrize("kernel", ["default", "lds"])
 def test_every_building_against_an_oracle_twin_of_its_own_parameters(kernel, monkeypatch):
-  _need_gpu()
+  need_gpu()
   from oracle import oracle as orc
-  from tests.golden_util import oracle_params, oracle_plan
-  from tests.test_gpu_parity import T_TOL, _plan, _step_in
   if kernel == "lds":
     monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
   g = load("h2_sb1_r9_random.npz")
@@ -76,12 +41,12 @@ def test_every_building_against_an_oracle_twin_of_its_own_parameters(kernel, mon
   rs = np.random.RandomState(11)
   init = np.clip(294.0 + rs.randn(B, 1, 1) + 0.8 * rs.randn(B, 68, 98), 285.0, 305.0)
   acts = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
-  bp = _random_params(B, seed=3)
-  sim = BatchedSimulator(_plan(p), SimConfig.sb1(), B, float(g["h_conv"]))
+  bp = random_params(B, seed=3)
+  sim = BatchedSimulator(plan_from_npz(p), SB1, B, float(g["h_conv"]))
   assert sim.launch_info["path"] == (0 if kernel == "lds" else 1)
   sim.set_building_params(bp)
   sim.reset(temps=torch.tensor(init.reshape(B, -1), dtype=torch.float64, device="cuda"))
-  rows = [_c_row(bp, b) for b in range(B)]
+  rows = [c_row(bp, b) for b in range(B)]
   sc = sim.scalars().cpu().numpy()
   for b in range(B):   # the reset's setpoints come from the building's row
     assert (sc[b, 0], sc[b, 1], sc[b, 4], sc[b, 8]) == (rows[b]["ahu_heat_sp"], rows[b]["ahu_cool_sp"],
@@ -89,9 +54,7 @@ def test_every_building_against_an_oracle_twin_of_its_own_parameters(kernel, mon
   plan = oracle_plan(p)
   twins = [orc.OracleBuilding(plan, oracle_params(g["params_json"], **rows[b]), 0.0, reset_temps=init[b].reshape(-1))
            for b in range(B)]
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  obs, rew, info = step_buffers(sim)
   c_dp = _col(sim, "differential_pressure_setpoint")
   c_fan = _col(sim, "discharge_fan_speed_percentage_command") + _col(sim, "supply_fan_speed_percentage_command")
   c_oa = _col(sim, "outside_air_flowrate_sensor")
@@ -100,25 +63,16 @@ def test_every_building_against_an_oracle_twin_of_its_own_parameters(kernel, mon
   f32 = np.float32
   for t in range(T):
     tt = t + 100
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, tt), obs, rew, info)
+    sim.step(torch.tensor(acts[t], device="cuda"), step_in(g, tt), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     r = rew.cpu().numpy().astype(np.float64)
     o_dev = obs.cpu().numpy()
     zt = sim.zone_temps().cpu().numpy()
     for b in range(B):
-      a = acts[t, b]
-      native = [f32((float(a[0]) + 1.0) / 2.0 * 45.0 + 310.0), f32((float(a[1]) + 1.0) / 2.0 * 15.0 + 285.0)]
-      o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
-          t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]),
-          e_carbon=float(g["e_carbon"][tt]), g_price=float(g["g_price"][tt]),
-          g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
+      o = twins[b].step(**step_kwargs(g, tt, t, SB1, acts[t, b]))
       assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
       assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
-      ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
-      assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b, i[b, :4], ref)
+      assert rates_match(i[b, :4], oracle_rates(o)), (t, b, i[b, :4], oracle_rates(o))
       assert abs(float(r[b]) - o["reward"]) < 1e-6, (t, b, r[b], o["reward"])
       # the reward's constants in the info row, and the observation columns that carry a parameter (no normaliser
       # here: an observation is the native value as a proto float)
@@ -150,7 +104,7 @@ def _same(x, y):
 
 @pytest.mark.parametrize("solver", ["gauss_seidel", "jacobi_fp32"])
 def test_a_table_of_the_defaults_is_bitwise_no_table(solver):
-  _need_gpu()
+  need_gpu()
   B, T = 8, 20
   gen = torch.Generator(device="cuda")
   gen.manual_seed(21)
@@ -160,7 +114,7 @@ def test_a_table_of_the_defaults_is_bitwise_no_table(solver):
                              for name in BUILDING_PARAM_NAMES})
   plain = BatchedEnvironment(_r9(), B, collect_info=True, solver=solver)
   table = BatchedEnvironment(_r9(), B, collect_info=True, solver=solver, building_params=defaults)
-  cleared = BatchedEnvironment(_r9(), B, collect_info=True, solver=solver, building_params=_random_params(B, 5))
+  cleared = BatchedEnvironment(_r9(), B, collect_info=True, solver=solver, building_params=random_params(B, 5))
   cleared.set_building_params(None)
   ref = _run(plain, acts, T)
   _same(ref, _run(table, acts, T))
@@ -173,12 +127,12 @@ def test_a_table_of_the_defaults_is_bitwise_no_table(solver):
 
 @pytest.mark.parametrize("solver", ["gauss_seidel", "jacobi_fp32"])
 def test_permuted_rows_permute_the_outputs_bitwise(solver):
-  _need_gpu()
+  need_gpu()
   B, T = 16, 12
   gen = torch.Generator(device="cuda")
   gen.manual_seed(22)
   acts = torch.rand((T, B, 2), generator=gen, device="cuda") * 2 - 1
-  bp = _random_params(B, seed=7, keep_default=())
+  bp = random_params(B, seed=7, keep_default=())
   perm = np.random.RandomState(1).permutation(B)
   pi = torch.tensor(perm, device="cuda")
   bp_pi = BuildingParams({k: v[perm] for k, v in bp.fields.items()})
@@ -194,10 +148,10 @@ def test_permuted_rows_permute_the_outputs_bitwise(solver):
 
 @pytest.mark.parametrize("rank,world", [(0, 1), (1, 2)])
 def test_mixed_batch_slices_equal_stand_alone_environments(rank, world):
-  _need_gpu()
+  need_gpu()
   plans = [_r9(), FloorPlan.from_file_input(rectangular_floor_plan((2, 3), (9, 10)), Materials.sb1(), 10.0, 300.0)]
   totals = [6, 5]
-  bp = _random_params(sum(totals), seed=9, keep_default=())
+  bp = random_params(sum(totals), seed=9, keep_default=())
   mixed = MixedBatchedEnvironment(list(zip(plans, totals)), rank=rank, world=world, collect_info=True,
                                   building_params=bp)
   singles = [BatchedEnvironment(p, hi - lo, collect_info=True, building_params=bp.rows(glo, ghi))
@@ -231,13 +185,13 @@ def test_mixed_batch_slices_equal_stand_alone_environments(rank, world):
 
 @pytest.mark.parametrize("solver", ["gauss_seidel", "jacobi_fp32"])
 def test_reset_sets_each_buildings_own_setpoints(solver):
-  _need_gpu()
+  need_gpu()
   B = 8
   env = BatchedEnvironment(_r9(), B, collect_info=True, solver=solver)
   env.reset()
   sc0 = env.sim.scalars().cpu().numpy()
   assert (sc0[:, 0] == SB1.ahu_heating_air_temp_setpoint).all() and (sc0[:, 4] == SB1.boiler_reheat_water_setpoint).all()
-  bp = _random_params(B, seed=13)
+  bp = random_params(B, seed=13)
   env.set_building_params(bp)
   # a new table does not rewrite the setpoints in force ...
   assert np.array_equal(env.sim.scalars().cpu().numpy(), sc0)
@@ -255,9 +209,9 @@ def test_reset_sets_each_buildings_own_setpoints(solver):
 
 
 def test_a_forked_building_keeps_its_slots_row():
-  _need_gpu()
+  need_gpu()
   B = 8
-  bp = _random_params(B, seed=17, keep_default=(0, 1, 2, 3))   # buildings 0..3: one row; 4..7: rows of their own
+  bp = random_params(B, seed=17, keep_default=(0, 1, 2, 3))   # buildings 0..3: one row; 4..7: rows of their own
   env = BatchedEnvironment(_r9(), B, collect_info=True, building_params=bp)
   gen = torch.Generator(device="cuda")
   gen.manual_seed(24)
@@ -278,7 +232,7 @@ def test_a_forked_building_keeps_its_slots_row():
 
 
 def test_the_c_entry_names_the_building_and_the_field():
-  _need_gpu()
+  need_gpu()
   B = 4
   sim = BatchedSimulator(_r9(), SB1, B, 10.0)
   fn = _ffi.entry("sb_set_building_params")

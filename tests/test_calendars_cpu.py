@@ -13,7 +13,7 @@ from sbsim_amd.environment import BatchedEnvironment, MixedBatchedEnvironment, S
 from sbsim_amd.host_inputs import Calendar, CalendarTimeline
 from tests import calendar_cases as cc
 from tests.golden_util import GOLDEN, load
-from tests.test_gpu_parity import _plan
+from tests.twins import plan_from_npz
 
 UTC, DT = cc.UTC, cc.DT
 STEPS = 30
@@ -118,7 +118,7 @@ def _env(**kw):
   args = dict(calendars=cc.calendars(), calendar_of=CALENDAR_OF,
               weather=host_inputs.WeatherController(273.0, 283.0, convection_coefficient=cc.H_CONV))
   args.update(kw)
-  return BatchedEnvironment(_plan(load("plan_small_test.npz")), B, **args)
+  return BatchedEnvironment(plan_from_npz(load("plan_small_test.npz")), B, **args)
 
 
 def _device_occupancy(k, **kw):
@@ -176,7 +176,7 @@ def test_the_environment_refuses_before_anything_is_created():
 
 
 def test_the_mixed_environment_and_the_logger_refuse_calendars():
-  plan = _plan(load("plan_small_test.npz"))
+  plan = plan_from_npz(load("plan_small_test.npz"))
   with pytest.raises(ValueError, match="calendars is not implemented for MixedBatchedEnvironment"):
     MixedBatchedEnvironment([(plan, B)], calendars=cc.calendars(), calendar_of=CALENDAR_OF)
   from sbsim_amd.episode_writer import BuildingLogger

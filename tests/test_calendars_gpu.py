@@ -19,17 +19,13 @@ from sbsim_amd.environment import BatchedEnvironment, BatchedSimulator, SimConfi
 from sbsim_amd.host_inputs import Calendar  # noqa: E402
 from tests import calendar_cases as cc  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_gpu_parity import _plan  # noqa: E402
+from tests.parity import need_gpu  # noqa: E402
+from tests.twins import plan_from_npz  # noqa: E402
 
 UTC, DT = cc.UTC, cc.DT
 B, K, T = 12, 3, 30
 CALENDAR_OF = np.arange(B) % K   # interleaved: neighbouring lanes read three different segments of the table
 EPISODE = dict(num_days_in_episode=cc.episode_days(40))
-
-
-def _need_gpu():
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
 
 
 def _actions(n_steps, n_buildings, seed=3):
@@ -75,8 +71,8 @@ def _plain(plan, k, n, **kw):
 def test_a_mixed_batch_equals_its_single_calendar_environments():
   tl = host_inputs.CalendarTimeline(cc.calendars(), CALENDAR_OF, cc.base_models(), cc.STARTS[0], None, 40)
   assert all(cc.crosses_comfort(tl, b, T) for b in range(B))   # every calendar crosses its own comfort switch in the run
-  _need_gpu()
-  plan = _plan(load("plan_small_test.npz"))
+  need_gpu()
+  plan = plan_from_npz(load("plan_small_test.npz"))
   # member j of every group takes the same actions: what differs between the groups is their calendars'
   acts = _actions(T, B // K)[:, np.arange(B) // K].contiguous()
   env = BatchedEnvironment(plan, B, calendars=cc.calendars(), calendar_of=CALENDAR_OF, collect_info=True, **EPISODE)
@@ -116,8 +112,8 @@ def test_device_occupancy_per_group():
   starts = [start, start + dt.timedelta(days=7), start + dt.timedelta(days=14)]
   for gen, s in zip(_generators(), starts):
     assert gen.hours[0] <= s.hour <= gen.hours[1] and gen.is_work_day(s)
-  _need_gpu()
-  plan = _plan(load("plan_small_test.npz"))
+  need_gpu()
+  plan = plan_from_npz(load("plan_small_test.npz"))
   acts = _actions(T, n, seed=5)
   kw = dict(occupancy_normalization_constant=2.0, holiday_calendar=None, collect_info=True, **EPISODE)
   env = BatchedEnvironment(plan, n, calendars=[Calendar(occupancy=g, start_timestamp=s) for g, s in zip(_generators(), starts)],
@@ -138,8 +134,8 @@ def test_device_occupancy_per_group():
 
 
 def test_per_building_episodes_with_calendars():
-  _need_gpu()
-  plan = _plan(load("plan_small_test.npz"))
+  need_gpu()
+  plan = plan_from_npz(load("plan_small_test.npz"))
   steps = np.array([5, 9, 12, 7, 12, 6, 11, 8, 5, 10, 12, 9], dtype=np.int64)   # mixed; autoresets inside the run
   offsets = np.array([0, 3, 1, 0, 2, 5, 4, 0, 0, 1, 0, 2], dtype=np.int64)
   mask = np.zeros(B, dtype=bool)
@@ -167,8 +163,8 @@ def test_per_building_episodes_with_calendars():
 
 
 def test_snapshot_and_restore_replay_bitwise_and_refuse_another_calendar_of():
-  _need_gpu()
-  plan = _plan(load("plan_small_test.npz"))
+  need_gpu()
+  plan = plan_from_npz(load("plan_small_test.npz"))
   acts = _actions(9, B, seed=4)
   offsets = np.arange(B, dtype=np.int64) % 5
   make = lambda cal_of: BatchedEnvironment(plan, B, calendars=cc.calendars(), calendar_of=cal_of, collect_info=True,
@@ -201,9 +197,9 @@ def test_snapshot_and_restore_replay_bitwise_and_refuse_another_calendar_of():
 
 
 def test_attach_groups_validates_before_anything_changes():
-  _need_gpu()
+  need_gpu()
   n = 6
-  sim = BatchedSimulator(_plan(load("plan_small_test.npz")), SimConfig.sb1(), n, 12.0)
+  sim = BatchedSimulator(plan_from_npz(load("plan_small_test.npz")), SimConfig.sb1(), n, 12.0)
   L = _ffi.load()
   attach = _ffi.occupancy_entry("sb_occupancy_attach_groups")
   cfg = lambda z, hours, seed=7, first=0, step=300.0: _ffi.OccupancyConfig(z, *hours, step, seed, first)
@@ -274,9 +270,9 @@ def test_a_state_forked_across_groups_keeps_the_groups_headcount():
   """A fork moves the occupants' state word with the building's state; the slot keeps its group (its configuration is
   the slot's, like its calendar): building 0 (3 occupants per zone) takes building 1's word (32 per zone) and counts
   only its own three."""
-  _need_gpu()
+  need_gpu()
   n = 6
-  sim = BatchedSimulator(_plan(load("plan_small_test.npz")), SimConfig.sb1(), n, 12.0)
+  sim = BatchedSimulator(plan_from_npz(load("plan_small_test.npz")), SimConfig.sb1(), n, 12.0)
   group_of = np.array([0, 1, 0, 1, 1, 0], dtype=np.int32)
   sim.occupancy_attach_groups([(3, (6, 9, 15, 18), 300.0, 7, 0), (32, (5, 8, 14, 19), 300.0, 7, 0)], group_of)
   sim.reset()

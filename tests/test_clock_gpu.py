@@ -20,7 +20,8 @@ torch = pytest.importorskip("torch")
 from sbsim_amd import host_inputs  # noqa: E402
 from sbsim_amd.environment import BatchedEnvironment, SimConfig  # noqa: E402
 from tests.golden_util import GOLDEN, load  # noqa: E402
-from tests.test_gpu_parity import _plan  # noqa: E402
+from tests.parity import need_gpu  # noqa: E402
+from tests.twins import plan_from_npz  # noqa: E402
 
 UTC = dt.timezone.utc
 DT = dt.timedelta(seconds=300)
@@ -30,11 +31,6 @@ CSV = os.path.join(GOLDEN, "local_weather_test_data.csv")
 START_TRACE = dt.datetime(2023, 7, 1, tzinfo=UTC)        # the trace's first time stamp
 SHORT = dict(num_days_in_episode=(T + 0.5) * 300.0 / 86400.0)   # episodes of T transitions
 F = {name: i for i, name in enumerate(host_inputs.CLOCK_FIELDS)}
-
-
-def _need_gpu():
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
 
 
 def _host_rows(start, n):
@@ -168,8 +164,8 @@ def _case(name):
                                   "building_params", "jacobi", "device_occupancy"])
 def test_every_building_equals_a_plain_environment_started_at_its_own_time(case):
   offs, start, kw, rejected = _case(case)   # (the crossings are asserted here, on the host)
-  _need_gpu()
-  plan = _plan(load("plan_small_test.npz"))
+  need_gpu()
+  plan = plan_from_npz(load("plan_small_test.npz"))
   got, per_building = _check_against_plain(plan, offs, start, kw, rejected=rejected)
   # the batch is not one clock: the time features of two neighbouring buildings differ at every call
   env = BatchedEnvironment(plan, B)
@@ -186,8 +182,8 @@ def test_every_building_equals_a_plain_environment_started_at_its_own_time(case)
 
 
 def test_offsets_of_zero_equal_an_environment_without_offsets():
-  _need_gpu()
-  plan = _plan(load("plan_small_test.npz"))
+  need_gpu()
+  plan = plan_from_npz(load("plan_small_test.npz"))
   acts = _actions(T)
   outs = []
   for offsets in (np.zeros(B, np.int64), None):
@@ -209,8 +205,8 @@ def test_second_episode_starts_from_the_last_stepped_instant():
   switch = _first_change(rows, "comfort")
   offs = np.array([0, switch - 3, switch - 6, switch - 1, switch + 20], dtype=np.int64)
   assert rows[switch - 3, F["comfort"]] != rows[switch - 3 + 6, F["comfort"]]   # first instant vs the terminal step's
-  _need_gpu()
-  plan = _plan(load("plan_small_test.npz"))
+  need_gpu()
+  plan = plan_from_npz(load("plan_small_test.npz"))
   short = lambda: dict(num_days_in_episode=6.5 * 300.0 / 86400.0)
   got, _ = _check_against_plain(plan, offs, START, short, n_calls=10)
   kinds = [int(g["step_type"][0]) for g in got]
@@ -218,8 +214,8 @@ def test_second_episode_starts_from_the_last_stepped_instant():
 
 
 def test_snapshot_restore_and_fork_keep_the_slots_offsets():
-  _need_gpu()
-  plan = _plan(load("plan_small_test.npz"))
+  need_gpu()
+  plan = plan_from_npz(load("plan_small_test.npz"))
   offs = _offsets()
   per_building = offs[np.arange(B) % 5]
   acts = _actions(9)
@@ -254,11 +250,11 @@ def test_snapshot_restore_and_fork_keep_the_slots_offsets():
 
 
 def test_the_c_entries_validate_before_anything_changes():
-  _need_gpu()
+  need_gpu()
   import ctypes as C
   from sbsim_amd import _ffi
   from sbsim_amd.environment import BatchedSimulator
-  sim = BatchedSimulator(_plan(load("plan_small_test.npz")), SimConfig.sb1(), 6, 12.0)
+  sim = BatchedSimulator(plan_from_npz(load("plan_small_test.npz")), SimConfig.sb1(), 6, 12.0)
   L, NF = _ffi.load(), _ffi.SB_CLOCK_FIELDS
   attach, seek = _ffi.clock_entry("sb_clock_attach"), _ffi.clock_entry("sb_clock_seek")
   rows, offs = np.zeros((10, NF)), np.array([0, 1, 2, 3, 4, 8], np.int32)

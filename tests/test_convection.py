@@ -5,6 +5,7 @@ import pytest
 
 from oracle.convection_oracle import ConvectionOracle, offsets
 from tests.golden_util import load
+from tests.twins import T_TOL, plan_from_npz, step_in, step_kwargs
 
 
 def _stats(grids, H, W):
@@ -145,12 +146,6 @@ def test_restatement_does_not_depend_on_sharding_and_calls_differ():
 
 
 # ------------------------------------------------------------------------------------- GPU
-def _need_gpu():
-  import torch
-  if not torch.cuda.is_available():
-    pytest.skip("needs an MI355X")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("kernel,distance,prob", [("reg", 5, 1.0), ("lds", 5, 1.0), ("reg", -1, 1.0), ("lds-columns", -1, 1.0),
                                                   ("reg", -1, 0.5), ("lds-columns", -1, 0.5), ("reg", 20, 1.0), ("lds-columns", 20, 0.7)])
@@ -161,13 +156,14 @@ def test_device_shuffle_equals_its_restatement_inside_a_rollout(kernel, distance
   samples the partner by rejection -- after every FD update: sweep
   counts, zone temperatures and the final grid against oracle twins whose grids get the
   restatement's shuffle after every step."""
-  _need_gpu()
+  from tests.parity import need_gpu
+  need_gpu()
   import torch
   from oracle import oracle as orc
   from sbsim_amd import _ffi
   from sbsim_amd.environment import BatchedSimulator, SimConfig
   from tests.golden_util import oracle_params, oracle_plan
-  from tests.test_gpu_parity import T_TOL, _plan, _step_in
+  from tests.parity import step_buffers
   if kernel.startswith("lds"):
     monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
   g = load("h2_sb1_r9_random.npz")
@@ -176,7 +172,7 @@ def test_device_shuffle_equals_its_restatement_inside_a_rollout(kernel, distance
   rs = np.random.RandomState(5)
   init = np.clip(294.0 + rs.randn(B, 1, 1) + 0.8 * rs.randn(B, 68, 98), 285.0, 305.0)
   acts = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
-  fp = _plan(p)
+  fp = plan_from_npz(p)
   sim = BatchedSimulator(fp, SimConfig.sb1(), B, float(g["h_conv"]),
                          orientation="columns" if kernel == "lds-columns" else "auto")
   assert sim.launch_info["path"] == (1 if kernel == "reg" else 0)
@@ -186,24 +182,13 @@ def test_device_shuffle_equals_its_restatement_inside_a_rollout(kernel, distance
   conv = ConvectionOracle(fp.zone_cell_lists(), 68, 98, prob, distance, seed=4242, first_building=first)
   plan, prm = oracle_plan(p), oracle_params(g["params_json"])
   twins = [orc.OracleBuilding(plan, prm, 0.0, reset_temps=init[b].reshape(-1)) for b in range(B)]
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  obs, rew, info = step_buffers(sim)
   for t in range(T):
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, t + 100), obs, rew, info)
+    sim.step(torch.tensor(acts[t], device="cuda"), step_in(g, t + 100), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     zt = sim.zone_temps().cpu().numpy()
     for b in range(B):
-      a = acts[t, b]
-      native = [np.float32((float(a[0]) + 1.0) / 2.0 * 45.0 + 310.0), np.float32((float(a[1]) + 1.0) / 2.0 * 15.0 + 285.0)]
-      tt = t + 100
-      o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
-          t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]),
-          e_carbon=float(g["e_carbon"][tt]), g_price=float(g["g_price"][tt]),
-          g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
+      o = twins[b].step(**step_kwargs(g, t + 100, t, SimConfig.sb1(), acts[t, b]))
       assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
       assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
     grids = np.stack([tw.grid() for tw in twins])
@@ -220,7 +205,8 @@ def test_device_shuffle_equals_its_restatement_inside_a_rollout(kernel, distance
 
 @pytest.mark.gpu
 def test_convection_attach_argument_checks():
-  _need_gpu()
+  from tests.parity import need_gpu
+  need_gpu()
   from sbsim_amd import _ffi
   from sbsim_amd.environment import BatchedSimulator, SimConfig
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
@@ -268,7 +254,8 @@ def test_single_building_adapter_with_reproducible_convection(plan_rooms, room_s
   convection gives the grid before the shuffle) -- the zone means follow it, every device state stays, and the next
   steps run from it.  sb_set_temps on its own: what goes in comes out, on five state layouts (k_sweep_roll, k_sweep_reg,
   k_sweep_two, k_sweep_band on three wavefronts, the LDS-grid kernel)."""
-  _need_gpu()
+  from tests.parity import need_gpu
+  need_gpu()
   if force_lds:
     monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
   import torch

@@ -22,7 +22,7 @@ torch = pytest.importorskip("torch")
 from sbsim_amd import _ffi  # noqa: E402
 from sbsim_amd.environment import BatchedSimulator, SimConfig  # noqa: E402
 from tests import convection_cases as cc  # noqa: E402
-from tests.test_gpu_parity import _need_gpu  # noqa: E402
+from tests.parity import need_gpu  # noqa: E402
 
 
 class _Shuffler:
@@ -77,7 +77,7 @@ def _assert_equal(got, want, what):
 
 @pytest.mark.parametrize("name", list(cc.CASES))
 def test_device_shuffle_is_the_restatements_permutation(name, monkeypatch):
-  _need_gpu()
+  need_gpu()
   case = cc.CASES[name]
   s = _Shuffler(case, monkeypatch)
   start = cc.input_grids(s.fp, case.B)
@@ -95,7 +95,7 @@ def test_device_shuffle_is_the_restatements_permutation(name, monkeypatch):
 def test_same_answer_whoever_runs_the_building(name, monkeypatch):
   """The hand-over batch on the whole device (one building per workgroup), and in two halves as simulators of their own
   with first_building moved to the half's start: bitwise the answer of the one-CU run, i.e. the restatement's."""
-  _need_gpu()
+  need_gpu()
   case = cc.CASES[name]
   want = cc.expected(case)[0]
   start = cc.input_grids(cc.floor_plan(case), case.B)
@@ -114,7 +114,7 @@ def test_same_answer_whoever_runs_the_building(name, monkeypatch):
 def test_reattach_resets_the_call_number_and_replaces_the_tables(monkeypatch):
   """One simulator, attached four times in a row (offset table, by-rank window, whole room, a smaller table), two
   launches after each: every one equals a fresh restatement's calls 0 and 1."""
-  _need_gpu()
+  need_gpu()
   base = cc.CASES["calls3-d5"]
   s = _Shuffler(base, monkeypatch, attach=False)
   grids = cc.input_grids(s.fp, base.B)
@@ -132,7 +132,7 @@ def test_reattach_resets_the_call_number_and_replaces_the_tables(monkeypatch):
 def test_refusals(monkeypatch):
   """A room of 2048 cells at attach; one building past 2^32 at attach; a forced Q too small for the largest room at the
   launch, which then does not happen: the grid stays."""
-  _need_gpu()
+  need_gpu()
   big = cc.Case("refused", "q", cc.REFUSED_ROOM, 1.0, 5, (cc.TABLE,), "", 8, B=1)
   s = _Shuffler(big, monkeypatch, attach=False)
   for p, distance in ((1.0, 5), (0.5, -1), (1.0, -1)):

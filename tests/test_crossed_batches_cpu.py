@@ -12,8 +12,8 @@ from sbsim_amd import _ffi, host_inputs
 from sbsim_amd.environment import BatchedSimulator, SimConfig
 from tests import crossed_batches as cb
 from tests.golden_util import load, oracle_params
-from tests.test_abi_cpu import _plan_info
 from tests.threshold_cases import floor_plan
+from tests.twins import native_value, plan_info
 
 SB_KERNEL_LDS = 0
 REGISTER_KERNELS = (1, 2, 3, 4, 5)   # sb_sweep_kernel: k_sweep_reg (one / two wavefronts), roll, two, band
@@ -79,7 +79,7 @@ def test_the_plan_is_17_by_29_with_six_zones_and_an_odd_cell_count():
   assert cb.B == 67 and cb.T == 12 and cb.B % 64 == 3 and cb.B % 16 == 3
   cp = plan.compile(300.0, cb.H_CONV)
   assert (cp.H, cp.W, cp.Z) == (17, 29, 6) or (cp.H, cp.W, cp.Z) == (15, 27, 6)   # (with or without the exterior ring)
-  rc, info = _plan_info(plan, n_obs=sc.layout.O, n_buildings=cb.B)
+  rc, info = plan_info(plan, n_obs=sc.layout.O, n_buildings=cb.B)
   assert rc == 0 and info["kernel"] in REGISTER_KERNELS and info["path"] == 1, info
 
 
@@ -92,7 +92,7 @@ def test_the_planner_picks_the_kernel_the_case_names(name, monkeypatch):
   if sc.bmaterials is None:
     kinds = []
     for plan in (sc.plan, sc.plan.transposed()):
-      rc, info = _plan_info(plan, n_obs=sc.layout.O, n_buildings=cb.B)
+      rc, info = plan_info(plan, n_obs=sc.layout.O, n_buildings=cb.B)
       assert rc == 0, _ffi.load().sb_last_error()
       kinds.append(info["kernel"])
     if sc.case["kernel"] == "lds":
@@ -146,7 +146,7 @@ def test_every_feature_of_the_case_bites(name):
     assert n_rejected == 0
   if case["actions"] == "dampers":
     row, b, col = sc.bad_command
-    assert not 0.0 <= float(cb.native_action((0.0, 1.0), sc.actions[row, b, col])) <= 1.0
+    assert not 0.0 <= float(native_value(sc.actions[row, b, col], 0.0, 1.0)) <= 1.0
     others = np.delete(sc.actions[:, :, 3:].reshape(-1), np.ravel_multi_index((row, b, col - 3), sc.actions[:, :, 3:].shape))
     assert (np.abs(others) <= 1.0).all()
     bad = [r for op, res in steps if op.row == row for r in [res[b]]]

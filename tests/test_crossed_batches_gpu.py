@@ -3,7 +3,7 @@ case -- 67 buildings of 493 cells, reset() and 12 steps with the case's partial 
 between -- and after every call EVERY building is held to its own twin, which was computed on the CPU without the library's
 clock tables: sweep counts, modes, dampers, request counts, step types, -inf rewards and histogram fractions equal; zone
 temperatures and grids within 1e-8 K; energy rates, rewards and the dollars reward's info columns within the bounds of
-tests/test_gpu_parity.py and tests/test_reward_function_gpu.py; observation columns equal where they are made of equal
+tests/twins.py and tests/test_reward_function_gpu.py; observation columns equal where they are made of equal
 quantities and within one float32 step of the native value and of the result where they are made of a temperature."""
 import time
 
@@ -16,8 +16,9 @@ torch = pytest.importorskip("torch")
 from sbsim_amd import host_inputs  # noqa: E402
 from sbsim_amd.environment import BatchedEnvironment  # noqa: E402
 from tests import crossed_batches as cb  # noqa: E402
-from tests.test_gpu_parity import T_TOL, _need_gpu  # noqa: E402
-from tests.test_reward_function_cpu import SET_FIELDS  # noqa: E402
+from tests.parity import need_gpu  # noqa: E402
+from tests.reward_cases import SET_FIELDS  # noqa: E402
+from tests.twins import RATE_RTOL, REWARD_TOL, T_TOL, rates_match  # noqa: E402
 
 INFO_COLUMNS = dict(zip(SET_FIELDS, range(7, 13)))   # RewardResponse field -> info column (tests/test_reward_function_gpu.py)
 B = cb.B
@@ -90,14 +91,14 @@ def _check_step(env, sc, ts, res, what, worst):
   for b in range(B):
     r = res[b]
     assert (int(info[b, 4]), int(info[b, 5])) == (r["n_sweeps"], r["converged"]), (what, b, info[b, 4:6], r["n_sweeps"])
-    assert np.allclose(info[b, :4], r["rates"], rtol=2e-6, atol=1e-6), (what, b, info[b, :4], r["rates"])
-    worst.note("energy rates (relative, above 1 W)", (np.abs(info[b, :4] - r["rates"]) / np.maximum(np.abs(r["rates"]), 1.0)).max(), 2e-6)
+    assert rates_match(info[b, :4], r["rates"]), (what, b, info[b, :4], r["rates"])
+    worst.note("energy rates (relative, above 1 W)", (np.abs(info[b, :4] - r["rates"]) / np.maximum(np.abs(r["rates"]), 1.0)).max(), RATE_RTOL)
     assert (int(step_type[b]), float(discount[b])) == (r["step_type"], r["discount"]), (what, b, step_type[b], discount[b])
     if np.isneginf(r["reward"]):
       assert np.isneginf(reward[b]), (what, b, reward[b])
     elif r["dollars"] is None:
-      worst.note("regret reward", abs(reward[b] - r["reward"]), 2e-6)
-      assert abs(reward[b] - r["reward"]) < 2e-6, (what, b, reward[b], r["reward"])
+      worst.note("regret reward", abs(reward[b] - r["reward"]), REWARD_TOL)
+      assert abs(reward[b] - r["reward"]) < REWARD_TOL, (what, b, reward[b], r["reward"])
     else:
       assert reward[b] == pytest.approx(r["dollars"]["agent_reward_value"], rel=2e-6, abs=0.0), (what, b)
       worst.note("dollars reward (relative)", abs(reward[b] - r["dollars"]["agent_reward_value"]) / abs(r["dollars"]["agent_reward_value"]), 2e-6)
@@ -115,7 +116,7 @@ def _check_step(env, sc, ts, res, what, worst):
 
 @pytest.mark.parametrize("name", list(cb.CASES))
 def test_every_building_of_a_crossed_batch_is_its_twin(name, monkeypatch):
-  _need_gpu()
+  need_gpu()
   t0 = time.time()
   sc = cb.scenario(name)
   want = cb.expected(name)
@@ -179,7 +180,7 @@ def _small_env(**kw):
 
 
 def test_the_refused_pairs_raise_before_any_step():
-  _need_gpu()
+  need_gpu()
   lengths = np.full(B, 5)
   device = lambda k: cb.scenario("histograms-per-building")._device_occupancy(k)
   (_, occ_msg), (_, cal_msg), (_, life_msg) = cb.REFUSED

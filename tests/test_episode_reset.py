@@ -12,6 +12,7 @@ import pytest
 
 from oracle import oracle as orc
 from tests.golden_util import load, oracle_params, oracle_plan
+from tests.twins import T_TOL, plan_from_npz, rates_match, step_in
 
 
 def _ulp32(a, b):
@@ -56,24 +57,21 @@ def test_hip_reset_between_episodes_against_reference_golden(path, monkeypatch):
     pytest.skip("no GPU")
   from sbsim_amd import _ffi
   from sbsim_amd.environment import ACTION_REJECTION_REWARD, BatchedSimulator, SimConfig
-  from tests.test_gpu_parity import T_TOL, _plan
+  from tests.parity import step_buffers
 
-  class _Episode:   # _step_in reads g[key][t]
+  class _Episode:   # step_in reads g[key][t]
     def __init__(self, g, ep):
       self.g, self.ep = g, ep
 
     def __getitem__(self, k):
       return self.g[self.ep + k]
 
-  from tests.test_gpu_parity import _step_in
   if path == "lds":
     monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
   g = load("h2_sb1_r9_episodes.npz")
   B = 5
-  sim = BatchedSimulator(_plan(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]))
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  sim = BatchedSimulator(plan_from_npz(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]))
+  obs, rew, info = step_buffers(sim)
   aux = [0.0] * _ffi.SB_NUM_AUX
   for ep in ("e1_", "e2_"):
     e = _Episode(g, ep)
@@ -84,14 +82,14 @@ def test_hip_reset_between_episodes_against_reference_golden(path, monkeypatch):
     for t in range(T):
       act = torch.tensor(np.tile(e["actions_norm"][t], (B, 1)), dtype=torch.float32, device="cuda")
       rej = torch.full((B,), int(e["rejected"][t]), dtype=torch.uint8, device="cuda")
-      si = _step_in(e, t)
+      si = step_in(e, t)
       si.reject_dev = rej.data_ptr()
       sim.step(act, si, obs, rew, info)
       i = info.cpu().numpy().astype(np.float64)
       assert (i[:, 4] == e["n_sweeps"][t]).all(), (ep, t, i[:, 4], e["n_sweeps"][t])
       assert np.abs(sim.zone_temps().cpu().numpy() - e["zone_temp_post"][t]).max() < T_TOL, (ep, t)
       assert np.array_equal(sim.modes().cpu().numpy(), np.tile(e["mode"][t], (B, 1))), (ep, t)
-      assert np.allclose(i[:, :4], e["rates"][t].astype(np.float64), rtol=2e-6, atol=1e-6), (ep, t, i[0, :4], e["rates"][t])
+      assert rates_match(i[:, :4], e["rates"][t].astype(np.float64)), (ep, t, i[0, :4], e["rates"][t])
       sc = sim.scalars().cpu().numpy()
       assert np.allclose(sc[:, 8], e["blr_tank_temp"][t], atol=1e-9), (ep, t)
       assert np.allclose(sc[:, 5], e["blr_flow"][t], atol=1e-12), (ep, t)   # reheat flow = sum of the open valves

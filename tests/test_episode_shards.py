@@ -109,10 +109,10 @@ def test_building_logger_writes_what_the_environment_computed(tmp_path):
     pytest.skip("needs an MI355X")
   from sbsim_amd.environment import BatchedEnvironment, SimConfig
   from sbsim_amd.episode_writer import BuildingLogger
-  from tests.test_gpu_parity import _plan
+  from tests.twins import plan_from_npz
   p = load("plan_r9_sb1.npz")
   B, T = 5, 14      # 07:00 + 14 x 5 min: the shards roll over to the 08 hour
-  env = BatchedEnvironment(_plan(p), B, config=SimConfig.sb1(), holiday_calendar=None, collect_info=True,
+  env = BatchedEnvironment(plan_from_npz(p), B, config=SimConfig.sb1(), holiday_calendar=None, collect_info=True,
                            observation_normalization={"zone_air_temperature_sensor": (294.0, 4.0)})
   logger = BuildingLogger(env, str(tmp_path), buildings=[1, 3], scenario_id="unit")
   env.reset()

@@ -26,14 +26,10 @@ torch = pytest.importorskip("torch")
 from sbsim_amd import _ffi, host_inputs  # noqa: E402
 from sbsim_amd.environment import BatchedSimulator, SimConfig  # noqa: E402
 from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan  # noqa: E402
+from tests.parity import need_gpu  # noqa: E402
 
 C_AIR, C_WATER = 1006.0, 4180.0   # utils/constants.py:21-24
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _need_gpu():
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
 
 
 def _plan2():
@@ -110,7 +106,7 @@ def test_reward_known_answers_through_k_post():
   """setpoint_energy_carbon_regret_test.py:30-167: every row's energy rates are PRODUCED by k_post from
   device state chosen for it (blower = flow * dp with full recirculation, air conditioning =
   flow * c_air * (setpoint - mixed), gas = the tank's dissipation, pump = flow * rho g head)."""
-  _need_gpu()
+  need_gpu()
   with open(os.path.join(GOLDEN, "reward_kat.json")) as fh:
     kat = json.load(fh)
   c = kat["config"]
@@ -156,7 +152,7 @@ def test_reward_known_answers_through_k_post():
 
 def test_boiler_known_answers_through_k_post():
   """boiler_test.py:131-176 (500.066862, 562.57521, 100695.0501, 125.0167, 0), :431-439 (312.5418), pump."""
-  _need_gpu()
+  need_gpu()
   t = Taps(boiler_water_pump_differential_head=3.0, boiler_water_pump_efficiency=0.6)
   si = t.step_in()
   for setpoint, flow, ret, outside, want in ((360.0, 0.0, 300.0, 280.0, 500.066862), (370.0, 0.0, 300.0, 280.0, 562.57521),
@@ -174,7 +170,7 @@ def test_boiler_known_answers_through_k_post():
 def test_boiler_tank_lag_known_answers_through_k_pre():
   """boiler_test.py:197-230 _adjust_temperature, reached through _set_current_temperature (both rates
   positive there: the rate that the row does not use is given a dummy value)."""
-  _need_gpu()
+  need_gpu()
   for sp, actual, secs, h, c_, want in ((330.0, 290.0, 60, 2.0, 0.5, 292.0), (300.0, 290.0, 600, 2.0, 0.5, 300.0),
                                         (320.0, 330.0, 60, 2.0, 0.5, 329.5), (320.0, 330.0, 600, 0.7, 2.0, 320.0),
                                         (330.0, 330.0, 60, 2.0, 0.5, 330.0)):
@@ -191,7 +187,7 @@ def test_boiler_tank_lag_known_answers_through_k_pre():
 def test_air_handler_known_answers():
   """air_handler_test.py:110-175 through k_pre (mixed / supply air temperature, setpoints 270 / 288) and
   :335-420 through k_post (thermal rate, fan powers: intake all the air, exhaust the fresh share)."""
-  _need_gpu()
+  need_gpu()
   for r, recirc, amb, want in ((0.3, 280, 240, 270), (0.6, 244, 270, 270), (0.1, 210, 316, 288), (0.4, 250, 316, 288),
                                (0.4, 286, 266, 0.4 * 286 + 0.6 * 266), (0.12, 198, 290, 0.12 * 198 + 0.88 * 290)):
     t = Taps(ahu_recirculation=r, ahu_heating_air_temp_setpoint=270.0, ahu_cooling_air_temp_setpoint=288.0)
@@ -214,7 +210,7 @@ def test_vav_known_answers_through_k_pre():
   """vav_test.py:198-262: zone supply temperature and the energy applied to the zone.  The formulas see
   only valve * max_water_flow and damper * max_air_flow: the reheat valve is opened by the thermostat
   (HEAT: 1, COOL: 0), the damper by the agent's supply_air_damper_percentage_command."""
-  _need_gpu()
+  need_gpu()
   for valve, max_w, damper, max_a, t_sa, t_w in ((0.5, 0.8, 0.3, 0.3, 270, 360), (0.1, 0.1, 0.4, 0.4, 210, 32),
                                                  (0, 0.2, 0.2, 0.9, 260, 270), (0.9, 0.4, 0.1, 0.6, 270, 430)):
     reheat, air = valve * max_w, damper * max_a
@@ -244,7 +240,7 @@ def test_vav_known_answers_through_k_pre():
 def test_vav_update_settings_table_through_k_pre(ts, zone_temp, damper, valve):
   """vav_test.py:150-174: thermostat 9-18 h, comfort (292, 295), eco (290, 297), previous update one
   hour earlier; the host schedule supplies the mode flags, k_pre does the control."""
-  _need_gpu()
+  need_gpu()
   now = dt.datetime.fromisoformat(ts)
   sched = host_inputs.SetpointSchedule(9, 18, (292, 295), (290, 297), holidays=set())
   t = Taps(comfort_temp_window=(292.0, 295.0), eco_temp_window=(290.0, 297.0), morning_start_hour=9, evening_start_hour=18)
@@ -259,7 +255,7 @@ def test_vav_update_settings_table_through_k_pre(ts, zone_temp, damper, valve):
 def test_thermostat_state_machine_through_k_pre():
   """thermostat_test.py:47-135 with its schedule (9-18 h, comfort (292, 295), eco (290, 297)).
   Modes: 0 OFF, 1 HEAT, 2 COOL, 3 PASSIVE_COOL."""
-  _need_gpu()
+  need_gpu()
   t = Taps(comfort_temp_window=(292.0, 295.0), eco_temp_window=(290.0, 297.0))
   low, high = 292.0, 295.0
   mid = (low + high) / 2

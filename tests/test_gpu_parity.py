@@ -25,42 +25,19 @@ from sbsim_amd.environment import (BatchedEnvironment, BatchedSimulator, SimConf
                                    observation_field_names)
 from sbsim_amd.floorplan import FloorPlan, Material, Materials  # noqa: E402
 from tests.golden_util import load, oracle_params, oracle_plan  # noqa: E402
-from tests.threshold_cases import oracle_twin  # noqa: E402
+from tests.parity import check_plan_against_oracle, need_experimental_kernels, need_gpu, step_buffers  # noqa: E402
+from tests.twins import (T_TOL, assert_step_matches, native_action, oracle_rates, plan_from_npz,  # noqa: E402
+                         rates_match, ringless_plan, step_in, step_kwargs)
 
-T_TOL = 1e-8
+SB1 = SimConfig.sb1()
 TEST_SMALL = Materials(Material(50., 700., 1.), Material(2., 500., 1800.), Material(.05, 500., 3000.))
-
-
-def _need_gpu():
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
-
-
-def _plan(p):
-  return FloorPlan(conductivity=p["conductivity"], heat_capacity=p["heat_capacity"],
-                   density=p["density"], exterior_space=p["exterior_space"],
-                   zone_label=p["zone_label"], diffusers=p["diffusers"],
-                   cv_size_cm=float(p["cv_size_cm"]), floor_height_cm=float(p["floor_height_cm"]),
-                   zone_names=tuple(str(z) for z in p["zone_names"]))
-
-
-def _step_in(g, t, has_action=True, occupancy=None):
-  si = _ffi.StepIn()
-  si.t_amb_now, si.t_amb_next = float(g["t_amb_now"][t]), float(g["t_amb_next"][t])
-  si.comfort_now, si.comfort_prev, si.comfort_next = (int(g["comfort_now"][t]), int(g["comfort_prev"][t]),
-                                                      int(g["comfort_next"][t]))
-  si.has_action = int(has_action)
-  si.occupancy = float(g["occupancy"][t]) if occupancy is None else occupancy
-  si.e_price, si.e_carbon = float(g["e_price"][t]), float(g["e_carbon"][t])
-  si.g_price, si.g_carbon = float(g["g_price"][t]), float(g["g_carbon"][t])
-  return si
 
 
 @pytest.mark.parametrize("tag,kernel", [("random", "reg"), ("const", "reg-pair"), ("const", "lds"),
                                         ("random", "lds-columns"), ("random", "reg-two"), ("random", "reg-band")])
 def test_one_day_rollout_against_reference_golden(tag, kernel, monkeypatch):
   """BASELINE.json configs[0] semantics on the GPU: SB1 physics on R9, 288 steps."""
-  _need_gpu()
+  need_gpu()
   g = load(f"h2_sb1_r9_{tag}.npz")
   B = 5
   # "reg": the library's own choice for R9 -- rows as lanes, grid in registers, one wavefront
@@ -78,7 +55,7 @@ def test_one_day_rollout_against_reference_golden(tag, kernel, monkeypatch):
     monkeypatch.setenv("SBSIM_NO_BAND_PATH", "1")      # without it step_band.hip on two wavefronts ("reg-band")
   if kernel == "reg-band":
     monkeypatch.setenv("SBSIM_BAND_PATH", "1")
-  sim = BatchedSimulator(_plan(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]),
+  sim = BatchedSimulator(plan_from_npz(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]),
                          orientation={"reg": "auto", "reg-pair": "columns", "lds": "rows",
                                       "lds-columns": "columns", "reg-two": "columns", "reg-band": "columns"}[kernel])
   assert sim.transposed == (kernel in ("reg-pair", "lds-columns", "reg-two", "reg-band"))
@@ -86,9 +63,7 @@ def test_one_day_rollout_against_reference_golden(tag, kernel, monkeypatch):
   assert sim.launch_info["path"] == (1 if kernel.startswith("reg") else 0)
   assert sim.launch_info["waves_per_building"] == (2 if kernel in ("reg-pair", "reg-band") else 1)
   sim.reset()
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  obs, rew, info = step_buffers(sim)
   T = len(g["n_sweeps"])
   col = observation_field_names([str(z) for z in g["zone_names"]], True)
   names, col_aux = col[0], col[4]
@@ -96,14 +71,14 @@ def test_one_day_rollout_against_reference_golden(tag, kernel, monkeypatch):
   worst_t, worst_r = 0.0, 0.0
   for t in range(T):
     act = torch.tensor(np.tile(g["actions_norm"][t], (B, 1)), dtype=torch.float32, device="cuda")
-    sim.step(act, _step_in(g, t), obs, rew, info)
+    sim.step(act, step_in(g, t), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     zt = sim.zone_temps().cpu().numpy()
     assert (i[:, 4] == g["n_sweeps"][t]).all(), (t, i[:, 4], g["n_sweeps"][t])
     worst_t = max(worst_t, np.abs(zt - g["zone_temp_post"][t]).max())
     assert np.abs(zt - g["zone_temp_post"][t]).max() < T_TOL, t
     ref_rates = g["rates"][t].astype(np.float64)
-    assert np.allclose(i[:, :4], ref_rates, rtol=2e-6, atol=1e-6), (t, i[0, :4], ref_rates)
+    assert rates_match(i[:, :4], ref_rates), (t, i[0, :4], ref_rates)
     r = rew.cpu().numpy().astype(np.float64)
     worst_r = max(worst_r, np.abs(r - float(g["reward"][t])).max())
     assert np.abs(r - float(g["reward"][t])).max() < 1e-6, t
@@ -134,7 +109,7 @@ def test_one_day_rollout_against_reference_golden(tag, kernel, monkeypatch):
 def test_thermostat_only_rollouts_on_reference_test_plans(name, golden):
   """Bare Simulator.step_sim() goldens: odd shapes (W odd, n<=1 cells), 100-sweep steps,
   and the reference KAT 301.895482 (simulator_flexible_floor_plan_test.py:1275-1312)."""
-  _need_gpu()
+  need_gpu()
   g = load(golden)
   p = load(f"plan_{name}.npz")
   import json
@@ -150,10 +125,9 @@ def test_thermostat_only_rollouts_on_reference_test_plans(name, golden):
       boiler_water_pump_efficiency=prm["blr_pump_eff"], boiler_heating_rate=prm["blr_heating_rate"],
       boiler_cooling_rate=prm["blr_cooling_rate"], initial_temp=float(g["initial_temp"]))
   B = 3
-  sim = BatchedSimulator(_plan(p), cfg, B, float(g["h_conv"]))
+  sim = BatchedSimulator(plan_from_npz(p), cfg, B, float(g["h_conv"]))
   sim.reset()
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  _, rew, info = step_buffers(sim)
   comfort = g["comfort"]
   for t in range(len(g["n_sweeps"])):
     si = _ffi.StepIn()
@@ -181,7 +155,7 @@ def test_divergent_buildings_against_oracle(mode, monkeypatch):
   words of max |delta| and leaves the few buildings those 32 bits cannot decide to its float64
   instantiation (the redo list, step_roll.hip): the library's pair of launches, the float64 kernel alone,
   and the pair with every third / every building forced through the list."""
-  _need_gpu()
+  need_gpu()
   if mode == "exact-only":
     monkeypatch.setenv("SBSIM_ROLL_EXACT", "1")
   if mode.startswith("redo"):
@@ -192,35 +166,19 @@ def test_divergent_buildings_against_oracle(mode, monkeypatch):
   rs = np.random.RandomState(7)
   init = np.clip(294.0 + rs.randn(B, 1, 1) + 0.3 * rs.randn(B, 68, 98), 285.0, 305.0)
   acts = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
-  sim = BatchedSimulator(_plan(p), SimConfig.sb1(), B, float(g["h_conv"]))
+  sim = BatchedSimulator(plan_from_npz(p), SimConfig.sb1(), B, float(g["h_conv"]))
   sim.reset(temps=torch.tensor(init.reshape(B, -1), dtype=torch.float64, device="cuda"))
   plan, prm = oracle_plan(p), oracle_params(g["params_json"])
   twins = [orc.OracleBuilding(plan, prm, 0.0, reset_temps=init[b].reshape(-1)) for b in range(B)]
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
-  rng_w, rng_a = (310.0, 355.0), (285.0, 300.0)
+  obs, rew, info = step_buffers(sim)
   for t in range(T):
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, t + 100), obs, rew, info)
+    sim.step(torch.tensor(acts[t], device="cuda"), step_in(g, t + 100), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     zt = sim.zone_temps().cpu().numpy()
     r = rew.cpu().numpy()
     for b in range(B):
-      a = acts[t, b]
-      native = [np.float32((float(a[0]) + 1.0) / 2.0 * (rng_w[1] - rng_w[0]) + rng_w[0]),
-                np.float32((float(a[1]) + 1.0) / 2.0 * (rng_a[1] - rng_a[0]) + rng_a[0])]
-      tt = t + 100
-      o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
-          t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]),
-          e_carbon=float(g["e_carbon"][tt]), g_price=float(g["g_price"][tt]),
-          g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
-      assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
-      assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
-      ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
-      assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b)
+      o = twins[b].step(**step_kwargs(g, t + 100, t, SB1, acts[t, b]))
+      assert_step_matches(i[b], zt[b], r[b], o, (t, b))
       assert abs(float(r[b]) - o["reward"]) < 1e-6, (t, b)
   grid = sim.temps().cpu().numpy()
   for b in range(B):
@@ -233,7 +191,7 @@ def test_set_temps_with_a_grid_whose_sum_changes(path, monkeypatch):
   convection's within-room permutation: a grid with ANOTHER sum must move the next step's recirculation temperature
   (simulator.py:423-426 takes building.temp.mean() every step; the library caches it in scal[11]).  Two steps, a
   non-permutation edit of every building's interior, two more steps -- against oracle twins that get the same edit."""
-  _need_gpu()
+  need_gpu()
   if path == "lds":
     monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
   g = load("h2_sb1_r9_random.npz")
@@ -242,34 +200,21 @@ def test_set_temps_with_a_grid_whose_sum_changes(path, monkeypatch):
   rs = np.random.RandomState(11)
   init = np.clip(294.0 + rs.randn(B, 1, 1) + 0.3 * rs.randn(B, 68, 98), 285.0, 305.0)
   acts = rs.uniform(-1, 1, size=(4, B, 2)).astype(np.float32)
-  sim = BatchedSimulator(_plan(p), SimConfig.sb1(), B, float(g["h_conv"]))
+  sim = BatchedSimulator(plan_from_npz(p), SimConfig.sb1(), B, float(g["h_conv"]))
   sim.reset(temps=torch.tensor(init.reshape(B, -1), dtype=torch.float64, device="cuda"))
   plan, prm = oracle_plan(p), oracle_params(g["params_json"])
   twins = [orc.OracleBuilding(plan, prm, 0.0, reset_temps=init[b].reshape(-1)) for b in range(B)]
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
-  rng_w, rng_a = (310.0, 355.0), (285.0, 300.0)
+  obs, rew, info = step_buffers(sim)
 
   def both(t):
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, t + 100), obs, rew, info)
+    sim.step(torch.tensor(acts[t], device="cuda"), step_in(g, t + 100), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     zt = sim.zone_temps().cpu().numpy()
+    r = rew.cpu().numpy()
     for b in range(B):
-      a, tt = acts[t, b], t + 100
-      native = [np.float32((float(a[0]) + 1.0) / 2.0 * (rng_w[1] - rng_w[0]) + rng_w[0]),
-                np.float32((float(a[1]) + 1.0) / 2.0 * (rng_a[1] - rng_a[0]) + rng_a[0])]
-      o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
-          t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]), e_carbon=float(g["e_carbon"][tt]),
-          g_price=float(g["g_price"][tt]), g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
-      assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
-      assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
+      o = twins[b].step(**step_kwargs(g, t + 100, t, SB1, acts[t, b]))
+      assert_step_matches(i[b], zt[b], r[b], o, (t, b))
       assert abs(i[b, 6] - o["t_supply_air"]) < 1e-4, (t, b, i[b, 6], o["t_supply_air"])   # (an fp32 output)
-      ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
-      assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b)
 
   both(0)
   both(1)
@@ -295,7 +240,7 @@ def test_iteration_limit_ends_the_step(limit):
   """simulator.py:348-368 with a limit that bites (the golden rollouts always converge): the
   register kernel starts sweep k+1 before it knows that sweep k was the last one allowed and has
   to undo it; sweep counts and grids against the oracle."""
-  _need_gpu()
+  need_gpu()
   import dataclasses
   g = load("h2_sb1_r9_random.npz")
   p = load("plan_r9_sb1.npz")
@@ -304,31 +249,18 @@ def test_iteration_limit_ends_the_step(limit):
   init = np.clip(294.0 + rs.randn(B, 1, 1) + 0.3 * rs.randn(B, 68, 98), 285.0, 305.0)
   acts = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
   cfg = dataclasses.replace(SimConfig.sb1(), iteration_limit=limit)
-  sim = BatchedSimulator(_plan(p), cfg, B, float(g["h_conv"]))
+  sim = BatchedSimulator(plan_from_npz(p), cfg, B, float(g["h_conv"]))
   assert sim.launch_info["path"] == 1
   sim.reset(temps=torch.tensor(init.reshape(B, -1), dtype=torch.float64, device="cuda"))
   plan, prm = oracle_plan(p), oracle_params(g["params_json"], iter_limit=limit)
   twins = [orc.OracleBuilding(plan, prm, 0.0, reset_temps=init[b].reshape(-1)) for b in range(B)]
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
-  rng_w, rng_a = (310.0, 355.0), (285.0, 300.0)
+  obs, rew, info = step_buffers(sim)
   hit = 0
   for t in range(T):
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, t + 100), obs, rew, info)
+    sim.step(torch.tensor(acts[t], device="cuda"), step_in(g, t + 100), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     for b in range(B):
-      a = acts[t, b]
-      native = [np.float32((float(a[0]) + 1.0) / 2.0 * (rng_w[1] - rng_w[0]) + rng_w[0]),
-                np.float32((float(a[1]) + 1.0) / 2.0 * (rng_a[1] - rng_a[0]) + rng_a[0])]
-      tt = t + 100
-      o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
-          t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]),
-          e_carbon=float(g["e_carbon"][tt]), g_price=float(g["g_price"][tt]),
-          g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
+      o = twins[b].step(**step_kwargs(g, t + 100, t, cfg, acts[t, b]))
       assert i[b, 4] == o["n_sweeps"] <= limit, (t, b, i[b, 4], o["n_sweeps"])
       assert i[b, 5] == o["converged"], (t, b, i[b, 5], o["converged"])
       hit += int(o["n_sweeps"] == limit)
@@ -342,21 +274,18 @@ def test_per_building_weather_and_per_zone_occupancy():
   """The optional DEVICE inputs of sb_step_in: `t_amb_dev` [B][2] (every building its own
   ambient temperature now / next) and `occupancy_dev` [Z] (per-zone occupancy) -- BASELINE.json
   configs[2] semantics (per-instance weather).  Each building against its own oracle twin."""
-  _need_gpu()
+  need_gpu()
   g = load("h2_sb1_r9_random.npz")
   p = load("plan_r9_sb1.npz")
   B, T = 8, 12
   rs = np.random.RandomState(3)
   init = np.clip(294.0 + rs.randn(B, 1, 1) + 0.2 * rs.randn(B, 68, 98), 285.0, 305.0)
   acts = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
-  sim = BatchedSimulator(_plan(p), SimConfig.sb1(), B, float(g["h_conv"]))
+  sim = BatchedSimulator(plan_from_npz(p), SimConfig.sb1(), B, float(g["h_conv"]))
   sim.reset(temps=torch.tensor(init.reshape(B, -1), dtype=torch.float64, device="cuda"))
   plan, prm = oracle_plan(p), oracle_params(g["params_json"])
   twins = [orc.OracleBuilding(plan, prm, 0.0, reset_temps=init[b].reshape(-1)) for b in range(B)]
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
-  rng_w, rng_a = (310.0, 355.0), (285.0, 300.0)
+  obs, rew, info = step_buffers(sim)
   offs = np.linspace(-12.0, 9.0, B)                       # building b lives in a climate offs[b] K away
   occ = np.array([0.0, 1.0, 2.5, 4.0, 0.5, 3.0, 1.5, 0.0, 2.0])[:sim.Z]
   occ_dev = torch.tensor(occ, dtype=torch.float64, device="cuda")
@@ -364,7 +293,7 @@ def test_per_building_weather_and_per_zone_occupancy():
     tt = t + 100
     amb = np.stack([float(g["t_amb_now"][tt]) + offs + 0.05 * t, float(g["t_amb_next"][tt]) + offs + 0.05 * (t + 1)], axis=1)
     amb_dev = torch.tensor(amb, dtype=torch.float64, device="cuda")
-    si = _step_in(g, tt)
+    si = step_in(g, tt)
     si.t_amb_dev = amb_dev.data_ptr()
     si.occupancy_dev = occ_dev.data_ptr()
     sim.step(torch.tensor(acts[t], device="cuda"), si, obs, rew, info)
@@ -372,19 +301,12 @@ def test_per_building_weather_and_per_zone_occupancy():
     zt = sim.zone_temps().cpu().numpy()
     r = rew.cpu().numpy()
     for b in range(B):
-      a = acts[t, b]
-      native = [np.float32((float(a[0]) + 1.0) / 2.0 * (rng_w[1] - rng_w[0]) + rng_w[0]),
-                np.float32((float(a[1]) + 1.0) / 2.0 * (rng_a[1] - rng_a[0]) + rng_a[0])]
-      o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(amb[b, 0]), h_conv=float(g["h_conv"]),
-          t_amb_next=float(amb[b, 1]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=occ, e_price=float(g["e_price"][tt]), e_carbon=float(g["e_carbon"][tt]),
-          g_price=float(g["g_price"][tt]), g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
+      kw = step_kwargs(g, tt, t, SB1, acts[t, b])
+      kw.update(t_amb_now=float(amb[b, 0]), t_amb_next=float(amb[b, 1]), occupancy=occ)   # the building's own
+      o = twins[b].step(**kw)
       assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
       assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
-      ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
-      assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b)
+      assert rates_match(i[b, :4], oracle_rates(o)), (t, b)
       assert abs(float(r[b]) - o["reward"]) < 1e-6, (t, b)
   grid = sim.temps().cpu().numpy()
   for b in range(B):
@@ -399,7 +321,7 @@ def test_device_side_per_building_weather_through_the_environment_api():
   (low, high), temperatures generated on the device from one host factor -- through
   BatchedEnvironment.reset()/step(); every building against an oracle twin driven by its own
   host WeatherController."""
-  _need_gpu()
+  need_gpu()
   import datetime as dt
   from sbsim_amd.environment import BatchedEnvironment
   from sbsim_amd.host_inputs import BatchedSinusoidWeather, WeatherController
@@ -411,7 +333,7 @@ def test_device_side_per_building_weather_through_the_environment_api():
   high = low + np.array([4.0, 9.5, 10.0, 12.0, 6.5, 20.0])
   weather = BatchedSinusoidWeather(low, high, convection_coefficient=float(g["h_conv"]))
   start = dt.datetime(2023, 7, 6, 9, 30, 0)
-  env = BatchedEnvironment(_plan(p), B, config=SimConfig.sb1(), weather=weather, start_timestamp=start,
+  env = BatchedEnvironment(plan_from_npz(p), B, config=SimConfig.sb1(), weather=weather, start_timestamp=start,
                            holiday_calendar=None, collect_info=True)
   ts0 = env.reset()
   names = env.field_names
@@ -421,7 +343,6 @@ def test_device_side_per_building_weather_through_the_environment_api():
   twins = [orc.OracleBuilding(plan, prm, float(env.config.initial_temp)) for _ in range(B)]
   ctrl = [WeatherController(lo, hi) for lo, hi in zip(low, high)]
   acts = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
-  rng_w, rng_a = env.config.action_ranges
   for t in range(T):
     now = env.current_simulation_timestamp
     si = env.make_step_in(now)
@@ -430,15 +351,12 @@ def test_device_side_per_building_weather_through_the_environment_api():
     info = env.info.cpu().numpy()
     nxt = now + dt.timedelta(seconds=300)
     for b in range(B):
-      a = acts[t, b]
-      native = [np.float32((float(a[0]) + 1.0) / 2.0 * (rng_w[1] - rng_w[0]) + rng_w[0]),
-                np.float32((float(a[1]) + 1.0) / 2.0 * (rng_a[1] - rng_a[0]) + rng_a[0])]
       o = twins[b].step(
           now_ts=300.0 * t, t_amb_now=ctrl[b].get_current_temp(now), h_conv=float(g["h_conv"]),
           t_amb_next=ctrl[b].get_current_temp(nxt), comfort_now=bool(si.comfort_now),
           comfort_prev=si.comfort_prev == 1, comfort_next=bool(si.comfort_next), occupancy=si.occupancy,
           e_price=si.e_price, e_carbon=si.e_carbon, g_price=si.g_price, g_carbon=si.g_carbon,
-          action=native, observe=True)
+          action=native_action(env.config, acts[t, b]), observe=True)
       assert int(info[b, 4]) == o["n_sweeps"], (t, b, info[b, 4], o["n_sweeps"])
       assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
       assert abs(float(out.reward[b]) - o["reward"]) < 1e-6, (t, b)
@@ -456,7 +374,7 @@ def test_full_size_batch_register_and_lds_kernels_agree(monkeypatch):
   with the tail scan, grid in LDS with the banded DPP sweep -- must take the same number of
   Gauss-Seidel sweeps for EVERY building at every step and end within 1e-9 K of each other;
   sb_reset(temps) / sb_get_temps round-trips the caller's layout exactly."""
-  _need_gpu()
+  need_gpu()
   B, T = 65536, 10
   p = load("plan_r9_sb1.npz")
   g = load("h2_sb1_r9_random.npz")
@@ -469,17 +387,15 @@ def test_full_size_batch_register_and_lds_kernels_agree(monkeypatch):
   for force_lds in (False, True):
     if force_lds:
       monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
-    sim = BatchedSimulator(_plan(p), SimConfig.sb1(), B, float(g["h_conv"]))
+    sim = BatchedSimulator(plan_from_npz(p), SimConfig.sb1(), B, float(g["h_conv"]))
     assert sim.launch_info["path"] == (0 if force_lds else 1)
     sim.reset(temps=init)
     assert torch.equal(sim.temps().reshape(B, -1), init)
     sims.append(sim)
-  obs = [torch.zeros((B, s.O), dtype=torch.float32, device="cuda") for s in sims]
-  rew = [torch.zeros((B,), dtype=torch.float32, device="cuda") for _ in sims]
-  info = [torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda") for _ in sims]
+  obs, rew, info = zip(*[step_buffers(s) for s in sims])
   total = 0.0
   for t in range(T):
-    si = _step_in(g, 100 + t)
+    si = step_in(g, 100 + t)
     for k, sim in enumerate(sims):
       sim.step(acts[t], si, obs[k], rew[k], info[k])
     assert torch.equal(info[0][:, 4], info[1][:, 4]), t          # sweeps, every building
@@ -500,7 +416,7 @@ def test_roll_kernel_workgroups_with_idle_and_drawing_wavefronts(B, monkeypatch)
   in LDS: batches that leave wavefronts of the last workgroup without a building (1, 3, 5) and one just
   above the 1,024 resident wavefronts (the first draws from the device counter) against the LDS-grid
   kernel -- equal sweep counts for every building, grids within 1e-9 K."""
-  _need_gpu()
+  need_gpu()
   T = 8
   p = load("plan_r9_sb1.npz")
   g = load("h2_sb1_r9_random.npz")
@@ -513,18 +429,16 @@ def test_roll_kernel_workgroups_with_idle_and_drawing_wavefronts(B, monkeypatch)
   for force_lds in (False, True):
     if force_lds:
       monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
-    sim = BatchedSimulator(_plan(p), SimConfig.sb1(), B, float(g["h_conv"]))
+    sim = BatchedSimulator(plan_from_npz(p), SimConfig.sb1(), B, float(g["h_conv"]))
     assert sim.launch_info["path"] == (0 if force_lds else 1)
     if not force_lds:
       assert sim.launch_info["kernel"] == 3 and sim.launch_info["waves_per_workgroup"] == 4
       assert sim.launch_info["workgroups"] == min((B + 3) // 4, 256)
     sim.reset(temps=init)
     sims.append(sim)
-  obs = [torch.zeros((B, s.O), dtype=torch.float32, device="cuda") for s in sims]
-  rew = [torch.zeros((B,), dtype=torch.float32, device="cuda") for _ in sims]
-  info = [torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda") for _ in sims]
+  obs, rew, info = zip(*[step_buffers(s) for s in sims])
   for t in range(T):
-    si = _step_in(g, 100 + t)
+    si = step_in(g, 100 + t)
     for k, sim in enumerate(sims):
       sim.step(acts[t], si, obs[k], rew[k], info[k])
     assert torch.equal(info[0][:, 4], info[1][:, 4]), t
@@ -543,7 +457,7 @@ def test_mixed_classes_at_size_block_and_lds_kernels_agree(rooms, room_shape, B,
   predicted blocks (step_two.hip; band: step_band.hip) and the LDS-grid kernel must take the same number
   of Gauss-Seidel sweeps for EVERY building at every step (tens of sweeps each, blocks overrunning now
   and then) and end within 1e-9 K of each other."""
-  _need_gpu()
+  need_gpu()
   if band:
     monkeypatch.setenv("SBSIM_BAND_PATH", "1")
   from sbsim_amd.floorplan import rectangular_floor_plan
@@ -567,12 +481,10 @@ def test_mixed_classes_at_size_block_and_lds_kernels_agree(rooms, room_shape, B,
     sim.reset(temps=init)
     assert torch.equal(sim.temps().reshape(B, -1), init)
     sims.append(sim)
-  obs = [torch.zeros((B, s.O), dtype=torch.float32, device="cuda") for s in sims]
-  rew = [torch.zeros((B,), dtype=torch.float32, device="cuda") for _ in sims]
-  info = [torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda") for _ in sims]
+  obs, rew, info = zip(*[step_buffers(s) for s in sims])
   total = 0.0
   for t in range(T):
-    si = _step_in(g, 100 + t)
+    si = step_in(g, 100 + t)
     for k, sim in enumerate(sims):
       sim.step(acts[t], si, obs[k], rew[k], info[k])
     assert torch.equal(info[0][:, 4], info[1][:, 4]), t          # sweeps, every building
@@ -590,7 +502,7 @@ def test_full_size_isothermal_fixed_point():
   T_amb <= cooling setpoint) and every thermostat OFF, is a fixed point of the step: VAV power
   0, one Gauss-Seidel sweep, the grid unchanged to round-off -- for all 65,536 buildings, on
   both sweep kernels."""
-  _need_gpu()
+  need_gpu()
   B = 65536
   p = load("plan_r9_sb1.npz")
   g = load("h2_sb1_r9_random.npz")
@@ -599,14 +511,12 @@ def test_full_size_isothermal_fixed_point():
     if force_lds:
       os.environ["SBSIM_FORCE_LDS_PATH"] = "1"
     try:
-      sim = BatchedSimulator(_plan(p), SimConfig.sb1(), B, float(g["h_conv"]))
+      sim = BatchedSimulator(plan_from_npz(p), SimConfig.sb1(), B, float(g["h_conv"]))
     finally:
       os.environ.pop("SBSIM_FORCE_LDS_PATH", None)
     sim.reset(initial_temp=t_amb)
-    obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-    rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-    info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
-    si = _step_in(g, 100)            # mid-morning: comfort window 294..297 K around 295 K
+    obs, rew, info = step_buffers(sim)
+    si = step_in(g, 100)            # mid-morning: comfort window 294..297 K around 295 K
     si.t_amb_now = si.t_amb_next = t_amb
     si.has_action = 0                 # setpoints stay at the constructor values (285 / 298 K)
     for _ in range(3):
@@ -621,10 +531,10 @@ def test_full_size_isothermal_fixed_point():
 def test_environment_api_episode_bookkeeping():
   """environment.py:1165-1212,1311-1368: restart / N transitions / termination / auto-reset,
   plus observation normalisation and auxiliary features."""
-  _need_gpu()
+  need_gpu()
   g = load("h2_sb1_r9_const.npz")
   from sbsim_amd.environment import SB1_OBSERVATION_NORMALIZATION
-  env = BatchedEnvironment(_plan(load("plan_r9_sb1.npz")), 4, num_days_in_episode=5 * 300 / 86400.0,
+  env = BatchedEnvironment(plan_from_npz(load("plan_r9_sb1.npz")), 4, num_days_in_episode=5 * 300 / 86400.0,
                            holiday_calendar=None, observation_normalization=SB1_OBSERVATION_NORMALIZATION,
                            collect_info=True)
   assert env.action_spec().shape == (2,) and env.observation_spec().shape == (46,)
@@ -653,10 +563,10 @@ def test_environment_api_episode_bookkeeping():
 def test_gym_vector_view_autoresets_like_gymnasium():
   """GymVectorEnv: (obs, reward, terminated, truncated, info) over a short episode and the
   next-step autoreset; the same numbers as the TimeStep API."""
-  _need_gpu()
+  need_gpu()
   from sbsim_amd.environment import BatchedEnvironment, GymVectorEnv
   B = 4
-  plan = _plan(load("plan_r9_sb1.npz"))
+  plan = plan_from_npz(load("plan_r9_sb1.npz"))
   steps = 5                                       # 5 transitions + the terminal step
   mk = lambda: BatchedEnvironment(plan, B, num_days_in_episode=steps * 300.0 / 86400.0, holiday_calendar=None)
   venv, ref = GymVectorEnv(mk()), mk()
@@ -684,7 +594,7 @@ def test_gym_vector_view_autoresets_like_gymnasium():
 
 
 def test_abi_error_paths():
-  _need_gpu()
+  need_gpu()
   L = _ffi.load()
   assert L.sb_abi_version() == _ffi.SB_ABI_VERSION
   h = C.c_void_p()
@@ -693,14 +603,10 @@ def test_abi_error_paths():
   p = load("plan_small_test.npz")
   cfg = SimConfig(ahu_heating_air_temp_setpoint=300.0, ahu_cooling_air_temp_setpoint=290.0)
   with pytest.raises(_ffi.SbsimError, match="cooling_air_temp_setpoint"):
-    BatchedSimulator(_plan(p), cfg, 2, 12.0)
-  sim = BatchedSimulator(_plan(p), SimConfig(), 2, 12.0)
+    BatchedSimulator(plan_from_npz(p), cfg, 2, 12.0)
+  sim = BatchedSimulator(plan_from_npz(p), SimConfig(), 2, 12.0)
   with pytest.raises(ValueError):
     sim.step(torch.zeros((3, 2), device="cuda"), _ffi.StepIn(), None, torch.zeros(2, device="cuda"))
-
-
-def _oracle_twin(plan, cfg, init_flat):
-  return oracle_twin(plan, cfg, init_flat)
 
 
 @pytest.mark.parametrize("rooms,room_shape,orientation,path", [
@@ -769,8 +675,8 @@ def test_mixed_floor_plans_against_oracle(rooms, room_shape, orientation, path, 
     kern, path = path, 1
     if kern == 5:
       monkeypatch.setenv("SBSIM_BAND_PATH", "1")
-  _check_plan_against_oracle(rectangular_floor_plan(rooms, room_shape), rooms[0] * rooms[1], orientation, path, monkeypatch,
-                             expect_kernel=kern, expect_waves=waves)
+  check_plan_against_oracle(rectangular_floor_plan(rooms, room_shape), rooms[0] * rooms[1], orientation, path, monkeypatch,
+                            expect_kernel=kern, expect_waves=waves)
 
 
 @pytest.mark.gpu
@@ -788,8 +694,8 @@ def test_block_kernels_tail_rows_and_overrun_blocks(haste, slack, kern, monkeypa
   monkeypatch.setenv("SBSIM_DEBUG_PRED_SLACK", str(slack))
   if kern == 5:
     monkeypatch.setenv("SBSIM_BAND_PATH", "1")
-  _check_plan_against_oracle(fp, 126, "rows", 1, monkeypatch, expect_steps=76 + 64 - 1 + 8 if kern == 4 else 76 + 8,
-                             expect_kernel=kern)
+  check_plan_against_oracle(fp, 126, "rows", 1, monkeypatch, expect_steps=76 + 64 - 1 + 8 if kern == 4 else 76 + 8,
+                            expect_kernel=kern)
 
 
 @pytest.mark.gpu
@@ -807,7 +713,7 @@ def test_two_rows_kernel_measure_free_periods(kappa, rooms, shape, zones, monkey
     monkeypatch.setenv("SBSIM_TWO_NO_SKIP", "1")
   else:
     monkeypatch.setenv("SBSIM_DEBUG_SKIP_KAPPA", kappa)
-  _check_plan_against_oracle(rectangular_floor_plan(rooms, shape), zones, "auto", 1, monkeypatch, expect_kernel=4, T=16)
+  check_plan_against_oracle(rectangular_floor_plan(rooms, shape), zones, "auto", 1, monkeypatch, expect_kernel=4, T=16)
 
 
 @pytest.mark.parametrize("kern", [5, 4])
@@ -819,8 +725,8 @@ def test_block_kernels_iteration_limit(limit, kern, monkeypatch):
   from sbsim_amd.floorplan import rectangular_floor_plan
   if kern == 5:
     monkeypatch.setenv("SBSIM_BAND_PATH", "1")
-  _check_plan_against_oracle(rectangular_floor_plan((8, 5), (12, 14)), 40, "auto", 1, monkeypatch,
-                             iteration_limit=limit, expect_kernel=kern)
+  check_plan_against_oracle(rectangular_floor_plan((8, 5), (12, 14)), 40, "auto", 1, monkeypatch,
+                            iteration_limit=limit, expect_kernel=kern)
 
 
 @pytest.mark.gpu
@@ -837,7 +743,7 @@ def test_band_kernel_four_wavefronts_tail_rows_and_overrun_blocks(haste, slack, 
   assert fp.shape == (260, 80)
   monkeypatch.setenv("SBSIM_DEBUG_PRED_HASTE", str(haste))
   monkeypatch.setenv("SBSIM_DEBUG_PRED_SLACK", str(slack))
-  _check_plan_against_oracle(fp, 36, "rows", 1, monkeypatch, expect_steps=80 + 8, expect_kernel=5, expect_waves=4, B=4, T=10)
+  check_plan_against_oracle(fp, 36, "rows", 1, monkeypatch, expect_steps=80 + 8, expect_kernel=5, expect_waves=4, B=4, T=10)
 
 
 @pytest.mark.gpu
@@ -845,113 +751,8 @@ def test_band_kernel_four_wavefronts_tail_rows_and_overrun_blocks(haste, slack, 
 def test_band_kernel_four_wavefronts_iteration_limit(limit, monkeypatch):
   """simulator.py:348-368 with a limit that bites, four wavefronts per building (203 x 87 inside the ring)."""
   from sbsim_amd.floorplan import rectangular_floor_plan
-  _check_plan_against_oracle(rectangular_floor_plan((10, 4), (19, 20)), 40, "rows", 1, monkeypatch,
-                             iteration_limit=limit, expect_kernel=5, expect_waves=4, B=4, T=8)
-
-
-def _need_experimental_kernels(variant, monkeypatch):
-  """The multi-sweep / overlapped streaming kernels are exact but slower than k_sweep_stream: since round 6 they are in the
-  library only when it is built with SBSIM_BUILD_EXPERIMENTAL=1 (sbsim_amd/build.py); the default library ignores the flags.
-  __graft_entry__.build() builds that library too (sbsim_amd/libsbsim_amd_exp.so): a test of those kernels loads it in
-  place of the default one for its duration."""
-  if variant and not _ffi.load().sb_has_experimental_kernels():
-    monkeypatch.setattr(_ffi, "LIB_PATH", os.path.join(os.path.dirname(_ffi.__file__), "libsbsim_amd_exp.so"))
-    monkeypatch.setattr(_ffi, "_lib", None)
-    assert _ffi.load().sb_has_experimental_kernels()
-
-
-def _check_plan_against_oracle(file_plan, n_zones, orientation, path, monkeypatch, expect_steps=None,
-                               iteration_limit=None, expect_kernel=None, B=6, T=14, expect_waves=None,
-                               init=None, acts=None, cfg=None, env=None, buildings=None, on_launch=None,
-                               golden=None, on_step=None, force_path=True, h_conv=None, step_sec=300.0,
-                               on_end=None):
-  """Every building against its oracle twin at every step.  `file_plan` may be a FloorPlan; `init` [B, H*W], `acts`
-  [T, B, 2] and `cfg` replace the seeded initial grids, actions and SimConfig.sb1(); `env` sets developer switches;
-  `buildings` names the buildings that get a twin (default: every one); `on_launch` is called with the launch_info;
-  `golden` replaces the step-input rows of h2_sb1_r9_random.npz; `on_step(sim, t, obs, outs)` is called after every
-  step's own checks with the observation rows (numpy) and the twins' results of the step ({building: dict});
-  `force_path=False` leaves the choice between the LDS-grid and the streaming kernel to the library (`path` is then
-  only what the launch must report); `h_conv` replaces the rows' convection coefficient and `step_sec` the 300 s between
-  the twins' timestamps (a cfg of another time_step_sec); `on_end(grid, twins)` is called with the final grids
-  [B, H, W] and the twins ({building: OracleBuilding}) before the final grids are compared.
-  Returns the info rows and the grids after every step."""
-  _need_gpu()
-  for k, v in dict(env or {}).items():
-    monkeypatch.setenv(k, v)
-  g = load("h2_sb1_r9_random.npz") if golden is None else golden
-  plan = file_plan if isinstance(file_plan, FloorPlan) else FloorPlan.from_file_input(file_plan, Materials.sb1(), 10.0, 300.0)
-  H, W = plan.shape
-  rs = np.random.RandomState(11)
-  init_r = np.clip(294.0 + 2.0 * rs.randn(B, 1) + 0.2 * rs.randn(B, H * W), 285.0, 305.0)
-  acts_r = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
-  init = init_r if init is None else init
-  acts = acts_r if acts is None else acts
-  cfg = SimConfig.sb1() if cfg is None else cfg
-  if iteration_limit is not None:
-    import dataclasses
-    cfg = dataclasses.replace(cfg, iteration_limit=iteration_limit)
-  if orientation == "generic":
-    monkeypatch.setenv("SBSIM_FORCE_GENERIC_SWEEP", "1")
-    orientation = "rows"
-  if path == 0 and force_path:
-    monkeypatch.setenv("SBSIM_FORCE_LDS_PATH", "1")
-  if path == 2 and H * W < 100000 and force_path:
-    monkeypatch.setenv("SBSIM_FORCE_STREAM_PATH", "1")   # small plans reach the streaming kernel only when told to
-  h_conv = float(g["h_conv"]) if h_conv is None else float(h_conv)
-  sim = BatchedSimulator(plan, cfg, B, h_conv, orientation=orientation)
-  assert sim.Z == n_zones and sim.launch_info["path"] == path
-  if expect_steps is not None:
-    assert sim.launch_info["sweep_steps"] == expect_steps   # the two-rows kernel with two tail rows
-  if expect_kernel is not None:
-    assert sim.launch_info["kernel"] == expect_kernel
-  if expect_waves is not None:
-    assert sim.launch_info["waves_per_building"] == expect_waves
-  if on_launch is not None:
-    on_launch(sim.launch_info)
-  sim.reset(temps=torch.tensor(init, dtype=torch.float64, device="cuda"))
-  checked = list(range(B)) if buildings is None else [int(b) for b in buildings]
-  twins = {b: _oracle_twin(plan, cfg, init[b]) for b in checked}
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
-  lo, hi = cfg.action_ranges
-  infos, grids = [], []
-  for t in range(T):
-    tt = 96 + t   # mid-morning: occupied, comfort mode
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, tt), obs, rew, info)
-    i = info.cpu().numpy().astype(np.float64)
-    zt = sim.zone_temps().cpu().numpy()
-    r = rew.cpu().numpy()
-    infos.append(i)
-    grids.append(sim.temps().cpu().numpy())
-    outs = {}
-    for b in checked:
-      a = acts[t, b]
-      native = [np.float32((float(a[0]) + 1.0) / 2.0 * (lo[1] - lo[0]) + lo[0]),
-                np.float32((float(a[1]) + 1.0) / 2.0 * (hi[1] - hi[0]) + hi[0])]
-      o = twins[b].step(
-          now_ts=step_sec * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=h_conv,
-          t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]),
-          e_carbon=float(g["e_carbon"][tt]), g_price=float(g["g_price"][tt]),
-          g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
-      assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
-      assert i[b, 5] == o["converged"], (t, b, i[b, 5], o["converged"])
-      assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
-      ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
-      assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b)
-      assert abs(float(r[b]) - o["reward"]) < 2e-6, (t, b)
-      outs[b] = o
-    if on_step is not None:
-      on_step(sim, t, obs.cpu().numpy(), outs)
-  grid = sim.temps().cpu().numpy()
-  if on_end is not None:
-    on_end(grid, twins)
-  for b in checked:
-    assert np.abs(grid[b] - twins[b].grid()).max() < T_TOL, b
-  sim.close()
-  return infos, grids
+  check_plan_against_oracle(rectangular_floor_plan((10, 4), (19, 20)), 40, "rows", 1, monkeypatch,
+                            iteration_limit=limit, expect_kernel=5, expect_waves=4, B=4, T=8)
 
 
 @pytest.mark.parametrize("rooms,room_shape,orientation,waves", [
@@ -968,13 +769,13 @@ def test_streaming_kernel_against_oracle(rooms, room_shape, orientation, waves, 
   LDS) forced onto floor plans the other kernels own: sweep counts EQUAL, temperatures within 1e-8 K of
   the CPU-oracle twins."""
   from sbsim_amd.floorplan import rectangular_floor_plan
-  _need_experimental_kernels(multi_sweep, monkeypatch)
+  need_experimental_kernels(multi_sweep, monkeypatch)
   if multi_sweep == "overlapped":   # step_stream.hip's k_sweep_stream_roll: sweeps overlapped on two grids that take turns (opt-in)
     monkeypatch.setenv("SBSIM_STREAM_ROLL", "1")
   elif multi_sweep:   # step_stream_ms.hip: up to four sweeps per pass over the grid (parallelogram tiling; opt-in)
     monkeypatch.setenv("SBSIM_STREAM_MS", "1")
-  _check_plan_against_oracle(rectangular_floor_plan(rooms, room_shape), rooms[0] * rooms[1], orientation, 2, monkeypatch,
-                             expect_kernel=6, expect_waves=waves)
+  check_plan_against_oracle(rectangular_floor_plan(rooms, room_shape), rooms[0] * rooms[1], orientation, 2, monkeypatch,
+                            expect_kernel=6, expect_waves=waves)
 
 
 @pytest.mark.parametrize("multi_sweep", [False, True, "overlapped"])
@@ -985,12 +786,12 @@ def test_floor_plan_beyond_one_cu_against_oracle(multi_sweep, monkeypatch):
   from sbsim_amd.floorplan import rectangular_floor_plan
   fp = rectangular_floor_plan((14, 9), (20, 43))
   assert fp.shape == (299, 401)
-  _need_experimental_kernels(multi_sweep, monkeypatch)
+  need_experimental_kernels(multi_sweep, monkeypatch)
   if multi_sweep == "overlapped":
     monkeypatch.setenv("SBSIM_STREAM_ROLL", "1")
   elif multi_sweep:
     monkeypatch.setenv("SBSIM_STREAM_MS", "1")
-  _check_plan_against_oracle(fp, 126, "rows", 2, monkeypatch, expect_kernel=6, expect_waves=5, B=2, T=3)
+  check_plan_against_oracle(fp, 126, "rows", 2, monkeypatch, expect_kernel=6, expect_waves=5, B=2, T=3)
 
 
 @pytest.mark.parametrize("kernel", ["auto", "lds", "stream"])
@@ -1000,21 +801,12 @@ def test_rectangular_building_without_exterior_ring(kernel, monkeypatch):
   trim box is the whole grid and the corner / edge formulas sit on its rim.  One cold thermostat-only
   step of the 3x3-room scenario: 100 sweeps, the reference's KAT 301.895482 (simulator_test.py:955-987)
   and its final grid (tests/golden/rect_building_cold200.npz, from the reference's own Building)."""
-  _need_gpu()
+  need_gpu()
   import json
   g = load("rect_building_cold200.npz")
   h = load("h1_r9_test_cold200.npz")
-  H, W = g["conductivity"].shape
-  rs, bs = g["room_shape"], g["building_shape"]
-  label = np.full((H, W), -1, dtype=np.int64)
-  for zx in range(bs[0]):
-    for zy in range(bs[1]):
-      x0, y0 = zx * (rs[0] + 1) + 2, zy * (rs[1] + 1) + 2  # building.py:167-180
-      label[x0:x0 + rs[0], y0:y0 + rs[1]] = zx * bs[1] + zy
-  plan = FloorPlan(conductivity=g["conductivity"], heat_capacity=g["heat_capacity"], density=g["density"],
-                   exterior_space=np.zeros((H, W), bool), zone_label=label, diffusers=g["diffusers"],
-                   cv_size_cm=float(g["cv_size_cm"]), floor_height_cm=float(g["floor_height_cm"]),
-                   skip_exterior_neighbors=False)
+  plan = ringless_plan(g)
+  H, W = plan.shape
   prm = json.loads(str(h["params_json"]))
   cfg = SimConfig(
       time_step_sec=prm["dt"], convergence_threshold=prm["conv_threshold"], iteration_limit=prm["iter_limit"],
@@ -1034,8 +826,7 @@ def test_rectangular_building_without_exterior_ring(kernel, monkeypatch):
   sim = BatchedSimulator(plan, cfg, B, 12.0)
   assert sim.launch_info["path"] == {"auto": 1, "lds": 0, "stream": 2}[kernel]
   sim.reset()
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  _, rew, info = step_buffers(sim)
   si = _ffi.StepIn()
   si.t_amb_now = si.t_amb_next = 296.0
   si.comfort_now = si.comfort_next = 0
@@ -1067,7 +858,7 @@ def test_mixed_environment_gives_every_building_its_own_generator_stream():
   to class or from rank to rank -- class k's building i draws as building sum(totals[:k]) + (its index inside the
   class) of the whole mixed batch.  Two classes of the SAME plan: class 1 equals a BatchedEnvironment whose generator
   starts at building 4, and differs from class 0; rank 1 of 2 continues where rank 0 stopped."""
-  _need_gpu()
+  need_gpu()
   from sbsim_amd import host_inputs
   from sbsim_amd.environment import BatchedEnvironment, MixedBatchedEnvironment
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
@@ -1110,7 +901,7 @@ def test_mixed_environment_equals_its_classes_stepped_alone():
   slice of the TimeStep equals what a BatchedEnvironment of that class alone returns for the same actions --
   observations in the first `observation_widths[k]` columns, zeros after -- over an episode end and the reset
   that follows; the classes share the clock."""
-  _need_gpu()
+  need_gpu()
   from sbsim_amd.environment import BatchedEnvironment, MixedBatchedEnvironment
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
   plans = [FloorPlan.from_file_input(rectangular_floor_plan(r, sh), Materials.sb1(), 10.0, 300.0)
@@ -1146,7 +937,7 @@ def test_bench_mixed_config_line_and_its_twins():
   """`bench.py --config mixed` (BASELINE.json configs[2]) at the full batch, two timed rounds: the JSON line
   parses, names the three classes' kernels, and 64 buildings per class agree with their CPU-oracle twins
   (sweep counts EQUAL, zone temperatures within 1e-8 K) at every step of the run."""
-  _need_gpu()
+  need_gpu()
   d = _run_bench(["--config", "mixed", "--buildings", "65535", "--steps", "2", "--warmup", "1", "--check-buildings", "64"])
   assert d["n_gpus"] == 1 and d["steps"] == 2 and d["unit"] == "zone-updates/s" and d["value"] > 1e7
   assert d["timed_through"] == "MixedBatchedEnvironment.step()" and d["config"]["observation_width"] == 3 * 126 + 19
@@ -1162,7 +953,7 @@ def test_bench_mixed_config_line_and_its_twins():
 def test_bench_policy_config_line_and_its_twins():
   """`bench.py --config policy` (BASELINE.json configs[4]: the batch driven by a SAC-shaped actor on the
   same GPU): the line parses and 64 buildings agree with their oracle twins fed the actor's actions."""
-  _need_gpu()
+  need_gpu()
   d = _run_bench(["--config", "policy", "--steps", "2", "--warmup", "2", "--check-buildings", "64"])
   assert d["n_gpus"] == 1 and d["gathered_returns"] == 65536 and d["value"] > 1e7
   par = d["config"]["parity_vs_oracle"]
@@ -1175,7 +966,7 @@ def test_bench_two_ranks_sharing_one_gpu(monkeypatch):
   """The N > 1 code path of bench.py on a one-GPU box (SBSIM_BENCH_SHARE_GPU=1: both ranks on device 0, gloo
   with host-staged collectives instead of RCCL): self-launch under torch.distributed.run, per-rank shards
   and seeds, barrier-bracketed timing, max over ranks, the gathered returns of both ranks, one JSON line."""
-  _need_gpu()
+  need_gpu()
   monkeypatch.setenv("SBSIM_BENCH_SHARE_GPU", "1")
   d = _run_bench(["--gpus", "2", "--buildings", "8192", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"])
   assert d["n_gpus"] == 2 and d["gathered_returns"] == 16384 and d["scaling"] == "weak"
@@ -1205,7 +996,7 @@ def test_bench_three_ranks_sharing_one_gpu(monkeypatch):
   class sharded three ways and gathered by class.  Three ranks, not eight: with this test's process and the launcher's
   that is five processes holding the one device, within what a shared GPU host allows; eight ranks of the same code
   are covered on CPU (tests/test_bench_launcher.py, tests/test_distributed_cpu.py)."""
-  _need_gpu()
+  need_gpu()
   monkeypatch.setenv("SBSIM_BENCH_SHARE_GPU", "1")
   d = _run_bench(["--gpus", "3", "--buildings", "8192", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"])
   assert d["n_gpus"] == 3 and d["gathered_returns"] == 24576 and d["scaling"] == "weak" and d["rccl_ranks"] == 3
@@ -1223,7 +1014,7 @@ def test_bench_three_ranks_sharing_one_gpu(monkeypatch):
 def test_bench_dump_outputs_are_reproducible(tmp_path):
   """`bench.py --dump-outputs DIR`: after the K timed steps (`--steps` sets K) the last step's outputs land in DIR as
   float32 / float64 .npy files, and two runs with the same arguments write the same arrays, bit for bit."""
-  _need_gpu()
+  need_gpu()
   B, K = 512, 3
   runs = []
   for k in range(2):
@@ -1246,7 +1037,7 @@ def test_bench_through_the_public_env_api_costs_the_same():
   """The headline line steps through BatchedSimulator.step(phases=...) so that HIP events can bracket the
   sweep kernel; `--through-env-api` times BatchedEnvironment.step() itself (host-side step inputs, sb_step,
   TimeStep): within 3 % of the phases path."""
-  _need_gpu()
+  need_gpu()
   import json
   common = ["--gpus", "1", "--steps", "20", "--warmup", "30", "--no-cpu-baseline", "--no-also"]
   seen = []
@@ -1270,7 +1061,7 @@ def test_bench_two_gpus_when_the_box_has_them(monkeypatch):
   one device the same command is refused before any environment is built -- one process per GPU, and RCCL cannot
   put two ranks on one device (SBSIM_BENCH_SHARE_GPU=1 is the explicit way to share it, over gloo)."""
   import subprocess, sys
-  _need_gpu()
+  need_gpu()
   monkeypatch.delenv("SBSIM_BENCH_SHARE_GPU", raising=False)
   if torch.cuda.device_count() < 2:
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

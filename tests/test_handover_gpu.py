@@ -5,12 +5,12 @@ building and nothing a kernel keeps from one building to the next is ever read. 
 
   * SBSIM_DEBUG_CUS=1 shrinks the launch to one CU's workgroups, and the divergent batches are large enough for every
     workgroup (wavefront, on k_sweep_roll and k_sweep_lds) to run at least four buildings: every building against its
-    own oracle twin at every step, at the bars of tests/test_gpu_parity.py (_check_plan_against_oracle, unchanged);
+    own oracle twin at every step, at the bars of tests/twins.py (tests/parity.py's check_plan_against_oracle, unchanged);
     k_sweep_jacobi bitwise against tests/jacobi_restatement.py;
   * the device's own geometry, no switch: just more buildings than are handed out by index, the drawn ones and a fixed
     sample of the others against their twins;
   * the same batch with SBSIM_DEBUG_CUS=1, =3 and unset: who runs a building must not change a bit of the result
-    (k_sweep_stream: tests/test_state_snapshot.py's _assert_close -- its zone sums are LDS atomics in arrival order).
+    (k_sweep_stream: tests/parity.py's assert_close -- its zone sums are LDS atomics in arrival order).
 
 Every case asserts its kernel, its wavefront count and its hand-over depth from launch_info.
 
@@ -23,13 +23,12 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-from sbsim_amd import _ffi  # noqa: E402
 from sbsim_amd.environment import BatchedSimulator  # noqa: E402
 from tests import handover_cases as hc  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_gpu_parity import _check_plan_against_oracle, _need_gpu, _step_in  # noqa: E402
-from tests.test_jacobi_gpu import _env as _jacobi_env, _rollout_against_restatement  # noqa: E402
-from tests.test_state_snapshot import _assert_close, _assert_same  # noqa: E402
+from tests.parity import (assert_close, assert_same, check_plan_against_oracle, jacobi_env, need_gpu,  # noqa: E402
+                          rollout_against_restatement, step_buffers)
+from tests.twins import step_in  # noqa: E402
 
 
 def _depth_check(case, B, cus):
@@ -52,9 +51,9 @@ def test_every_building_against_its_twin_four_handovers_deep(name, monkeypatch):
   init, acts, _ = hc.case_batch(case)
   env = dict(case.env)
   env[hc.SWITCH] = "1"
-  infos, _ = _check_plan_against_oracle(fp, fp.n_zones, case.orientation, case.path, monkeypatch, expect_kernel=case.kernel,
-                                        expect_waves=case.waves, B=case.B, T=case.T, init=init, acts=acts,
-                                        cfg=hc.config(case), env=env, on_launch=_depth_check(case, case.B, 1))
+  infos, _ = check_plan_against_oracle(fp, fp.n_zones, case.orientation, case.path, monkeypatch, expect_kernel=case.kernel,
+                                       expect_waves=case.waves, B=case.B, T=case.T, init=init, acts=acts,
+                                       cfg=hc.config(case), env=env, on_launch=_depth_check(case, case.B, 1))
   n, conv = np.stack([i[:, 4] for i in infos]), np.stack([i[:, 5] for i in infos])
   assert hc.spread(n, conv, case.limit) is not None   # (equal to the oracle's, which the CPU test holds to the spread)
 
@@ -63,7 +62,7 @@ def test_every_building_against_its_twin_four_handovers_deep(name, monkeypatch):
 def test_drawn_buildings_on_the_devices_own_geometry(name, monkeypatch):
   """No switch: B = the buildings handed out by index + 7, so buildings static .. static + 6 are exactly the drawn ones.
   All of them, and a fixed sample of 8 of the others, against their twins at every step."""
-  _need_gpu()
+  need_gpu()
   case = hc.natural_case(name)
   monkeypatch.delenv(hc.SWITCH, raising=False)
   static = hc.natural_static(case)
@@ -75,25 +74,25 @@ def test_drawn_buildings_on_the_devices_own_geometry(name, monkeypatch):
     _depth_check(case, B, None)(info)
     assert hc.static_count(info) == static, (info, static)   # the device is the one the probe assumed
 
-  _check_plan_against_oracle(fp, fp.n_zones, case.orientation, case.path, monkeypatch, expect_kernel=case.kernel,
-                             expect_waves=case.waves, B=B, T=case.T, init=init, acts=acts, cfg=hc.config(case),
-                             env=dict(case.env), buildings=hc.natural_checked(static), on_launch=check)
+  check_plan_against_oracle(fp, fp.n_zones, case.orientation, case.path, monkeypatch, expect_kernel=case.kernel,
+                            expect_waves=case.waves, B=B, T=case.T, init=init, acts=acts, cfg=hc.config(case),
+                            env=dict(case.env), buildings=hc.natural_checked(static), on_launch=check)
 
 
 @pytest.mark.parametrize("name", list(hc.JACOBI_CASES))
 def test_jacobi_every_building_bitwise_four_handovers_deep(name, monkeypatch):
   """k_sweep_jacobi's `next` broadcast: every building of a divergent batch, every step, bitwise against the restatement
   (tests/test_jacobi_gpu.py's rollout check with the whole batch sampled)."""
-  _need_gpu()
+  need_gpu()
   case = hc.JACOBI_CASES[name]
   fp = hc.floor_plan(case)
   monkeypatch.setenv(hc.SWITCH, "1")
-  env = _jacobi_env(fp, case.B, config=hc.config(case))
+  env = jacobi_env(fp, case.B, config=hc.config(case))
   _depth_check(case, case.B, 1)(env.sim.launch_info)   # (one building per workgroup at a time)
   env.reset()
   init, _, _ = hc.case_batch(case)
   env.sim.reset(temps=torch.tensor(init.astype(np.float32).astype(np.float64), dtype=torch.float64, device="cuda"))
-  seen = _rollout_against_restatement(env, case.T, case.B, seed=7)
+  seen = rollout_against_restatement(env, case.T, case.B, seed=7)
   print(f"{name}: iteration counts {sorted(set(seen))}")
   # the restatement's own iteration counts: some buildings end at the limit, others well before it
   assert max(seen) == case.limit and min(seen) < case.limit // 2 and len(set(seen)) >= 5, sorted(set(seen))
@@ -114,13 +113,10 @@ def _record(case, fp, init, acts, cus, monkeypatch):
   info = dict(sim.launch_info)
   _depth_check(case, case.B, cus)(info)
   sim.reset(temps=torch.tensor(init, dtype=torch.float64, device="cuda"))
-  B = case.B
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  inf = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  obs, rew, inf = step_buffers(sim)
   out = []
   for t in range(case.T):
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, hc.tc.TT0 + t), obs, rew, inf)
+    sim.step(torch.tensor(acts[t], device="cuda"), step_in(g, hc.tc.TT0 + t), obs, rew, inf)
     out.append([obs.clone(), rew.clone(), inf.clone(), sim.temps(), sim.scalars(), sim.modes(), sim.zone_temps()])
   sim.close()
   return info, out
@@ -130,8 +126,8 @@ def _record(case, fp, init, acts, cus, monkeypatch):
 def test_result_does_not_depend_on_who_runs_a_building(name, monkeypatch):
   """SBSIM_DEBUG_CUS=1, =3 and unset: the planner's choice (kernel, path, wavefronts, LDS bytes, sweep steps) is the
   same, only the workgroup count follows the switch; obs, reward, info, grids, scalars, modes and zone temperatures are
-  torch.equal (k_sweep_stream: _assert_close)."""
-  _need_gpu()
+  torch.equal (k_sweep_stream: assert_close)."""
+  need_gpu()
   case = hc.CASES.get(name) or hc.JACOBI_CASES[name]
   fp = hc.floor_plan(case)
   init, acts, _ = hc.case_batch(case)
@@ -145,5 +141,5 @@ def test_result_does_not_depend_on_who_runs_a_building(name, monkeypatch):
     assert hc.static_count(info) <= hc.static_count(base)
     # the capped geometry: as many workgroups as `cus` CUs hold, i.e. cus times what one CU holds
     assert info["workgroups"] == min(cus * runs[1][0]["workgroups"], base["workgroups"]), (cus, info, base)
-    (_assert_close if case.kernel == hc.STREAM else _assert_same)(runs[cus][1], runs[None][1])
+    (assert_close if case.kernel == hc.STREAM else assert_same)(runs[cus][1], runs[None][1])
   assert float(runs[None][1][-1][2][:, 4].sum()) > 0   # (the sweeps ran)

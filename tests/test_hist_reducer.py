@@ -71,14 +71,14 @@ def test_device_reducer_against_reference_golden(case):
     pytest.skip("needs a GPU")
   from sbsim_amd import _ffi
   from sbsim_amd.environment import BatchedSimulator, SimConfig
-  from tests.test_gpu_parity import _plan, _step_in
+  from tests.twins import plan_from_npz, step_in
   g, gh, m = load("h2_sb1_r9_random.npz"), load("hist_reducer.npz"), _meta()
   cfg = m["cases"][case]
   norm = None
   if "mean" in cfg:   # the affine normalisation the golden inputs were made with (mean, variance)
     norm = {n.split("/", 1)[1]: (mu, sg * sg) for n, mu, sg in zip(m["source_names"], cfg["mean"], cfg["sigma"])}
   B = 3
-  sim = BatchedSimulator(_plan(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]),
+  sim = BatchedSimulator(plan_from_npz(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]),
                          observation_normalization=norm, zone_names=[str(z) for z in g["zone_names"]],
                          histogram_parameters=[(n, b) for n, b in cfg["params"]],
                          normalize_reduce=cfg["normalize_reduce"])
@@ -92,7 +92,7 @@ def test_device_reducer_against_reference_golden(case):
   checked = 0
   for t in range(max(m["steps"]) + 1):
     act = torch.tensor(np.tile(g["actions_norm"][t], (B, 1)), dtype=torch.float32, device="cuda")
-    sim.step(act, _step_in(g, t), obs, rew, None)
+    sim.step(act, step_in(g, t), obs, rew, None)
     if t in m["steps"]:
       want = gh[f"{case}_expected"][m["steps"].index(t)]
       got = obs.cpu().numpy()[:, :n_dev]

@@ -9,7 +9,7 @@ from oracle import oracle as orc
 from sbsim_amd import _ffi
 from sbsim_amd.floorplan import jacobi_cv_tensors
 from tests import irregular_plans as ip
-from tests.test_abi_cpu import _plan_info
+from tests.twins import oracle_plan_of, plan_info
 
 
 def _sets(cp) -> int:
@@ -33,7 +33,7 @@ def test_planner_picks_the_pinned_kernel(name, monkeypatch):
   fp = ip.device_plan(name)
   cp = fp.compile(ip.DT, ip.H_CONV)
   assert (cp.n_classes, _sets(cp), cp.Z) == (c.n_classes, c.n_sets, c.n_zones)
-  rc, info = _plan_info(fp, n_obs=3 * cp.Z + 19)
+  rc, info = plan_info(fp, n_obs=3 * cp.Z + 19)
   assert rc == 0, _ffi.load().sb_last_error()
   assert (info["kernel"], info["waves_per_building"]) == (c.kernel, c.waves)
   if c.steps is not None:
@@ -118,9 +118,9 @@ def test_plan_no_kernel_holds_is_refused_with_a_message():
   s = ip.Sketch(1100, 1100).out(300, 800, 300, 800)
   s.rooms((2, 290, 810, 1098), (2, 290, 810, 1098))
   fp = s.plan()
-  rc, _ = _plan_info(fp, n_obs=22)
+  rc, _ = plan_info(fp, n_obs=22)
   assert rc == -4 and len(_ffi.load().sb_last_error()) > 20
-  rc, _ = _plan_info(fp.transposed(), n_obs=22)
+  rc, _ = plan_info(fp.transposed(), n_obs=22)
   assert rc == -4 and len(_ffi.load().sb_last_error()) > 20
   assert ip.u_ladder(255).compile(ip.DT, ip.H_CONV).n_classes == 255
   with pytest.raises(ValueError, match="cell classes"):
@@ -135,8 +135,7 @@ def _inputs(fp, seed):
   q = np.zeros((H, W))
   for z, cells in enumerate(fp.zone_cell_lists()):
     q.reshape(-1)[cells] = qz[z] * fp.diffusers.reshape(-1)[cells]
-  oplan = orc.OraclePlan(fp.conductivity, fp.density, fp.heat_capacity, fp.exterior_space, fp.zone_cell_lists(),
-                         fp.diffusers, fp.cv_size_cm, fp.floor_height_cm)
+  oplan = oracle_plan_of(fp)
   return prev, q, qz, oplan
 
 

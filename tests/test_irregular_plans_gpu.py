@@ -2,7 +2,7 @@
 picks for it (pinned), against the CPU oracle, which reads k, rho, c, the exterior mask, the zones and the diffusers
 and never FloorPlan.compile()'s class tables -- so one comparison checks compile(), the planner's tables and the kernel
 together.  Sweep counts and converged flags EQUAL, zone and grid temperatures within 1e-8 K, rates and reward at the
-suite's tolerances (tests/test_gpu_parity.py).  With notches and courtyards the AC rate also checks the grid mean
+suite's tolerances (tests/twins.py).  With notches and courtyards the AC rate also checks the grid mean
 behind the recirculation temperature: ambient cells inside the trim box count in it."""
 import numpy as np
 import pytest
@@ -13,10 +13,9 @@ torch = pytest.importorskip("torch")
 from sbsim_amd import _ffi  # noqa: E402
 from sbsim_amd.environment import BatchedSimulator, SimConfig  # noqa: E402
 from tests import irregular_plans as ip  # noqa: E402
-from tests import jacobi_restatement as jr  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_gpu_parity import T_TOL, _check_plan_against_oracle, _need_gpu, _step_in  # noqa: E402
-from tests.threshold_cases import oracle_twin  # noqa: E402
+from tests.parity import check_plan_against_oracle, jacobi_tap_bitwise, need_gpu, step_buffers  # noqa: E402
+from tests.twins import T_TOL, assert_step_matches, oracle_twin, step_in, step_kwargs  # noqa: E402
 
 B, T = 4, 8
 
@@ -26,8 +25,8 @@ def _run(name, monkeypatch, **kw):
   for k, v in c.env:
     monkeypatch.setenv(k, v)
   path = {ip.LDS: 0, ip.STREAM: 2}.get(c.kernel, 1)
-  return _check_plan_against_oracle(ip.plan(name), c.n_zones, c.orientation, path, monkeypatch, expect_steps=c.steps,
-                                    expect_kernel=c.kernel, expect_waves=c.waves, B=B, T=T, **kw)
+  return check_plan_against_oracle(ip.plan(name), c.n_zones, c.orientation, path, monkeypatch, expect_steps=c.steps,
+                                   expect_kernel=c.kernel, expect_waves=c.waves, B=B, T=T, **kw)
 
 
 @pytest.mark.parametrize("name", list(ip.CASES))
@@ -55,7 +54,7 @@ def test_iteration_limit_on_irregular_plans(name, limit, monkeypatch):
 def test_set_temps_inside_a_courtyard_plan(name, monkeypatch):
   """Two steps, an edit of interior cells only that changes the grid's sum, two more steps, against oracle twins that
   get the same edit (tests/test_gpu_parity.py's R9 case has no exterior space inside its trim box)."""
-  _need_gpu()
+  need_gpu()
   c = ip.CASES[name]
   for k, v in c.env:
     monkeypatch.setenv(k, v)
@@ -70,30 +69,16 @@ def test_set_temps_inside_a_courtyard_plan(name, monkeypatch):
   assert (sim.launch_info["kernel"], sim.launch_info["waves_per_building"]) == (c.kernel, c.waves)
   sim.reset(temps=torch.tensor(init, dtype=torch.float64, device="cuda"))
   twins = [oracle_twin(fp, cfg, init[b]) for b in range(B)]
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
-  lo, hi = cfg.action_ranges
+  obs, rew, info = step_buffers(sim)
 
   def both(t):
     tt = 96 + t
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, tt), obs, rew, info)
+    sim.step(torch.tensor(acts[t], device="cuda"), step_in(g, tt), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
-    zt = sim.zone_temps().cpu().numpy()
+    zt, r = sim.zone_temps().cpu().numpy(), rew.cpu().numpy()
     for b in range(B):
-      a = acts[t, b]
-      native = [np.float32((float(a[0]) + 1.0) / 2.0 * (lo[1] - lo[0]) + lo[0]),
-                np.float32((float(a[1]) + 1.0) / 2.0 * (hi[1] - hi[0]) + hi[0])]
-      o = twins[b].step(
-          now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
-          t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-          comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-          occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]), e_carbon=float(g["e_carbon"][tt]),
-          g_price=float(g["g_price"][tt]), g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
-      assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
-      assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
-      ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
-      assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b)
+      o = twins[b].step(**step_kwargs(g, tt, t, cfg, acts[t, b]))
+      assert_step_matches(i[b], zt[b], r[b], o, (t, b))
 
   both(0)
   both(1)
@@ -118,21 +103,12 @@ def test_set_temps_inside_a_courtyard_plan(name, monkeypatch):
 @pytest.mark.parametrize("limit", [100, 2])
 def test_jacobi_tap_on_irregular_plans_bitwise(name, limit):
   """solver="jacobi_fp32" on the L and courtyard plans: sb_tap_jacobi bitwise against tests/jacobi_restatement.py."""
-  _need_gpu()
+  need_gpu()
   fp = ip.plan(name)
   cfg = SimConfig.sb1()
   cfg.iteration_limit = limit
   h = 100.0
   sim = BatchedSimulator(fp, cfg, B, h, solver="jacobi_fp32")
   assert sim.launch_info["kernel"] == _ffi.SB_KERNEL_JACOBI
-  tt = jr.tensors(fp, cfg.time_step_sec, h)
-  rs = np.random.RandomState(3)
-  tprev = (288.0 + 8.0 * rs.rand(B, *fp.shape)).astype(np.float32)
-  q = np.stack([jr.input_q(fp, rs.uniform(-3000.0, 3000.0, fp.n_zones)) for _ in range(B)])
-  tinf = rs.uniform(265.0, 305.0, B)
-  grid, iters, conv = sim.tap_jacobi(tprev, q, tinf)
-  for b in range(B):
-    want, wi, wc = jr.fd_timestep(tt, tprev[b], q[b], tinf[b], cfg.time_step_sec, cfg.convergence_threshold, limit)
-    assert (iters[b], bool(conv[b])) == (wi, wc), (b, iters[b], wi)
-    assert np.array_equal(np.asarray(grid[b], np.float32).view(np.uint32), np.asarray(want, np.float32).view(np.uint32))
+  jacobi_tap_bitwise(sim, fp, cfg, h, seed=3, limit=limit)
   sim.close()

@@ -7,15 +7,11 @@ from sbsim_amd import _ffi
 from sbsim_amd.floorplan import JACOBI_FIELDS, FloorPlan, Materials, jacobi_cv_tensors, rectangular_floor_plan
 from tests import jacobi_restatement as jr
 from tests.golden_util import load
+from tests.jacobi_cases import GOLDEN_PLANS, golden_plan
+from tests.twins import plan_from_npz
 
 f32 = np.float32
 PLANS = ("plan_r9_sb1.npz", "plan_r9_test.npz", "plan_small_test.npz", "plan_weird_test.npz")
-
-
-def _plan(p):
-  return FloorPlan(conductivity=p["conductivity"], heat_capacity=p["heat_capacity"], density=p["density"],
-                   exterior_space=p["exterior_space"], zone_label=p["zone_label"], diffusers=p["diffusers"],
-                   cv_size_cm=float(p["cv_size_cm"]), floor_height_cm=float(p["floor_height_cm"]))
 
 
 def _box(H=6, W=7):
@@ -33,7 +29,7 @@ def _box(H=6, W=7):
 
 @pytest.mark.parametrize("name", PLANS)
 def test_compile_jacobi_tables_expand_to_the_cv_tensors(name):
-  fp = _plan(load(name))
+  fp = plan_from_npz(load(name))
   jp = fp.compile_jacobi(300.0, 100.0)
   t = jacobi_cv_tensors(fp, 300.0, 100.0)
   e = jp.expand()
@@ -117,7 +113,7 @@ def _f32_quotient_via_f64(num, den):
 def test_division_route_is_correctly_rounded_on_the_plans_denominators(name):
   """k_sweep_jacobi computes num / den as float((double)num * (1.0 / (double)den)).  Over every denominator of the
   plan: random numerators across binades, and numerators next to the midpoints of the binary32 quotients."""
-  fp = _plan(load(name))
+  fp = plan_from_npz(load(name))
   dens = np.unique(fp.compile_jacobi(300.0, 100.0).class_f32[:, 6])
   rs = np.random.RandomState(7)
   for den in dens:
@@ -162,19 +158,6 @@ def test_solver_switch_refuses_what_it_cannot_do_without_a_gpu():
 
 
 # ---- against the reference's own TFSimulator (tests/golden/jacobi_*.npz, tools/gen_golden_jacobi.py) ----
-GOLDEN_PLANS = {"r9_test": "plan_r9_test.npz", "small_test": "plan_small_test.npz", "weird_test": "plan_weird_test.npz",
-                "r9_sb1": "plan_r9_sb1.npz", "tf10x9": None}
-
-
-def golden_plan(name):
-  """The FloorPlan of a fixture plan: the shipped plan dumps, or the 10 x 9 plan of tf_simulator_test.py stored with
-  the tensors."""
-  if GOLDEN_PLANS[name] is not None:
-    return _plan(load(GOLDEN_PLANS[name]))
-  t = load("jacobi_tensors.npz")
-  return _plan({k[len("tf10x9_plan_"):]: t[k] for k in t.files if k.startswith("tf10x9_plan_")})
-
-
 @pytest.mark.parametrize("name", sorted(GOLDEN_PLANS))
 def test_cv_tensors_equal_the_reference_bitwise(name):
   """(a): u, v, the oriented k and h tensors, den and the exterior mask of TFSimulator equal jacobi_cv_tensors and the

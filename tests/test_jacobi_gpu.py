@@ -12,113 +12,58 @@ from sbsim_amd.environment import BatchedEnvironment, BatchedSimulator, MixedBat
 from sbsim_amd.floorplan import FloorPlan  # noqa: E402
 from tests import jacobi_restatement as jr  # noqa: E402
 from tests.golden_util import load  # noqa: E402
+from tests.jacobi_cases import GOLDEN_PLANS, golden_plan  # noqa: E402
+from tests.parity import (JACOBI_H_CONV as H_CONV, bits_equal, jacobi_env, jacobi_tap_bitwise, need_gpu,  # noqa: E402
+                          rollout_against_restatement, step_buffers)
+from tests.twins import RATE_ATOL, RATE_RTOL, plan_from_npz, step_in  # noqa: E402
 
 f32 = np.float32
 PLANS = ("plan_r9_sb1.npz", "plan_r9_test.npz", "plan_small_test.npz", "plan_weird_test.npz")
-H_CONV = 100.0   # BatchedEnvironment's default weather: WeatherController(273, 283, convection_coefficient=100)
-
-
-def _need_gpu():
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
-
-
-def _plan(p):
-  return FloorPlan(conductivity=p["conductivity"], heat_capacity=p["heat_capacity"], density=p["density"],
-                   exterior_space=p["exterior_space"], zone_label=p["zone_label"], diffusers=p["diffusers"],
-                   cv_size_cm=float(p["cv_size_cm"]), floor_height_cm=float(p["floor_height_cm"]),
-                   zone_names=tuple(str(z) for z in p["zone_names"]))
-
-
-def _bits_equal(a, b):
-  return np.array_equal(np.asarray(a, f32).view(np.uint32), np.asarray(b, f32).view(np.uint32))
 
 
 @pytest.mark.parametrize("name", PLANS)
 @pytest.mark.parametrize("limit", [100, 2])
 def test_tap_equals_the_restatement_bitwise(name, limit):
-  _need_gpu()
-  fp = _plan(load(name))
+  need_gpu()
+  fp = plan_from_npz(load(name))
   cfg = SimConfig.sb1()
   cfg.iteration_limit = limit
   n = 4
   sim = BatchedSimulator(fp, cfg, n, H_CONV, solver="jacobi_fp32")
   assert sim.launch_info["kernel"] == _ffi.SB_KERNEL_JACOBI
   assert sim.launch_info["state_bytes_per_env_step"] == 8 * fp.shape[0] * fp.shape[1]
-  tt = jr.tensors(fp, cfg.time_step_sec, H_CONV)
-  rs = np.random.RandomState(11)
-  tprev = (288.0 + 8.0 * rs.rand(n, *fp.shape)).astype(f32)
-  q = np.stack([jr.input_q(fp, rs.uniform(-3000.0, 3000.0, fp.n_zones)) for _ in range(n)])
-  tinf = rs.uniform(265.0, 305.0, n)
-  grid, iters, conv = sim.tap_jacobi(tprev, q, tinf)
-  for b in range(n):
-    want, wi, wc = jr.fd_timestep(tt, tprev[b], q[b], tinf[b], cfg.time_step_sec, cfg.convergence_threshold, limit)
-    assert (iters[b], bool(conv[b])) == (wi, wc), (b, iters[b], wi)
-    assert _bits_equal(grid[b], want), (b, np.abs(grid[b] - want).max())
+  jacobi_tap_bitwise(sim, fp, cfg, H_CONV, seed=11, limit=limit)
   sim.close()
-
-
-def _rollout_against_restatement(env, steps, sample, seed):
-  """Every step: the device grid after it equals the restatement of the step from the grid before it, the device's
-  own q (the zone power of the previous step) and the step's ambient temperature."""
-  sim, fp = env.sim, env._plan_for_tests
-  tt = jr.tensors(fp, env.config.time_step_sec, H_CONV)
-  rs = np.random.RandomState(seed)
-  B = env.batch_size
-  iters_seen = []
-  for t in range(steps):
-    picks = rs.choice(B, size=min(sample, B), replace=False)
-    pk = torch.as_tensor(picks, device=sim.tdev)
-    before = sim.temps()[pk].cpu().numpy().astype(f32)
-    qz = sim.zone_power()[pk].cpu().numpy()
-    tinf = env.make_step_in(env.current_simulation_timestamp).t_amb_now
-    act = torch.tensor(rs.uniform(-1, 1, (B, env.action_spec().shape[0])), dtype=torch.float32, device="cuda")
-    env.step(act)
-    after = sim.temps()[pk].cpu().numpy()
-    info = env.info[pk].cpu().numpy()
-    for k, b in enumerate(picks):
-      want, wi, wc = jr.fd_timestep(tt, before[k], jr.input_q(fp, qz[k]), tinf, env.config.time_step_sec,
-                                    env.config.convergence_threshold, env.config.iteration_limit)
-      assert int(info[k, 4]) == wi and bool(info[k, 5]) == wc, (t, b, info[k, 4], wi)
-      assert np.array_equal(after[k], want.astype(np.float64)), (t, b, np.abs(after[k] - want).max())
-      iters_seen.append(wi)
-  return iters_seen
-
-
-def _env(fp, B, **kw):
-  env = BatchedEnvironment(fp, B, holiday_calendar=None, collect_info=True, solver="jacobi_fp32", **kw)
-  env._plan_for_tests = fp
-  return env
 
 
 def test_random_action_rollout_every_step_bitwise():
   """288 steps (one day of 5-minute steps) of 256 SB1 R9 buildings under random actions, 8 buildings a step checked."""
-  _need_gpu()
-  fp = _plan(load("plan_r9_sb1.npz"))
-  env = _env(fp, 256)
+  need_gpu()
+  fp = plan_from_npz(load("plan_r9_sb1.npz"))
+  env = jacobi_env(fp, 256)
   env.reset()
-  seen = _rollout_against_restatement(env, 288, 8, seed=3)
+  seen = rollout_against_restatement(env, 288, 8, seed=3)
   assert min(seen) >= 1 and max(seen) < env.config.iteration_limit
   env.close()
 
 
 def test_full_size_batch_sampled_bitwise():
   """65,536 R9 buildings: the persistent grid's draw counter and the resident workgroups at scale."""
-  _need_gpu()
-  fp = _plan(load("plan_r9_sb1.npz"))
-  env = _env(fp, 65536)
+  need_gpu()
+  fp = plan_from_npz(load("plan_r9_sb1.npz"))
+  env = jacobi_env(fp, 65536)
   env.reset()
   g = torch.Generator(device="cuda").manual_seed(5)
   init = (290.0 + 6.0 * torch.rand((65536, fp.shape[0] * fp.shape[1]), generator=g, device="cuda")).double()
   env.sim.reset(temps=init)   # (float32-representable)
   del init
-  _rollout_against_restatement(env, 5, 64, seed=9)
+  rollout_against_restatement(env, 5, 64, seed=9)
   env.close()
 
 
 def test_mixed_batch_equals_the_single_class_environments():
-  _need_gpu()
-  plans = [_plan(load(n)) for n in ("plan_r9_sb1.npz", "plan_r9_test.npz", "plan_small_test.npz")]
+  need_gpu()
+  plans = [plan_from_npz(load(n)) for n in ("plan_r9_sb1.npz", "plan_r9_test.npz", "plan_small_test.npz")]
   counts = [24, 16, 8]
   mixed = MixedBatchedEnvironment(list(zip(plans, counts)), holiday_calendar=None, collect_info=True,
                                   solver="jacobi_fp32")
@@ -143,8 +88,8 @@ def test_mixed_batch_equals_the_single_class_environments():
 
 
 def test_mixed_batch_takes_one_solver_per_class():
-  _need_gpu()
-  plans = [_plan(load(n)) for n in ("plan_r9_sb1.npz", "plan_small_test.npz")]
+  need_gpu()
+  plans = [plan_from_npz(load(n)) for n in ("plan_r9_sb1.npz", "plan_small_test.npz")]
   mixed = MixedBatchedEnvironment([(plans[0], 4), (plans[1], 4)], holiday_calendar=None,
                                   solver=["jacobi_fp32", "gauss_seidel"])
   assert mixed.envs[0].sim.launch_info["kernel"] == _ffi.SB_KERNEL_JACOBI
@@ -155,8 +100,8 @@ def test_mixed_batch_takes_one_solver_per_class():
 
 
 def test_jacobi_refusals():
-  _need_gpu()
-  fp = _plan(load("plan_small_test.npz"))
+  need_gpu()
+  fp = plan_from_npz(load("plan_small_test.npz"))
   with pytest.raises(ValueError, match="orientation"):
     BatchedSimulator(fp, SimConfig.sb1(), 2, H_CONV, solver="jacobi_fp32", orientation="columns")
 
@@ -192,8 +137,8 @@ def C_byref(x):
 
 
 def test_reset_rounds_the_grid_to_float32_and_keeps_float64_zone_means():
-  _need_gpu()
-  fp = _plan(load("plan_r9_sb1.npz"))
+  need_gpu()
+  fp = plan_from_npz(load("plan_r9_sb1.npz"))
   sim = BatchedSimulator(fp, SimConfig.sb1(), 2, H_CONV, solver="jacobi_fp32")
   N = fp.shape[0] * fp.shape[1]
   rs = np.random.RandomState(4)
@@ -209,14 +154,13 @@ def test_reset_rounds_the_grid_to_float32_and_keeps_float64_zone_means():
 
 
 # ---- against the reference's own TFSimulator (tests/golden/jacobi_*.npz, tools/gen_golden_jacobi.py) ----
-from tests.test_jacobi_cpu import GOLDEN_PLANS, golden_plan  # noqa: E402
 
 
 @pytest.mark.parametrize("name", sorted(GOLDEN_PLANS))
 @pytest.mark.parametrize("limit", [100, 2])
 def test_tap_equals_the_reference_fd_timestep_bitwise(name, limit):
   """(b): k_sweep_jacobi on the reference's finite_differences_timestep cases: grid, iterations, converged flag."""
-  _need_gpu()
+  need_gpu()
   g = load("jacobi_fd.npz")
   fp = golden_plan(name)
   cfg = SimConfig.sb1()
@@ -229,13 +173,13 @@ def test_tap_equals_the_reference_fd_timestep_bitwise(name, limit):
   grid, iters, conv = sim.tap_jacobi(tprev, q, tinf)
   for b, k in enumerate(keys):
     assert (int(iters[b]), bool(conv[b])) == (int(g[k + "_iterations"]), bool(g[k + "_converged"])), k
-    assert _bits_equal(grid[b], g[k + "_grid"]), (k, np.abs(grid[b] - g[k + "_grid"]).max())
+    assert bits_equal(grid[b], g[k + "_grid"]), (k, np.abs(grid[b] - g[k + "_grid"]).max())
   sim.close()
 
 
 def test_plan_beyond_8192_cvs_equals_the_restatement_bitwise():
   """The 1,024-thread instantiation (plans of 8,193 .. 20,480 CVs): 83 x 129 = 10,707 CVs."""
-  _need_gpu()
+  need_gpu()
   from sbsim_amd.floorplan import Materials, rectangular_floor_plan
   fp = FloorPlan.from_file_input(rectangular_floor_plan((3, 4), (25, 30)), Materials.sb1(), 10.0, 300.0)
   assert 8192 < fp.shape[0] * fp.shape[1] <= 20480
@@ -251,7 +195,7 @@ def test_plan_beyond_8192_cvs_equals_the_restatement_bitwise():
   for b in range(3):
     want, wi, wc = jr.fd_timestep(tt, tprev[b], q[b], tinf[b], cfg.time_step_sec, cfg.convergence_threshold, 100)
     assert (iters[b], bool(conv[b])) == (wi, wc)
-    assert _bits_equal(grid[b], want), (b, np.abs(grid[b] - want).max())
+    assert bits_equal(grid[b], want), (b, np.abs(grid[b] - want).max())
   sim.close()
 
 
@@ -261,7 +205,7 @@ ZONE_TOL = 1e-4   # K: the device algebra is float64 around the float32 grid; th
 def test_thermostat_only_rollout_against_the_reference():
   """(c) 288 thermostat-only steps of TFSimulator on r9_test: iteration counts equal at every step, zone temperatures
   within ZONE_TOL."""
-  _need_gpu()
+  need_gpu()
   import json
   g = load("jacobi_h1_r9_test.npz")
   prm = json.loads(str(g["params_json"]))
@@ -276,10 +220,9 @@ def test_thermostat_only_rollout_against_the_reference():
       boiler_water_pump_efficiency=prm["blr_pump_eff"], boiler_heating_rate=prm["blr_heating_rate"],
       boiler_cooling_rate=prm["blr_cooling_rate"], initial_temp=float(g["initial_temp"]))
   B = 3
-  sim = BatchedSimulator(_plan(load("plan_r9_test.npz")), cfg, B, float(g["h_conv"]), solver="jacobi_fp32")
+  sim = BatchedSimulator(plan_from_npz(load("plan_r9_test.npz")), cfg, B, float(g["h_conv"]), solver="jacobi_fp32")
   sim.reset()
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  _, rew, info = step_buffers(sim)
   comfort = g["comfort"]
   worst = 0.0
   for t in range(len(g["n_sweeps"])):
@@ -305,19 +248,16 @@ def test_random_action_rollout_against_the_reference():
   within ZONE_TOL, rewards and the blower, gas and pump rates within the library's rtol 2e-6 / abs 1e-6.  The
   air-conditioning rate is flow * c_air * (supply - mixed), and the mixed-air temperature takes the grid mean: a float32
   mean (NumPy's pairwise float32 sum) in the reference, a float64 one here.  It is held to flow * c_air * ZONE_TOL."""
-  _need_gpu()
-  from tests.test_gpu_parity import _step_in
+  need_gpu()
   g = load("jacobi_h2_sb1_r9_random.npz")
   B = 4
-  sim = BatchedSimulator(_plan(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]), solver="jacobi_fp32")
+  sim = BatchedSimulator(plan_from_npz(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]), solver="jacobi_fp32")
   sim.reset()
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  obs, rew, info = step_buffers(sim)
   worst_t = worst_r = worst_rate = 0.0
   for t in range(len(g["n_sweeps"])):
     act = torch.tensor(np.tile(g["actions_norm"][t], (B, 1)), dtype=torch.float32, device="cuda")
-    sim.step(act, _step_in(g, t), obs, rew, info)
+    sim.step(act, step_in(g, t), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     assert (i[:, 4] == g["n_sweeps"][t]).all(), (t, i[:, 4], g["n_sweeps"][t])
     d = np.abs(sim.zone_temps().cpu().numpy() - g["zone_temp_post"][t]).max()
@@ -325,13 +265,13 @@ def test_random_action_rollout_against_the_reference():
     assert d < ZONE_TOL, (t, d)
     ref_rates = g["rates"][t].astype(np.float64)
     keep = [0, 2, 3]   # blower, gas, pump: as on the Gauss-Seidel path
-    assert np.allclose(i[:, keep], ref_rates[keep], rtol=2e-6, atol=1e-6), (t, i[0, :4], ref_rates)
+    assert np.allclose(i[:, keep], ref_rates[keep], rtol=RATE_RTOL, atol=RATE_ATOL), (t, i[0, :4], ref_rates)
     ac_tol = float(g["ahu_flow"][t]) * 1006.0 * ZONE_TOL + 1e-3   # flow * c_air * (the mean's gap, < ZONE_TOL)
     worst_rate = max(worst_rate, float(np.abs(i[:, 1] - ref_rates[1]).max()))
     assert np.abs(i[:, 1] - ref_rates[1]).max() <= ac_tol, (t, i[0, 1], ref_rates[1], ac_tol)
     r = rew.cpu().numpy().astype(np.float64)
     worst_r = max(worst_r, np.abs(r - float(g["reward"][t])).max())
-    assert np.allclose(r, float(g["reward"][t]), rtol=2e-6, atol=1e-6), (t, r, g["reward"][t])
+    assert np.allclose(r, float(g["reward"][t]), rtol=RATE_RTOL, atol=RATE_ATOL), (t, r, g["reward"][t])
   print(f"[jacobi sb1 r9 random] max |dT_zone| vs reference = {worst_t:.3e} K, max |d reward| = {worst_r:.3e}, "
         f"max |d air-conditioning W| = {worst_rate:.3e}")
   sim.close()

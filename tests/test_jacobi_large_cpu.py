@@ -9,26 +9,13 @@ import pytest
 
 from sbsim_amd import _ffi
 from sbsim_amd.environment import BatchedSimulator, SimConfig
-from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
+from sbsim_amd.floorplan import FloorPlan
 from tests import jacobi_restatement as jr
 from tests.golden_util import load
+from tests.jacobi_cases import PLAN_155, PLAN_SB1, large_case, large_plan
 
 f32 = np.float32
-PLAN_155 = ((6, 5), (24, 29))      # 155 x 155 = 24,025 CVs: the first size class beyond the LDS limit
-PLAN_SB1 = ((14, 9), (20, 43))     # 299 x 401 = 119,899 CVs, 126 zones: the benchmark's SB1 stand-in
 SB_ERR_NO_DEVICE, SB_ERR_TOO_LARGE = -2, -4
-
-
-def large_plan(rooms, room_shape):
-  return FloorPlan.from_file_input(rectangular_floor_plan(rooms, room_shape), Materials.sb1(), 10.0, 300.0)
-
-
-def large_case(seed, shape, n_zones):
-  """tools/gen_golden_jacobi.py's large_case: (Tprev float32, zone powers, T_inf) of a stored seed."""
-  rs = np.random.RandomState(seed)
-  prev = (285.0 + 12.0 * rs.rand(*shape)).astype(f32)
-  qz = rs.uniform(-4000.0, 4000.0, n_zones)
-  return prev, qz, float(rs.uniform(265.0, 305.0))
 
 
 def _create_code(fp, monkeypatch):

@@ -11,9 +11,9 @@ from sbsim_amd import _ffi  # noqa: E402
 from sbsim_amd.environment import BatchedSimulator, MixedBatchedEnvironment, SimConfig  # noqa: E402
 from tests import jacobi_restatement as jr  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_jacobi_cpu import GOLDEN_PLANS, golden_plan  # noqa: E402
-from tests.test_jacobi_gpu import H_CONV, _bits_equal, _env, _need_gpu, _plan  # noqa: E402
-from tests.test_jacobi_large_cpu import PLAN_155, PLAN_SB1, large_case, large_plan  # noqa: E402
+from tests.jacobi_cases import GOLDEN_PLANS, PLAN_155, PLAN_SB1, golden_plan, large_case, large_plan  # noqa: E402
+from tests.parity import JACOBI_H_CONV as H_CONV, bits_equal, jacobi_env, need_gpu  # noqa: E402
+from tests.twins import plan_from_npz  # noqa: E402
 
 f32 = np.float32
 FORCE = "SBSIM_FORCE_JACOBI_GLOBAL"
@@ -27,7 +27,7 @@ def _is_global(sim):
 @pytest.mark.parametrize("limit", [100, 2])
 def test_tap_on_large_plans_equals_the_restatement_bitwise(plan, limit):
   """Three buildings with different seeded Tprev, q and T_inf; on 155 x 155 two of them are the reference's cases."""
-  _need_gpu()
+  need_gpu()
   fp = large_plan(*plan)
   g = load("jacobi_fd_large.npz")
   golden = [int(s) for s in g["seeds"]] if plan == PLAN_155 else []
@@ -47,11 +47,11 @@ def test_tap_on_large_plans_equals_the_restatement_bitwise(plan, limit):
     want, wi, wc = jr.fd_timestep(tt, tprev[b], q[b], tinf[b], cfg.time_step_sec, cfg.convergence_threshold, limit)
     print(f"[tap {fp.shape} limit {limit} seed {seed}] {wi} iterations, converged={wc}; device {iters[b]}, {conv[b]}")
     assert (iters[b], bool(conv[b])) == (wi, wc), (b, iters[b], wi)
-    assert _bits_equal(grid[b], want), (b, np.abs(grid[b] - want).max())
+    assert bits_equal(grid[b], want), (b, np.abs(grid[b] - want).max())
     if seed in golden:
       key = f"{seed}_{limit}"
       assert (int(iters[b]), bool(conv[b])) == (int(g[key + "_iterations"]), bool(g[key + "_converged"])), key
-      assert _bits_equal(grid[b], g[key + "_grid"]), key
+      assert bits_equal(grid[b], g[key + "_grid"]), key
   sim.close()
 
 
@@ -59,7 +59,7 @@ def test_tap_on_large_plans_equals_the_restatement_bitwise(plan, limit):
 @pytest.mark.parametrize("limit", [100, 2])
 def test_forced_global_tap_equals_the_reference_fd_timestep_bitwise(name, limit, monkeypatch):
   """test_tap_equals_the_reference_fd_timestep_bitwise's cases on k_sweep_jacobi_g."""
-  _need_gpu()
+  need_gpu()
   monkeypatch.setenv(FORCE, "1")
   g = load("jacobi_fd.npz")
   fp = golden_plan(name)
@@ -74,7 +74,7 @@ def test_forced_global_tap_equals_the_reference_fd_timestep_bitwise(name, limit,
   grid, iters, conv = sim.tap_jacobi(tprev, q, tinf)
   for b, k in enumerate(keys):
     assert (int(iters[b]), bool(conv[b])) == (int(g[k + "_iterations"]), bool(g[k + "_converged"])), k
-    assert _bits_equal(grid[b], g[k + "_grid"]), (k, np.abs(grid[b] - g[k + "_grid"]).max())
+    assert bits_equal(grid[b], g[k + "_grid"]), (k, np.abs(grid[b] - g[k + "_grid"]).max())
   sim.close()
 
 
@@ -112,9 +112,9 @@ def _rollout(env, steps, sample, seed, zone_tol=None):
 
 
 def test_random_action_rollout_on_the_155_plan_every_step_bitwise():
-  _need_gpu()
+  need_gpu()
   fp = large_plan(*PLAN_155)
-  env = _env(fp, 64)
+  env = jacobi_env(fp, 64)
   assert _is_global(env.sim), env.sim.launch_info
   env.reset()
   seen = _rollout(env, 24, 4, seed=6, zone_tol=1e-11)
@@ -125,9 +125,9 @@ def test_random_action_rollout_on_the_155_plan_every_step_bitwise():
 
 def test_more_buildings_than_resident_workgroups_on_the_sb1_sized_plan():
   """1,536 buildings of 299 x 401: the draw counter, and a workgroup's scratch area reused by its next building."""
-  _need_gpu()
+  need_gpu()
   fp = large_plan(*PLAN_SB1)
-  env = _env(fp, 1536)
+  env = jacobi_env(fp, 1536)
   assert _is_global(env.sim) and env.sim.launch_info["workgroups"] < 1536, env.sim.launch_info
   env.reset()
   g = torch.Generator(device="cuda").manual_seed(8)
@@ -143,11 +143,11 @@ def test_more_buildings_than_resident_workgroups_on_the_sb1_sized_plan():
 def test_r9_batch_is_the_same_on_both_kernels(monkeypatch):
   """256 R9 buildings, 20 random-action steps on k_sweep_jacobi and on k_sweep_jacobi_g: grids, info, rewards and
   observations bit for bit (both kernels add the float64 zone and grid sums in the same order)."""
-  _need_gpu()
-  fp = _plan(load("plan_r9_sb1.npz"))
+  need_gpu()
+  fp = plan_from_npz(load("plan_r9_sb1.npz"))
 
   def run(path):
-    env = _env(fp, 256)
+    env = jacobi_env(fp, 256)
     assert env.sim.launch_info["kernel"] == _ffi.SB_KERNEL_JACOBI and env.sim.launch_info["path"] == path
     env.reset()
     rs = np.random.RandomState(21)
@@ -169,8 +169,8 @@ def test_r9_batch_is_the_same_on_both_kernels(monkeypatch):
 
 def test_mixed_batch_with_a_small_and_a_large_class():
   """Resets and steps; every building of the large class equals the restatement of each step bit for bit."""
-  _need_gpu()
-  r9, p155 = _plan(load("plan_r9_sb1.npz")), large_plan(*PLAN_155)
+  need_gpu()
+  r9, p155 = plan_from_npz(load("plan_r9_sb1.npz")), large_plan(*PLAN_155)
   mixed = MixedBatchedEnvironment([(r9, 4), (p155, 4)], holiday_calendar=None, collect_info=True, solver="jacobi_fp32")
   infos = [e.sim.launch_info for e in mixed.envs]
   assert [i["kernel"] for i in infos] == [_ffi.SB_KERNEL_JACOBI] * 2
@@ -196,11 +196,11 @@ def test_mixed_batch_with_a_small_and_a_large_class():
 
 
 def test_refusals_are_unchanged_on_a_large_plan():
-  _need_gpu()
+  need_gpu()
   fp = large_plan(*PLAN_155)
   with pytest.raises(ValueError, match="orientation"):
     BatchedSimulator(fp, SimConfig.sb1(), 2, H_CONV, solver="jacobi_fp32", orientation="columns")
-  env = _env(fp, 2)
+  env = jacobi_env(fp, 2)
   env.reset()
   with pytest.raises(ValueError, match="jacobi_fp32"):
     env.snapshot()

@@ -6,6 +6,7 @@ from oracle import oracle as orc
 from sbsim_amd.floorplan import FloorPlan
 from tests.golden_util import load, oracle_plan
 from tests.kernel_model import FastSweepModel, model_fd_timestep
+from tests.twins import oracle_plan_of
 
 
 def _plan_from_golden(p):
@@ -79,8 +80,7 @@ def test_register_sweep_schedule_matches_oracle(rooms, room_shape, transpose, mo
   q = np.zeros((H, W))
   for z, cells in enumerate(fp.zone_cell_lists()):
     q.reshape(-1)[cells] = qz[z] * fp.diffusers.reshape(-1)[cells]
-  plan = orc.OraclePlan(fp.conductivity, fp.density, fp.heat_capacity, fp.exterior_space,
-                        fp.zone_cell_lists(), fp.diffusers, fp.cv_size_cm, fp.floor_height_cm)
+  plan = oracle_plan_of(fp)
   ref, n_ref, _ = orc.fd_timestep(plan, prev, q, 279.5, h, dt, 0.05, 40)
   got, n_got = m.fd_timestep(prev, 279.5, qz, 0.05, 40, schedule=schedule)
   assert n_got == n_ref and n_ref >= 3
@@ -115,8 +115,7 @@ def test_overlapped_sweeps_stop_at_the_iteration_limit():
   q = np.zeros((H, W))
   for z, cells in enumerate(fp.zone_cell_lists()):
     q.reshape(-1)[cells] = qz[z] * fp.diffusers.reshape(-1)[cells]
-  plan = orc.OraclePlan(fp.conductivity, fp.density, fp.heat_capacity, fp.exterior_space,
-                        fp.zone_cell_lists(), fp.diffusers, fp.cv_size_cm, fp.floor_height_cm)
+  plan = oracle_plan_of(fp)
   for limit in (1, 3):
     ref, n_ref, _ = orc.fd_timestep(plan, prev, q, 279.5, h, dt, 1e-9, limit)
     got, n_got = m.fd_timestep(prev, 279.5, qz, 1e-9, limit, schedule="rolling")

@@ -9,6 +9,7 @@ import pytest
 from oracle.occupancy_oracle import DeviceOccupancyOracle, philox4x32_10
 from sbsim_amd import host_inputs
 from tests.golden_util import load
+from tests.twins import native_action, plan_from_npz
 
 UTC = dt.timezone.utc
 
@@ -75,15 +76,10 @@ def test_device_generator_does_not_depend_on_sharding():
 
 
 # ------------------------------------------------------------------------------------- GPU
-def _need_gpu():
-  import torch
-  if not torch.cuda.is_available():
-    pytest.skip("needs an MI355X")
-
-
 @pytest.mark.gpu
 def test_device_occupancy_equals_its_restatement():
-  _need_gpu()
+  from tests.parity import need_gpu
+  need_gpu()
   import torch
   from sbsim_amd.environment import BatchedSimulator, SimConfig
   from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
@@ -111,18 +107,18 @@ def test_device_occupancy_equals_its_restatement():
 def test_environment_with_per_building_randomized_occupancy():
   """Per-building occupancy reaches the reward (productivity term) and the num_occupants feature;
   every building against its own oracle twin fed with the restatement's occupancy."""
-  _need_gpu()
+  from tests.parity import need_gpu
+  need_gpu()
   import torch
   from oracle import oracle as orc
   from sbsim_amd.environment import BatchedEnvironment, SimConfig
   from tests.golden_util import oracle_params, oracle_plan
-  from tests.test_gpu_parity import _plan
   g = load("h2_sb1_r9_random.npz")
   p = load("plan_r9_sb1.npz")
   B, T = 6, 40
   start = dt.datetime(2023, 7, 6, 8, 0, 0)
   occ = host_inputs.BatchedRandomizedArrivalDepartureOccupancy(10, 3, 12, 13, 23, 300, seed=77, holiday_calendar=None)
-  env = BatchedEnvironment(_plan(p), B, config=SimConfig.sb1(), occupancy=occ, start_timestamp=start,
+  env = BatchedEnvironment(plan_from_npz(p), B, config=SimConfig.sb1(), occupancy=occ, start_timestamp=start,
                            occupancy_normalization_constant=125.0, holiday_calendar=None, collect_info=True)
   ts0 = env.reset()
   model = DeviceOccupancyOracle(B, env.sim.Z, 10, 3, 12, 13, 23, 300.0, seed=77)
@@ -146,13 +142,11 @@ def test_environment_with_per_building_randomized_occupancy():
     obs = env._obs.cpu().numpy()
     assert np.allclose(obs[:, col], ((n_obs - 125.0) / 126.0).astype(np.float32)), t
     for b in range(B):
-      native = [np.float32((float(act[b, 0]) + 1.0) / 2.0 * 45.0 + 310.0),
-                np.float32((float(act[b, 1]) + 1.0) / 2.0 * 15.0 + 285.0)]
       o = twins[b].step(
           now_ts=300.0 * t, t_amb_now=si.t_amb_now, h_conv=float(g["h_conv"]), t_amb_next=si.t_amb_next,
           comfort_now=bool(si.comfort_now), comfort_prev=(si.comfort_prev == 1), comfort_next=bool(si.comfort_next),
           occupancy=occ_rew[b], e_price=si.e_price, e_carbon=si.e_carbon, g_price=si.g_price,
-          g_carbon=si.g_carbon, action=native, observe=True)
+          g_carbon=si.g_carbon, action=native_action(env.config, act[b]), observe=True)
       assert abs(float(r[b]) - o["reward"]) < 1e-6, (t, b, r[b], o["reward"])
     differ = differ or len(set(occ_rew.sum(axis=1))) > 1
     now = nxt

@@ -17,6 +17,7 @@ import pytest
 from oracle import oracle as orc
 from tests import regimes as rg
 from tests.golden_util import load, oracle_params
+from tests.twins import oracle_plan_of, step_kwargs
 
 REGIMES = list(rg.REGIMES)
 PAIRS = [(c, r) for c in rg.CASES for r in REGIMES]
@@ -30,8 +31,7 @@ def test_oracle_equals_the_reference_at_the_regime(name):
   g, regime = load(rg.GOLDEN), rg.REGIMES[name]
   assert list(g["regimes"]) == REGIMES
   fp = rg.apply(FloorPlan.from_file_input(g["floor_plan"], Materials.sb1(), 10.0, 300.0), regime)
-  oplan = orc.OraclePlan(fp.conductivity, fp.density, fp.heat_capacity, fp.exterior_space, fp.zone_cell_lists(),
-                         fp.diffusers, fp.cv_size_cm, fp.floor_height_cm)
+  oplan = oracle_plan_of(fp)
   prm = oracle_params(g[f"{name}/params_json"])
   cfg = rg.case_config(rg.CASES["reg32-15x23"], regime)
   assert (prm.dt, prm.conv_threshold, prm.iter_limit) == (regime.time_step_sec, regime.convergence_threshold, cfg.iteration_limit)
@@ -220,7 +220,7 @@ def test_mixed_materials_batch_conditions_on_the_oracle():
   for t in range(rg.MIXED_T):
     hsp, csp = rg.setpoints(g, t, cfg)
     for b in range(rg.MIXED_B):
-      o = twins[b].step(**rg.mixed_step_kwargs(g, t, cfg, hs[b], acts[t, b]), trace=True)
+      o = twins[b].step(**step_kwargs(g, rg.tc.TT0 + t, t, cfg, acts[t, b], h_conv=hs[b]), trace=True)
       assert (np.abs(o["max_delta"] - theta) > 1e-9 * theta).all(), (t, b)
       for tz in (o["zone_temp_pre"], o["zone_temp_post"], o["zone_air_temp"]):
         for edge in (hsp, csp, 0.5 * (csp - hsp) + hsp):

@@ -1,9 +1,9 @@
 """GPU parity outside SB1's one coefficient regime (tests/regimes.py): every sweep kernel's smallest pinned plan at every
 regime, every building against its CPU-oracle twin at every step.
 
-Through tests/test_gpu_parity.py's _check_plan_against_oracle at its own bars -- sweep counts and converged flags EQUAL,
+Through tests/parity.py's check_plan_against_oracle at the bars of tests/twins.py -- sweep counts and converged flags EQUAL,
 zone means and the final grid within T_TOL = 1e-8 K, rates at rtol 2e-6 / atol 1e-6, reward within 2e-6 -- with
-tests/test_zone_ladder_gpu.py's per-zone hook on top (modes, dampers, zone powers, request counts, flows, observation
+tests/parity.py's per-zone hook on top (modes, dampers, zone powers, request counts, flows, observation
 columns).  tests/test_regimes_cpu.py pins the oracle to the reference at these regimes and checks on the oracle alone
 that the inputs make "EQUAL" a fair demand: no sweep's max|delta| within a relative 1e-9 of the threshold, no zone mean
 within 1e-6 K of a thermostat threshold.
@@ -22,12 +22,12 @@ torch = pytest.importorskip("torch")
 from sbsim_amd import _ffi  # noqa: E402
 from sbsim_amd.environment import BatchedSimulator  # noqa: E402
 from sbsim_amd.host_inputs import BuildingMaterials  # noqa: E402
-from tests import jacobi_restatement as jr  # noqa: E402
 from tests import regimes as rg  # noqa: E402
 from tests import zone_ladder as zl  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_gpu_parity import T_TOL, _check_plan_against_oracle, _need_gpu, _step_in  # noqa: E402
-from tests.test_zone_ladder_gpu import JACOBI_ZONE_TOL, _zone_checks  # noqa: E402
+from tests.parity import (check_plan_against_oracle, jacobi_tap_bitwise, jacobi_zone_means_follow_grid, need_gpu,  # noqa: E402
+                          step_buffers, zone_checks)
+from tests.twins import T_TOL, assert_step_matches, step_in, step_kwargs  # noqa: E402
 
 REGIMES = list(rg.REGIMES)
 
@@ -41,7 +41,7 @@ def _run(case_name, regime_name, monkeypatch):
   orientation = c.orientation
   if (kernel, path) != (c.kernel, c.path):      # rg.ROLL_CAPACITY: the planner's own choice, no switch of the case's path
     assert path == 0 and not env
-  zone_hook = _zone_checks(cfg)
+  zone_hook = zone_checks(cfg)
   worst = [0.0, 0.0]
 
   def on_step(sim, t, obs, outs):
@@ -53,10 +53,10 @@ def _run(case_name, regime_name, monkeypatch):
     worst[1] = max(float(np.abs(grid[b] - tw.grid()).max()) for b, tw in twins.items())
     print(f"REGIME-DT {case_name} {regime_name} zone {worst[0]:.3e} grid {worst[1]:.3e}")
 
-  infos, _ = _check_plan_against_oracle(fp, fp.n_zones, orientation, path, monkeypatch, expect_steps=steps,
-                                        expect_kernel=kernel, expect_waves=waves, B=rg.B, T=rg.T, init=init, acts=acts,
-                                        cfg=cfg, env=env, on_step=on_step, on_end=on_end, h_conv=regime.h_conv,
-                                        step_sec=regime.time_step_sec, force_path=(kernel, path) == (c.kernel, c.path))
+  infos, _ = check_plan_against_oracle(fp, fp.n_zones, orientation, path, monkeypatch, expect_steps=steps,
+                                       expect_kernel=kernel, expect_waves=waves, B=rg.B, T=rg.T, init=init, acts=acts,
+                                       cfg=cfg, env=env, on_step=on_step, on_end=on_end, h_conv=regime.h_conv,
+                                       step_sec=regime.time_step_sec, force_path=(kernel, path) == (c.kernel, c.path))
   assert len(infos) == rg.T
 
 
@@ -80,7 +80,7 @@ def test_jacobi_float32_class_tensors_at_every_regime(kind, regime, monkeypatch)
   """solver="jacobi_fp32" at Z = NW on the LDS-resident plan and on the global-memory variant: sb_tap_jacobi bitwise
   against the restatement with iteration counts and flags EQUAL (the float32 roundings of the class tensors differ at
   every regime), then three real steps whose zone means are the float64 means of the float32 grid."""
-  _need_gpu()
+  need_gpu()
   env, nw = zl.JACOBI[kind]
   for k, v in env:
     monkeypatch.setenv(k, v)
@@ -93,32 +93,9 @@ def test_jacobi_float32_class_tensors_at_every_regime(kind, regime, monkeypatch)
   sim = BatchedSimulator(fp, cfg, Bn, r.h_conv, solver="jacobi_fp32")
   assert sim.launch_info["kernel"] == _ffi.SB_KERNEL_JACOBI and sim.launch_info["path"] == (2 if env else 0)
   assert sim.launch_info["waves_per_building"] == nw and sim.Z == Z
-  tt = jr.tensors(fp, cfg.time_step_sec, r.h_conv)
-  rs = np.random.RandomState(13)
-  tprev = (288.0 + 8.0 * rs.rand(Bn, *fp.shape)).astype(np.float32)
-  q = np.stack([jr.input_q(fp, rs.uniform(-3000.0, 3000.0, Z)) for _ in range(Bn)])
-  tinf = rs.uniform(265.0, 305.0, Bn)
-  grid, iters, conv = sim.tap_jacobi(tprev, q, tinf)
-  for b in range(Bn):
-    want, wi, wc = jr.fd_timestep(tt, tprev[b], q[b], tinf[b], cfg.time_step_sec, cfg.convergence_threshold,
-                                  cfg.iteration_limit)
-    assert (iters[b], bool(conv[b])) == (wi, wc), (b, iters[b], wi)
-    assert np.array_equal(np.asarray(grid[b], np.float32).view(np.uint32), np.asarray(want, np.float32).view(np.uint32))
+  iters, conv = jacobi_tap_bitwise(sim, fp, cfg, r.h_conv, seed=13)
   print(f"REGIME-JACOBI {kind} {regime} iterations {[int(i) for i in iters]} converged {[int(x) for x in conv]}")
-  init = zl.initial_grids(fp, Bn)
-  acts = zl.actions(3, Bn)
-  sim.reset(temps=torch.tensor(init, dtype=torch.float64, device="cuda"))
-  obs = torch.zeros((Bn, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((Bn,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((Bn, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
-  zlab = fp.zone_label.reshape(-1)
-  for t in range(3):
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, 96 + t), obs, rew, info)
-    flat = sim.temps().cpu().numpy().reshape(Bn, -1)
-    assert np.array_equal(flat, flat.astype(np.float32).astype(np.float64))       # a float32 grid, widened
-    means = np.stack([flat[:, zlab == z].mean(axis=1) for z in range(Z)], axis=1)
-    zt = sim.zone_temps().cpu().numpy()
-    assert np.abs(zt - means).max() <= JACOBI_ZONE_TOL, (t, np.abs(zt - means).max())
+  jacobi_zone_means_follow_grid(sim, fp, g, zl.initial_grids(fp, Bn), zl.actions(3, Bn))
   sim.close()
 
 
@@ -126,7 +103,7 @@ def test_one_batch_carries_four_regimes_on_the_materials_handle():
   """sb_create_materials / k_sweep_lds<true>: building b with the materials and h_conv of regime rg.MIXED[b % 4]
   (tests/test_building_materials_gpu.py spans factors of 0.2 .. 4; this spans six decades), every building against an
   oracle twin on the plan with its materials substituted."""
-  _need_gpu()
+  need_gpu()
   g = load("h2_sb1_r9_random.npz")
   fp, cfg, ids, mats, hs, init, acts = rg.mixed_batch()
   B, T = rg.MIXED_B, rg.MIXED_T
@@ -136,23 +113,16 @@ def test_one_batch_carries_four_regimes_on_the_materials_handle():
   assert sim.launch_info["kernel"] == rg.hc.LDS
   sim.reset(temps=torch.tensor(init, dtype=torch.float64, device="cuda"))
   twins = rg.mixed_twins(fp, cfg, ids, mats, init)
-  obs = torch.zeros((B, sim.O), dtype=torch.float32, device="cuda")
-  rew = torch.zeros((B,), dtype=torch.float32, device="cuda")
-  info = torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda")
+  obs, rew, info = step_buffers(sim)
   worst, counts = 0.0, set()
   for t in range(T):
-    sim.step(torch.tensor(acts[t], device="cuda"), _step_in(g, rg.tc.TT0 + t), obs, rew, info)
+    sim.step(torch.tensor(acts[t], device="cuda"), step_in(g, rg.tc.TT0 + t), obs, rew, info)
     i = info.cpu().numpy().astype(np.float64)
     zt, r = sim.zone_temps().cpu().numpy(), rew.cpu().numpy()
     for b in range(B):
-      o = twins[b].step(**rg.mixed_step_kwargs(g, t, cfg, hs[b], acts[t, b]))
-      assert i[b, 4] == o["n_sweeps"], (t, b, i[b, 4], o["n_sweeps"])
-      assert i[b, 5] == o["converged"], (t, b, i[b, 5], o["converged"])
+      o = twins[b].step(**step_kwargs(g, rg.tc.TT0 + t, t, cfg, acts[t, b], h_conv=hs[b]))
       worst = max(worst, float(np.abs(zt[b] - o["zone_temp_post"]).max()))
-      assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
-      ref = np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)
-      assert np.allclose(i[b, :4], ref, rtol=2e-6, atol=1e-6), (t, b, i[b, :4], ref)
-      assert abs(float(r[b]) - o["reward"]) < 2e-6, (t, b)
+      assert_step_matches(i[b], zt[b], r[b], o, (t, b))
       counts.add(o["n_sweeps"])
   grid = sim.temps().cpu().numpy()
   gw = max(float(np.abs(grid[b] - twins[b].grid()).max()) for b in range(B))

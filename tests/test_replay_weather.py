@@ -7,6 +7,7 @@ import pytest
 
 from sbsim_amd import host_inputs
 from tests.golden_util import load
+from tests.twins import T_TOL, native_action, plan_from_npz
 
 UTC = dt.timezone.utc
 
@@ -49,7 +50,6 @@ def test_device_replay_weather_through_the_environment_api(tmp_path):
   from oracle import oracle as orc
   from sbsim_amd.environment import BatchedEnvironment, SimConfig
   from tests.golden_util import oracle_params, oracle_plan
-  from tests.test_gpu_parity import T_TOL, _plan
   path = _csv(tmp_path)
   p = load("plan_r9_sb1.npz")
   g = load("h2_sb1_r9_random.npz")
@@ -58,7 +58,7 @@ def test_device_replay_weather_through_the_environment_api(tmp_path):
   weather = host_inputs.BatchedReplayWeather(path, offsets, convection_coefficient=float(g["h_conv"]))
   one = host_inputs.ReplayWeatherController(path, float(g["h_conv"]))
   start = dt.datetime(2023, 7, 6, 9, 30, 0, tzinfo=UTC)
-  env = BatchedEnvironment(_plan(p), B, config=SimConfig.sb1(), weather=weather, start_timestamp=start,
+  env = BatchedEnvironment(plan_from_npz(p), B, config=SimConfig.sb1(), weather=weather, start_timestamp=start,
                            holiday_calendar=None, collect_info=True)
   ts0 = env.reset()
   oat = env.field_names.index("air_handler_id/outside_air_temperature_sensor")
@@ -67,7 +67,6 @@ def test_device_replay_weather_through_the_environment_api(tmp_path):
   twins = [orc.OracleBuilding(plan, prm, float(env.config.initial_temp)) for _ in range(B)]
   rs = np.random.RandomState(9)
   acts = rs.uniform(-1, 1, size=(T, B, 2)).astype(np.float32)
-  rng_w, rng_a = env.config.action_ranges
   shift = [dt.timedelta(seconds=float(o)) for o in offsets]
   for t in range(T):
     now = env.current_simulation_timestamp
@@ -77,15 +76,12 @@ def test_device_replay_weather_through_the_environment_api(tmp_path):
     info = env.info.cpu().numpy()
     nxt = now + dt.timedelta(seconds=300)
     for b in range(B):
-      a = acts[t, b]
-      native = [np.float32((float(a[0]) + 1.0) / 2.0 * (rng_w[1] - rng_w[0]) + rng_w[0]),
-                np.float32((float(a[1]) + 1.0) / 2.0 * (rng_a[1] - rng_a[0]) + rng_a[0])]
       o = twins[b].step(
           now_ts=300.0 * t, t_amb_now=one.get_current_temp(now + shift[b]), h_conv=float(g["h_conv"]),
           t_amb_next=one.get_current_temp(nxt + shift[b]), comfort_now=bool(si.comfort_now),
           comfort_prev=si.comfort_prev == 1, comfort_next=bool(si.comfort_next), occupancy=si.occupancy,
           e_price=si.e_price, e_carbon=si.e_carbon, g_price=si.g_price, g_carbon=si.g_carbon,
-          action=native, observe=True)
+          action=native_action(env.config, acts[t, b]), observe=True)
       assert int(info[b, 4]) == o["n_sweeps"], (t, b, info[b, 4], o["n_sweeps"])
       assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
       assert abs(float(out.reward[b]) - o["reward"]) < 1e-6, (t, b)

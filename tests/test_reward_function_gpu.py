@@ -18,7 +18,9 @@ from sbsim_amd.environment import BatchedEnvironment, BatchedSimulator, EnvSnaps
 from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan  # noqa: E402
 from sbsim_amd.host_inputs import BuildingParams, SetpointEnergyCarbonReward  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_reward_function_cpu import SET_FIELDS, fixture, restate  # noqa: E402
+from tests.parity import need_gpu  # noqa: E402
+from tests.reward_cases import SET_FIELDS, fixture, restate  # noqa: E402
+from tests.twins import plan_from_npz  # noqa: E402
 
 C_AIR = 1006.0   # utils/constants.py:21
 SB1 = SimConfig.sb1()
@@ -26,14 +28,8 @@ REWARD = SetpointEnergyCarbonReward(1.5, 0.75, 0.2, reward_normalizer_shift=-3.0
 INFO_COLUMNS = dict(zip(SET_FIELDS, range(7, 13)))   # RewardResponse field -> info column
 
 
-def _need_gpu():
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
-
-
 def _small():
-  from tests.test_gpu_parity import _plan
-  return _plan(load("plan_small_test.npz"))
+  return plan_from_npz(load("plan_small_test.npz"))
 
 
 def _row_plan(zones):
@@ -106,7 +102,7 @@ def _check_rates(info, blower, ac, gas, pump, name):   # (the tolerances of test
 def test_named_known_answers_through_k_post():
   """setpoint_energy_carbon_reward_test.py:31-148: the values that test asserts, to its four decimals.  Its RewardInfo
   holds two air handlers and two boilers; the building here has one of each with their summed rates."""
-  _need_gpu()
+  need_gpu()
   doc = fixture()
   c = doc["named"]["config"]
   per_w_s = lambda per_kwh: per_kwh / 3600.0 / 1000.0
@@ -140,7 +136,7 @@ def test_random_rows_through_k_post():
   """Every RewardResponse field of the fixture's seeded rows (the reference function with its own cost models), to
   float32 rounding: 1-3 zones on either side of the window, empty zones, cooling, a gas rate the regret function
   would cap, shift and scale."""
-  _need_gpu()
+  need_gpu()
   rows = fixture()["random"]
   taps = {}
   for row in rows:
@@ -216,7 +212,7 @@ def _restated_rewards(env, step, reward_function):
 
 @pytest.mark.parametrize("solver", ["gauss_seidel", "jacobi_fp32"])
 def test_whole_steps_equal_the_restatement_and_change_nothing_but_the_reward(solver):
-  _need_gpu()
+  need_gpu()
   B, T = 4, 3
   acts = _actions(T, B, 31)
   plain = BatchedEnvironment(_small(), B, collect_info=True, solver=solver)
@@ -247,7 +243,7 @@ def test_whole_steps_equal_the_restatement_and_change_nothing_but_the_reward(sol
 
 
 def test_the_default_is_untouched_by_a_kind_set_in_between():
-  _need_gpu()
+  need_gpu()
   B, T = 4, 3
   acts = _actions(T, B, 32)
   never = BatchedEnvironment(_small(), B, collect_info=True)
@@ -269,7 +265,7 @@ def test_the_default_is_untouched_by_a_kind_set_in_between():
 
 
 def test_per_building_rows_keep_applying():
-  _need_gpu()
+  need_gpu()
   B, T = 4, 2
   acts = _actions(T, B, 33)[:, :1].expand(T, B, 2).contiguous()   # the same actions for every building
   rows = {"max_productivity_personhour_usd": np.array([300.0, 450.0, 300.0, 120.0])}
@@ -292,7 +288,7 @@ def test_per_building_rows_keep_applying():
 
 
 def test_a_rejected_building_gets_minus_infinity():
-  _need_gpu()
+  need_gpu()
   B = 4
   env = BatchedEnvironment(_small(), B, collect_info=True, reward_function=REWARD)
   _start(env)
@@ -304,7 +300,7 @@ def test_a_rejected_building_gets_minus_infinity():
 
 
 def test_mixed_classes_with_a_reward_function_each():
-  _need_gpu()
+  need_gpu()
   plans = [_small(), _row_plan(3)]
   rewards = [None, REWARD]
   T = 3
@@ -334,7 +330,7 @@ def test_mixed_classes_with_a_reward_function_each():
 
 
 def test_snapshots_carry_the_reward_function():
-  _need_gpu()
+  need_gpu()
   B = 4
   acts = _actions(5, B, 36)
   plain = BatchedEnvironment(_small(), B, collect_info=True)
@@ -365,7 +361,7 @@ def test_snapshots_carry_the_reward_function():
 
 
 def test_refusals():
-  _need_gpu()
+  need_gpu()
   sim = BatchedSimulator(_small(), SB1, 2, 12.0)
   fn = _ffi.reward_entry("sb_set_reward_function")
   good = (1, 1.0, 1.0, 0.2, 0.0, 1.0)

@@ -9,6 +9,7 @@ import pytest
 from oracle import oracle as orc
 from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
 from tests.roll_free_model import RollFreeModel
+from tests.twins import oracle_plan_of
 
 PLANS = [((3, 3), (20, 30), 3),   # R9: 66 x 96, two tail rows
          ((2, 3), (30, 30), 3),   # 65 x 94: one tail row
@@ -25,8 +26,7 @@ def _case(rooms, shape, seed=5):
   q = np.zeros((H, W))
   for z, cells in enumerate(fp.zone_cell_lists()):
     q.reshape(-1)[cells] = qz[z] * fp.diffusers.reshape(-1)[cells]
-  plan = orc.OraclePlan(fp.conductivity, fp.density, fp.heat_capacity, fp.exterior_space,
-                        fp.zone_cell_lists(), fp.diffusers, fp.cv_size_cm, fp.floor_height_cm)
+  plan = oracle_plan_of(fp)
   return cp, plan, prev, qz, q
 
 

@@ -15,7 +15,7 @@ wavefront takes its first building through the ramp-up) -- and one batch of 2,04
 
 Both instantiations share the update's arithmetic and its order: temperature grids, zone sums, sweep counts and converged
 flags must be EQUAL bit for bit.  Sweep counts must be EQUAL to the twins', zone temperatures within 1e-8 K of theirs
-(tests/test_gpu_parity.py's bar) at every step.
+(tests/twins.py's T_TOL) at every step.
 
 The switches are read once in sb_create, so every configuration (default / exact / forced redo) is ONE child process (this
 file with --worker) that runs its cases one after the other, under a time limit; a child that fails ends every test that
@@ -57,8 +57,12 @@ REDO_CASE = "r9-limit100"
 
 
 def _plan(spec):
-  from tests.test_roll_free_gpu import _plan as plan_of
-  return plan_of(spec)
+  from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
+  if spec == "ringless":
+    from tests.golden_util import load
+    from tests.twins import ringless_plan
+    return ringless_plan(load("rect_building_cold200.npz"))
+  return FloorPlan.from_file_input(rectangular_floor_plan(*spec), Materials.sb1(), 10.0, 300.0)
 
 
 def worker(names, out_dir: str, with_twins: bool) -> None:
@@ -68,7 +72,7 @@ def worker(names, out_dir: str, with_twins: bool) -> None:
   import dataclasses
   import torch
   from sbsim_amd.environment import BatchedEnvironment, SimConfig
-  from tests import threshold_cases as tc
+  from tests.twins import native_action, oracle_twin
   for case in names:
     pname, B, limit = CASES[case]
     plan = _plan(PLANS[pname][0])
@@ -80,7 +84,7 @@ def worker(names, out_dir: str, with_twins: bool) -> None:
     env.sim.reset(temps=torch.tensor(t_init, dtype=torch.float64, device="cuda")[:, None].expand(B, H * W).contiguous())
     acts = np.random.RandomState(1234).uniform(-1.0, 1.0, size=(STEPS, B, 2)).astype(np.float32)
     n_twins = N_TWINS if with_twins else 0
-    twins = [tc.oracle_twin(plan, cfg, np.full(H * W, float(t_init[b]))) for b in range(n_twins)]
+    twins = [oracle_twin(plan, cfg, np.full(H * W, float(t_init[b]))) for b in range(n_twins)]
     for tw in twins:
       tw.observe_boiler(0.0)
     nsw, conv, zt, tw_nsw, tw_conv, tw_zt = [], [], [], [], [], []
@@ -95,7 +99,7 @@ def worker(names, out_dir: str, with_twins: bool) -> None:
         o = tw.step(now_ts=300.0 * t, t_amb_now=si.t_amb_now, h_conv=100.0, t_amb_next=si.t_amb_next,
                     comfort_now=bool(si.comfort_now), comfort_prev=si.comfort_prev == 1, comfort_next=bool(si.comfort_next),
                     occupancy=si.occupancy, e_price=si.e_price, e_carbon=si.e_carbon, g_price=si.g_price,
-                    g_carbon=si.g_carbon, action=tc.native_action(cfg, acts[t, b]))
+                    g_carbon=si.g_carbon, action=native_action(cfg, acts[t, b]))
         tw_nsw.append(o["n_sweeps"])
         tw_conv.append(int(o["converged"]))
         tw_zt.append(np.asarray(o["zone_temp_post"], dtype=np.float64))
@@ -150,12 +154,6 @@ def _same_bits(a, b):
   return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
-def _need_gpu():
-  torch = pytest.importorskip("torch")
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
-
-
 def _compare(fast, exact, case):
   """`fast` (the library's kernel, with its twins) against `exact` (the float64 instantiation alone)."""
   limit, cold_keeps_going = CASES[case][2], PLANS[CASES[case][0]][2]
@@ -179,7 +177,9 @@ def _compare(fast, exact, case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", list(CASES))
 def test_ramp_up_is_bit_identical_to_the_float64_instantiation_and_matches_the_twins(case, tmp_path_factory):
-  _need_gpu()
+  pytest.importorskip("torch")
+  from tests.parity import need_gpu
+  need_gpu()
   _compare(_result("default", case, tmp_path_factory), _result("exact", case, tmp_path_factory), case)
 
 
@@ -187,7 +187,9 @@ def test_ramp_up_is_bit_identical_to_the_float64_instantiation_and_matches_the_t
 def test_float64_ramp_up_behind_the_fast_one_on_the_redo_list(tmp_path_factory):
   """SBSIM_DEBUG_FORCE_REDO=3: every third building leaves the fast kernel at its stopping sweep and is redone by the
   float64 instantiation -- in the same step, from its untouched state.  Nothing may differ from the run without the switch."""
-  _need_gpu()
+  pytest.importorskip("torch")
+  from tests.parity import need_gpu
+  need_gpu()
   fast, exact = _result("default", REDO_CASE, tmp_path_factory), _result("exact", REDO_CASE, tmp_path_factory)
   redo = _result("redo", REDO_CASE, tmp_path_factory)
   redo["twins"], redo["twins_conv"], redo["twins_zt"] = fast["twins"], fast["twins_conv"], fast["twins_zt"]   # (the same batch: the twins are the default child's)

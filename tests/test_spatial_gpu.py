@@ -20,18 +20,14 @@ from tests import convection_cases as cc  # noqa: E402
 from tests import handover_cases as hc  # noqa: E402
 from tests import spatial_restatement as sr  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_jacobi_gpu import _plan  # noqa: E402
+from tests.parity import need_gpu  # noqa: E402
+from tests.twins import plan_from_npz  # noqa: E402
 
 SHORT = dict(num_days_in_episode=12 / 288, holiday_calendar=None)
 
 
-def _need_gpu():
-  if not torch.cuda.is_available():
-    pytest.skip("no GPU")
-
-
 def _small():
-  return _plan(load("plan_small_test.npz"))
+  return plan_from_npz(load("plan_small_test.npz"))
 
 
 def _r9():
@@ -114,7 +110,7 @@ def test_every_layout_against_the_restatement(name, monkeypatch):
   """Pools (1, 1): the map is temps() rounded to float32; (4, 4): on 68 x 98 the last column of tiles is ragged; (H, W):
   a 1 x 1 map, one wave-order tile; none: zone statistics only, a map request raises.  R9 also (5, 7) and a ragged
   wave-order pool (9, 8)."""
-  _need_gpu()
+  need_gpu()
   sim, fp = _layout_sim(name, monkeypatch)
   H, W = fp.shape
   seen = _put(sim, fp, _grids(fp, sim.B))
@@ -143,7 +139,7 @@ def test_every_layout_against_the_restatement(name, monkeypatch):
 def test_room_shapes(plan):
   """Rooms of 1, 2, 3, 64, 65 and 600 cells (a lone lane, one full round, one cell into the second); an L-shaped room
   and a zone of distant pieces; a zone made of two rooms."""
-  _need_gpu()
+  need_gpu()
   fp = cc.PLANS[plan]()
   if plan == "sizes":
     assert sorted(len(c) for c in fp.zone_cell_lists()) == [1, 2, 3, 64, 65, 600]
@@ -157,7 +153,7 @@ def test_room_shapes(plan):
 
 def test_same_bits_on_every_layout(monkeypatch):
   """The same R9 input on the register layout, the LDS grid by rows and the LDS grid transposed: byte-identical."""
-  _need_gpu()
+  need_gpu()
   outs = []
   for name in ("roll", "lds-rows", "lds-columns"):
     sim, fp = _layout_sim(name, monkeypatch, B=3)
@@ -178,7 +174,7 @@ def test_same_bits_on_every_layout(monkeypatch):
 
 
 def test_picks():
-  _need_gpu()
+  need_gpu()
   fp = _small()
   B = 4
   sim = BatchedSimulator(fp, SimConfig.sb1(), B, 100.0)
@@ -226,7 +222,7 @@ def test_picks():
 def test_grid_stride_on_one_cu(monkeypatch):
   """The tiny plan under SBSIM_DEBUG_CUS=1 with B = 4 * 32 + 3: every workgroup runs several rows, the last round is
   partly empty; every row must be right, picked or not."""
-  _need_gpu()
+  need_gpu()
   monkeypatch.setenv(hc.SWITCH, "1")
   fp = cc._plan(cc.TINY)
   B = cc.B_HANDOVER
@@ -244,7 +240,7 @@ def test_after_real_steps(solver):
   """Three steps of random actions (R9 on the default kernel: the ring now holds the step's ambient temperature, the
   uniform case; the small plan on the Jacobi solver): the outputs are the restatement of temps() bit for bit, and the
   zone mean is within 1e-9 K of zone_temps()."""
-  _need_gpu()
+  need_gpu()
   fp = _r9() if solver == "gauss_seidel" else _small()
   B = 4
   env = BatchedEnvironment(fp, B, solver=solver, spatial=SpatialOutputs(pool=(4, 4)), **SHORT)
@@ -265,7 +261,7 @@ def _direct(env):
 
 
 def test_environment_outputs_follow_reset_step_snapshot_and_fork():
-  _need_gpu()
+  need_gpu()
   fp, B = _small(), 4
   env = BatchedEnvironment(fp, B, spatial=SpatialOutputs(pool=(4, 4)), **SHORT)
   assert env.final_temperature_map is None and env.final_zone_temp_stats is None
@@ -304,7 +300,7 @@ def test_environment_with_episodes_per_building():
   """Episode lengths 2, 3, 5, 2, 7, 12, 3.  The twin has every length 12 and runs the same actions: until a building's
   first episode ends, the two environments' copies of it are in the same state, so a direct call on the twin after the
   step is the call "just before the reset" of the buildings that end in that step."""
-  _need_gpu()
+  need_gpu()
   fp = _small()
   steps = np.array([2, 3, 5, 2, 7, 12, 3])
   B = len(steps)
@@ -349,7 +345,7 @@ def test_environment_with_episodes_per_building():
 
 
 def test_mixed_batch_and_the_default():
-  _need_gpu()
+  need_gpu()
   small, tiny = _small(), cc._plan(cc.TINY)
   assert small.shape != tiny.shape
   mixed = MixedBatchedEnvironment([(small, 3), (tiny, 2)], spatial=SpatialOutputs(pool=(4, 4)), **SHORT)
@@ -380,7 +376,7 @@ def test_mixed_batch_and_the_default():
 
 
 def test_refusals_of_the_c_entries():
-  _need_gpu()
+  need_gpu()
   fp, B = _small(), 2
   attach, run = _ffi.spatial_entry("sb_spatial_attach"), _ffi.spatial_entry("sb_spatial")
   err = lambda: _ffi.load().sb_last_error().decode()

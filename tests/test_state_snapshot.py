@@ -10,12 +10,13 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from oracle import oracle as orc  # noqa: E402  (checker only)
-from sbsim_amd import _ffi, host_inputs  # noqa: E402
+from sbsim_amd import host_inputs  # noqa: E402
 from sbsim_amd.environment import (BatchedEnvironment, BatchedSimulator, EnvSnapshot,  # noqa: E402
                                    MixedBatchedEnvironment, SimConfig)
 from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan  # noqa: E402
 from tests.golden_util import load, oracle_params, oracle_plan  # noqa: E402
-from tests.test_gpu_parity import T_TOL, _need_gpu, _plan, _step_in  # noqa: E402
+from tests.parity import assert_close, assert_same, need_gpu, step_buffers  # noqa: E402
+from tests.twins import T_TOL, copy_twin, plan_from_npz, step_in, step_kwargs  # noqa: E402
 
 # the six wavefront schedules of test_one_day_rollout_against_reference_golden, plus the streaming kernel
 SCHEDULES = {
@@ -37,17 +38,11 @@ def _r9_sim(schedule, B, monkeypatch):
   for k, v in env.items():
     monkeypatch.setenv(k, v)
   g = load("h2_sb1_r9_random.npz")
-  sim = BatchedSimulator(_plan(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]), orientation=orientation)
+  sim = BatchedSimulator(plan_from_npz(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]), orientation=orientation)
   assert sim.launch_info["kernel"] == kernel, (schedule, sim.launch_info)
   for k in env:
     monkeypatch.delenv(k)
   return sim, g
-
-
-def _bufs(sim):
-  B = sim.B
-  return (torch.zeros((B, sim.O), dtype=torch.float32, device="cuda"), torch.zeros((B,), dtype=torch.float32, device="cuda"),
-          torch.zeros((B, _ffi.SB_INFO_STRIDE), dtype=torch.float32, device="cuda"))
 
 
 def _seeded(B, T, seed):
@@ -61,47 +56,29 @@ def _run(sim, g, acts, t0, steps, bufs, record=False):
   obs, rew, info = bufs
   out = []
   for t in range(t0, t0 + steps):
-    sim.step(acts[t], _step_in(g, 100 + t), obs, rew, info)
+    sim.step(acts[t], step_in(g, 100 + t), obs, rew, info)
     if record:
       out.append([obs.clone(), rew.clone(), info.clone(), sim.temps(), sim.scalars(), sim.modes(), sim.zone_temps()])
   return out
 
 
-def _assert_same(a, b):
-  for t, (x, y) in enumerate(zip(a, b)):
-    for k, (u, v) in enumerate(zip(x, y)):
-      assert torch.equal(u, v), (t, k, float((u.double() - v.double()).abs().max()))
-
-
-def _assert_close(a, b):
-  """k_sweep_stream adds a building's zone sums with LDS atomics from several wavefronts, in the order they arrive: its
-  zone means and grid sum are not bitwise repeatable from run to run, snapshot or not.  A replay on it meets the bar of
-  the layout test instead: equal sweep counts and modes, grids within 1e-9 K."""
-  for t, (x, y) in enumerate(zip(a, b)):
-    obs, rew, info, temps, scal, modes, zt = zip(x, y)
-    assert torch.equal(*modes) and torch.equal(info[0][:, 4], info[1][:, 4]), t
-    assert float((temps[0] - temps[1]).abs().max()) < 1e-9 and float((zt[0] - zt[1]).abs().max()) < 1e-9, t
-    assert float((rew[0] - rew[1]).abs().max()) < 1e-6 and torch.allclose(obs[0], obs[1], rtol=1e-5, atol=1e-5), t
-    assert torch.allclose(scal[0], scal[1], rtol=1e-12, atol=1e-9), t
-
-
 @pytest.mark.parametrize("schedule", list(SCHEDULES))
 def test_restore_replays_bitwise_on_every_schedule(schedule, monkeypatch):
-  _need_gpu()
+  need_gpu()
   B = 64
   sim, g = _r9_sim(schedule, B, monkeypatch)
   init, acts = _seeded(B, 50, 11)
   sim.reset(temps=init)
-  bufs = _bufs(sim)
+  bufs = step_buffers(sim)
   _run(sim, g, acts, 0, 20, bufs)
   snap = sim.save_state()
   first = _run(sim, g, acts, 20, 30, bufs, record=True)
   sim.load_state(snap)
   again = _run(sim, g, acts, 20, 30, bufs, record=True)
   if schedule == "stream":
-    _assert_close(first, again)
+    assert_close(first, again)
   else:
-    _assert_same(first, again)
+    assert_same(first, again)
   assert float(first[-1][2][:, 4].sum()) > 0   # (the sweeps ran)
   sim.close()
 
@@ -128,7 +105,7 @@ def _env_run(env, acts, steps, record=True):
 
 
 def test_restore_replays_bitwise_with_device_occupancy_convection_and_weather():
-  _need_gpu()
+  need_gpu()
   B = 64
   env = _stochastic_env(B)
   gen = torch.Generator(device="cuda")
@@ -143,7 +120,7 @@ def test_restore_replays_bitwise_with_device_occupancy_convection_and_weather():
   assert env.current_simulation_timestamp == now
   assert torch.equal(ts.observation, snap.observation) and bool((ts.step_type == 1).all())
   again = _env_run(env, acts[20:], 30)
-  _assert_same(first, again)
+  assert_same(first, again)
   env.close()
 
 
@@ -152,7 +129,7 @@ def _check_golden_from(sim, g, t0, bufs):
   B = sim.B
   for t in range(t0, len(g["n_sweeps"])):
     act = torch.tensor(np.tile(g["actions_norm"][t], (B, 1)), dtype=torch.float32, device="cuda")
-    sim.step(act, _step_in(g, t), obs, rew, info)
+    sim.step(act, step_in(g, t), obs, rew, info)
     i = info.cpu().numpy()
     assert (i[:, 4] == g["n_sweeps"][t]).all(), t
     assert np.abs(sim.zone_temps().cpu().numpy() - g["zone_temp_post"][t]).max() < T_TOL, t
@@ -163,14 +140,14 @@ def _check_golden_from(sim, g, t0, bufs):
 
 
 def test_restored_day_matches_the_reference_golden_twice(monkeypatch):
-  _need_gpu()
+  need_gpu()
   sim, g = _r9_sim("reg", 5, monkeypatch)
   sim.reset()
-  bufs = _bufs(sim)
+  bufs = step_buffers(sim)
   obs, rew, info = bufs
   for t in range(144):
     act = torch.tensor(np.tile(g["actions_norm"][t], (5, 1)), dtype=torch.float32, device="cuda")
-    sim.step(act, _step_in(g, t), obs, rew, info)
+    sim.step(act, step_in(g, t), obs, rew, info)
   assert np.abs(sim.temps().cpu().numpy() - g["grid_144"]).max() < T_TOL
   snap = sim.save_state()
   _check_golden_from(sim, g, 144, bufs)
@@ -181,26 +158,11 @@ def test_restored_day_matches_the_reference_golden_twice(monkeypatch):
 
 
 def _twin_step(twin, g, tt, t, a):
-  rng_w, rng_a = (310.0, 355.0), (285.0, 300.0)
-  native = [np.float32((float(a[0]) + 1.0) / 2.0 * (rng_w[1] - rng_w[0]) + rng_w[0]),
-            np.float32((float(a[1]) + 1.0) / 2.0 * (rng_a[1] - rng_a[0]) + rng_a[0])]
-  return twin.step(now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
-                   t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-                   comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-                   occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]), e_carbon=float(g["e_carbon"][tt]),
-                   g_price=float(g["g_price"][tt]), g_carbon=float(g["g_carbon"][tt]), action=native, observe=True)
-
-
-def _copy_twin(dst, src):
-  for k in ("temp", "input_q", "mode", "damper", "valve", "zone_air_temp"):
-    getattr(dst, k)[:] = getattr(src, k)
-  for name, ctype in orc._State._fields_:
-    if not hasattr(ctype, "contents"):   # the scalars, not the array pointers
-      setattr(dst.state, name, getattr(src.state, name))
+  return twin.step(**step_kwargs(g, tt, t, SimConfig.sb1(), a))
 
 
 def test_fork_against_the_oracle(monkeypatch):
-  _need_gpu()
+  need_gpu()
   B = 16
   sim, g = _r9_sim("reg", B, monkeypatch)
   init, acts = _seeded(B, 30, 13)
@@ -210,10 +172,10 @@ def test_fork_against_the_oracle(monkeypatch):
   plan, prm = oracle_plan(p), oracle_params(g["params_json"])
   init_np = init.cpu().numpy()
   twins = [orc.OracleBuilding(plan, prm, 0.0, reset_temps=init_np[b]) for b in range(B)]
-  bufs = _bufs(sim)
+  bufs = step_buffers(sim)
   obs, rew, info = bufs
   for t in range(10):
-    sim.step(acts[t], _step_in(g, 100 + t), obs, rew, info)
+    sim.step(acts[t], step_in(g, 100 + t), obs, rew, info)
     for b in range(B):
       _twin_step(twins[b], g, 100 + t, t, acts_np[t, b])
   src = [3, 3, 0, 7, 7, 7, 15, 2, 9, 9, 1, 4, 4, 12, 3, 0]
@@ -221,10 +183,10 @@ def test_fork_against_the_oracle(monkeypatch):
   sim.load_state(sim.save_state(rows=uniq), pick=inv, clock=False)
   copies = [orc.OracleBuilding(plan, prm, 0.0, reset_temps=init_np[b]) for b in range(B)]
   for b in range(B):
-    _copy_twin(copies[b], twins[src[b]])
+    copy_twin(copies[b], twins[src[b]])
   twins = copies
   for t in range(10, 30):
-    sim.step(acts[t], _step_in(g, 100 + t), obs, rew, info)
+    sim.step(acts[t], step_in(g, 100 + t), obs, rew, info)
     i = info.cpu().numpy()
     zt = sim.zone_temps().cpu().numpy()
     for b in range(B):
@@ -238,7 +200,7 @@ def test_fork_against_the_oracle(monkeypatch):
 
 
 def test_environment_fork_identity_and_broadcast():
-  _need_gpu()
+  need_gpu()
   B, k = 16, 5
   plan = FloorPlan.from_file_input(rectangular_floor_plan((3, 3), (20, 30)), Materials.sb1(), 10.0, 300.0)
   envs = [BatchedEnvironment(plan, B, collect_info=True) for _ in range(2)]
@@ -251,7 +213,7 @@ def test_environment_fork_identity_and_broadcast():
   before = [envs[0].sim.temps(), envs[0].sim.scalars(), envs[0].sim.modes(), envs[0].sim.zone_temps()]
   envs[0].fork(torch.arange(B, device="cuda"))
   after = [envs[0].sim.temps(), envs[0].sim.scalars(), envs[0].sim.modes(), envs[0].sim.zone_temps()]
-  _assert_same([before], [after])
+  assert_same([before], [after])
   envs[0].fork(torch.full((B,), k, dtype=torch.int64, device="cuda"))
   same = acts[8:, k:k + 1].expand(-1, B, -1).contiguous()   # building k's actions in every row
   forked = _env_run(envs[0], same, 10)
@@ -269,7 +231,7 @@ def test_environment_fork_identity_and_broadcast():
 
 @pytest.mark.parametrize("src,dst", [("reg", "lds-columns"), ("lds-columns", "reg")])
 def test_snapshot_moves_between_layouts_and_orientations(src, dst, monkeypatch):
-  _need_gpu()
+  need_gpu()
   B = 64
   a, g = _r9_sim(src, B, monkeypatch)
   b, _ = _r9_sim(dst, B, monkeypatch)
@@ -277,7 +239,7 @@ def test_snapshot_moves_between_layouts_and_orientations(src, dst, monkeypatch):
   init, acts = _seeded(B, 40, 17)
   a.reset(temps=init)
   b.reset(temps=init)   # (b's own clock: reset once, like a's)
-  ba, bb = _bufs(a), _bufs(b)
+  ba, bb = step_buffers(a), step_buffers(b)
   _run(a, g, acts, 0, 20, ba)
   b.load_state(a.save_state())
   assert torch.equal(a.temps(), b.temps()) and torch.equal(a.scalars(), b.scalars())
@@ -293,7 +255,7 @@ def test_snapshot_moves_between_layouts_and_orientations(src, dst, monkeypatch):
 
 
 def test_disk_checkpoint_restores_in_a_new_environment(tmp_path):
-  _need_gpu()
+  need_gpu()
   B = 32
   env = _stochastic_env(B)
   gen = torch.Generator(device="cuda")
@@ -309,12 +271,12 @@ def test_disk_checkpoint_restores_in_a_new_environment(tmp_path):
   ts = fresh.restore(EnvSnapshot.from_state_dict(torch.load(path), "cuda"))
   assert bool((ts.step_type == 1).all())
   again = _env_run(fresh, acts[15:], 10)
-  _assert_same(first, again)
+  assert_same(first, again)
   fresh.close()
 
 
 def test_mixed_environment_restore_and_cross_class_fork():
-  _need_gpu()
+  need_gpu()
   plans = [FloorPlan.from_file_input(rectangular_floor_plan(r, s), Materials.sb1(), 10.0, 300.0)
            for r, s in (((3, 3), (20, 30)), ((2, 3), (9, 10)), ((2, 2), (5, 9)))]
   env = MixedBatchedEnvironment([(plans[0], 8), (plans[1], 6), (plans[2], 4)], collect_info=True)
@@ -336,7 +298,7 @@ def test_mixed_environment_restore_and_cross_class_fork():
   first = run(8, 10)
   env.restore(snaps)
   again = run(8, 10)
-  _assert_same(first, again)
+  assert_same(first, again)
   src = torch.arange(B, device="cuda")
   src[0] = 9   # building 9 is in the second class
   with pytest.raises(ValueError):
@@ -349,28 +311,28 @@ def test_mixed_environment_restore_and_cross_class_fork():
 
 
 def test_full_size_round_trip_is_bitwise():
-  _need_gpu()
+  need_gpu()
   B = 65536
   g = load("h2_sb1_r9_random.npz")
-  sim = BatchedSimulator(_plan(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]))
+  sim = BatchedSimulator(plan_from_npz(load("plan_r9_sb1.npz")), SimConfig.sb1(), B, float(g["h_conv"]))
   gen = torch.Generator(device="cuda")
   gen.manual_seed(5)
   t0 = (294.0 + torch.randn((B, 1), generator=gen, device="cuda", dtype=torch.float64)).clamp(285.0, 305.0)
   init = (t0 + 0.05 * torch.randn((B, 68 * 98), generator=gen, device="cuda", dtype=torch.float64)).contiguous()
   acts = torch.rand((3, B, 2), generator=gen, device="cuda") * 2 - 1
   sim.reset(temps=init)
-  _run(sim, g, acts, 0, 3, _bufs(sim))
+  _run(sim, g, acts, 0, 3, step_buffers(sim))
   want = [sim.temps(), sim.scalars(), sim.modes(), sim.zone_temps()]
   snap = sim.save_state()
   sim.reset(temps=init)   # everything else
   sim.load_state(snap)
   got = [sim.temps(), sim.scalars(), sim.modes(), sim.zone_temps()]
-  _assert_same([want], [got])
+  assert_same([want], [got])
   sim.close()
 
 
 def test_refusals_before_any_launch(monkeypatch):
-  _need_gpu()
+  need_gpu()
   sim, g = _r9_sim("reg", 8, monkeypatch)
   snap = sim.save_state()
   other_plan = FloorPlan.from_file_input(rectangular_floor_plan((2, 3), (9, 10)), Materials.sb1(), 10.0, 300.0)
@@ -379,10 +341,10 @@ def test_refusals_before_any_launch(monkeypatch):
     other.load_state(snap)
   cfg = SimConfig.sb1()
   cfg.boiler_heating_rate = 0.6
-  other_cfg = BatchedSimulator(_plan(load("plan_r9_sb1.npz")), cfg, 8, float(g["h_conv"]))
+  other_cfg = BatchedSimulator(plan_from_npz(load("plan_r9_sb1.npz")), cfg, 8, float(g["h_conv"]))
   with pytest.raises(ValueError):
     other_cfg.load_state(snap)
-  occ = BatchedSimulator(_plan(load("plan_r9_sb1.npz")), SimConfig.sb1(), 8, float(g["h_conv"]))
+  occ = BatchedSimulator(plan_from_npz(load("plan_r9_sb1.npz")), SimConfig.sb1(), 8, float(g["h_conv"]))
   occ.occupancy_attach(10, (5, 10, 15, 19), 300.0, 1)
   with pytest.raises(ValueError):
     occ.load_state(snap)

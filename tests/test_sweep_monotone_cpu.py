@@ -9,6 +9,7 @@ import pytest
 
 from oracle import oracle as orc
 from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
+from tests.twins import oracle_plan_of
 
 PLANS = {
     "R9": ((3, 3), (20, 30)),
@@ -36,8 +37,7 @@ def test_class_coefficients_are_a_contraction(name):
 @pytest.mark.parametrize("name,seed", [("R9", 0), ("R9", 1), ("SB2-synth", 2), ("SB1-synth", 3), ("small", 4)])
 def test_max_delta_never_grows_between_sweeps(name, seed):
   plan = _plan(name)
-  oplan = orc.OraclePlan(plan.conductivity, plan.density, plan.heat_capacity, plan.exterior_space,
-                         plan.zone_cell_lists(), plan.diffusers, plan.cv_size_cm, plan.floor_height_cm)
+  oplan = oracle_plan_of(plan)
   H, W = plan.shape
   rs = np.random.RandomState(seed)
   prev = np.clip(294.0 + 3.0 * rs.randn(H * W), 280.0, 310.0)           # a rough field: every mode is excited

@@ -24,7 +24,8 @@ from sbsim_amd.environment import BatchedSimulator, SimConfig  # noqa: E402
 from tests import jacobi_restatement as jr  # noqa: E402
 from tests import threshold_cases as tc  # noqa: E402
 from tests.golden_util import load  # noqa: E402
-from tests.test_gpu_parity import _check_plan_against_oracle, _need_experimental_kernels, _need_gpu  # noqa: E402
+from tests.parity import check_plan_against_oracle, need_experimental_kernels, need_gpu  # noqa: E402
+from tests.twins import oracle_twin, step_kwargs  # noqa: E402
 
 # id: (plan, orientation, path, environment, sb_sweep_kernel, wavefronts per building or None, experimental library)
 KERNELS = {
@@ -60,12 +61,12 @@ class _Case:
   """A kernel's floor plan, inputs and oracle series; runs one configuration against the oracle twins."""
 
   def __init__(self, kernel, monkeypatch):
-    _need_gpu()
+    need_gpu()
     name, self.orientation, self.path, env, self.kern, self.waves, exp = KERNELS[kernel]
     self.mp = monkeypatch
     for k, v in env.items():
       monkeypatch.setenv(k, v)
-    _need_experimental_kernels(exp, monkeypatch)
+    need_experimental_kernels(exp, monkeypatch)
     self.g = load("h2_sb1_r9_random.npz")
     self.plan = tc.floor_plan(name)
     self.cfg = SimConfig.sb1()
@@ -77,16 +78,16 @@ class _Case:
 
   def run(self, theta, limit, steps=T):
     cfg = dataclasses.replace(self.cfg, convergence_threshold=theta, iteration_limit=limit)
-    return _check_plan_against_oracle(self.plan, self.plan.n_zones, self.orientation, self.path, self.mp,
-                                      expect_kernel=self.kern, expect_waves=self.waves, B=tc.B, T=steps,
-                                      init=self.init, acts=self.acts, cfg=cfg)
+    return check_plan_against_oracle(self.plan, self.plan.n_zones, self.orientation, self.path, self.mp,
+                                     expect_kernel=self.kern, expect_waves=self.waves, B=tc.B, T=steps,
+                                     init=self.init, acts=self.acts, cfg=cfg)
 
   def oracle_grid(self, k):
     """g_k: the oracle's grid after k sweeps of the first step (no zone power yet)."""
     if k not in self._grids:
-      tw = tc.oracle_twin(self.plan, dataclasses.replace(self.cfg, convergence_threshold=0.0, iteration_limit=k),
+      tw = oracle_twin(self.plan, dataclasses.replace(self.cfg, convergence_threshold=0.0, iteration_limit=k),
                           self.init[tc.TARGETS[0]])
-      tw.step(**tc.oracle_step_kwargs(self.g, 0, self.cfg, self.acts[0, tc.TARGETS[0]]))
+      tw.step(**step_kwargs(self.g, tc.TT0, 0, self.cfg, self.acts[0, tc.TARGETS[0]]))
       self._grids[k] = tw.temp.copy()
     return self._grids[k]
 
@@ -167,7 +168,7 @@ def test_jacobi_stops_where_float32_rounding_puts_the_threshold(kind, at_limit):
   """k_sweep_jacobi compares the float32 max|delta| with float32(threshold) (NumPy 2 / TF): thresholds at d_k, just
   above and just below the midpoint between d_k and the float32 below it, and at the midpoint (ties to even), with and
   without an iteration limit at k.  Iterations, converged flag and grid bit for bit against the restatement."""
-  _need_gpu()
+  need_gpu()
   fp, tprev, q, tinf = tc.jacobi_tap()
   cfg = SimConfig.sb1()
   tt = jr.tensors(fp, cfg.time_step_sec, 100.0)

@@ -12,11 +12,7 @@ from sbsim_amd.environment import SimConfig
 from tests import jacobi_restatement as jr
 from tests import threshold_cases as tc
 from tests.golden_util import load
-
-
-def _oplan(plan):
-  return orc.OraclePlan(plan.conductivity, plan.density, plan.heat_capacity, plan.exterior_space,
-                        plan.zone_cell_lists(), plan.diffusers, plan.cv_size_cm, plan.floor_height_cm)
+from tests.twins import oracle_plan_of, oracle_twin, step_kwargs
 
 
 @pytest.mark.parametrize("name", ["R9", "47x48", "narrow"])
@@ -25,7 +21,7 @@ def test_trace_is_the_max_delta_between_consecutive_grids(name):
   initial grid); the trace leaves the timestep's results alone, and OracleBuilding.step(trace=True) reports the same
   series for the first step after a reset (no zone power yet)."""
   plan = tc.floor_plan(name)
-  op = _oplan(plan)
+  op = oracle_plan_of(plan)
   g = load("h2_sb1_r9_random.npz")
   init, acts = tc.case_inputs(plan.shape[0] * plan.shape[1])
   t_amb, h = float(g["t_amb_now"][tc.TT0]), float(g["h_conv"])
@@ -46,9 +42,9 @@ def test_trace_is_the_max_delta_between_consecutive_grids(name):
   t2, n2, c2, m2 = orc.fd_timestep(op, init[1], q, t_amb, h, 300.0, thr, L, trace=True)
   assert (n1, c1) == (n2, c2) == (5, True) and np.array_equal(t1, t2) and np.array_equal(m2, m[:5])
   cfg = dataclasses.replace(SimConfig.sb1(), convergence_threshold=0.0, iteration_limit=L)
-  o = tc.oracle_twin(plan, cfg, init[1]).step(**tc.oracle_step_kwargs(g, 0, cfg, acts[0, 1]), trace=True)
+  o = oracle_twin(plan, cfg, init[1]).step(**step_kwargs(g, tc.TT0, 0, cfg, acts[0, 1]), trace=True)
   assert np.array_equal(o["max_delta"], m)
-  plain = tc.oracle_twin(plan, cfg, init[1]).step(**tc.oracle_step_kwargs(g, 0, cfg, acts[0, 1]))
+  plain = oracle_twin(plan, cfg, init[1]).step(**step_kwargs(g, tc.TT0, 0, cfg, acts[0, 1]))
   assert "max_delta" not in plain and plain["n_sweeps"] == o["n_sweeps"] and plain["reward"] == o["reward"]
 
 
@@ -72,7 +68,7 @@ def test_placements_hold_on_the_oracle(name):
     assert tc.check(m, p) is None
     for b in tc.TARGETS:
       c = dataclasses.replace(cfg, convergence_threshold=p.theta, iteration_limit=p.limit)
-      o = tc.oracle_twin(plan, c, init[b]).step(**tc.oracle_step_kwargs(g, 0, c, acts[0, b]))
+      o = oracle_twin(plan, c, init[b]).step(**step_kwargs(g, tc.TT0, 0, c, acts[0, b]))
       assert (o["n_sweeps"], o["converged"]) == (p.n, p.converged), (p, b)
   # every chosen sweep has an 'above' and a 'below' placement with the limit and without
   assert len(pl) >= 3 * len(ks) and {p.k for p in pl.values()} == set(ks), sorted(pl)

@@ -9,7 +9,7 @@ from sbsim_amd import _ffi
 from sbsim_amd.environment import SimConfig
 from sbsim_amd.floorplan import jacobi_cv_tensors
 from tests import zone_ladder as zl
-from tests.test_abi_cpu import _plan_info
+from tests.twins import oracle_plan_of, plan_info
 
 KIB160 = 160 * 1024
 
@@ -20,7 +20,7 @@ def _info(name, monkeypatch):
     monkeypatch.setenv(k, v)
   fp = zl.device_plan(name)
   cp = fp.compile(300.0, 12.0)
-  rc, info = _plan_info(fp, n_obs=3 * cp.Z + 19)
+  rc, info = plan_info(fp, n_obs=3 * cp.Z + 19)
   assert rc == 0, _ffi.load().sb_last_error()
   return fp, cp, info
 
@@ -91,8 +91,7 @@ def _inputs(fp, seed):
   q = np.zeros((H, W))
   for z, cells in enumerate(fp.zone_cell_lists()):
     q.reshape(-1)[cells] = qz[z] * fp.diffusers.reshape(-1)[cells]
-  oplan = orc.OraclePlan(fp.conductivity, fp.density, fp.heat_capacity, fp.exterior_space, fp.zone_cell_lists(),
-                         fp.diffusers, fp.cv_size_cm, fp.floor_height_cm)
+  oplan = oracle_plan_of(fp)
   return prev, q, qz, oplan
 
 

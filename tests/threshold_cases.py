@@ -23,13 +23,14 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from oracle import oracle as orc
+from tests.twins import oracle_twin, plan_from_npz, step_kwargs
 
 DELTA = 1e-10          # K: theta's distance from m_k
 THR_FAR = 1e-9         # K: step_two_impl.h's thr_far band above the threshold
 B = 6                  # buildings per case
 TARGETS = (1, 4, 5)    # the buildings that start from the target state
-TT0 = 96               # the step inputs' row of h2_sb1_r9_random.npz (mid-morning: occupied, comfort mode)
+TT0 = 96               # step t reads row TT0 + t of h2_sb1_r9_random.npz (mid-morning: occupied, comfort mode), as
+                       # tests/parity.py's check_plan_against_oracle gives the device
 SEED = 23
 KINDS = ("above", "below", "limit-above", "limit-below")
 
@@ -59,53 +60,13 @@ def floor_plan(name: str):
     return irregular_plans.plan(spec[len("irregular:"):])
   if isinstance(spec, str):
     from tests.golden_util import load
-    p = load(spec)
-    return FloorPlan(conductivity=p["conductivity"], heat_capacity=p["heat_capacity"], density=p["density"],
-                     exterior_space=p["exterior_space"], zone_label=p["zone_label"], diffusers=p["diffusers"],
-                     cv_size_cm=float(p["cv_size_cm"]), floor_height_cm=float(p["floor_height_cm"]),
-                     zone_names=tuple(str(z) for z in p["zone_names"]))
+    return plan_from_npz(load(spec))
   return FloorPlan.from_file_input(rectangular_floor_plan(*spec), Materials.sb1(), 10.0, 300.0)
 
 
 def hi32(x: float) -> int:
   """The high 32 bits of a float64 (sign, exponent, 20 mantissa bits): what k_sweep_roll's fast instantiation compares."""
   return int(np.array(x, dtype=np.float64).view(np.uint64)) >> 32
-
-
-def oracle_twin(plan, cfg, init_flat) -> orc.OracleBuilding:
-  """The CPU oracle of one building of a BatchedSimulator(plan, cfg) reset to ``init_flat``."""
-  oplan = orc.OraclePlan(plan.conductivity, plan.density, plan.heat_capacity, plan.exterior_space,
-                         plan.zone_cell_lists(), plan.diffusers, plan.cv_size_cm, plan.floor_height_cm)
-  c = cfg
-  oprm = orc.OracleParams(
-      dt=c.time_step_sec, conv_threshold=c.convergence_threshold, iter_limit=c.iteration_limit,
-      vav_max_air_flow=c.vav_max_air_flow_rate, vav_max_water_flow=c.vav_reheat_max_water_flow_rate,
-      ahu_recirc=c.ahu_recirculation, ahu_heat_sp=c.ahu_heating_air_temp_setpoint,
-      ahu_cool_sp=c.ahu_cooling_air_temp_setpoint, ahu_dp=c.ahu_fan_differential_pressure,
-      ahu_eff=c.ahu_fan_efficiency, ahu_max_flow=c.ahu_max_air_flow_rate, blr_setpoint=c.boiler_reheat_water_setpoint,
-      blr_head=c.boiler_water_pump_differential_head, blr_pump_eff=c.boiler_water_pump_efficiency,
-      comfort_lo=c.comfort_temp_window[0], comfort_hi=c.comfort_temp_window[1],
-      eco_lo=c.eco_temp_window[0], eco_hi=c.eco_temp_window[1],
-      blr_heating_rate=c.boiler_heating_rate, blr_cooling_rate=c.boiler_cooling_rate, ahu_has_weather=1)
-  return orc.OracleBuilding(oplan, oprm, 0.0, reset_temps=init_flat)
-
-
-def native_action(cfg, a) -> List[np.float32]:
-  lo, hi = cfg.action_ranges
-  return [np.float32((float(a[0]) + 1.0) / 2.0 * (lo[1] - lo[0]) + lo[0]),
-          np.float32((float(a[1]) + 1.0) / 2.0 * (hi[1] - hi[0]) + hi[0])]
-
-
-def oracle_step_kwargs(g, t: int, cfg, a) -> dict:
-  """OracleBuilding.step's arguments for step t of a case (the same inputs tests/test_gpu_parity.py's
-  _check_plan_against_oracle gives the device: row TT0 + t of h2_sb1_r9_random.npz)."""
-  tt = TT0 + t
-  return dict(now_ts=300.0 * t, t_amb_now=float(g["t_amb_now"][tt]), h_conv=float(g["h_conv"]),
-              t_amb_next=float(g["t_amb_next"][tt]), comfort_now=bool(g["comfort_now"][tt]),
-              comfort_prev=g["comfort_prev"][tt] == 1, comfort_next=bool(g["comfort_next"][tt]),
-              occupancy=float(g["occupancy"][tt]), e_price=float(g["e_price"][tt]), e_carbon=float(g["e_carbon"][tt]),
-              g_price=float(g["g_price"][tt]), g_carbon=float(g["g_carbon"][tt]), action=native_action(cfg, a),
-              observe=True)
 
 
 def case_inputs(n_cells: int, T: int = 3, seed: int = SEED) -> Tuple[np.ndarray, np.ndarray]:
@@ -121,7 +82,7 @@ def case_inputs(n_cells: int, T: int = 3, seed: int = SEED) -> Tuple[np.ndarray,
 def series(plan, cfg, g, init_flat, a) -> np.ndarray:
   """m_1, m_2, ...: the max|delta| of every sweep of the first step after the reset, run to cfg's iteration limit."""
   tw = oracle_twin(plan, dataclasses.replace(cfg, convergence_threshold=0.0), init_flat)
-  return tw.step(**oracle_step_kwargs(g, 0, cfg, a), trace=True)["max_delta"]
+  return tw.step(**step_kwargs(g, TT0, 0, cfg, a), trace=True)["max_delta"]
 
 
 def expected(m: Sequence[float], theta: float, limit: int) -> Tuple[int, bool]:

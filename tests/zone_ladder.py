@@ -191,7 +191,7 @@ AHU_CAP = 0.5             # m3/s: ahu_max_air_flow_rate of the CAP_CASES (33 zon
 
 
 def step_rows() -> dict:
-  """The step-input rows of h2_sb1_r9_random.npz (tests/test_gpu_parity.py's _check_plan_against_oracle reads rows
+  """The step-input rows of h2_sb1_r9_random.npz (tests/parity.py's check_plan_against_oracle reads rows
   96 + t) with a mild ambient temperature inside the comfort window.  One room behind a one-CV wall follows the golden's
   winter morning (281 K) within a step, every zone then calls for heat and all zones look alike.  At 295 K the zones'
   own offsets and the thermostats' hysteresis keep two or three modes among the zones over the first steps."""
@@ -209,7 +209,7 @@ _ROLLOUTS: Dict[Tuple[str, Optional[float]], list] = {}
 def oracle_rollout(name: str, ahu_cap: Optional[float] = None) -> list:
   """[T][B] results of OracleBuilding.step on the case's plan, initial grids, actions and step rows (computed once)."""
   from sbsim_amd.environment import SimConfig
-  from tests.threshold_cases import oracle_step_kwargs, oracle_twin
+  from tests.twins import oracle_twin, step_kwargs
   key = (name, ahu_cap)
   if key not in _ROLLOUTS:
     cfg = SimConfig.sb1()
@@ -218,5 +218,5 @@ def oracle_rollout(name: str, ahu_cap: Optional[float] = None) -> list:
     fp, g = plan(name), step_rows()
     init, acts = initial_grids(fp), actions()
     twins = [oracle_twin(fp, cfg, init[b]) for b in range(B)]
-    _ROLLOUTS[key] = [[twins[b].step(**oracle_step_kwargs(g, t, cfg, acts[t, b])) for b in range(B)] for t in range(T)]
+    _ROLLOUTS[key] = [[twins[b].step(**step_kwargs(g, 96 + t, t, cfg, acts[t, b])) for b in range(B)] for t in range(T)]
   return _ROLLOUTS[key]
