@@ -333,6 +333,29 @@ int sb_occupancy_peek(sb_handle *h, int32_t local_hour, int32_t is_work_day, flo
 int sb_convection_attach(sb_handle *h, double p, int32_t distance, uint64_t seed, int64_t first_building,
                          int32_t transposed);
 
+/* The same shuffle with the reference's OWN draws, per building (conv_seeded.hip): building b stands for a reference
+ * process that called random.seed(seeds_host[b]) once (stochastic_convection_simulator.py:59-60), i.e. one MT19937 per
+ * building, seeded the way CPython seeds an int and consumed in the reference's order -- per room (plan order) and per
+ * cell (the caller's raster order) one uniform(0, 1), for a moving cell one choice among its in-room candidates in window
+ * raster order, then one shuffle of the room's swap list; p == 1 with distance == -1: one shuffle of the room's cells.
+ * After every call a building's grid is the reference's, bit for bit (sbsim_amd/host_convection.py is the host twin).
+ * Same checks as sb_convection_attach; p == 0 or distance == 0 detaches whichever generator is attached.  Attaching either
+ * kind replaces the other (sb_convection_attach's own detach form leaves a seeded generator in force: detach that one
+ * here); a refused call leaves the attachment as it was.  SB_ERR_UNSUPPORTED, the message naming the host mode: a window of
+ * more than 64 offsets (distance >= 20, or -1 with p < 1), a room of more than 2047 cells, a Jacobi handle.
+ * The generators are state of the building SLOTS: [B][625] uint32 on the device, 624 words and the index of the next one
+ * (sb_convection_rng_get / _set: stream-ordered device copies, no allocation, no synchronisation; a stored index above
+ * 624 counts as 624).  sb_reset and sb_reset_buildings leave them where they are -- the reference seeds in its constructor
+ * only -- and sb_state_save / sb_state_load do not move them: a snapshot's owner saves and restores the table with the two
+ * calls here.  sb_state_clock.conv_calls counts the calls as before. */
+int sb_convection_attach_seeded(sb_handle *h, double p, int32_t distance, const uint64_t *seeds_host /* [B] */,
+                                int32_t transposed);
+int sb_convection_rng_get(sb_handle *h, uint32_t *out_dev /* [B][625] */, void *stream);
+int sb_convection_rng_set(sb_handle *h, const uint32_t *in_dev /* [B][625] */, void *stream);
+/* One convection pass on the current state with the attached generator of either kind (what sb_step's POST phase
+ * launches): a test tap.  SB_ERR_INVALID without one. */
+int sb_convection_apply(sb_handle *h, void *stream);
+
 /* SURVEY.md 8(f) rank 4 (first half) -- floor-plan preprocessing without OpenCV, on the host (no
  * device needed).  floor_plan / zone_map: [H][W] file-input codes 0 = interior space, 1 = wall,
  * 2 = exterior space (simulator/constants.py:24-36); zone_map may be NULL (= floor_plan).

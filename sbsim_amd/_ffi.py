@@ -166,7 +166,8 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_set_reward_function", "sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials",
            "sb_get_building_coef", "sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in",
            "sb_debug_plan_digest", "sb_reset_buildings", "sb_observe_buildings", "sb_occupancy_attach_groups",
-           "sb_spatial_shape", "sb_spatial_attach", "sb_spatial")
+           "sb_spatial_shape", "sb_spatial_attach", "sb_spatial",
+           "sb_convection_attach_seeded", "sb_convection_rng_get", "sb_convection_rng_set", "sb_convection_apply")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
@@ -177,6 +178,9 @@ PLAN_DIGEST_ENTRIES = ("sb_debug_plan_digest",)
 EPISODES_ENTRIES = ("sb_reset_buildings", "sb_observe_buildings")
 OCCUPANCY_ENTRIES = ("sb_occupancy_attach_groups",)
 SPATIAL_ENTRIES = ("sb_spatial_shape", "sb_spatial_attach", "sb_spatial")
+CONVECTION_SEEDED_ENTRIES = ("sb_convection_attach_seeded", "sb_convection_rng_get", "sb_convection_rng_set", "sb_convection_apply")
+SB_CONV_RNG_WORDS = 625                  # a building's row of the seeded generators: MT19937's 624 words, then the index
+SB_CONV_SEEDED_MAX_WORKGROUPS = 4096     # k_convect_seeded's grid cap (conv_seeded.hip): buildings beyond it take the grid stride
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -282,6 +286,11 @@ def load():
     L.sb_spatial_shape.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.sb_spatial_attach.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
     L.sb_spatial.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
+  if all(hasattr(L, name) for name in CONVECTION_SEEDED_ENTRIES):
+    L.sb_convection_attach_seeded.argtypes = [vp, C.c_double, C.c_int32, C.POINTER(C.c_uint64), C.c_int32]
+    L.sb_convection_rng_get.argtypes = [vp, vp, vp]
+    L.sb_convection_rng_set.argtypes = [vp, vp, vp]
+    L.sb_convection_apply.argtypes = [vp, vp]
   if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
     L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
@@ -336,6 +345,12 @@ def episodes_entry(name: str):
 
 def spatial_entry(name: str):
   """The spatial-outputs entry `name` (sb_spatial_shape, sb_spatial_attach, sb_spatial): see entry()."""
+  return entry(name)
+
+
+def convection_seeded_entry(name: str):
+  """The seeded-convection entry `name` (sb_convection_attach_seeded, sb_convection_rng_get, sb_convection_rng_set,
+  sb_convection_apply): see entry()."""
   return entry(name)
 
 

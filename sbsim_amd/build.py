@@ -15,11 +15,12 @@ CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["sbsim_hip.hip", "runtime.hip",                    # host: sb_create; the step runtime
            "step_reg.hip", "step_roll.hip", "step_two.hip", "step_two_64.hip", "step_two_76.hip", "step_two_80.hip", "step_band.hip", "step_band_68.hip", "step_band_72.hip", "step_band_76.hip", "step_band_80.hip", "step_band_84.hip", "step_band_88.hip", "step_band_92.hip", "step_band_96.hip", "step_stream.hip", "step_lds.hip", "step_jacobi.hip", "step_jacobi_global.hip",    # one translation unit per step kernel
            "generators.hip",                                 # occupancy / convection generators
+           "conv_seeded.hip",                                # the reference's seeded convection shuffle, one MT19937 per building
            "spatial.hip",                                    # zone statistics and pooled maps from the device state
            "planner.cpp", "floorplan.cpp", "episode.cpp",    # host-only: the launch planner, floor-plan preprocessing, episode shards
            "spatial_plan.cpp"]                               # host-only: k_spatial's index tables
 HEADERS = [os.path.join(CSRC, "sb_device.h"), os.path.join(CSRC, "sb_host.h"), os.path.join(CSRC, "sweep_common.h"), os.path.join(CSRC, "step_two_impl.h"), os.path.join(CSRC, "step_two_cfg.h"), os.path.join(CSRC, "step_band_impl.h"), os.path.join(CSRC, "step_band_cfg.h"),
-           *(os.path.join(CSRC, h) for h in ("planner.h", "spatial.h", "sb_error.h", "sb_layout.h", "step_roll_cfg.h", "step_reg_cfg.h", "step_stream_cfg.h", "step_stream_ms_cfg.h", "step_lds_cfg.h")),
+           *(os.path.join(CSRC, h) for h in ("planner.h", "spatial.h", "conv_seeded.h", "sb_error.h", "sb_layout.h", "step_roll_cfg.h", "step_reg_cfg.h", "step_stream_cfg.h", "step_stream_ms_cfg.h", "step_lds_cfg.h")),
            os.path.join(ROOT, "include", "sbsim_amd.h")]
 # SBSIM_BUILD_EXPERIMENTAL=1: also the sweep kernels that are exact and tested but slower than what they were meant to replace
 # (step_stream_ms.hip: several sweeps per pass; step_stream.hip's k_sweep_stream_roll: overlapped sweeps) -- opt-in at run time

@@ -680,6 +680,9 @@ int sb_step_phases(sb_handle *h, const float *actions_dev, const sb_step_in *in,
     if (h->conv_attached) { // simulator_flexible_floor_plan.py:156: after the FD update; the zone sums of
       const int rc = sb_launch_convection(h, (hipStream_t)stream); // k_post do not change (values move inside rooms)
       if (rc != SB_OK) return rc;
+    } else if (seeded_in_force(h)) { // sb_convection_attach_seeded: the same place, the reference's own draws per building
+      const int rc = sb_launch_convection_seeded(h, (hipStream_t)stream);
+      if (rc != SB_OK) return rc;
     }
     launch_post(h, s, dim3(std::max(1, std::min((d.B + 63) / 64, h->cus * 16))), (hipStream_t)stream, -1);
     ++h->steps_since_reset;

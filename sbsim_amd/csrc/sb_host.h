@@ -165,6 +165,9 @@ struct sb_handle {
   long long conv_first = 0;
   uint32_t conv_calls = 0;
   bool conv_attached = false;
+  // sb_convection_attach_seeded (conv_seeded.hip): the buildings' Mersenne Twisters, [B][625]; the tables above are shared
+  DevBuf<uint32_t> conv_rng;
+  bool conv_seeded = false;
   DevBuf<uint32_t> occ_state; // sb_occupancy_attach
   sb_occupancy_config occ{};
   uint32_t occ_queries = 0;
@@ -236,5 +239,9 @@ int apply_building_materials(sb_handle *h, const std::vector<double> &tab, hipSt
 
 // generators.hip: the convection shuffle between the sweep and the reward (sb_step)
 int sb_launch_convection(sb_handle *h, hipStream_t stream);
+// conv_seeded.hip: the seeded shuffle in its place.  In force after sb_convection_attach_seeded until either attach call
+// replaces or detaches it: sb_convection_attach leaves conv_first >= 0 and conv_attached set, the seeded attach -1 and clear.
+int sb_launch_convection_seeded(sb_handle *h, hipStream_t stream);
+inline bool seeded_in_force(const sb_handle *h) { return h->conv_seeded && !h->conv_attached && h->conv_first < 0; }
 
 #endif // SBSIM_AMD_SB_HOST_H_

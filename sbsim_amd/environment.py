@@ -265,9 +265,10 @@ def histogram_reducer_layout(source_names: Sequence[str],
 class SimState:
   """A snapshot of a ``BatchedSimulator``'s buildings (sb_state_save): device tensors of ``n`` rows in a form that does
   not depend on the state layout, the sweep kernel or the orientation the library chose, the handle's counters
-  (``clock``: occupancy queries, convection calls, steps since the last reset, reset once), and a fingerprint of what
-  the rows mean -- floor plan and zone count, the compiled plan tables, ``SimConfig.to_params()``, the device
-  generators attached and their ``first_building``.  ``BatchedSimulator.load_state`` refuses another fingerprint."""
+  (``clock``: occupancy queries, convection calls, steps since the last reset, reset once), with the seeded convection
+  (``convection_attach_seeded``) the generators of every building slot (``conv_rng``; a snapshot of ``rows`` carries
+  none: a forked building keeps its own slot's stream), and a fingerprint of what the rows mean -- floor plan and zone
+  count, the compiled plan tables, ``SimConfig.to_params()``, the device generators attached and their ``first_building``.  ``BatchedSimulator.load_state`` refuses another fingerprint."""
   grid: torch.Tensor              # [n, H*W] float64, the caller's orientation
   zone: torch.Tensor              # [n, 4, Z] float64: zone means, VAV zone-air temperature, damper, zone heat input
   mode: torch.Tensor              # [n, Z] int32: thermostat mode | reheat valve << 8
@@ -276,6 +277,7 @@ class SimState:
   occ: Optional[torch.Tensor]     # [n, Z] int32 (occupant bits) when device occupancy is attached
   clock: Tuple[int, int, int, int]
   fingerprint: Tuple
+  conv_rng: Optional[torch.Tensor] = None   # [B, 625] int32 (bit patterns): the seeded convection generators of every slot
 
   @property
   def n(self) -> int:
@@ -295,6 +297,8 @@ class SimState:
   def state_dict(self) -> dict:
     d = {k: (None if t is None else t.cpu()) for k, t in self.tensors().items()}
     d.update(clock=list(self.clock), fingerprint=list(self.fingerprint))
+    if self.conv_rng is not None:   # (only with the seeded convection: older readers see the dict they know)
+      d["conv_rng"] = self.conv_rng.cpu()
     return d
 
   @staticmethod
@@ -303,7 +307,7 @@ class SimState:
       raise ValueError("not a SimState state_dict: fingerprint or clock missing")
     to = lambda t: None if t is None else t.to(device).contiguous()
     return SimState(to(d["grid"]), to(d["zone"]), to(d["mode"]), to(d["scal"]), to(d["nsw"]), to(d.get("occ")),
-                    tuple(int(x) for x in d["clock"]), _as_fingerprint(d["fingerprint"]))
+                    tuple(int(x) for x in d["clock"]), _as_fingerprint(d["fingerprint"]), to(d.get("conv_rng")))
 
 
 def _as_fingerprint(f) -> Tuple:
@@ -359,6 +363,7 @@ class BatchedSimulator:
     self.plan, self.config, self.B, self.device = plan, config, int(n_buildings), int(device)
     self._h_conv = float(h_conv)
     self._occ_attached = self._conv_attached = None   # the arguments of the device generators (SimState fingerprint)
+    self._conv_seeded = False      # convection_attach_seeded is in force: SimState carries the generators (conv_rng)
     self._building_params = None   # set_building_params: the per-building table in force (None: the config's values)
     self._reward_function = None   # set_reward_function: None -- the default regret function of the SimConfig
     self._materials_handle = building_materials is not None   # sb_create_materials made the handle
@@ -606,8 +611,57 @@ class BatchedSimulator:
     self._refuse_on_jacobi("the convection shuffle")
     _ffi.check(self._lib.sb_convection_attach(self._h, float(p), int(distance), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                               int(first_building), int(self.transposed)), "sb_convection_attach")
+    if (p == 0.0 or distance == 0) and self._conv_seeded:   # (the C entry's detach form leaves a seeded generator in force)
+      seeds = np.zeros(self.B, np.uint64)
+      _ffi.check(_ffi.convection_seeded_entry("sb_convection_attach_seeded")(
+          self._h, 0.0, 0, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(self.transposed)), "sb_convection_attach_seeded")
+    self._conv_seeded = False
     self._conv_attached = (None if p == 0.0 or distance == 0
                            else (float(p), int(distance), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_building)))
+
+  def convection_attach_seeded(self, p: float, distance: int, seeds) -> None:
+    """sb_convection_attach_seeded: the reference's seeded shuffle per building, draw for draw -- building b is the
+    reference process that called random.seed(seeds[b]) (``seeds``: an integer s, building b gets s + b, or an integer
+    array [B]; see ``host_inputs.SeededStochasticConvectionSimulator``).  Replaces a counter-based generator; p == 0 or
+    distance == 0 detaches.  ValueError, the attachment left as it was: bad seeds, a window of more than 64 offsets
+    (distance >= 20, or -1 with p < 1), a room of more than 2047 cells, solver='jacobi_fp32'."""
+    seeds = host_inputs.SeededStochasticConvectionSimulator(p, distance, seeds).seeds_for(self.B)
+    if self.solver == "jacobi_fp32":
+      raise ValueError("the seeded convection shuffle is not implemented for solver='jacobi_fp32'; the host mode replays it "
+                       "(host_convection.SeededHostConvection)")
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+    with torch.cuda.device(self.device):
+      rc = _ffi.convection_seeded_entry("sb_convection_attach_seeded")(
+          self._h, float(p), int(distance), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(self.transposed))
+    if rc == -5:   # SB_ERR_UNSUPPORTED
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_convection_attach_seeded")
+    detached = p == 0.0 or distance == 0
+    self._conv_seeded = not detached
+    # (the seeds are where the streams started, not where they are: the snapshot carries the streams themselves)
+    self._conv_attached = None if detached else ("seeded", float(p), int(distance))
+
+  def convection_rng(self) -> torch.Tensor:
+    """sb_convection_rng_get: the buildings' generators, int32 [B, 625] on the device (bit patterns of MT19937's 624
+    words and the index of the next word: ``random.Random(seed).getstate()[1]`` as uint32)."""
+    out = torch.empty((self.B, _ffi.SB_CONV_RNG_WORDS), dtype=torch.int32, device=self.tdev)
+    _ffi.check(_ffi.convection_seeded_entry("sb_convection_rng_get")(self._h, C.c_void_p(out.data_ptr()), self._stream()),
+               "sb_convection_rng_get")
+    return out
+
+  def set_convection_rng(self, t: torch.Tensor) -> None:
+    """sb_convection_rng_set: the buildings' generators <- t (int32 [B, 625] on the device, contiguous).  An index word
+    above 624 counts as 624."""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (self.B, _ffi.SB_CONV_RNG_WORDS)
+        or t.device != self.tdev or not t.is_contiguous()):
+      raise ValueError(f"the generators must be a contiguous int32 [{self.B}, {_ffi.SB_CONV_RNG_WORDS}] tensor on {self.tdev}")
+    _ffi.check(_ffi.convection_seeded_entry("sb_convection_rng_set")(self._h, C.c_void_p(t.data_ptr()), self._stream()),
+               "sb_convection_rng_set")
+
+  def convection_apply(self) -> None:
+    """sb_convection_apply: one convection pass on the current grids with the attached generator of either kind (what a
+    step runs after its finite-difference update) -- a test tap; the zone means are not recomputed."""
+    _ffi.check(_ffi.convection_seeded_entry("sb_convection_apply")(self._h, self._stream()), "sb_convection_apply")
 
   def occupancy_peek(self, local_hour: int, is_work_day: bool, count: Optional[torch.Tensor] = None,
                      total: Optional[torch.Tensor] = None) -> None:
@@ -903,6 +957,8 @@ class BatchedSimulator:
         self._h, None if pick is None else C.c_void_p(pick.data_ptr()), n, C.byref(st.view()), C.byref(clk),
         int(self.transposed), self._stream()), "sb_state_save")
     st.clock = (clk.occ_queries, clk.conv_calls, clk.steps_since_reset, clk.was_reset)
+    if self._conv_seeded and rows is None:   # the slots' streams (rows: a fork's source rows -- streams stay with the slots)
+      st.conv_rng = self.convection_rng()
     return st
 
   def load_state(self, state: SimState, pick: Optional[torch.Tensor] = None, clock: bool = True) -> None:
@@ -932,10 +988,21 @@ class BatchedSimulator:
         raise ValueError(f"a SimState of {n} rows loads into {self.B} buildings only with a pick")
     else:
       pick = self._check_index(pick, self.B, -(1 << 31), n, "pick")
+    restore_rng = self._conv_seeded and clock and pick is None   # (a fork leaves every slot's stream in place)
+    if restore_rng:
+      if state.conv_rng is None:
+        raise ValueError("this SimState carries no convection generators (conv_rng), the simulator has the seeded convection "
+                         "attached: a restore would not replay")
+      t = state.conv_rng
+      if (tuple(t.shape) != (self.B, _ffi.SB_CONV_RNG_WORDS) or t.dtype != torch.int32 or t.device != self.tdev
+          or not t.is_contiguous()):
+        raise ValueError(f"SimState.conv_rng: expected a contiguous int32 [{self.B}, {_ffi.SB_CONV_RNG_WORDS}] tensor on {self.tdev}")
     clk = _ffi.StateClock(*state.clock) if clock else None
     _ffi.check(_ffi.state_entry("sb_state_load")(
         self._h, None if pick is None else C.c_void_p(pick.data_ptr()), C.byref(state.view()),
         C.byref(clk) if clk is not None else None, int(self.transposed), self._stream()), "sb_state_load")
+    if restore_rng:
+      self.set_convection_rng(state.conv_rng)
 
   def _check_index(self, t: torch.Tensor, length: Optional[int], lo: int, hi: int, what: str) -> torch.Tensor:
     """A device index vector, checked on the host: int32 / int64, 1-D (of `length`), values in [lo, hi) (lo < 0: a
@@ -1152,6 +1219,8 @@ class BatchedEnvironment:
       raise ValueError("Discount factor must be in (0,1]")   # environment.py:454-455
     if solver == "jacobi_fp32" and convection_simulator is not None:
       raise ValueError("a convection_simulator is not implemented for solver='jacobi_fp32'")
+    if isinstance(convection_simulator, host_inputs.SeededStochasticConvectionSimulator):
+      seeds = convection_simulator.seeds_for(int(n_buildings))   # (checked here: nothing is created for seeds of another shape)
     self.per_building_episodes = bool(per_building_episodes) or episode_steps is not None
     if self.per_building_episodes and isinstance(occupancy, host_inputs.BatchedRandomizedArrivalDepartureOccupancy):
       raise ValueError("per_building_episodes: BatchedRandomizedArrivalDepartureOccupancy is not supported -- each of its "
@@ -1205,7 +1274,10 @@ class BatchedEnvironment:
         raise ValueError("BatchedSinusoidWeather needs one (low, high) pair per building")
       self._weather_lohi = torch.tensor(np.stack([self.weather.low, self.weather.high], axis=1),
                                         dtype=torch.float64, device=self.sim.tdev).contiguous()
-    if convection_simulator is not None:   # simulator_flexible_floor_plan.py:71,156
+    if isinstance(convection_simulator, host_inputs.SeededStochasticConvectionSimulator):
+      c = convection_simulator
+      self.sim.convection_attach_seeded(c.p, c.distance, seeds)
+    elif convection_simulator is not None:   # simulator_flexible_floor_plan.py:71,156
       c = convection_simulator
       self.sim.convection_attach(c.p, c.distance, c.seed or 0, getattr(c, "first_building", 0))
     self._occ_count = self._occ_total = None
@@ -1729,6 +1801,9 @@ class MixedBatchedEnvironment:
     if env_kwargs.get("calendars") is not None or env_kwargs.get("calendar_of") is not None:
       raise ValueError("calendars is not implemented for MixedBatchedEnvironment: calendar_of indexes the buildings of one "
                        "BatchedEnvironment, and the classes of a mixed batch are block-partitioned over classes and ranks")
+    if isinstance(env_kwargs.get("convection_simulator"), host_inputs.SeededStochasticConvectionSimulator):
+      raise ValueError("SeededStochasticConvectionSimulator is not implemented for MixedBatchedEnvironment (its seeds belong "
+                       "to the buildings of one BatchedEnvironment); use host_inputs.StochasticConvectionSimulator")
     from . import distributed as _sd
     self.device = int(device)
     self.tdev = torch.device("cuda", self.device)

@@ -455,6 +455,54 @@ class StochasticConvectionSimulator:
     self.p, self.distance, self.seed, self.first_building = float(p), int(distance), seed, int(first_building)
 
 
+class SeededStochasticConvectionSimulator:
+  """StochasticConvectionSimulator(p, distance, seed) with the reference's OWN draws, one seeded generator per building
+  (``sb_convection_attach_seeded``, ``BatchedEnvironment(convection_simulator=...)``): building b is the reference
+  process that called ``random.seed(seeds[b])`` -- its grid after every step is the reference's, bit for bit
+  (``host_convection.SeededHostConvection(p, distance, seeds[b])`` is the host twin).  ``seeds``: an integer s -- building
+  b gets s + b, so building 0 is the reference run with seed s -- or an integer array [B].  Seeds are uint64: a
+  non-integer dtype, a negative value, a value of 2^64 or more or another shape is a ValueError.  Slower than the
+  counter-based ``StochasticConvectionSimulator`` (one serial chain of draws per building); windows of more than 64
+  offsets (distance >= 20, or -1 with p < 1) and rooms of more than 2047 cells are refused."""
+
+  def __init__(self, p: float, distance: int, seeds):
+    self.p, self.distance = float(p), int(distance)
+    if isinstance(seeds, (int, np.integer)) and not isinstance(seeds, (bool, np.bool_)):
+      self.seeds = int(seeds)
+      self._check_range(self.seeds, self.seeds)
+    else:
+      if isinstance(seeds, (list, tuple)) and seeds and all(
+          isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in seeds):
+        self._check_range(min(int(v) for v in seeds), max(int(v) for v in seeds))   # (Python ints beyond int64)
+        a = np.array([int(v) for v in seeds], dtype=np.uint64)
+      else:
+        a = np.asarray(seeds)
+      if a.dtype.kind not in "iu":
+        raise ValueError(f"seeds must be an integer or an integer array [B], got dtype {a.dtype}")
+      if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"seeds must be an integer or an integer array [B], got shape {a.shape}")
+      self._check_range(int(a.min()), int(a.max()))
+      self.seeds = a.astype(np.uint64)
+
+  @staticmethod
+  def _check_range(lo: int, hi: int) -> None:
+    if lo < 0:
+      raise ValueError(f"seeds must not be negative (random.seed takes the absolute value: two buildings would share a "
+                       f"stream), got {lo}")
+    if hi >= 1 << 64:
+      raise ValueError(f"seeds must be below 2^64, got {hi}")
+
+  def seeds_for(self, n_buildings: int) -> np.ndarray:
+    """The buildings' seeds, uint64 [n_buildings]; ValueError for an array of another length or s + B - 1 >= 2^64."""
+    B = int(n_buildings)
+    if isinstance(self.seeds, int):
+      self._check_range(self.seeds, self.seeds + B - 1)
+      return np.array([self.seeds + b for b in range(B)], dtype=np.uint64)
+    if self.seeds.shape != (B,):
+      raise ValueError(f"seeds must be an integer or an integer array [{B}], got shape {self.seeds.shape}")
+    return self.seeds.copy()
+
+
 # --------------------------------------------------------------------------- tariffs
 # Units: kg carbon / MWh (reward/electricity_energy_cost.py:39-64).
 CARBON_EMISSION_BY_HOUR = (
