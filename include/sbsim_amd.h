@@ -799,6 +799,57 @@ int sb_spatial_attach(sb_handle *h, int32_t pool_h, int32_t pool_w, int32_t tran
  * attached, a call before sb_reset, a call before sb_spatial_attach. */
 int sb_spatial(sb_handle *h, const int32_t *pick_dev, int32_t n, double *zone_stats_dev, float *map_dev, void *stream);
 
+/* Start temperatures per building (the reference: FloorPlanBasedBuilding(initial_temp=, reset_temp_values=),
+ * simulator/building.py:650,680,784-792 -- reset() copies a recorded [H, W] grid into building.temp).  Attached, they are a
+ * third source of sb_reset's / sb_reset_buildings' cell values, kept in the handle: with temps_dev == NULL, cell g of
+ * building b at the start of its episode number e holds, in float64, one rounding per operation, no FMA contraction:
+ *
+ *     v = grids[grid_of[b]][g]      if grids are given (grid_of NULL: grid 0)
+ *         initial_temp[b]           else if given
+ *         the call's initial_temp   otherwise
+ *     if offset:  v = v + offset[b]
+ *     if jitter:  v = v + u(b, e)
+ *
+ * Nothing is added for a field that is absent.  u(b, e) = lo + (hi - lo) * ((r >> 11) * 2^-53), r = (c[1] << 32) | c[0]
+ * of the Philox4x32-10 block with key (lo32(seed), hi32(seed)) and counter (lo32(gb), hi32(gb), e,
+ * SB_INITIAL_CONDITIONS_TAG), gb = first_building + b: shards of one batch draw the same numbers.  One block per building
+ * and reset.  The tag keeps these counters apart from the other generators' under the same seed: the occupancy's last
+ * word is query * 8 + block (it reaches the tag after 406 million queries of one handle), the convection shuffle's a grid
+ * cell (< 2^21) or 0x80000000 | 2 * room (+ 1).
+ * e is the building's own episode number: 0 at attach, used and then incremented by every reset of the building --
+ * sb_reset (every building) or sb_reset_buildings (the masked ones), also when an explicit temps_dev supplied the values
+ * (which still wins).  sb_set_temps is untouched.  A Jacobi handle stores (float)v; its zone means and grid mean are v's.
+ * A start through the attached conditions is bit for bit what sb_reset(temps_dev = the same values as an array) leaves.
+ *
+ * Configuration of the buildings' slots plus one counter: sb_state_save / sb_state_load carry neither, a restore or a
+ * fork leaves the counters where they are.  A checkpoint keeps them with sb_initial_conditions_episodes_get / _set
+ * (stream-ordered device copies of the [B] counters, no allocation, no synchronisation; the draw's counter
+ * word is e's 32 bits). */
+#define SB_INITIAL_CONDITIONS_TAG 0xC1C00000u
+typedef struct sb_initial_conditions {
+  const double *grids;        /* HOST [n_grids][H*W] in the orientation the handle runs, or NULL */
+  int32_t n_grids;            /* K >= 1 with grids, 0 without */
+  int32_t has_jitter;
+  const int32_t *grid_of;     /* HOST [B], values in [0, n_grids), or NULL (every building grid 0: n_grids must be 1) */
+  const double *initial_temp; /* HOST [B] or NULL; only without grids */
+  const double *offset;       /* HOST [B] or NULL */
+  double jitter_lo, jitter_hi; /* has_jitter: one uniform draw in [lo, hi) per building and episode */
+  uint64_t seed;
+  int64_t first_building;     /* global index of this handle's building 0 (as sb_occupancy_config's) */
+} sb_initial_conditions;
+/* Copies the arrays to device buffers of the handle (synchronously: the host arrays may go away on return) and zeroes the
+ * episode counters; conditions attached earlier are replaced once the device is idle.  SB_ERR_INVALID, the handle
+ * unchanged, the message naming the field (and the building): a null argument, n_grids < 0 or without grids (or grids
+ * with n_grids == 0), n_grids > 1 without grid_of, a grid_of outside [0, n_grids), initial_temp together with grids, a
+ * value that is not finite, jitter_lo > jitter_hi, first_building < 0, nothing given at all; a call while a stream is being
+ * captured into a graph (the call synchronises the device, which a capture refuses). */
+int sb_initial_conditions_attach(sb_handle *h, const sb_initial_conditions *ic);
+/* Back to the handle without: the resets launch the kernels they launched before the attach, with the same arguments. */
+int sb_initial_conditions_detach(sb_handle *h);
+/* SB_ERR_UNSUPPORTED on a handle without attached conditions. */
+int sb_initial_conditions_episodes_get(sb_handle *h, int32_t *out_dev /* [B] */, void *stream);
+int sb_initial_conditions_episodes_set(sb_handle *h, const int32_t *in_dev /* [B] */, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

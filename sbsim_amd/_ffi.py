@@ -150,6 +150,12 @@ class StructDesc(C.Structure):   # sb_struct_desc
               ("slot_table", _dp), ("h_conv", C.c_double), ("dx", C.c_double), ("dx2", C.c_double), ("zh", C.c_double)]
 
 
+class InitialConditionsDesc(C.Structure):   # sb_initial_conditions (HOST pointers)
+  _fields_ = [("grids", _dp), ("n_grids", C.c_int32), ("has_jitter", C.c_int32), ("grid_of", _ip), ("initial_temp", _dp),
+              ("offset", _dp), ("jitter_lo", C.c_double), ("jitter_hi", C.c_double), ("seed", C.c_uint64),
+              ("first_building", C.c_int64)]
+
+
 # sb_sweep_kernel
 SWEEP_KERNELS = {0: "k_sweep_lds", 1: "k_sweep_reg", 2: "k_sweep_reg (two wavefronts)", 3: "k_sweep_roll", 4: "k_sweep_two",
                  5: "k_sweep_band", 6: "k_sweep_stream", 7: "k_sweep_jacobi"}
@@ -167,7 +173,9 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_get_building_coef", "sb_clock_attach", "sb_clock_seek", "sb_clock_detach", "sb_observe_step_in",
            "sb_debug_plan_digest", "sb_reset_buildings", "sb_observe_buildings", "sb_occupancy_attach_groups",
            "sb_spatial_shape", "sb_spatial_attach", "sb_spatial",
-           "sb_convection_attach_seeded", "sb_convection_rng_get", "sb_convection_rng_set", "sb_convection_apply")
+           "sb_convection_attach_seeded", "sb_convection_rng_get", "sb_convection_rng_set", "sb_convection_apply",
+           "sb_initial_conditions_attach", "sb_initial_conditions_detach", "sb_initial_conditions_episodes_get",
+           "sb_initial_conditions_episodes_set")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
@@ -181,6 +189,9 @@ SPATIAL_ENTRIES = ("sb_spatial_shape", "sb_spatial_attach", "sb_spatial")
 CONVECTION_SEEDED_ENTRIES = ("sb_convection_attach_seeded", "sb_convection_rng_get", "sb_convection_rng_set", "sb_convection_apply")
 SB_CONV_RNG_WORDS = 625                  # a building's row of the seeded generators: MT19937's 624 words, then the index
 SB_CONV_SEEDED_MAX_WORKGROUPS = 4096     # k_convect_seeded's grid cap (conv_seeded.hip): buildings beyond it take the grid stride
+INITIAL_CONDITIONS_ENTRIES = ("sb_initial_conditions_attach", "sb_initial_conditions_detach",
+                              "sb_initial_conditions_episodes_get", "sb_initial_conditions_episodes_set")
+SB_INITIAL_CONDITIONS_TAG = 0xC1C00000   # include/sbsim_amd.h: the last counter word of the start temperatures' draws
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -291,6 +302,11 @@ def load():
     L.sb_convection_rng_get.argtypes = [vp, vp, vp]
     L.sb_convection_rng_set.argtypes = [vp, vp, vp]
     L.sb_convection_apply.argtypes = [vp, vp]
+  if all(hasattr(L, name) for name in INITIAL_CONDITIONS_ENTRIES):
+    L.sb_initial_conditions_attach.argtypes = [vp, C.POINTER(InitialConditionsDesc)]
+    L.sb_initial_conditions_detach.argtypes = [vp]
+    L.sb_initial_conditions_episodes_get.argtypes = [vp, vp, vp]
+    L.sb_initial_conditions_episodes_set.argtypes = [vp, vp, vp]
   if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
     L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
@@ -351,6 +367,12 @@ def spatial_entry(name: str):
 def convection_seeded_entry(name: str):
   """The seeded-convection entry `name` (sb_convection_attach_seeded, sb_convection_rng_get, sb_convection_rng_set,
   sb_convection_apply): see entry()."""
+  return entry(name)
+
+
+def initial_conditions_entry(name: str):
+  """The start-temperatures entry `name` (sb_initial_conditions_attach, sb_initial_conditions_detach,
+  sb_initial_conditions_episodes_get, sb_initial_conditions_episodes_set): see entry()."""
   return entry(name)
 
 

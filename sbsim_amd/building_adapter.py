@@ -189,8 +189,12 @@ class HipSimulatorBuilding:
                device: int = 0, weather=None, occupancy=None, start_timestamp=dt.datetime(2023, 7, 6, 7, 0, 0),
                holiday_calendar="us", agent_id: str = "", scenario_id: str = "",
                air_handler_id: str = "air_handler_id", boiler_id: str = "boiler_id",
-               convection_simulator=None, reproducible_convection: bool = False, reward_function=None):
-    """convection_simulator: host_inputs.StochasticConvectionSimulator(p, distance, seed) -- the shuffle after every
+               convection_simulator=None, reproducible_convection: bool = False, reward_function=None,
+               reset_temp_values=None):
+    """reset_temp_values: FloorPlanBasedBuilding's argument (simulator/building.py:680,784-792) -- a float64 [H, W] grid
+    every reset() copies into the temperatures (host_inputs.InitialConditions(reset_temp_values=...)); None: every CV
+    starts at the SimConfig's initial_temp.
+    convection_simulator: host_inputs.StochasticConvectionSimulator(p, distance, seed) -- the shuffle after every
     finite-difference update (simulator_flexible_floor_plan.py:71, 156).  By default it runs on the device
     (statistically the reference's process); reproducible_convection=True (one building only) runs the
     reference's seeded shuffle on the host instead, draw for draw (host_convection.py): the temperature array
@@ -206,11 +210,18 @@ class HipSimulatorBuilding:
       self._host_convection = SeededHostConvection(c.p, c.distance, c.seed)
       self._rooms = [[(int(x), int(y)) for x, y in zip(*np.unravel_index(cells, plan.shape))] for cells in plan.zone_cell_lists()]
       convection_simulator = None
+    initial_conditions = None
+    if reset_temp_values is not None:
+      g = np.asarray(reset_temp_values, dtype=np.float64)
+      if g.ndim != 2:
+        raise ValueError(f"reset_temp_values must be one [H, W] grid, got shape {g.shape}")
+      initial_conditions = host_inputs.InitialConditions(reset_temp_values=g)
     # identity normalisation: request_observations returns native values (Environment normalises them itself)
     self.env = BatchedEnvironment(plan, n_replicas, config=self.config, weather=weather, occupancy=occupancy,
                                   start_timestamp=start_timestamp, device=device, observation_normalization=None,
                                   holiday_calendar=holiday_calendar, collect_info=True,
-                                  convection_simulator=convection_simulator, reward_function=reward_function)
+                                  convection_simulator=convection_simulator, reward_function=reward_function,
+                                  initial_conditions=initial_conditions)
     if self.env._occ_count is not None:
       raise ValueError("HipSimulatorBuilding takes a host-side occupancy model (one building)")
     sim = self.env.sim

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "philox.h"
 #include "sb_host.h"
 
 using namespace sb;
@@ -38,21 +39,88 @@ __device__ __forceinline__ void reset_episode(double *S, const EpisodeArgs &ep, 
   if (ep.mask && ep.eff) ep.eff[b] = ep.offs0[b] - ep.restart_pos;
 }
 
+// sb_initial_conditions_attach: the third source of a reset's cell values, after `temps` and before the call's scalar
+// (include/sbsim_amd.h states the formula).  The arrays are the handle's; a NULL one is an absent field.
+struct StartView {
+  const double *grids; // [K][N] in the handle's orientation
+  const int *grid_of;  // [B]; NULL: grid 0
+  const double *base;  // [B] initial_temp
+  const double *offset; // [B]
+  int *episode;        // [B] the number of the building's next episode
+  double lo, hi;       // the jitter's interval
+  uint64_t seed;
+  long long first;     // global index of building 0
+  int jitter;
+};
+
+// One building's start: where a cell's value comes from and what is added to it.  Everything here is the wavefront's
+// (uniform); `e` is lane 0's alone.
+struct Start {
+  const double *grid; // the building's grid; NULL: `base` in every cell
+  double base, offset, u;
+  bool has_offset, has_jitter;
+  int e;
+  __device__ __forceinline__ double at(int g) const {
+    double v = grid ? grid[g] : base;
+    if (has_offset) v = v + offset; // (nothing is added for an absent field: -0.0 stays -0.0)
+    if (has_jitter) v = v + u;
+    return v;
+  }
+};
+
+__device__ __forceinline__ double wave_first(double x) { // lane 0's value in every lane (a scalar register pair)
+  const long long bits = __double_as_longlong(x);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)bits), hi = __builtin_amdgcn_readfirstlane((unsigned)(bits >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// The top of a building's reset with conditions attached.  The draw is one Philox block per building, in lane 0, and
+// broadcast: u = lo + (hi - lo) * ((r >> 11) * 2^-53), r the block's first two words.
+__device__ __forceinline__ Start start_of(const StartView &ic, int b, int lane, int N, double initial_temp) {
+  Start st;
+  st.grid = ic.grids ? ic.grids + (size_t)(ic.grid_of ? ic.grid_of[b] : 0) * N : nullptr;
+  st.base = ic.base ? ic.base[b] : initial_temp;
+  st.has_offset = ic.offset != nullptr;
+  st.offset = st.has_offset ? ic.offset[b] : 0.0;
+  st.has_jitter = ic.jitter != 0;
+  st.e = lane == 0 ? ic.episode[b] : 0;
+  st.u = 0.0;
+  if (st.has_jitter) {
+    double u = 0.0;
+    if (lane == 0) {
+      const unsigned long long gb = (unsigned long long)(ic.first + b);
+      uint32_t c[4] = {(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)st.e, SB_INITIAL_CONDITIONS_TAG};
+      philox4x32_10(c, (uint32_t)ic.seed, (uint32_t)(ic.seed >> 32));
+      const uint64_t r = ((uint64_t)c[1] << 32) | c[0];
+      u = ic.lo + (ic.hi - ic.lo) * ((double)(r >> 11) * 0x1p-53);
+    }
+    st.u = wave_first(u);
+  }
+  return st;
+}
+
 // Simulator.reset(): grid (either state layout), zone means, device scalars.
 // temps_only (sb_set_temps): the grid inside the building and the zone means follow `temps`; every device state stays.
-__global__ void k_reset(Dev a, EpisodeArgs ep, double initial_temp, const double *temps, int first, int steps_since_reset, int temps_only) {
+// IC (k_reset_ic): a cell without `temps` takes its value from the attached conditions, and the building's episode
+// counter advances whichever source its values had.  The sums add the same values in the same lane order either way.
+template <bool IC>
+__device__ __forceinline__ void reset_grid(Dev a, EpisodeArgs ep, StartView ic, double initial_temp,
+                                           const double *temps, int first, int steps_since_reset, int temps_only) {
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int nwaves = gridDim.x * (blockDim.x >> 6);
   for (int b = wave; b < a.B; b += nwaves) {
     if (skips(ep.mask, b)) continue; // (b is the wavefront's: uniform)
+    Start st{};
+    if (IC) st = start_of(ic, b, lane, a.N, initial_temp);
+    auto start = [&](int g) { return temps ? temps[(size_t)b * a.N + g] : IC ? st.at(g) : initial_temp; };
     double s = 0.0, rlo = INFINITY, rhi = -INFINITY;
     if (a.reg) {
       double *T = a.temp + (size_t)b * a.state_doubles;
       const double *S0 = a.scal + (size_t)b * kNScal;
       const bool ring_uniform = S0[16] == S0[17]; // (temps_only) the ring holds one value: the ambient temperature of the last step
       for (int g = lane; g < a.N; g += 64) {
-        double v = temps ? temps[(size_t)b * a.N + g] : initial_temp;
+        double v = start(g);
         const int cs = a.cell_state[g];
         if (cs >= 0) {
           T[cs] = v;
@@ -71,7 +139,7 @@ __global__ void k_reset(Dev a, EpisodeArgs ep, double initial_temp, const double
       double *T = a.temp + (size_t)b * a.Np;
       for (int i = lane; i < a.Np; i += 64) {
         const int g = i - kPad;
-        double v = (g >= 0 && g < a.N) ? (temps ? temps[(size_t)b * a.N + g] : initial_temp) : 0.0;
+        double v = (g >= 0 && g < a.N) ? start(g) : 0.0;
         T[i] = v;
         s += v;
       }
@@ -83,7 +151,7 @@ __global__ void k_reset(Dev a, EpisodeArgs ep, double initial_temp, const double
       for (int i = b0 + lane; i < b1; i += 64) {
         int li = a.zone_cells_l[i];
         int g = a.pitch == a.W ? li : (li / a.pitch) * a.W + (li % a.pitch);
-        zs += temps ? temps[(size_t)b * a.N + g] : initial_temp;
+        zs += start(g);
       }
       zs = wave_sum(zs);
       if (lane == 0) {
@@ -110,8 +178,17 @@ __global__ void k_reset(Dev a, EpisodeArgs ep, double initial_temp, const double
       S[16] = a.reg && a.n_ring > 0 ? rlo : 0.0; // extremes of the exterior-space ring (register path)
       S[17] = a.reg && a.n_ring > 0 ? rhi : 0.0;
       reset_episode(S, ep, b, first, steps_since_reset);
+      if (IC) ic.episode[b] = st.e + 1;
     }
   }
+}
+
+__global__ void k_reset(Dev a, EpisodeArgs ep, double initial_temp, const double *temps, int first, int steps_since_reset, int temps_only) {
+  reset_grid<false>(a, ep, StartView{}, initial_temp, temps, first, steps_since_reset, temps_only);
+}
+
+__global__ void k_reset_ic(Dev a, EpisodeArgs ep, StartView ic, double initial_temp, const double *temps, int first, int steps_since_reset) {
+  reset_grid<true>(a, ep, ic, initial_temp, temps, first, steps_since_reset, 0);
 }
 
 // in: the observation's inputs as a step's "now" half (aux, num_occupants_dev, occupancy_norm, the weather at t);
@@ -278,15 +355,21 @@ __global__ void __launch_bounds__(kStateThreads) k_state(Dev a, sb_state_view v,
 // SB_KERNEL_JACOBI: Simulator.reset() on the float32 grid.  The grid is stored rounded to float32 (as the reference's first
 // FD update reads it); the zone means and the grid mean the first step reads are the float64 values, as the reference's
 // are.  The scalars as k_reset sets them.  One wavefront per building.
-__global__ void k_reset_jacobi(Dev a, EpisodeArgs ep, float *grid, double initial_temp, const double *temps, int first, int steps_since_reset) {
+// IC (k_reset_jacobi_ic): as reset_grid's -- the stored cell is (float)v of the float64 v, rounded once.
+template <bool IC>
+__device__ __forceinline__ void reset_jacobi(Dev a, EpisodeArgs ep, StartView ic, float *grid,
+                                             double initial_temp, const double *temps, int first, int steps_since_reset) {
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int nwaves = gridDim.x * (blockDim.x >> 6);
   for (int b = wave; b < a.B; b += nwaves) {
     if (skips(ep.mask, b)) continue;
+    Start st{};
+    if (IC) st = start_of(ic, b, lane, a.N, initial_temp);
+    auto start = [&](int g) { return temps ? temps[(size_t)b * a.N + g] : IC ? st.at(g) : initial_temp; };
     double s = 0.0;
     for (int g = lane; g < a.N; g += 64) {
-      const double v = temps ? temps[(size_t)b * a.N + g] : initial_temp;
+      const double v = start(g);
       grid[(size_t)b * a.N + g] = (float)v;
       s += v;
     }
@@ -294,7 +377,7 @@ __global__ void k_reset_jacobi(Dev a, EpisodeArgs ep, float *grid, double initia
     for (int z = 0; z < a.Z; ++z) {
       double zs = 0.0;
       const int b0 = a.zone_off[z], b1 = a.zone_off[z + 1];
-      for (int i = b0 + lane; i < b1; i += 64) zs += temps ? temps[(size_t)b * a.N + a.zone_cells_l[i]] : initial_temp;
+      for (int i = b0 + lane; i < b1; i += 64) zs += start(a.zone_cells_l[i]);
       zs = wave_sum(zs);
       if (lane == 0) {
         const size_t o = (size_t)b * a.Z + z;
@@ -315,8 +398,18 @@ __global__ void k_reset_jacobi(Dev a, EpisodeArgs ep, float *grid, double initia
       S[12] = S[13] = S[14] = S[15] = 0.0;
       S[16] = S[17] = 0.0; // (the register path's ring extremes: no ring here)
       reset_episode(S, ep, b, first, steps_since_reset);
+      if (IC) ic.episode[b] = st.e + 1;
     }
   }
+}
+
+__global__ void k_reset_jacobi(Dev a, EpisodeArgs ep, float *grid, double initial_temp, const double *temps, int first, int steps_since_reset) {
+  reset_jacobi<false>(a, ep, StartView{}, grid, initial_temp, temps, first, steps_since_reset);
+}
+
+__global__ void k_reset_jacobi_ic(Dev a, EpisodeArgs ep, StartView ic, float *grid, double initial_temp, const double *temps, int first,
+                                  int steps_since_reset) {
+  reset_jacobi<true>(a, ep, ic, grid, initial_temp, temps, first, steps_since_reset);
 }
 
 __global__ void k_copy_temps_jacobi(const float *grid, size_t n, double *out) {
@@ -501,7 +594,16 @@ int sb_get_launch_info(const sb_handle *h, sb_launch_info *out) {
 static void launch_reset(sb_handle *h, const EpisodeArgs &ep, double initial_temp, const double *temps_dev, hipStream_t stream) {
   const int wpb = 4;
   const int blocks = std::min((h->d.B + wpb - 1) / wpb, 4096);
-  if (h->kernel == SB_KERNEL_JACOBI)
+  if (h->ic_attached) { // the conditions' kernels: the values without temps_dev, the episode counters either way
+    const StartView ic{h->ic_grids.p, h->ic_grid_of.p, h->ic_base.p, h->ic_offset.p, h->ic_episode.p,
+                       h->ic_lo, h->ic_hi, h->ic_seed, h->ic_first, h->ic_jitter ? 1 : 0};
+    if (h->kernel == SB_KERNEL_JACOBI)
+      hipLaunchKernelGGL(k_reset_jacobi_ic, dim3(blocks), dim3(64 * wpb), 0, stream, h->d, ep, ic, h->jgrid.p,
+                         initial_temp, temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset);
+    else
+      hipLaunchKernelGGL(k_reset_ic, dim3(blocks), dim3(64 * wpb), 0, stream, h->d, ep, ic, initial_temp,
+                         temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset);
+  } else if (h->kernel == SB_KERNEL_JACOBI)
     hipLaunchKernelGGL(k_reset_jacobi, dim3(blocks), dim3(64 * wpb), 0, stream, h->d, ep, h->jgrid.p,
                        initial_temp, temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset);
   else
@@ -1008,6 +1110,92 @@ int sb_clock_detach(sb_handle *h) {
   if (!h) return fail(SB_ERR_INVALID, "sb_clock_detach: null handle");
   SB_ON_DEVICE(h->device);
   return drop_clock(h);
+}
+
+/* ---- start temperatures per building ---- */
+static int drop_initial_conditions(sb_handle *h) { // the kernels in flight read the arrays: they go once the device is idle
+  if (!h->ic_attached) return SB_OK;
+  SB_HIP(hipDeviceSynchronize());
+  h->ic_attached = false; // (launch_reset: the kernels of the handle without, from here on)
+  auto drop = [](auto &buf) {
+    if (buf.p) (void)hipFree(buf.p);
+    buf.p = nullptr;
+  };
+  drop(h->ic_grids); drop(h->ic_grid_of); drop(h->ic_base); drop(h->ic_offset); drop(h->ic_episode);
+  h->ic_n_grids = 0;
+  h->ic_jitter = false;
+  return SB_OK;
+}
+
+int sb_initial_conditions_attach(sb_handle *h, const sb_initial_conditions *ic) {
+  const std::string who = "sb_initial_conditions_attach: ";
+  if (!h || !ic) return fail(SB_ERR_INVALID, who + "null argument");
+  const int B = h->d.B;
+  const size_t N = (size_t)h->d.N;
+  if (ic->n_grids < 0 || (ic->grids != nullptr) != (ic->n_grids > 0))
+    return fail(SB_ERR_INVALID, who + "reset_temp_values: grids and n_grids >= 1 go together");
+  if (ic->n_grids > 1 && !ic->grid_of) return fail(SB_ERR_INVALID, who + "grid_of: needed with more than one grid");
+  if (ic->grid_of && !ic->grids) return fail(SB_ERR_INVALID, who + "grid_of: given without grids");
+  if (ic->grids && ic->initial_temp)
+    return fail(SB_ERR_INVALID, who + "initial_temp: not together with grids (two bases)");
+  if (!ic->grids && !ic->initial_temp && !ic->offset && !ic->has_jitter)
+    return fail(SB_ERR_INVALID, who + "no field given (sb_initial_conditions_detach returns to the handle without)");
+  if (ic->first_building < 0) return fail(SB_ERR_INVALID, who + "first_building must be >= 0");
+  for (size_t i = 0; i < (size_t)ic->n_grids * N; ++i)
+    if (!std::isfinite(ic->grids[i]))
+      return fail(SB_ERR_INVALID, who + "reset_temp_values: grid " + std::to_string(i / N) + " cell " + std::to_string(i % N) + " is not finite");
+  const struct { const char *name; const double *v; } rows[] = {{"initial_temp", ic->initial_temp}, {"offset", ic->offset}};
+  for (int b = 0; b < B; ++b) {
+    if (ic->grid_of && (ic->grid_of[b] < 0 || ic->grid_of[b] >= ic->n_grids))
+      return fail(SB_ERR_INVALID, who + "building " + std::to_string(b) + ": grid_of " + std::to_string(ic->grid_of[b]) +
+                                      " is outside the " + std::to_string(ic->n_grids) + " grids");
+    for (const auto &r : rows)
+      if (r.v && !std::isfinite(r.v[b]))
+        return fail(SB_ERR_INVALID, who + "building " + std::to_string(b) + ": " + r.name + " is not finite");
+  }
+  if (ic->has_jitter && !(std::isfinite(ic->jitter_lo) && std::isfinite(ic->jitter_hi) && ic->jitter_lo <= ic->jitter_hi))
+    return fail(SB_ERR_INVALID, who + "jitter: needs finite lo <= hi");
+  SB_ON_DEVICE(h->device);
+  if (const hipError_t e = hipDeviceSynchronize(); e != hipSuccess) { // (also what a capture in progress refuses)
+    const bool capturing = e == hipErrorStreamCaptureUnsupported || e == hipErrorStreamCaptureImplicit;
+    return fail(capturing ? SB_ERR_INVALID : SB_ERR_HIP, who + (capturing ? "not while a stream is being captured into a graph"
+                                                                          : hipGetErrorString(e)));
+  }
+  SB_CHECK(drop_initial_conditions(h));
+  if (ic->grids) SB_CHECK(upload(h->ic_grids, ic->grids, (size_t)ic->n_grids * N));
+  if (ic->grid_of) SB_CHECK(upload(h->ic_grid_of, ic->grid_of, (size_t)B));
+  if (ic->initial_temp) SB_CHECK(upload(h->ic_base, ic->initial_temp, (size_t)B));
+  if (ic->offset) SB_CHECK(upload(h->ic_offset, ic->offset, (size_t)B));
+  SB_CHECK(alloc_zero(h->ic_episode, (size_t)B));
+  h->ic_n_grids = ic->n_grids;
+  h->ic_jitter = ic->has_jitter != 0;
+  h->ic_lo = ic->jitter_lo; h->ic_hi = ic->jitter_hi;
+  h->ic_seed = ic->seed;
+  h->ic_first = ic->first_building;
+  h->ic_attached = true;
+  return SB_OK;
+}
+
+int sb_initial_conditions_detach(sb_handle *h) {
+  if (!h) return fail(SB_ERR_INVALID, "sb_initial_conditions_detach: null handle");
+  SB_ON_DEVICE(h->device);
+  return drop_initial_conditions(h);
+}
+
+int sb_initial_conditions_episodes_get(sb_handle *h, int32_t *out_dev, void *stream) {
+  if (!h || !out_dev) return fail(SB_ERR_INVALID, "sb_initial_conditions_episodes_get: null argument");
+  if (!h->ic_attached) return fail(SB_ERR_UNSUPPORTED, "sb_initial_conditions_episodes_get: the handle has no initial conditions (sb_initial_conditions_attach)");
+  SB_ON_DEVICE(h->device);
+  SB_HIP(hipMemcpyAsync(out_dev, h->ic_episode.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return SB_OK;
+}
+
+int sb_initial_conditions_episodes_set(sb_handle *h, const int32_t *in_dev, void *stream) {
+  if (!h || !in_dev) return fail(SB_ERR_INVALID, "sb_initial_conditions_episodes_set: null argument");
+  if (!h->ic_attached) return fail(SB_ERR_UNSUPPORTED, "sb_initial_conditions_episodes_set: the handle has no initial conditions (sb_initial_conditions_attach)");
+  SB_ON_DEVICE(h->device);
+  SB_HIP(hipMemcpyAsync(h->ic_episode.p, in_dev, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return SB_OK;
 }
 
 /* ---- the reward function ---- */

@@ -207,6 +207,17 @@ struct sb_handle {
   int sp_state_len = 0;             // elements of a building's state (the source indices' first range)
   int sp_stage_bytes = 0;           // > 0: the state is staged in this much LDS per workgroup; 0: gathered from global memory
   DevBuf<int> sp_tile_src, sp_tile_off, sp_tile_cnt, sp_zone_off, sp_zone_src;
+  // sb_initial_conditions_attach (runtime.hip): the start temperatures' arrays and the buildings' episode counters
+  bool ic_attached = false;
+  int ic_n_grids = 0;               // K; 0: no grids
+  DevBuf<double> ic_grids;          // [K][N] in the handle's orientation
+  DevBuf<int> ic_grid_of;           // [B]; NULL: every building grid 0
+  DevBuf<double> ic_base, ic_offset; // [B] initial_temp, offset; NULL: absent
+  DevBuf<int> ic_episode;           // [B] the number of the building's next episode
+  bool ic_jitter = false;
+  double ic_lo = 0.0, ic_hi = 0.0;
+  uint64_t ic_seed = 0;
+  long long ic_first = 0;
   // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
   DevBuf<float> jgrid, jtab, jscratch; // (jscratch: k_sweep_jacobi_g's per-workgroup grids)
   DevBuf<double> jrden;

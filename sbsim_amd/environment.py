@@ -371,6 +371,7 @@ class BatchedSimulator:
     self._clock_offsets = None   # clock_attach: the buildings' offsets into the timeline (None: one clock for the batch)
     self._calendars = None   # clock_attach(calendar_of=...): hashes of the concatenated rows and of calendar_of
     self._spatial = (False, None)   # spatial_attach: (attached, the map's shape or None); configuration, not state
+    self._initial_conditions = None   # initial_conditions_attach: the host_inputs.InitialConditions in force
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -563,7 +564,17 @@ class BatchedSimulator:
     return C.c_void_p(torch.cuda.current_stream(self.tdev).cuda_stream)
 
   # ---- Simulator.reset() ----
+  def _refuse_two_bases(self, initial_temp: Optional[float]) -> None:
+    ic = self._initial_conditions
+    if initial_temp is not None and ic is not None and ic.has_base:
+      raise ValueError("initial_temp given while the attached initial conditions hold "
+                       + ("reset_temp_values" if ic.n_grids else "initial_temp") + ": two bases for the same cells "
+                       "(initial_conditions_detach, or leave initial_temp out)")
+
   def reset(self, initial_temp: Optional[float] = None, temps: Optional[torch.Tensor] = None) -> None:
+    """sb_reset.  ``temps``: every cell's value, float64 [B, H*W]; otherwise the attached initial conditions
+    (``initial_conditions_attach``), otherwise ``initial_temp`` (None: the SimConfig's) in every cell."""
+    self._refuse_two_bases(initial_temp)
     ptr = None
     if temps is not None:
       if temps.dtype != torch.float64 or tuple(temps.shape) != (self.B, self.H * self.W) or not temps.is_contiguous():
@@ -739,6 +750,7 @@ class BatchedSimulator:
     launch), and what the library refuses (before the first ``reset``, a negative restart_pos, a restart that leaves a
     building without two rows of the table)."""
     fn = _ffi.episodes_entry("sb_reset_buildings")
+    self._refuse_two_bases(initial_temp)
     m = self._host_mask(mask)
     ptr = None
     if temps is not None:
@@ -905,6 +917,72 @@ class BatchedSimulator:
     """The reward function in force (None: the default regret function)."""
     return self._reward_function
 
+  # ---- start temperatures per building (sb_initial_conditions_attach) ----
+  def initial_conditions_attach(self, ic: host_inputs.InitialConditions) -> None:
+    """sb_initial_conditions_attach: from now on every reset without ``temps`` -- ``reset``, ``reset_buildings`` -- takes
+    its cells from ``ic`` (``ic.start_temps(b, e)``, e the building's own episode number: 0 now, incremented by every
+    reset of the building).  The library copies the arrays (the grids transposed here when the device runs the plan
+    transposed); the call synchronises the device, not under stream capture.  Configuration of the slots plus one
+    counter: snapshots carry neither (``initial_condition_episodes`` is how a checkpoint keeps the counters)."""
+    if not isinstance(ic, host_inputs.InitialConditions):
+      raise ValueError("initial_conditions_attach needs a host_inputs.InitialConditions (initial_conditions_detach clears them)")
+    ic.check(self.B, (self.H, self.W))
+    fn = _ffi.initial_conditions_entry("sb_initial_conditions_attach")
+    d = _ffi.InitialConditionsDesc()
+    keep = []
+    if ic.reset_temp_values is not None:
+      g = ic.reset_temp_values.transpose(0, 2, 1) if self.transposed else ic.reset_temp_values
+      g = np.ascontiguousarray(g, dtype=np.float64)
+      keep.append(g)
+      d.grids, d.n_grids = g.ctypes.data_as(_ffi._dp), int(g.shape[0])
+    for name, ptr_t, dtype in (("grid_of", _ffi._ip, np.int32), ("initial_temp", _ffi._dp, np.float64),
+                               ("offset", _ffi._dp, np.float64)):
+      a = getattr(ic, name)
+      if a is not None:
+        a = np.ascontiguousarray(a, dtype=dtype)
+        keep.append(a)
+        setattr(d, name, a.ctypes.data_as(ptr_t))
+    if ic.jitter is not None:
+      d.has_jitter, d.jitter_lo, d.jitter_hi, d.seed = 1, ic.jitter[0], ic.jitter[1], ic.jitter[2]
+    d.first_building = ic.first_building
+    with torch.cuda.device(self.device):
+      rc = fn(self._h, C.byref(d))
+    if rc == -1:   # SB_ERR_INVALID
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_initial_conditions_attach")
+    self._initial_conditions = ic
+
+  def initial_conditions_detach(self) -> None:
+    """sb_initial_conditions_detach: the resets fill from ``initial_temp`` again, with the kernels of a handle that never
+    had conditions."""
+    with torch.cuda.device(self.device):
+      _ffi.check(_ffi.initial_conditions_entry("sb_initial_conditions_detach")(self._h), "sb_initial_conditions_detach")
+    self._initial_conditions = None
+
+  @property
+  def initial_conditions(self) -> Optional[host_inputs.InitialConditions]:
+    return self._initial_conditions
+
+  def initial_condition_episodes(self) -> torch.Tensor:
+    """sb_initial_conditions_episodes_get: int32 [B] on the device, the number of every building's NEXT episode.
+    ``save_state`` / ``load_state`` leave the counters alone; a checkpoint keeps them with this pair."""
+    out = torch.empty((self.B,), dtype=torch.int32, device=self.tdev)
+    rc = _ffi.initial_conditions_entry("sb_initial_conditions_episodes_get")(self._h, C.c_void_p(out.data_ptr()), self._stream())
+    if rc == -5:   # SB_ERR_UNSUPPORTED
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_initial_conditions_episodes_get")
+    return out
+
+  def set_initial_condition_episodes(self, t: torch.Tensor) -> None:
+    """sb_initial_conditions_episodes_set: the counters <- t (int32 [B] on the device, contiguous)."""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (self.B,) or t.device != self.tdev
+        or not t.is_contiguous()):
+      raise ValueError(f"the episode numbers must be a contiguous int32 [{self.B}] tensor on {self.tdev}")
+    rc = _ffi.initial_conditions_entry("sb_initial_conditions_episodes_set")(self._h, C.c_void_p(t.data_ptr()), self._stream())
+    if rc == -5:
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_initial_conditions_episodes_set")
+
   # ---- state snapshots (sb_state_save / sb_state_load) ----
   def state_fingerprint(self) -> Tuple:
     """What a SimState of this simulator means: plan shape and zones, a hash of the compiled plan tables (in the
@@ -934,6 +1012,8 @@ class BatchedSimulator:
       fp += (("clock", _sha(self._clock_offsets)),)
     if self._calendars is not None:   # (only with calendars: checkpoints from before them still load)
       fp += (("calendars",) + self._calendars,)
+    if self._initial_conditions is not None:   # (configuration of the slots: a snapshot restores where it is the same)
+      fp += (("initial_conditions", self._initial_conditions.digest()),)
     return fp
 
   def save_state(self, rows: Optional[torch.Tensor] = None) -> SimState:
@@ -1185,8 +1265,14 @@ class BatchedEnvironment:
                building_materials: Optional[host_inputs.BuildingMaterials] = None, start_offsets=None,
                per_building_episodes: bool = False, episode_steps=None,
                calendars: Optional[Sequence[host_inputs.Calendar]] = None, calendar_of=None,
-               spatial: Optional[host_inputs.SpatialOutputs] = None):
-    """``spatial``: a ``host_inputs.SpatialOutputs`` -- ``temperature_map`` and / or ``zone_temp_stats`` of the state
+               spatial: Optional[host_inputs.SpatialOutputs] = None,
+               initial_conditions: Optional[host_inputs.InitialConditions] = None):
+    """``initial_conditions``: a ``host_inputs.InitialConditions`` -- start temperatures per building (recorded grids,
+    a number per building, an offset, a draw per episode), attached before the first ``reset()`` and used by every reset
+    of a building: ``reset()``, the autoreset of ``per_building_episodes``, ``reset_buildings(mask)`` (INTEGRATION.md
+    4o; ``set_initial_conditions`` between episodes).  None (the default): every cell starts at
+    ``SimConfig.initial_temp``, and nothing of this is built or launched.
+    ``spatial``: a ``host_inputs.SpatialOutputs`` -- ``temperature_map`` and / or ``zone_temp_stats`` of the state
     the returned observation describes, refreshed with one launch per call; with
     ``per_building_episodes`` also ``final_temperature_map`` / ``final_zone_temp_stats``, written like
     ``final_observation``.  None (the default): the attributes are None and nothing is built or launched.
@@ -1221,6 +1307,10 @@ class BatchedEnvironment:
       raise ValueError("a convection_simulator is not implemented for solver='jacobi_fp32'")
     if isinstance(convection_simulator, host_inputs.SeededStochasticConvectionSimulator):
       seeds = convection_simulator.seeds_for(int(n_buildings))   # (checked here: nothing is created for seeds of another shape)
+    if initial_conditions is not None:   # (likewise)
+      if not isinstance(initial_conditions, host_inputs.InitialConditions):
+        raise ValueError("initial_conditions must be a host_inputs.InitialConditions (or None)")
+      initial_conditions.check(int(n_buildings), tuple(plan.shape))
     self.per_building_episodes = bool(per_building_episodes) or episode_steps is not None
     if self.per_building_episodes and isinstance(occupancy, host_inputs.BatchedRandomizedArrivalDepartureOccupancy):
       raise ValueError("per_building_episodes: BatchedRandomizedArrivalDepartureOccupancy is not supported -- each of its "
@@ -1263,6 +1353,8 @@ class BatchedEnvironment:
       self.sim.set_building_params(building_params)
     if reward_function is not None:
       self.sim.set_reward_function(reward_function)
+    if initial_conditions is not None:
+      self.sim.initial_conditions_attach(initial_conditions)
     self._weather_lohi = self._weather_replay = None
     if isinstance(self.weather, host_inputs.BatchedReplayWeather):
       if self.weather.offsets_sec.shape[0] != self.batch_size:
@@ -1616,6 +1708,18 @@ class BatchedEnvironment:
     """BatchedSimulator.set_reward_function: the reward of the steps from now on (None: the default regret function)."""
     self.sim.set_reward_function(reward_function)
 
+  def set_initial_conditions(self, initial_conditions: Optional[host_inputs.InitialConditions]) -> None:
+    """The start temperatures of the resets from now on (between episodes; None: ``SimConfig.initial_temp`` in every
+    cell again).  New conditions start every building's episode count at 0."""
+    if initial_conditions is None:
+      self.sim.initial_conditions_detach()
+    else:
+      self.sim.initial_conditions_attach(initial_conditions)
+
+  @property
+  def initial_conditions(self) -> Optional[host_inputs.InitialConditions]:
+    return self.sim.initial_conditions
+
   # ---- snapshots ----
   _HOST_CLOCK = ("_now", "_step_count", "_episode_count", "_episode_ended", "_needs_reset", "_prev_thermostat_ts")
 
@@ -1786,8 +1890,13 @@ class MixedBatchedEnvironment:
 
   def __init__(self, classes: Sequence[Tuple[FloorPlan, int]], device: int = 0, rank: int = 0, world: int = 1,
                building_params: Optional[host_inputs.BuildingParams] = None, reward_function=None,
-               building_materials: Optional[Sequence[Optional[host_inputs.BuildingMaterials]]] = None, **env_kwargs):
-    """``building_materials``: a list / tuple with one ``host_inputs.BuildingMaterials`` or None per class (material
+               building_materials: Optional[Sequence[Optional[host_inputs.BuildingMaterials]]] = None,
+               initial_conditions: Optional[Sequence[Optional[host_inputs.InitialConditions]]] = None, **env_kwargs):
+    """``initial_conditions``: a list / tuple with one ``host_inputs.InitialConditions`` or None per class (a grid
+    belongs to a floor plan); a class's [B] arrays have one row per building of the class over every rank
+    (``class_totals[k]`` rows), this rank takes its share, and ``first_building`` moves to the share's first GLOBAL
+    building of the mixed batch, as the generators' does.
+    ``building_materials``: a list / tuple with one ``host_inputs.BuildingMaterials`` or None per class (material
     slots are a floor plan's own, so a table belongs to one class); a class's table has one row per building of the
     class over every rank (``class_totals[k]`` rows), and this rank takes its share (``class_ranges[k]``).
     ``building_params``: one row per GLOBAL building of the mixed batch (``sum(class_totals)`` rows, class-major);
@@ -1820,6 +1929,7 @@ class MixedBatchedEnvironment:
     self.global_rows = _sd.class_global_rows(self.class_totals, self.rank, self.world)
     self._check_building_params(building_params)
     self._check_building_materials(building_materials)
+    self._check_initial_conditions(initial_conditions, [plan for plan, _ in classes])
     rewards = self._per_class_rewards(reward_function, len(classes))
     lo = 0
     for k, (plan, n) in enumerate(classes):
@@ -1848,6 +1958,8 @@ class MixedBatchedEnvironment:
       kw["reward_function"] = rewards[k]
       if building_materials is not None and building_materials[k] is not None:
         kw["building_materials"] = building_materials[k].rows(*self.class_ranges[k])
+      if initial_conditions is not None and initial_conditions[k] is not None:
+        kw["initial_conditions"] = self._class_initial_conditions(initial_conditions[k], k)
       with torch.cuda.stream(stream):
         env = BatchedEnvironment(plan, int(n), device=self.device, **kw)
       self.envs.append(env)
@@ -1915,6 +2027,28 @@ class MixedBatchedEnvironment:
     None clears every class's table."""
     self._check_building_params(params)
     self._on_streams(lambda k, env: env.set_building_params(None if params is None else params.rows(*self.global_rows[k])))
+
+  def _class_initial_conditions(self, ic: host_inputs.InitialConditions, k: int) -> host_inputs.InitialConditions:
+    """Class k's conditions on this rank: its share of the rows, drawing as global building ``global_rows[k][0] + i``."""
+    lo, hi = self.class_ranges[k]
+    share = ic.rows(lo, hi)   # (first_building + lo: the position inside the class)
+    share.first_building = ic.first_building + self.global_rows[k][0]
+    return share
+
+  def _check_initial_conditions(self, conditions, plans) -> None:
+    if conditions is None:
+      return
+    if not isinstance(conditions, (list, tuple)) or len(conditions) != len(plans):
+      raise ValueError(f"initial_conditions: a list with one host_inputs.InitialConditions or None per class ({len(plans)})")
+    for k, (ic, plan) in enumerate(zip(conditions, plans)):
+      if ic is None:
+        continue
+      if not isinstance(ic, host_inputs.InitialConditions):
+        raise ValueError(f"initial_conditions[{k}] must be a host_inputs.InitialConditions or None")
+      try:
+        ic.check(self.class_totals[k], tuple(plan.shape))
+      except ValueError as e:
+        raise ValueError(f"initial_conditions[{k}]: {e}") from None
 
   def _check_building_materials(self, materials) -> None:
     if materials is None:

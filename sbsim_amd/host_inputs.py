@@ -13,7 +13,9 @@ Naive timestamps are interpreted exactly as the reference does: as UTC wall-cloc
 from __future__ import annotations
 
 import csv
+import dataclasses
 import datetime as dt
+import hashlib
 import math
 from typing import Dict, Iterable, List, Mapping, NamedTuple, Optional, Sequence, Set, Tuple
 from zoneinfo import ZoneInfo
@@ -1357,3 +1359,194 @@ def effective_building_materials(materials: Optional[BuildingMaterials], slot_ta
     for name, a in materials.fields.items():
       out[name] = a.copy()
   return out
+
+
+# ---------------------------------------------------------------- start temperatures per building
+INITIAL_CONDITIONS_TAG = 0xC1C00000   # SB_INITIAL_CONDITIONS_TAG (include/sbsim_amd.h): the draws' last counter word
+_M32 = 0xFFFFFFFF
+
+
+def _philox_block(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int, int, int]:
+  """One Philox4x32-10 block on Python integers (csrc/philox.h): the four output words of a four-word counter under a
+  two-word key."""
+  c0, c1, c2, c3 = (int(c) & _M32 for c in counter)
+  k0, k1 = (int(k) & _M32 for k in key)
+  for _ in range(10):
+    hi0, lo0 = divmod(0xD2511F53 * c0, 1 << 32)
+    hi1, lo1 = divmod(0xCD9E8D57 * c2, 1 << 32)
+    c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+    k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+  return c0, c1, c2, c3
+
+
+def _per_building(name: str, arr, dtype) -> np.ndarray:
+  a = np.array(arr)
+  if a.ndim != 1 or a.shape[0] == 0:
+    raise ValueError(f"{name} must have shape [B], got {a.shape}")
+  if dtype is np.int32:
+    if a.dtype.kind not in "iu":
+      raise ValueError(f"{name} must be an integer array, got dtype {a.dtype}")
+    return a.astype(np.int64)
+  a = a.astype(np.float64)
+  bad = np.nonzero(~np.isfinite(a))[0]
+  if bad.size:
+    raise ValueError(f"building {int(bad[0])}: {name} is not finite")
+  return a
+
+
+@dataclasses.dataclass
+class InitialConditions:
+  """Start temperatures per building (sb_initial_conditions_attach): what every ``reset()`` of a building -- of the
+  whole batch, of a mask, an autoreset -- writes into its grid, kept on the device.  The reference's
+  ``FloorPlanBasedBuilding(initial_temp=, reset_temp_values=)`` (simulator/building.py:650,680,784-792) for a batch.
+
+      ic = InitialConditions(reset_temp_values=recorded_grid)                       # every building, every episode
+      ic = InitialConditions(reset_temp_values=grids, grid_of=which)                # K grids [K, H, W], one per building
+      ic = InitialConditions(initial_temp=t0, jitter=(-0.5, 0.5, seed))             # a number per building and a draw
+      env = BatchedEnvironment(plan, B, initial_conditions=ic)
+
+  ``reset_temp_values``: float64 [H, W] or [K, H, W] in the caller's orientation; ``grid_of``: int [B], building b's
+  grid (None: grid 0); ``initial_temp``: float64 [B], only without grids; ``offset``: float64 [B], added to every cell
+  of the building; ``jitter``: (lo, hi, seed), one uniform draw in [lo, hi) per building and episode, added to every
+  cell, seed a uint64; ``first_building``: the global index of building 0 (shards of one batch draw the same numbers).
+  ``start_temps`` states the value of every cell.  ValueError, naming the field (and the building): K == 0, K > 1
+  without ``grid_of``, a ``grid_of`` out of range or without grids, ``initial_temp`` together with grids, a value that
+  is not finite, lo > hi, a seed outside uint64, [B] arrays of different lengths, no field at all; ``check`` adds what
+  needs the batch: a grid of another shape than the plan's, [B] arrays of another length."""
+  reset_temp_values: Optional[np.ndarray] = None
+  grid_of: Optional[np.ndarray] = None
+  initial_temp: Optional[np.ndarray] = None
+  offset: Optional[np.ndarray] = None
+  jitter: Optional[Tuple[float, float, int]] = None
+  first_building: int = 0
+
+  def __post_init__(self):
+    if self.reset_temp_values is not None:
+      g = np.array(self.reset_temp_values, dtype=np.float64)
+      if g.ndim == 2:
+        g = g[None]
+      if g.ndim != 3 or 0 in g.shape[1:]:
+        raise ValueError(f"reset_temp_values must have shape [H, W] or [K, H, W], got {np.shape(self.reset_temp_values)}")
+      if g.shape[0] == 0:
+        raise ValueError("reset_temp_values: K == 0 grids (pass None for no grids)")
+      bad = np.argwhere(~np.isfinite(g))
+      if bad.size:
+        raise ValueError(f"reset_temp_values: grid {int(bad[0][0])} cell ({int(bad[0][1])}, {int(bad[0][2])}) is not finite")
+      g.setflags(write=False)
+      self.reset_temp_values = g
+    if self.grid_of is not None:
+      if self.reset_temp_values is None:
+        raise ValueError("grid_of needs reset_temp_values: the grids it indexes")
+      k = _per_building("grid_of", self.grid_of, np.int32)
+      bad = np.nonzero((k < 0) | (k >= self.n_grids))[0]
+      if bad.size:
+        raise ValueError(f"building {int(bad[0])}: grid_of {int(k[bad[0]])} is outside the {self.n_grids} grids")
+      self.grid_of = k.astype(np.int32)
+      self.grid_of.setflags(write=False)
+    elif self.n_grids > 1:
+      raise ValueError(f"reset_temp_values holds {self.n_grids} grids: grid_of must say which one a building starts from")
+    if self.initial_temp is not None:
+      if self.reset_temp_values is not None:
+        raise ValueError("initial_temp and reset_temp_values are two bases for the same cells: give one")
+      self.initial_temp = _per_building("initial_temp", self.initial_temp, np.float64)
+      self.initial_temp.setflags(write=False)
+    if self.offset is not None:
+      self.offset = _per_building("offset", self.offset, np.float64)
+      self.offset.setflags(write=False)
+    if self.jitter is not None:
+      try:
+        lo, hi, seed = self.jitter
+      except (TypeError, ValueError):
+        raise ValueError("jitter must be (lo, hi, seed)") from None
+      lo, hi = float(lo), float(hi)
+      if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError(f"jitter: lo and hi must be finite, got ({lo}, {hi})")
+      if lo > hi:
+        raise ValueError(f"jitter: lo {lo} > hi {hi}")
+      if isinstance(seed, (bool, float)) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"jitter: seed must be an integer in [0, 2^64), got {seed!r}")
+      self.jitter = (lo, hi, int(seed))
+    if isinstance(self.first_building, bool) or int(self.first_building) != self.first_building or self.first_building < 0:
+      raise ValueError(f"first_building must be an integer >= 0, got {self.first_building!r}")
+    self.first_building = int(self.first_building)
+    if self.reset_temp_values is None and self.initial_temp is None and self.offset is None and self.jitter is None:
+      raise ValueError("InitialConditions needs at least one field (pass None instead of an InitialConditions to clear them)")
+    lengths = {name: int(a.shape[0]) for name, a in self._per_building_fields().items()}
+    if len(set(lengths.values())) > 1:
+      raise ValueError("the [B] arrays have different lengths: " + ", ".join(f"{n} {l}" for n, l in lengths.items()))
+
+  def _per_building_fields(self) -> Dict[str, np.ndarray]:
+    return {n: a for n, a in (("grid_of", self.grid_of), ("initial_temp", self.initial_temp), ("offset", self.offset))
+            if a is not None}
+
+  @property
+  def n_grids(self) -> int:
+    return 0 if self.reset_temp_values is None else int(self.reset_temp_values.shape[0])
+
+  @property
+  def n_buildings(self) -> Optional[int]:
+    """B of the [B] arrays; None when there is none (one grid, a jitter): such conditions fit every batch size."""
+    for a in self._per_building_fields().values():
+      return int(a.shape[0])
+    return None
+
+  @property
+  def has_base(self) -> bool:
+    """Whether the conditions say what a cell starts from (grids or ``initial_temp``) and not only what is added."""
+    return self.reset_temp_values is not None or self.initial_temp is not None
+
+  def check(self, n_buildings: int, shape: Tuple[int, int]) -> None:
+    """What needs the batch: the grids have the plan's shape, the [B] arrays the batch's length."""
+    if self.reset_temp_values is not None and tuple(self.reset_temp_values.shape[1:]) != tuple(shape):
+      raise ValueError(f"reset_temp_values: grids of shape {tuple(self.reset_temp_values.shape[1:])}, the floor plan is "
+                       f"{tuple(shape)}")
+    for name, a in self._per_building_fields().items():
+      if a.shape[0] != n_buildings:
+        raise ValueError(f"{name} has {a.shape[0]} rows, the batch {n_buildings} buildings")
+
+  def rows(self, lo: int, hi: int) -> "InitialConditions":
+    """Buildings lo .. hi-1 (a class's or a rank's share of a larger batch): their rows, and ``first_building`` moved so
+    that they draw what they drew in the whole batch."""
+    n = self.n_buildings
+    if lo < 0 or hi <= lo or (n is not None and hi > n):
+      raise ValueError(f"rows [{lo}, {hi}) outside the conditions' {n} buildings")
+    cut = lambda a: None if a is None else a[lo:hi]
+    return InitialConditions(self.reset_temp_values, cut(self.grid_of), cut(self.initial_temp), cut(self.offset), self.jitter,
+                             self.first_building + lo)
+
+  def draw(self, b: int, e: int) -> float:
+    """u(b, e): the jitter of building b's episode number e -- lo + (hi - lo) * ((r >> 11) * 2^-53), r the first two
+    words of the Philox4x32-10 block keyed by the seed with counter (global building lo, hi, e, INITIAL_CONDITIONS_TAG)."""
+    lo, hi, seed = self.jitter
+    gb = self.first_building + int(b)
+    c = _philox_block((gb & _M32, gb >> 32, int(e) & _M32, INITIAL_CONDITIONS_TAG), (seed & _M32, seed >> 32))
+    r = (c[1] << 32) | c[0]
+    return lo + (hi - lo) * (float(r >> 11) * 2.0 ** -53)
+
+  def start_temps(self, b: int, e: int, initial_temp: Optional[float] = None, shape: Optional[Tuple[int, int]] = None) -> np.ndarray:
+    """The grid [H, W] (caller's orientation) building b starts its episode number e from, in float64 with one rounding
+    per operation -- what the device writes.  ``initial_temp`` / ``shape``: the reset call's scalar
+    (``SimConfig.initial_temp``) and the plan's shape, needed where the conditions hold neither grids nor ``initial_temp``
+    (``shape`` also with ``initial_temp`` alone)."""
+    if self.reset_temp_values is not None:
+      v = self.reset_temp_values[0 if self.grid_of is None else int(self.grid_of[b])].copy()
+    else:
+      if shape is None:
+        raise ValueError("start_temps needs the plan's shape without grids")
+      if self.initial_temp is None and initial_temp is None:
+        raise ValueError("start_temps needs the reset call's initial_temp: the conditions hold no base")
+      v = np.full(tuple(shape), float(self.initial_temp[b]) if self.initial_temp is not None else float(initial_temp))
+    if self.offset is not None:
+      v = v + float(self.offset[b])
+    if self.jitter is not None:
+      v = v + self.draw(b, e)
+    return v
+
+  def digest(self) -> str:
+    """A hash of everything attached (``BatchedSimulator.state_fingerprint``)."""
+    h = hashlib.sha256()
+    for a in (self.reset_temp_values, self.grid_of, self.initial_temp, self.offset):
+      h.update(b"-" if a is None else str((a.dtype.str, a.shape)).encode() + np.ascontiguousarray(a).tobytes())
+    h.update(repr((None if self.jitter is None else (self.jitter[0].hex(), self.jitter[1].hex(), self.jitter[2]),
+                   self.first_building)).encode())
+    return h.hexdigest()
