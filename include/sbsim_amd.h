@@ -850,6 +850,73 @@ int sb_initial_conditions_detach(sb_handle *h);
 int sb_initial_conditions_episodes_get(sb_handle *h, int32_t *out_dev /* [B] */, void *stream);
 int sb_initial_conditions_episodes_set(sb_handle *h, const int32_t *in_dev /* [B] */, void *stream);
 
+/* Per-building parameters and materials re-drawn at every episode start, on the device (no reference counterpart in
+ * one object: the reference builds one simulator per building and episode, so a new episode can mean a new building).
+ * A randomisation names fields of the two per-building tables -- a sb_building_param k (id = k), a material field
+ * f = kind * M + slot or f = 3 * M, the convection coefficient (id = SB_RAND_MATERIAL + f) -- and a distribution for
+ * each.  The value of field F of building b in its episode number e, in float64, one rounding per operation, no FMA
+ * contraction:
+ *
+ *     (c0, c1, c2, c3) = Philox4x32-10(key = (lo32(seed), hi32(seed)),
+ *                                      counter = (lo32(gb), hi32(gb), e, SB_RANDOMIZATION_TAG | id(F))),  gb = first_building + b
+ *     SB_RAND_UNIFORM:  d = lo + (hi - lo) * (((c1 << 32 | c0) >> 11) * 2^-53)
+ *     SB_RAND_CHOICE:   d = choices[((uint64)c0 * n_choices) >> 32]          (n_choices <= 65,536; integers only)
+ *     value = d, or base[F][b] * d with `scale` set; base: the row in force at attach (sb_params' / the plan's value
+ *     where the handle had no row)
+ *
+ * A draw depends on (seed, gb, e, F) alone: not on the other fields, their order, or the shard the building lives in.
+ * The tag's counter words collide with no other generator's under the same seed.  The last word here is
+ * 0xE9150000 | id with id <= 0x100 + 3 * 255 = 0x3FD, i.e. 0xE9150000 .. 0xE91503FD.  SB_INITIAL_CONDITIONS_TAG is the
+ * one word 0xC1C00000, outside that range.  The convection shuffles' last word is a grid cell (< 2^21) or
+ * 0x80000000 | 2 * room (+ 1) with room < 2^15, at most 0x8000FFFF.  The occupancy generator's is query * 8 + block: it
+ * reaches 0xE9150000 after 488 million queries of one handle (a step makes one), beyond any run.
+ *
+ * e is the feature's own counter (int32 [B] on the device): 0 at attach, used and then incremented by every reset of the
+ * building -- sb_reset (every building), sb_reset_buildings (the masked ones) -- whatever the source of the cell values.
+ * Inside a reset, on the caller's stream and before the reset kernel: k_randomize writes the drawn values of the
+ * resetting buildings into the two tables, a masked k_class_coef re-folds exactly their coefficient rows, and the reset
+ * kernel then takes the AHU and boiler setpoints from the new row.  The step before ran with the old row.  Of a building
+ * that is not reset not one bit changes: table rows, coefficient rows, counter.
+ * Configuration of the slots plus one counter: sb_state_save / sb_state_load carry neither. */
+#define SB_RANDOMIZATION_TAG 0xE9150000u
+#define SB_RAND_MATERIAL 0x100     /* id of material field f: SB_RAND_MATERIAL + f */
+#define SB_RAND_MAX_CHOICES 65536
+enum sb_rand_kind { SB_RAND_UNIFORM = 0, SB_RAND_CHOICE = 1 };
+typedef struct sb_rand_field {
+  int32_t id;             /* sb_building_param k, or SB_RAND_MATERIAL + f */
+  int32_t kind;           /* sb_rand_kind */
+  int32_t scale;          /* != 0: value = base * d */
+  int32_t n_choices;      /* SB_RAND_CHOICE: K, 1 .. SB_RAND_MAX_CHOICES */
+  double lo, hi;          /* SB_RAND_UNIFORM: finite, lo <= hi */
+  const double *choices;  /* SB_RAND_CHOICE: HOST [K], finite */
+} sb_rand_field;
+/* Attaches (replacing an earlier attachment, whose rows return to their base first): copies the descriptors, the choice
+ * tables and the base rows of the named fields to device buffers of the handle, zeroes the counters.  Parameter fields
+ * on a handle that never had a table allocate one from sb_params (the per-building code paths, as
+ * sb_set_building_params).  Synchronises the device: SB_ERR_INVALID while a stream is being captured.  Refused, the
+ * handle unchanged, the message naming the field (and the building where the check depends on its base row):
+ * SB_ERR_INVALID for n_fields <= 0, an unknown or repeated field, lo > hi, a bound or choice that is not finite,
+ * n_choices outside 1 .. 65,536, first_building < 0, and any possible draw sb_set_building_params /
+ * sb_set_building_materials would refuse, taken over the closed range of every field (positive fields and
+ * material values > 0, h_conv >= 0, the largest ahu_heat_sp below the smallest ahu_cool_sp, comfort_lo <= comfort_hi
+ * and eco_lo <= eco_hi at their worst, w_prod + w_cost + w_carbon > 0 at its smallest); SB_ERR_UNSUPPORTED for a
+ * material field on a handle sb_create_materials did not make.
+ * While attached, sb_set_building_params and sb_set_building_materials are refused (SB_ERR_INVALID): detach first. */
+int sb_randomization_attach(sb_handle *h, const sb_rand_field *fields, int32_t n_fields, uint64_t seed,
+                            int64_t first_building);
+/* Both tables back to their base rows bit for bit (a parameter table the attach allocated goes), the coefficient rows
+ * re-folded, the counters dropped.  The resets launch what they launched before the attach.  No-op without one. */
+int sb_randomization_detach(sb_handle *h);
+/* The [B] counters, stream-ordered device copies; SB_ERR_UNSUPPORTED without an attachment.  _set also writes the rows
+ * in force for the new counters t: values(b, t[b] - 1) where t[b] >= 1, the base row where t[b] == 0, and re-folds the
+ * coefficient rows -- a checkpoint is the snapshot plus the counters. */
+int sb_randomization_episodes_get(sb_handle *h, int32_t *out_dev /* [B] */, void *stream);
+int sb_randomization_episodes_set(sb_handle *h, const int32_t *in_dev /* [B] */, void *stream);
+/* The rows in force, stream-ordered: DEVICE [SB_NUM_BUILDING_PARAMS][B] (sb_params' values on a handle without a
+ * table) and DEVICE [3 M + 1][B] (SB_ERR_UNSUPPORTED on a handle sb_create_materials did not make). */
+int sb_get_building_params(sb_handle *h, double *out_dev, void *stream);
+int sb_get_building_materials(sb_handle *h, double *out_dev, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

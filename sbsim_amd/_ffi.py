@@ -156,6 +156,11 @@ class InitialConditionsDesc(C.Structure):   # sb_initial_conditions (HOST pointe
               ("first_building", C.c_int64)]
 
 
+class RandField(C.Structure):   # sb_rand_field (choices: a HOST pointer)
+  _fields_ = [("id", C.c_int32), ("kind", C.c_int32), ("scale", C.c_int32), ("n_choices", C.c_int32),
+              ("lo", C.c_double), ("hi", C.c_double), ("choices", _dp)]
+
+
 # sb_sweep_kernel
 SWEEP_KERNELS = {0: "k_sweep_lds", 1: "k_sweep_reg", 2: "k_sweep_reg (two wavefronts)", 3: "k_sweep_roll", 4: "k_sweep_two",
                  5: "k_sweep_band", 6: "k_sweep_stream", 7: "k_sweep_jacobi"}
@@ -175,7 +180,9 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_spatial_shape", "sb_spatial_attach", "sb_spatial",
            "sb_convection_attach_seeded", "sb_convection_rng_get", "sb_convection_rng_set", "sb_convection_apply",
            "sb_initial_conditions_attach", "sb_initial_conditions_detach", "sb_initial_conditions_episodes_get",
-           "sb_initial_conditions_episodes_set")
+           "sb_initial_conditions_episodes_set",
+           "sb_randomization_attach", "sb_randomization_detach", "sb_randomization_episodes_get",
+           "sb_randomization_episodes_set", "sb_get_building_params", "sb_get_building_materials")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
@@ -192,6 +199,13 @@ SB_CONV_SEEDED_MAX_WORKGROUPS = 4096     # k_convect_seeded's grid cap (conv_see
 INITIAL_CONDITIONS_ENTRIES = ("sb_initial_conditions_attach", "sb_initial_conditions_detach",
                               "sb_initial_conditions_episodes_get", "sb_initial_conditions_episodes_set")
 SB_INITIAL_CONDITIONS_TAG = 0xC1C00000   # include/sbsim_amd.h: the last counter word of the start temperatures' draws
+RANDOMIZATION_ENTRIES = ("sb_randomization_attach", "sb_randomization_detach", "sb_randomization_episodes_get",
+                         "sb_randomization_episodes_set", "sb_get_building_params", "sb_get_building_materials")
+SB_RANDOMIZATION_TAG = 0xE9150000        # include/sbsim_amd.h: the redraws' last counter word is this | the field's id
+SB_RAND_MATERIAL = 0x100                 # id of material field f: SB_RAND_MATERIAL + f
+SB_RAND_MAX_CHOICES = 65536
+SB_RAND_UNIFORM, SB_RAND_CHOICE = 0, 1   # sb_rand_kind
+SB_RAND_BLOCKS_PER_CU, SB_RAND_THREADS = 8, 256   # k_randomize's grid cap (randomize.hip): work beyond it takes the grid stride
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -307,6 +321,11 @@ def load():
     L.sb_initial_conditions_detach.argtypes = [vp]
     L.sb_initial_conditions_episodes_get.argtypes = [vp, vp, vp]
     L.sb_initial_conditions_episodes_set.argtypes = [vp, vp, vp]
+  if all(hasattr(L, name) for name in RANDOMIZATION_ENTRIES):
+    L.sb_randomization_attach.argtypes = [vp, C.POINTER(RandField), C.c_int32, C.c_uint64, C.c_int64]
+    L.sb_randomization_detach.argtypes = [vp]
+    for name in RANDOMIZATION_ENTRIES[2:]:
+      getattr(L, name).argtypes = [vp, vp, vp]
   if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
     L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
@@ -373,6 +392,13 @@ def convection_seeded_entry(name: str):
 def initial_conditions_entry(name: str):
   """The start-temperatures entry `name` (sb_initial_conditions_attach, sb_initial_conditions_detach,
   sb_initial_conditions_episodes_get, sb_initial_conditions_episodes_set): see entry()."""
+  return entry(name)
+
+
+def randomization_entry(name: str):
+  """The episode-randomisation entry `name` (sb_randomization_attach, sb_randomization_detach,
+  sb_randomization_episodes_get, sb_randomization_episodes_set, sb_get_building_params, sb_get_building_materials): see
+  entry()."""
   return entry(name)
 
 

@@ -460,11 +460,14 @@ __global__ void __launch_bounds__(64) k_post(Dev a, StepArgs s, sb_reward_config
 // operation -- this file is built with -ffp-contract=off, and float64 division is correctly rounded -- so a row equals the
 // host's bit for bit.  desc: {material slot, neighbour count, present mask, half-factor mask}; tab: [3 M + 1][B], field
 // kind * M + slot (conductivity, heat capacity, density), h_conv last; out: [B][ncls + 1][8], row ncls the pad class.
-__global__ void __launch_bounds__(256) k_class_coef(const int4 *desc, const double *diff, const double *tab, int B, int ncls,
-                                                    int M, double dt, double dx, double dx2, double zh, double *out) {
+// MASKED (sb_randomization_attach's redraw): only the buildings with mask[b] != 0; the arithmetic is the one body.
+template <bool MASKED>
+__device__ __forceinline__ void class_coef(const int4 *desc, const double *diff, const double *tab, int B, int ncls, int M,
+                                           double dt, double dx, double dx2, double zh, double *out, const uint8_t *mask) {
   const size_t n = (size_t)B * (ncls + 1);
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int b = (int)(i / (ncls + 1)), c = (int)(i - (size_t)b * (ncls + 1));
+    if (MASKED && !mask[b]) continue;
     double bn[4] = {0.0, 0.0, 0.0, 0.0}, ap = 0.0, gc = 0.0, sc = 0.0;
     if (c == ncls) {
       ap = 1.0; // the pad class: T' = Tprev
@@ -501,6 +504,17 @@ __global__ void __launch_bounds__(256) k_class_coef(const int4 *desc, const doub
     o[0] = make_double2(bn[0], bn[1]); o[1] = make_double2(bn[2], bn[3]);
     o[2] = make_double2(ap, gc); o[3] = make_double2(sc, 0.0);
   }
+}
+
+__global__ void __launch_bounds__(256) k_class_coef(const int4 *desc, const double *diff, const double *tab, int B, int ncls,
+                                                    int M, double dt, double dx, double dx2, double zh, double *out) {
+  class_coef<false>(desc, diff, tab, B, ncls, M, dt, dx, dx2, zh, out, nullptr);
+}
+
+__global__ void __launch_bounds__(256) k_class_coef_masked(const int4 *desc, const double *diff, const double *tab, int B, int ncls,
+                                                           int M, double dt, double dx, double dx2, double zh, double *out,
+                                                           const uint8_t *mask) {
+  class_coef<true>(desc, diff, tab, B, ncls, M, dt, dx, dx2, zh, out, mask);
 }
 
 // k_post of the handle's reward function (sb_set_reward_function); only >= 0: that building alone
@@ -551,6 +565,20 @@ int launch_sweep(const sb_handle *h, hipStream_t stream) {
   return (int)hipErrorInvalidValue;
 }
 
+int launch_class_coef(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream) {
+  const Dev &d = h->d;
+  const size_t n = (size_t)d.B * (d.ncls + 1);
+  const int blocks = (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)h->cus * 32));
+  if (mask_dev)
+    hipLaunchKernelGGL(k_class_coef_masked, dim3(blocks), dim3(256), 0, stream, h->mat_desc.p, h->mat_diff.p, h->mat_tab.p, d.B,
+                       d.ncls, h->mat_slots, d.p.dt, h->mat_dx, h->mat_dx2, h->mat_zh, h->ctab_b.p, mask_dev);
+  else
+    hipLaunchKernelGGL(k_class_coef, dim3(blocks), dim3(256), 0, stream, h->mat_desc.p, h->mat_diff.p, h->mat_tab.p, d.B, d.ncls,
+                       h->mat_slots, d.p.dt, h->mat_dx, h->mat_dx2, h->mat_zh, h->ctab_b.p);
+  SB_HIP(hipGetLastError());
+  return SB_OK;
+}
+
 // sb_create_materials / sb_set_building_materials: the value table and k_class_coef on `stream`, and waits for them (the
 // copy reads host memory that goes away with this call)
 int apply_building_materials(sb_handle *h, const std::vector<double> &tab, hipStream_t stream) {
@@ -563,11 +591,7 @@ int apply_building_materials(sb_handle *h, const std::vector<double> &tab, hipSt
   }
   const std::vector<double> &src = tab.empty() ? own : tab;
   SB_HIP(hipMemcpyAsync(h->mat_tab.p, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-  const size_t n = (size_t)B * (d.ncls + 1);
-  const int blocks = (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)h->cus * 32));
-  hipLaunchKernelGGL(k_class_coef, dim3(blocks), dim3(256), 0, stream, h->mat_desc.p, h->mat_diff.p, h->mat_tab.p, B, d.ncls,
-                     M, d.p.dt, h->mat_dx, h->mat_dx2, h->mat_zh, h->ctab_b.p);
-  SB_HIP(hipGetLastError());
+  SB_CHECK(launch_class_coef(h, nullptr, stream));
   SB_HIP(hipStreamSynchronize(stream));
   return SB_OK;
 }
@@ -626,6 +650,7 @@ static void episode_bounds(sb_handle *h) {
 int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *stream) {
   if (!h) return fail(SB_ERR_INVALID, "sb_reset: null handle");
   SB_ON_DEVICE(h->device);
+  if (h->rz_attached) SB_CHECK(sb_randomization_redraw(h, nullptr, (hipStream_t)stream)); // the new episode's rows, before the reset reads them
   launch_reset(h, EpisodeArgs{nullptr, h->ep_start.p, nullptr, nullptr, 0}, initial_temp, temps_dev, (hipStream_t)stream);
   h->was_reset = true;
   h->steps_since_reset = 0;
@@ -681,6 +706,7 @@ int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host, int32_t restart_p
   SB_ON_DEVICE(h->device);
   SB_CHECK(upload_mask(h, mask_host, "sb_reset_buildings", (hipStream_t)stream));
   if (!h->ep_start.p) SB_CHECK(alloc_zero(h->ep_start, (size_t)B));
+  if (h->rz_attached) SB_CHECK(sb_randomization_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // the masked buildings' new rows
   launch_reset(h, EpisodeArgs{h->ep_mask.p, h->ep_start.p, clk ? h->clock_eff.p : nullptr, h->clock_offs.p, restart_pos},
                initial_temp, temps_dev, (hipStream_t)stream);
   SB_HIP(hipGetLastError());
@@ -906,6 +932,9 @@ static const char *const kBuildingParamNames[SB_NUM_BUILDING_PARAMS] = {
     "blr_len", "blr_radius", "blr_capacity", "blr_ins_k", "blr_ins_thick", "comfort_lo", "comfort_hi", "eco_lo",
     "eco_hi", "max_prod", "min_prod", "max_elec", "max_gas", "prod_delta", "prod_stiff", "w_prod", "w_cost",
     "w_carbon"};
+} // extern "C"
+const char *building_param_name(int k) { return kBuildingParamNames[k]; }
+extern "C" {
 
 // Building b's effective row (tab: [SB_NUM_BUILDING_PARAMS][B]) against the reference's constructor checks.
 static int check_building_row(const std::vector<double> &tab, int B, int b) {
@@ -935,6 +964,8 @@ int sb_set_building_params(sb_handle *h, int32_t n_fields, const int32_t *fields
   if (n_fields < 0 || n_fields > SB_NUM_BUILDING_PARAMS)
     return fail(SB_ERR_INVALID, "sb_set_building_params: n_fields must be in 0 .. SB_NUM_BUILDING_PARAMS");
   if (n_fields > 0 && (!fields || !values)) return fail(SB_ERR_INVALID, "sb_set_building_params: null argument");
+  if (h->rz_attached)
+    return fail(SB_ERR_INVALID, "sb_set_building_params: a randomisation is attached, which owns the rows (sb_randomization_detach first)");
   const int B = h->d.B;
   std::vector<double> tab;
   if (n_fields > 0) {
@@ -975,17 +1006,21 @@ int sb_set_building_params(sb_handle *h, int32_t n_fields, const int32_t *fields
 }
 
 /* ---- per-building materials ---- */
-static std::string material_field_name(int f, int M) {
+} // extern "C"
+std::string material_field_name(int f, int M) {
   static const char *const kinds[3] = {"conductivity", "heat_capacity", "density"};
   if (f == 3 * M) return "h_conv";
   return std::string(kinds[f / M]) + "[" + std::to_string(f % M) + "]";
 }
+extern "C" {
 
 int sb_set_building_materials(sb_handle *h, int32_t n_fields, const int32_t *fields, const double *values, void *stream) {
   if (!h) return fail(SB_ERR_INVALID, "sb_set_building_materials: null handle");
   if (!h->materials)
     return fail(SB_ERR_UNSUPPORTED, "sb_set_building_materials: the handle has one coefficient table for every building "
                                     "(sb_create / sb_create_jacobi); create it with sb_create_materials");
+  if (h->rz_attached)
+    return fail(SB_ERR_INVALID, "sb_set_building_materials: a randomisation is attached, which owns the rows (sb_randomization_detach first)");
   const int M = h->mat_slots, F = 3 * M + 1, B = h->d.B;
   if (n_fields < 0 || n_fields > F)
     return fail(SB_ERR_INVALID, "sb_set_building_materials: n_fields must be in 0 .. 3 * n_slots + 1");

@@ -218,6 +218,19 @@ struct sb_handle {
   double ic_lo = 0.0, ic_hi = 0.0;
   uint64_t ic_seed = 0;
   long long ic_first = 0;
+  // sb_randomization_attach (randomize.hip): the fields' descriptors and choice tables, their base rows, the counters
+  bool rz_attached = false;
+  int rz_n_fields = 0;
+  bool rz_materials = false;        // some field is a material field: a redraw re-folds the coefficient rows
+  bool rz_own_bp = false;           // the attach allocated the parameter table (the handle had none): detach drops it
+  DevBuf<unsigned char> rz_desc;    // [n_fields] sb::RandField, then the choice tables (doubles)
+  size_t rz_choices_at = 0;         // byte offset of the choice tables in rz_desc
+  DevBuf<double> rz_base;           // [n_fields][B] the rows in force at attach
+  DevBuf<int> rz_episode;           // [B] the number of the building's next episode
+  std::vector<double> rz_base_bp;   // host: [SB_NUM_BUILDING_PARAMS][B] the whole table at attach (sb_params' values without one)
+  std::vector<double> rz_base_mat;  // host: [3 M + 1][B] likewise; empty on a handle without materials
+  uint64_t rz_seed = 0;
+  long long rz_first = 0;
   // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
   DevBuf<float> jgrid, jtab, jscratch; // (jscratch: k_sweep_jacobi_g's per-workgroup grids)
   DevBuf<double> jrden;
@@ -247,6 +260,17 @@ int launch_sweep(const sb_handle *h, hipStream_t stream);
 // runtime.hip: uploads the buildings' values (tab: [3 M + 1][B]; empty: the plan's own in every row) and runs k_class_coef
 // on `stream`, and waits for both
 int apply_building_materials(sb_handle *h, const std::vector<double> &tab, hipStream_t stream);
+
+// runtime.hip: k_class_coef on `stream` from the values in force (mat_tab); mask (DEVICE [B]) != NULL: the masked form,
+// which re-folds the rows of the buildings with mask[b] != 0 and touches no other
+int launch_class_coef(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream);
+// runtime.hip: the names sb_set_building_params / sb_set_building_materials use in their messages
+const char *building_param_name(int k);
+std::string material_field_name(int f, int M);
+
+// randomize.hip: the redraw at the top of a reset (sb_reset: mask_dev NULL, every building; sb_reset_buildings: its
+// device mask), stream-ordered launches only.  Only called while a randomisation is attached.
+int sb_randomization_redraw(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream);
 
 // generators.hip: the convection shuffle between the sweep and the reward (sb_step)
 int sb_launch_convection(sb_handle *h, hipStream_t stream);

@@ -372,6 +372,8 @@ class BatchedSimulator:
     self._calendars = None   # clock_attach(calendar_of=...): hashes of the concatenated rows and of calendar_of
     self._spatial = (False, None)   # spatial_attach: (attached, the map's shape or None); configuration, not state
     self._initial_conditions = None   # initial_conditions_attach: the host_inputs.InitialConditions in force
+    self._randomization = None   # randomization_attach: the host_inputs.EpisodeRandomization in force
+    self._randomization_base = None   # ... and the rows in force when it was attached, by name
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -830,6 +832,8 @@ class BatchedSimulator:
     the building's slot, not to its state: snapshots do not carry it and a forked building keeps its own row.  It
     applies from the next reset, step or observation; a reset sets the AHU and boiler setpoints from it."""
     fn = _ffi.entry("sb_set_building_params")
+    if self._randomization is not None:
+      raise ValueError("set_building_params: an episode randomisation is attached, which owns the rows (randomization_detach first)")
     if params is None:
       _ffi.check(fn(self._h, 0, None, None, self._stream()), "sb_set_building_params")
       self._building_params = None
@@ -861,6 +865,8 @@ class BatchedSimulator:
       raise ValueError("set_building_materials needs a simulator created with building_materials=... (its floor plan is "
                        "compiled into structural classes and runs on k_sweep_lds)")
     fn = _ffi.materials_entry("sb_set_building_materials")
+    if self._randomization is not None:
+      raise ValueError("set_building_materials: an episode randomisation is attached, which owns the rows (randomization_detach first)")
     if materials is None:
       with torch.cuda.device(self.device):
         _ffi.check(fn(self._h, 0, None, None, self._stream()), "sb_set_building_materials")
@@ -983,6 +989,101 @@ class BatchedSimulator:
       raise ValueError((self._lib.sb_last_error() or b"").decode())
     _ffi.check(rc, "sb_initial_conditions_episodes_set")
 
+  # ---- parameters and materials re-drawn per episode (sb_randomization_attach) ----
+  def _randomization_bases(self):
+    """The rows a randomisation attached now would take as its base: those of the attachment it replaces, else the rows
+    in force (parameters by SimConfig field; materials None on a simulator created without ``building_materials``)."""
+    if self._randomization_base is not None:
+      return self._randomization_base
+    return self.building_params(), (self.building_materials() if self._materials_handle else None)
+
+  def randomization_attach(self, er: host_inputs.EpisodeRandomization) -> None:
+    """sb_randomization_attach: from now on every reset of a building -- ``reset``, ``reset_buildings``, the autoreset --
+    first writes ``er.values(b, e, base)`` into the building's rows of the two per-building tables and re-folds its
+    coefficient rows, e the building's own episode number: 0 now, incremented by every reset of the building; base: the
+    rows in force now.  Checked on the host first (``er.check``); the call synchronises the device, not under stream
+    capture.  While attached, ``set_building_params`` / ``set_building_materials`` are refused, and
+    ``building_params()`` / ``building_materials()`` keep returning the base rows (``building_param_rows()`` /
+    ``building_material_rows()`` are the rows in force)."""
+    if not isinstance(er, host_inputs.EpisodeRandomization):
+      raise ValueError("randomization_attach needs a host_inputs.EpisodeRandomization (randomization_detach clears it)")
+    if torch.cuda.is_current_stream_capturing():   # (the library's hipDeviceSynchronize would refuse, and invalidate the capture)
+      raise ValueError("randomization_attach: not while the stream is being captured into a graph (the call synchronises the device)")
+    bases = self._randomization_bases()
+    er.check(self.B, bases[0], bases[1], self.solver)
+    fn = _ffi.randomization_entry("sb_randomization_attach")
+    arr, keep = er.c_fields(len(self._slot_table) if self._materials_handle else None)
+    with torch.cuda.device(self.device):
+      rc = fn(self._h, arr, len(er.fields), er.seed, er.first_building)
+    del keep
+    if rc in (-1, -5):   # SB_ERR_INVALID, SB_ERR_UNSUPPORTED
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_randomization_attach")
+    self._randomization, self._randomization_base = er, bases
+
+  def randomization_detach(self) -> None:
+    """sb_randomization_detach: both tables back to the rows of the attach, bit for bit, the coefficient rows re-folded;
+    the resets launch what they launched before."""
+    if torch.cuda.is_current_stream_capturing():
+      raise ValueError("randomization_detach: not while the stream is being captured into a graph (the call synchronises the device)")
+    with torch.cuda.device(self.device):
+      _ffi.check(_ffi.randomization_entry("sb_randomization_detach")(self._h), "sb_randomization_detach")
+    self._randomization = self._randomization_base = None
+
+  @property
+  def randomization(self) -> Optional[host_inputs.EpisodeRandomization]:
+    return self._randomization
+
+  def randomization_base(self) -> Dict[str, np.ndarray]:
+    """The rows in force when the randomisation was attached, by name: what ``EpisodeRandomization.values`` takes as
+    ``base``."""
+    if self._randomization is None:
+      raise ValueError("randomization_base: no episode randomisation is attached")
+    return dict(self._randomization_base[0], **(self._randomization_base[1] or {}))
+
+  def _rows_out(self, name: str, n_rows: int) -> torch.Tensor:
+    out = torch.empty((n_rows, self.B), dtype=torch.float64, device=self.tdev)
+    with torch.cuda.device(self.device):
+      rc = _ffi.randomization_entry(name)(self._h, C.c_void_p(out.data_ptr()), self._stream())
+    if rc == -5:   # SB_ERR_UNSUPPORTED
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, name)
+    return out
+
+  def building_param_rows(self) -> torch.Tensor:
+    """sb_get_building_params: the parameter rows in force on the device, float64 [SB_NUM_BUILDING_PARAMS, B] (row k:
+    ``_ffi.BUILDING_PARAM_FIELDS[k]``; the SimConfig's values without a table).  Stream-ordered."""
+    return self._rows_out("sb_get_building_params", _ffi.SB_NUM_BUILDING_PARAMS)
+
+  def building_material_rows(self) -> torch.Tensor:
+    """sb_get_building_materials: the material rows in force, float64 [3 M + 1, B] (row kind * M + slot; 3 M: the
+    convection coefficient), on a simulator created with ``building_materials``.  Stream-ordered."""
+    if not self._materials_handle:
+      raise ValueError("building_material_rows needs a simulator created with building_materials=...")
+    return self._rows_out("sb_get_building_materials", 3 * len(self._slot_table) + 1)
+
+  def randomization_episodes(self) -> torch.Tensor:
+    """sb_randomization_episodes_get: int32 [B] on the device, the number of every building's NEXT episode.  Snapshots
+    carry neither the rows nor the counters: a checkpoint keeps the counters with this pair."""
+    out = torch.empty((self.B,), dtype=torch.int32, device=self.tdev)
+    rc = _ffi.randomization_entry("sb_randomization_episodes_get")(self._h, C.c_void_p(out.data_ptr()), self._stream())
+    if rc == -5:   # SB_ERR_UNSUPPORTED
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_randomization_episodes_get")
+    return out
+
+  def set_randomization_episodes(self, t: torch.Tensor) -> None:
+    """sb_randomization_episodes_set: the counters <- t (int32 [B] on the device, contiguous), and the rows in force
+    <- ``values(b, t[b] - 1)`` (the base row where t[b] == 0), coefficient rows included."""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (self.B,) or t.device != self.tdev
+        or not t.is_contiguous()):
+      raise ValueError(f"the episode numbers must be a contiguous int32 [{self.B}] tensor on {self.tdev}")
+    with torch.cuda.device(self.device):
+      rc = _ffi.randomization_entry("sb_randomization_episodes_set")(self._h, C.c_void_p(t.data_ptr()), self._stream())
+    if rc == -5:
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, "sb_randomization_episodes_set")
+
   # ---- state snapshots (sb_state_save / sb_state_load) ----
   def state_fingerprint(self) -> Tuple:
     """What a SimState of this simulator means: plan shape and zones, a hash of the compiled plan tables (in the
@@ -1014,6 +1115,8 @@ class BatchedSimulator:
       fp += (("calendars",) + self._calendars,)
     if self._initial_conditions is not None:   # (configuration of the slots: a snapshot restores where it is the same)
       fp += (("initial_conditions", self._initial_conditions.digest()),)
+    if self._randomization is not None:   # (likewise; the rows and the counters are not in a snapshot)
+      fp += (("episode_randomization", self._randomization.digest()),)
     return fp
 
   def save_state(self, rows: Optional[torch.Tensor] = None) -> SimState:
@@ -1266,8 +1369,12 @@ class BatchedEnvironment:
                per_building_episodes: bool = False, episode_steps=None,
                calendars: Optional[Sequence[host_inputs.Calendar]] = None, calendar_of=None,
                spatial: Optional[host_inputs.SpatialOutputs] = None,
-               initial_conditions: Optional[host_inputs.InitialConditions] = None):
-    """``initial_conditions``: a ``host_inputs.InitialConditions`` -- start temperatures per building (recorded grids,
+               initial_conditions: Optional[host_inputs.InitialConditions] = None,
+               episode_randomization: Optional[host_inputs.EpisodeRandomization] = None):
+    """``episode_randomization``: a ``host_inputs.EpisodeRandomization`` -- per-building parameters and materials drawn
+    anew at every reset of a building, on the device (``set_episode_randomization`` between episodes,
+    ``randomized_values()`` the values in force).  None (the default): nothing of this is built or launched.
+    ``initial_conditions``: a ``host_inputs.InitialConditions`` -- start temperatures per building (recorded grids,
     a number per building, an offset, a draw per episode), attached before the first ``reset()`` and used by every reset
     of a building: ``reset()``, the autoreset of ``per_building_episodes``, ``reset_buildings(mask)`` (INTEGRATION.md
     4o; ``set_initial_conditions`` between episodes).  None (the default): every cell starts at
@@ -1344,6 +1451,15 @@ class BatchedEnvironment:
                          "would draw for all the others too")
       if start_offsets is not None:   # (checked here: nothing is created for offsets the timeline would refuse)
         start_offsets = host_inputs.check_start_offsets(start_offsets, int(n_buildings))
+    if episode_randomization is not None:   # (checked here: nothing is created for a randomisation the library would refuse)
+      if not isinstance(episode_randomization, host_inputs.EpisodeRandomization):
+        raise ValueError("episode_randomization must be a host_inputs.EpisodeRandomization (or None)")
+      if building_params is not None and not isinstance(building_params, host_inputs.BuildingParams):
+        raise ValueError("building_params must be a host_inputs.BuildingParams (or None)")
+      episode_randomization.check(
+          int(n_buildings), host_inputs.effective_building_params(building_params, self.config, int(n_buildings)),
+          None if building_materials is None else host_inputs.effective_building_materials(
+              building_materials, plan.material_slots()[1], h_conv, int(n_buildings)), solver)
     self.sim = BatchedSimulator(plan, self.config, n_buildings, h_conv, device,
                                 observation_normalization,
                                 histogram_parameters=observation_histogram_parameters,
@@ -1355,6 +1471,8 @@ class BatchedEnvironment:
       self.sim.set_reward_function(reward_function)
     if initial_conditions is not None:
       self.sim.initial_conditions_attach(initial_conditions)
+    if episode_randomization is not None:
+      self.sim.randomization_attach(episode_randomization)
     self._weather_lohi = self._weather_replay = None
     if isinstance(self.weather, host_inputs.BatchedReplayWeather):
       if self.weather.offsets_sec.shape[0] != self.batch_size:
@@ -1720,6 +1838,42 @@ class BatchedEnvironment:
   def initial_conditions(self) -> Optional[host_inputs.InitialConditions]:
     return self.sim.initial_conditions
 
+  def set_episode_randomization(self, episode_randomization: Optional[host_inputs.EpisodeRandomization]) -> None:
+    """The randomisation of the resets from now on (between episodes; None: the rows return to those of the attach and
+    stay).  A new one starts every building's episode count at 0, with the same base rows."""
+    if episode_randomization is None:
+      self.sim.randomization_detach()
+    else:
+      self.sim.randomization_attach(episode_randomization)
+
+  @property
+  def episode_randomization(self) -> Optional[host_inputs.EpisodeRandomization]:
+    return self.sim.randomization
+
+  def randomized_values(self) -> Dict[str, torch.Tensor]:
+    """The values in force of the randomised fields, on the device (e.g. as privileged input of a critic): SimConfig
+    field -> float64 [B] ([B, 2] for a window), material kind -> [B, M], "convection_coefficient" -> [B].  Copies,
+    ordered on the current stream."""
+    er = self.sim.randomization
+    if er is None:
+      raise ValueError("randomized_values: no episode randomisation is attached")
+    out: Dict[str, torch.Tensor] = {}
+    if er.has_params:
+      rows = self.sim.building_param_rows()
+      index = {name: k for k, name in enumerate(_ffi.BUILDING_PARAM_FIELDS)}
+      for name in dict.fromkeys(f.name.partition("[")[0] for f in er.fields if f.param is not None):
+        ks = [index[c] for c in host_inputs.BUILDING_PARAM_NAMES[name]]
+        out[name] = rows[ks[0]].clone() if len(ks) == 1 else rows[ks].t().contiguous()
+    if er.has_materials:
+      rows = self.sim.building_material_rows()
+      M = (rows.shape[0] - 1) // 3
+      for kind in dict.fromkeys(f.material[0] for f in er.fields if f.material is not None):
+        if kind == 3:
+          out["convection_coefficient"] = rows[3 * M].clone()
+        else:
+          out[host_inputs._MATERIAL_KINDS[kind]] = rows[kind * M:(kind + 1) * M].t().contiguous()
+    return out
+
   # ---- snapshots ----
   _HOST_CLOCK = ("_now", "_step_count", "_episode_count", "_episode_ended", "_needs_reset", "_prev_thermostat_ts")
 
@@ -1891,8 +2045,12 @@ class MixedBatchedEnvironment:
   def __init__(self, classes: Sequence[Tuple[FloorPlan, int]], device: int = 0, rank: int = 0, world: int = 1,
                building_params: Optional[host_inputs.BuildingParams] = None, reward_function=None,
                building_materials: Optional[Sequence[Optional[host_inputs.BuildingMaterials]]] = None,
-               initial_conditions: Optional[Sequence[Optional[host_inputs.InitialConditions]]] = None, **env_kwargs):
-    """``initial_conditions``: a list / tuple with one ``host_inputs.InitialConditions`` or None per class (a grid
+               initial_conditions: Optional[Sequence[Optional[host_inputs.InitialConditions]]] = None,
+               episode_randomization=None, **env_kwargs):
+    """``episode_randomization``: one ``host_inputs.EpisodeRandomization`` for every class, or a list / tuple with one or
+    None per class (material slots are a floor plan's own); ``first_building`` moves to the class's first GLOBAL building
+    on this rank, as for ``initial_conditions``.
+    ``initial_conditions``: a list / tuple with one ``host_inputs.InitialConditions`` or None per class (a grid
     belongs to a floor plan); a class's [B] arrays have one row per building of the class over every rank
     (``class_totals[k]`` rows), this rank takes its share, and ``first_building`` moves to the share's first GLOBAL
     building of the mixed batch, as the generators' does.
@@ -1931,6 +2089,15 @@ class MixedBatchedEnvironment:
     self._check_building_materials(building_materials)
     self._check_initial_conditions(initial_conditions, [plan for plan, _ in classes])
     rewards = self._per_class_rewards(reward_function, len(classes))
+    if isinstance(episode_randomization, (list, tuple)):
+      if len(episode_randomization) != len(classes):
+        raise ValueError(f"episode_randomization: one per class ({len(classes)}), or one for all")
+      randomizations = list(episode_randomization)
+    else:
+      randomizations = [episode_randomization] * len(classes)
+    for k, er in enumerate(randomizations):
+      if er is not None and not isinstance(er, host_inputs.EpisodeRandomization):
+        raise ValueError(f"episode_randomization[{k}] must be a host_inputs.EpisodeRandomization or None")
     lo = 0
     for k, (plan, n) in enumerate(classes):
       # per-building generators (convection shuffle, randomized occupancy) draw from streams keyed by the GLOBAL
@@ -1960,6 +2127,8 @@ class MixedBatchedEnvironment:
         kw["building_materials"] = building_materials[k].rows(*self.class_ranges[k])
       if initial_conditions is not None and initial_conditions[k] is not None:
         kw["initial_conditions"] = self._class_initial_conditions(initial_conditions[k], k)
+      if randomizations[k] is not None:   # drawing as global building global_rows[k][0] + i
+        kw["episode_randomization"] = randomizations[k].rows(first)
       with torch.cuda.stream(stream):
         env = BatchedEnvironment(plan, int(n), device=self.device, **kw)
       self.envs.append(env)

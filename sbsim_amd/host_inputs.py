@@ -12,6 +12,7 @@ Naive timestamps are interpreted exactly as the reference does: as UTC wall-cloc
 """
 from __future__ import annotations
 
+import copy
 import csv
 import dataclasses
 import datetime as dt
@@ -1550,3 +1551,346 @@ class InitialConditions:
     h.update(repr((None if self.jitter is None else (self.jitter[0].hex(), self.jitter[1].hex(), self.jitter[2]),
                    self.first_building)).encode())
     return h.hexdigest()
+
+
+# ---------------------------------------------------------------- parameters and materials re-drawn per episode
+RANDOMIZATION_TAG = 0xE9150000   # SB_RANDOMIZATION_TAG (include/sbsim_amd.h): the draws' last counter word is this | id
+RAND_MATERIAL = 0x100            # SB_RAND_MATERIAL: id of material field f
+RAND_MAX_CHOICES = 65536
+
+
+class Uniform:
+  """d = lo + (hi - lo) * u, u the 53-bit uniform of the field's Philox block: a value in [lo, hi].  ``scale``: the
+  field's value is the building's own base row times d.  For a window field (``comfort_temp_window``,
+  ``eco_temp_window``) lo and hi are pairs, one interval per edge: ``Uniform((293.0, 296.5), (295.0, 299.0))`` draws
+  edge 0 in [293, 295] and edge 1 in [296.5, 299]."""
+
+  def __init__(self, lo, hi, scale: bool = False):
+    self.lo, self.hi, self.scale = lo, hi, bool(scale)
+
+  def __repr__(self) -> str:
+    return f"Uniform({self.lo!r}, {self.hi!r}, scale={self.scale})"
+
+
+class Choice:
+  """d = values[(c0 * K) >> 32], c0 the first word of the field's Philox block: one of K <= 65,536 values, integer
+  arithmetic only (a log-spaced table is how a log-uniform draw stays bit for bit).  ``scale`` as ``Uniform``'s."""
+
+  def __init__(self, values, scale: bool = False):
+    self.values, self.scale = values, bool(scale)
+
+  def __repr__(self) -> str:
+    return f"Choice({self.values!r}, scale={self.scale})"
+
+
+class _RandField(NamedTuple):
+  name: str        # as messages and ``values`` name it: the SimConfig field (with [edge]), kind[slot], convection_coefficient
+  param: Optional[int]                  # sb_building_param, or None for a material field
+  material: Optional[Tuple[int, int]]   # (kind, slot); kind 3: the convection coefficient
+  choice: bool
+  scale: bool
+  lo: float
+  hi: float
+  values: Tuple[float, ...]
+
+  def ident(self, n_slots: Optional[int]) -> int:
+    if self.param is not None:
+      return self.param
+    if n_slots is None:
+      raise ValueError(f"{self.name}: a material field's number needs the plan's slot count (n_slots)")
+    kind, slot = self.material
+    return RAND_MATERIAL + (3 * n_slots if kind == 3 else kind * n_slots + slot)
+
+  def span(self) -> Tuple[float, float]:
+    return (min(self.values), max(self.values)) if self.choice else (self.lo, self.hi)
+
+
+def _items(table, what: str):
+  if table is None:
+    return []
+  if isinstance(table, Mapping):
+    return list(table.items())
+  try:
+    return [(k, v) for k, v in table]
+  except (TypeError, ValueError):
+    raise ValueError(f"{what} must be a mapping (or a list of pairs) of field -> distribution") from None
+
+
+class EpisodeRandomization:
+  """Per-building parameters and materials re-drawn at every episode start, on the device (sb_randomization_attach;
+  INTEGRATION.md 4p): domain randomisation for batches whose buildings restart on their own.
+
+      er = EpisodeRandomization(
+          params={"ahu_fan_efficiency": Uniform(0.7, 0.95),
+                  "vav_max_air_flow_rate": Uniform(0.8, 1.2, scale=True),
+                  "comfort_temp_window": Uniform((293.0, 296.5), (295.0, 299.0))},
+          materials={"conductivity": {0: Choice([20., 35., 50., 80.])}, "convection_coefficient": Uniform(6.0, 25.0)},
+          seed=7)
+      env = BatchedEnvironment(plan, B, episode_steps=lengths, building_materials=bm, episode_randomization=er)
+
+  ``params``: SimConfig field name (``BUILDING_PARAM_NAMES``) -> ``Uniform`` / ``Choice``; a window field takes a
+  ``Uniform`` with pair bounds or a pair of distributions, one per edge.  ``materials``: "conductivity" / "heat_capacity"
+  / "density" -> {slot of ``FloorPlan.material_slots()``: distribution}, "convection_coefficient" -> distribution.
+  ``values`` states the value of every field of building b in its episode e; a field's draw depends on (seed, global
+  building, e, field) alone.  ValueError, naming the field: an unknown, per-batch or repeated field, lo > hi, a bound or
+  choice that is not finite, K == 0 or K > 65,536, a seed outside uint64, first_building < 0; ``check`` adds what needs
+  the batch."""
+
+  def __init__(self, params=None, materials=None, seed: int = 0, first_building: int = 0):
+    from . import _ffi
+    index = {name: k for k, name in enumerate(_ffi.BUILDING_PARAM_FIELDS)}
+    fields: List[_RandField] = []
+    seen = set()
+
+    def add(name, param, material, dist):
+      key = (param, material)
+      if key in seen:
+        raise ValueError(f"{name} is named twice")
+      seen.add(key)
+      if isinstance(dist, Uniform):
+        try:
+          lo, hi = float(dist.lo), float(dist.hi)
+        except (TypeError, ValueError):
+          raise ValueError(f"{name}: Uniform needs one lo and one hi, got ({dist.lo!r}, {dist.hi!r})") from None
+        if not (math.isfinite(lo) and math.isfinite(hi)):
+          raise ValueError(f"{name}: lo and hi must be finite, got ({lo}, {hi})")
+        if lo > hi:
+          raise ValueError(f"{name}: lo {lo} > hi {hi}")
+        fields.append(_RandField(name, param, material, False, dist.scale, lo, hi, ()))
+      elif isinstance(dist, Choice):
+        v = np.array(dist.values, dtype=np.float64)
+        if v.ndim != 1:
+          raise ValueError(f"{name}: Choice needs a list of values, got shape {v.shape}")
+        if v.size == 0 or v.size > RAND_MAX_CHOICES:
+          raise ValueError(f"{name}: a Choice needs 1 .. 65,536 values, got K == {v.size}")
+        if not np.isfinite(v).all():
+          raise ValueError(f"{name}: choice {int(np.argmin(np.isfinite(v)))} is not finite")
+        fields.append(_RandField(name, param, material, True, dist.scale, 0.0, 0.0, tuple(float(x) for x in v)))
+      else:
+        raise ValueError(f"{name}: the distribution must be a Uniform or a Choice, got {dist!r}")
+
+    for name, dist in _items(params, "params"):
+      if name in PER_BATCH_CONFIG_FIELDS:
+        raise ValueError(f"{name!r} is one value per batch (the sweep or the host reads it), not per building")
+      if name not in BUILDING_PARAM_NAMES:
+        raise ValueError(f"unknown per-building parameter {name!r}; allowed: {', '.join(BUILDING_PARAM_NAMES)}")
+      c_names = BUILDING_PARAM_NAMES[name]
+      if len(c_names) == 1:
+        add(name, index[c_names[0]], None, dist)
+        continue
+      if isinstance(dist, Uniform):   # pair bounds: one interval per edge
+        try:
+          edges = [Uniform(dist.lo[j], dist.hi[j], dist.scale) for j in range(len(c_names))]
+          if len(dist.lo) != len(c_names) or len(dist.hi) != len(c_names):
+            raise TypeError
+        except (TypeError, IndexError):
+          raise ValueError(f"{name}: a window's Uniform takes pairs, (lo0, lo1) and (hi0, hi1): one interval per edge") from None
+      elif isinstance(dist, (list, tuple)) and len(dist) == len(c_names):
+        edges = list(dist)
+      else:
+        raise ValueError(f"{name}: a window takes a Uniform with pair bounds or a pair of distributions, one per edge")
+      for j, c_name in enumerate(c_names):
+        add(f"{name}[{j}]", index[c_name], None, edges[j])
+    for kind, table in _items(materials, "materials"):
+      if kind == "convection_coefficient":
+        add(kind, None, (3, 0), table)
+      elif kind in _MATERIAL_KINDS:
+        for slot, dist in _items(table, kind):
+          if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or slot < 0 or slot >= 255:
+            raise ValueError(f"{kind}: a material slot is an integer in 0 .. 254 (FloorPlan.material_slots()), got {slot!r}")
+          add(f"{kind}[{int(slot)}]", None, (_MATERIAL_KINDS.index(kind), int(slot)), dist)
+      else:
+        raise ValueError(f"unknown material field {kind!r}; allowed: {', '.join(_MATERIAL_KINDS)}, convection_coefficient")
+    if not fields:
+      raise ValueError("EpisodeRandomization needs at least one field (pass None instead of one to clear it)")
+    if isinstance(seed, (bool, float)) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+      raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    if isinstance(first_building, (bool, float)) or int(first_building) != first_building or first_building < 0:
+      raise ValueError(f"first_building must be an integer >= 0, got {first_building!r}")
+    self.fields = tuple(fields)
+    self.seed, self.first_building = int(seed), int(first_building)
+
+  @property
+  def has_materials(self) -> bool:
+    return any(f.material is not None for f in self.fields)
+
+  @property
+  def has_params(self) -> bool:
+    return any(f.param is not None for f in self.fields)
+
+  def rows(self, lo: int, hi: int = None) -> "EpisodeRandomization":
+    """The same randomisation for buildings lo .. of a larger batch: ``first_building`` moved so that they draw what they
+    drew in the whole batch."""
+    if lo < 0:
+      raise ValueError(f"rows: lo must be >= 0, got {lo}")
+    out = copy.copy(self)
+    out.first_building = self.first_building + int(lo)
+    return out
+
+  def draw(self, field: _RandField, b: int, e: int, n_slots: Optional[int] = None) -> float:
+    """d of ``field`` for building b in its episode number e (the formula of include/sbsim_amd.h, on Python integers and
+    IEEE doubles: one rounding per operation)."""
+    gb = self.first_building + int(b)
+    c = _philox_block((gb & _M32, gb >> 32, int(e) & _M32, RANDOMIZATION_TAG | field.ident(n_slots)),
+                      (self.seed & _M32, self.seed >> 32))
+    if field.choice:
+      return field.values[(c[0] * len(field.values)) >> 32]
+    r = (c[1] << 32) | c[0]
+    return field.lo + (field.hi - field.lo) * (float(r >> 11) * 2.0 ** -53)
+
+  @staticmethod
+  def _base_of(field: _RandField, base, b: int) -> float:
+    if field.param is not None:
+      name, _, edge = field.name.partition("[")
+      a = base[name][b]
+      return float(a[int(edge[:-1])]) if edge else float(a)
+    kind, slot = field.material
+    return float(base["convection_coefficient"][b]) if kind == 3 else float(base[_MATERIAL_KINDS[kind]][b][slot])
+
+  @staticmethod
+  def _base_column(field: _RandField, base) -> np.ndarray:
+    """``_base_of`` for every building at once: float64 [B]."""
+    if field.param is not None:
+      name, _, edge = field.name.partition("[")
+      a = np.asarray(base[name], dtype=np.float64)
+      return a[:, int(edge[:-1])] if edge else a
+    kind, slot = field.material
+    return np.asarray(base["convection_coefficient"] if kind == 3 else np.asarray(base[_MATERIAL_KINDS[kind]])[:, slot], dtype=np.float64)
+
+  def values(self, b: int, e: int, base: Optional[Mapping[str, np.ndarray]] = None, n_slots: Optional[int] = None) -> Dict[str, object]:
+    """The value of every randomised field of building b in its episode number e -- what the device writes.  ``base``:
+    the rows in force at attach, by name (``building_params()`` merged with ``building_materials()``: float64 [B],
+    [B, 2] for a window, [B, M] for a material kind); needed for ``scale`` fields and for material fields (whose numbers
+    depend on M; ``n_slots`` gives M without a base).  Returns SimConfig field -> float ([2] for a window, with the edge
+    that is not randomised from ``base``), material kind -> float64 [M] (the slots not randomised from ``base``),
+    "convection_coefficient" -> float."""
+    if n_slots is None and base is not None and "conductivity" in base:
+      n_slots = int(np.asarray(base["conductivity"]).shape[1])
+    out: Dict[str, object] = {}
+    for f in self.fields:
+      d = self.draw(f, b, e, n_slots)
+      if f.scale:
+        if base is None:
+          raise ValueError(f"{f.name}: a scale field needs the base rows")
+        d = self._base_of(f, base, b) * d
+      if f.param is not None:
+        name, _, edge = f.name.partition("[")
+        if edge:
+          if name not in out:
+            if base is None and sum(g.name.startswith(name + "[") for g in self.fields) < 2:
+              raise ValueError(f"{name}: one edge is randomised, the other needs the base rows")
+            out[name] = np.array(base[name][b], dtype=np.float64) if base is not None else np.zeros(2)
+          out[name][int(edge[:-1])] = d
+        else:
+          out[name] = d
+      elif f.material[0] == 3:
+        out["convection_coefficient"] = d
+      else:
+        kind = _MATERIAL_KINDS[f.material[0]]
+        if kind not in out:
+          if base is None:
+            raise ValueError(f"{f.name}: a material field needs the base rows (the slots that are not randomised)")
+          out[kind] = np.array(base[kind][b], dtype=np.float64)
+        out[kind][f.material[1]] = d
+    return out
+
+  def check(self, n_buildings: int, base_params: Mapping[str, np.ndarray], base_materials: Optional[Mapping[str, np.ndarray]],
+            solver: str = "gauss_seidel") -> None:
+    """What needs the batch, as sb_randomization_attach checks it: material fields need a simulator created with
+    ``building_materials`` (``base_materials`` None: there is none) and not solver="jacobi_fp32"; a slot beyond the
+    plan's; and every possible draw against the rows' checks, on the closed range of every field, per building where
+    ``scale`` makes the range depend on the base row.  ValueError naming the field and, for these, the building."""
+    B = int(n_buildings)
+    if self.has_materials:
+      if solver == "jacobi_fp32":
+        f = next(f for f in self.fields if f.material is not None)
+        raise ValueError(f"{f.name}: material fields are not implemented for solver='jacobi_fp32' (its float32 class table "
+                         "is one per batch)")
+      if base_materials is None:
+        f = next(f for f in self.fields if f.material is not None)
+        raise ValueError(f"{f.name}: material fields need an environment created with building_materials=... (its floor "
+                         "plan is compiled into structural classes)")
+    base = dict(base_params)
+    if base_materials is not None:
+      base.update(base_materials)
+    M = None if base_materials is None else int(np.asarray(base_materials["conductivity"]).shape[1])
+    span: Dict[Tuple, Tuple[np.ndarray, np.ndarray]] = {}
+
+    def first_bad(ok) -> int:
+      return int(np.argmin(ok))
+
+    for f in self.fields:
+      if f.material is not None and f.material[0] != 3 and f.material[1] >= M:
+        raise ValueError(f"{f.name}: the floor plan has {M} material slots (FloorPlan.material_slots())")
+      lo, hi = f.span()
+      b0 = self._base_column(f, base) if f.scale else None
+      with np.errstate(over="ignore", invalid="ignore"):   # (an overflow is what the next lines refuse)
+        x, y = (b0 * lo, b0 * hi) if f.scale else (np.full(B, lo), np.full(B, hi))
+      ok = np.isfinite(x) & np.isfinite(y)
+      if not ok.all():
+        raise ValueError(f"building {first_bad(ok)}: {f.name} can be drawn not finite")
+      span[(f.param, f.material)] = (np.minimum(x, y), np.maximum(x, y))
+      mn = span[(f.param, f.material)][0]
+      if f.material is not None:
+        ok = (mn >= 0.0) if f.material[0] == 3 else (mn > 0.0)
+        if not ok.all():
+          b = first_bad(ok)
+          raise ValueError(f"building {b}: {f.name} must " + ("not be negative" if f.material[0] == 3 else "be positive")
+                           + f", and can be drawn as {mn[b]}")
+      elif f.name in _POSITIVE_PARAMS and not (mn > 0.0).all():
+        b = first_bad(mn > 0.0)
+        raise ValueError(f"building {b}: {f.name} must be positive, and can be drawn as {mn[b]}")
+    if not self.has_params:
+      return
+    from . import _ffi
+    index = {name: k for k, name in enumerate(_ffi.BUILDING_PARAM_FIELDS)}
+
+    def rng(name: str, edge: Optional[int] = None):
+      """(drawn, lowest, highest) possible value per building of a SimConfig field (or a window's edge)."""
+      k = index[BUILDING_PARAM_NAMES[name][edge or 0]]
+      if (k, None) in span:
+        return (True,) + span[(k, None)]
+      a = np.asarray(base[name], dtype=np.float64)
+      a = a[:, edge] if edge is not None else a
+      return False, a, a
+
+    dh, _, heat_hi = rng("ahu_heating_air_temp_setpoint")
+    dc, cool_lo, _ = rng("ahu_cooling_air_temp_setpoint")
+    if (dh or dc) and not (cool_lo > heat_hi).all():   # air_handler.py:60-64
+      b = first_bad(cool_lo > heat_hi)
+      which = "ahu_heating_air_temp_setpoint" if dh else "ahu_cooling_air_temp_setpoint"
+      raise ValueError(f"building {b}: {which}: the largest possible heating setpoint {heat_hi[b]} must be below the "
+                       f"smallest possible cooling setpoint {cool_lo[b]}")
+    for name, msg in _WINDOWS.items():
+      d0, _, lo_hi = rng(name, 0)
+      d1, hi_lo, _ = rng(name, 1)
+      if (d0 or d1) and not (lo_hi <= hi_lo).all():
+        raise ValueError(f"building {first_bad(lo_hi <= hi_lo)}: {name}: {msg} in every possible draw")
+    w = [rng(n) for n in ("productivity_weight", "energy_cost_weight", "carbon_emission_weight")]
+    if any(x[0] for x in w) and not (w[0][1] + w[1][1] + w[2][1] > 0.0).all():
+      b = first_bad(w[0][1] + w[1][1] + w[2][1] > 0.0)
+      which = ("productivity_weight", "energy_cost_weight", "carbon_emission_weight")[[x[0] for x in w].index(True)]
+      raise ValueError(f"building {b}: {which}: productivity_weight + energy_cost_weight + carbon_emission_weight must be "
+                       "positive at their smallest draws (the reward divides by it)")
+
+  def c_fields(self, n_slots: Optional[int]):
+    """sb_randomization_attach's ``fields`` for a plan of n_slots material slots: the ctypes array and what it points into."""
+    import ctypes as C
+    from . import _ffi
+    arr = (_ffi.RandField * len(self.fields))()
+    keep = []
+    for i, f in enumerate(self.fields):
+      arr[i].id, arr[i].scale = f.ident(n_slots), int(f.scale)
+      if f.choice:
+        v = np.ascontiguousarray(f.values, dtype=np.float64)
+        keep.append(v)
+        arr[i].kind, arr[i].n_choices, arr[i].choices = _ffi.SB_RAND_CHOICE, len(f.values), v.ctypes.data_as(_ffi._dp)
+      else:
+        arr[i].kind, arr[i].lo, arr[i].hi = _ffi.SB_RAND_UNIFORM, f.lo, f.hi
+    return arr, keep
+
+  def digest(self) -> str:
+    """A hash of everything attached (``BatchedSimulator.state_fingerprint``): the fields in the order of their numbers."""
+    rows = sorted((f.param is None, f.param, f.material, f.choice, f.scale, f.lo.hex(), f.hi.hex(),
+                   tuple(v.hex() for v in f.values)) for f in self.fields)
+    return hashlib.sha256(repr((rows, self.seed, self.first_building)).encode()).hexdigest()
