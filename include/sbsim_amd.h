@@ -917,6 +917,106 @@ int sb_randomization_episodes_set(sb_handle *h, const int32_t *in_dev /* [B] */,
 int sb_get_building_params(sb_handle *h, double *out_dev, void *stream);
 int sb_get_building_materials(sb_handle *h, double *out_dev, void *stream);
 
+/* A start time and weather per building, drawn anew at every episode start, on the device (the reference constructs a
+ * new Environment(start_timestamp=...) with a new weather controller per episode, environment.py:1165-1212,
+ * weather_controller.py:60-93).  Up to four fields of building b are drawn at every reset of b, each with its own
+ * distribution; a field that is absent stays what it is:
+ *
+ *     SB_START_OFFSET        the building's attached clock offset (sb_clock_attach's offsets[b]), in rows of the table
+ *     SB_START_WEATHER_LOW   weather_lohi_dev[2 b]      (the [B][2] array the caller passes in every sb_step_in)
+ *     SB_START_WEATHER_HIGH  weather_lohi_dev[2 b + 1]
+ *     SB_START_WEATHER_SHIFT weather_offset_dev[b]      (the [B] array of a replay weather, seconds)
+ *
+ *     (c0, c1, c2, c3) = Philox4x32-10(key = (lo32(seed), hi32(seed)),
+ *                                      counter = (lo32(gb), hi32(gb), e, SB_EPISODE_STARTS_TAG | id)),  gb = first_building + b
+ *     SB_RAND_UNIFORM, SB_RAND_CHOICE:  sb_randomization_attach's formulas (float64, one rounding per operation)
+ *     SB_RAND_UNIFORM_INT:  d = lo + step * (((uint64)c0 * K) >> 32),  K = (hi - lo) / step + 1 <= 2^22   (integers only)
+ *     offset = d, or the offset given to sb_clock_attach + d with `relative` set; a weather field's value is d.
+ *
+ * The offset takes SB_RAND_UNIFORM_INT or a SB_RAND_CHOICE of whole numbers, the weather fields SB_RAND_UNIFORM or
+ * SB_RAND_CHOICE.  A draw depends on (seed, gb, e, id) alone.
+ * The counters stay apart from every other generator's under the same seed.  The last word here is 0xE5A70000 .. 0xE5A70003.
+ * sb_randomization_attach's is 0xE9150000 .. 0xE91503FD, SB_INITIAL_CONDITIONS_TAG the one word 0xC1C00000, the
+ * convection shuffles' a grid cell (< 2^21) or 0x80000000 | 2 * room (+ 1), at most 0x8000FFFF: none of them inside
+ * 0xE5A70000 .. 0xE5A70003.  The occupancy generator's is query * 8 + block: it reaches 0xE5A70000 after 481 million
+ * queries of one handle (a step makes one), beyond any run.
+ *
+ * e is this feature's own counter (int32 [B] on the device): 0 at attach, used and then incremented by every reset of the
+ * building -- sb_reset (every building), sb_reset_buildings (the masked ones).  It is independent of the counters of
+ * sb_randomization_attach and sb_initial_conditions_attach, whose draws an attachment here does not change by one bit.
+ * Inside a reset, on the caller's stream, after sb_randomization_attach's redraw and before the reset kernel: ONE launch
+ * of k_episode_starts writes the drawn values of the resetting buildings and advances their counters; the reset kernel
+ * then computes the building's effective offset from the new offset (sb_reset: the kernel writes effective = offset
+ * itself), and the observation that follows reads the new rows and the new weather.  The step before ran at the old
+ * instant under the old weather.  Of a building that is not reset not one bit changes: offset, effective offset, weather
+ * entries, counter.
+ * The previous thermostat update: with SB_START_OFFSET attached the row offset[b] + prev_pos means nothing after a
+ * reset that moved the offset, so a clocked k_pre takes comfort_prev from the building's scalar state, as it does after
+ * sb_reset_buildings; it equals the row lookup whenever no request was rejected.
+ * Bounds without a host copy of the draws: no reset copies a drawn value to the host.  The host shadow sb_clock_seek and
+ * sb_reset_buildings check against holds, for every building, the largest offset it may have (the attached one, or the
+ * largest possible draw if that is larger); attach verifies that the table holds that offset plus two rows.
+ * Configuration of the slots plus one counter: sb_state_save / sb_state_load carry neither. */
+#define SB_EPISODE_STARTS_TAG 0xE5A70000u
+#define SB_RAND_UNIFORM_INT 2      /* a sb_rand_kind of sb_start_field alone */
+#define SB_START_MAX_K (1 << 22)
+typedef enum sb_start_field_id {
+  SB_START_OFFSET = 0, SB_START_WEATHER_LOW, SB_START_WEATHER_HIGH, SB_START_WEATHER_SHIFT, SB_START_FIELDS
+} sb_start_field_id;
+typedef struct sb_start_field {
+  int32_t present;        /* 0: the field is not drawn, the rest is ignored */
+  int32_t kind;           /* sb_rand_kind, or SB_RAND_UNIFORM_INT */
+  int32_t n_choices;      /* SB_RAND_CHOICE: K, 1 .. SB_RAND_MAX_CHOICES */
+  int32_t step;           /* SB_RAND_UNIFORM_INT: >= 1 */
+  double lo, hi;          /* SB_RAND_UNIFORM: finite, lo <= hi; SB_RAND_UNIFORM_INT: whole numbers, 0 <= lo <= hi */
+  const double *choices;  /* SB_RAND_CHOICE: HOST [K], finite (SB_START_OFFSET: whole numbers >= 0) */
+} sb_start_field;
+typedef struct sb_episode_starts {
+  sb_start_field field[SB_START_FIELDS];
+  int32_t relative;           /* != 0: offset = the offset given to sb_clock_attach + d */
+  int32_t reserved;
+  double *weather_lohi_dev;   /* DEVICE [B][2]; needed by SB_START_WEATHER_LOW / _HIGH, NULL otherwise */
+  double *weather_offset_dev; /* DEVICE [B]; needed by SB_START_WEATHER_SHIFT, NULL otherwise */
+  uint64_t seed;
+  int64_t first_building;     /* global index of this handle's building 0 */
+} sb_episode_starts;
+/* Attaches (replacing an earlier attachment, whose base values this one inherits): keeps the two weather pointers, copies
+ * the arrays behind them and the attached offsets as the base values, zeroes the counters.  Nothing is drawn before the
+ * next reset.  Synchronises the device: SB_ERR_INVALID while a stream is being captured.  Refused, the handle unchanged,
+ * the message naming the field (and the building where the check depends on one):
+ * SB_ERR_INVALID for a null argument, no field present, an unknown kind or one the field does not take, lo > hi, a bound
+ * or choice that is not finite, an offset bound or choice that is negative or no whole number, step < 1, K > 2^22,
+ * n_choices outside 1 .. 65,536, first_building < 0, a weather field without its array, a possible draw with low > high
+ * (against the other entry's array where only one of the two is drawn), a largest possible offset that leaves no two
+ * rows of the table; SB_ERR_UNSUPPORTED for SB_START_OFFSET on a handle without a clock (sb_clock_attach first).
+ * (A table that holds several calendars' rows one after the other looks like any other to the library: a drawn offset
+ * would walk from one calendar into the next, so BatchedEnvironment refuses `calendars` together with drawn offsets.)
+ * sb_clock_attach and sb_clock_detach drop an attachment with the calendar its offsets belonged to. */
+int sb_episode_starts_attach(sb_handle *h, const sb_episode_starts *es);
+/* From its next reset on, every building returns to the offset given to sb_clock_attach and to the weather entries as
+ * they were at attach, bit for bit; the episode in progress finishes where it is.  The counters go.  Until every
+ * building has been reset once (sb_reset does it for all) the resets still launch k_episode_starts, which then writes
+ * the base values; after that the handle launches what it launched before the attach.  No-op without an attachment. */
+int sb_episode_starts_detach(sb_handle *h);
+/* The [B] counters, stream-ordered device copies; SB_ERR_UNSUPPORTED without an attachment.  _set also writes the values
+ * in force for the new counters t: the draw of episode t[b] - 1 where t[b] >= 1, the base values where t[b] == 0; the
+ * effective offset keeps the building's restart position. */
+int sb_episode_starts_episodes_get(sb_handle *h, int32_t *out_dev /* [B] */, void *stream);
+int sb_episode_starts_episodes_set(sb_handle *h, const int32_t *in_dev /* [B] */, void *stream);
+/* The offsets in force, stream-ordered: offsets_dev DEVICE [B] (the attached offsets, drawn or not) and effective_dev
+ * DEVICE [B] (what the kernels index: offset - the building's restart position); either may be NULL.  Works on every
+ * handle with a clock, attachment or not; SB_ERR_UNSUPPORTED without a clock.  The weather values in force are the
+ * caller's own arrays. */
+int sb_episode_starts_values_get(sb_handle *h, int32_t *offsets_dev, int32_t *effective_dev, void *stream);
+/* The host route to new start times: offsets_host HOST [B] int32 replaces the offsets given to sb_clock_attach, each
+ * taken by its building at its next reset (sb_reset: every building; sb_reset_buildings: the masked ones, whose kernel
+ * computes effective = offset - restart_pos from it); the episodes in progress keep their effective offsets.  The copy is
+ * queued on `stream`, which is synchronised (the host array may go away on return).  Until a building's next reset the
+ * host shadow holds the larger of its two offsets.  SB_ERR_INVALID: a null argument, a negative offset or one past
+ * n_rows - 2 (the message names the building), a capturing stream, an attachment of sb_episode_starts_attach that draws
+ * the offsets; SB_ERR_UNSUPPORTED without a clock. */
+int sb_clock_set_offsets(sb_handle *h, const int32_t *offsets_host /* [B] */, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

@@ -161,6 +161,17 @@ class RandField(C.Structure):   # sb_rand_field (choices: a HOST pointer)
               ("lo", C.c_double), ("hi", C.c_double), ("choices", _dp)]
 
 
+class StartField(C.Structure):   # sb_start_field (choices: a HOST pointer)
+  _fields_ = [("present", C.c_int32), ("kind", C.c_int32), ("n_choices", C.c_int32), ("step", C.c_int32),
+              ("lo", C.c_double), ("hi", C.c_double), ("choices", _dp)]
+
+
+class EpisodeStartsDesc(C.Structure):   # sb_episode_starts (the two weather arrays: DEVICE pointers)
+  _fields_ = [("field", StartField * 4), ("relative", C.c_int32), ("reserved", C.c_int32),
+              ("weather_lohi_dev", C.c_void_p), ("weather_offset_dev", C.c_void_p), ("seed", C.c_uint64),
+              ("first_building", C.c_int64)]
+
+
 # sb_sweep_kernel
 SWEEP_KERNELS = {0: "k_sweep_lds", 1: "k_sweep_reg", 2: "k_sweep_reg (two wavefronts)", 3: "k_sweep_roll", 4: "k_sweep_two",
                  5: "k_sweep_band", 6: "k_sweep_stream", 7: "k_sweep_jacobi"}
@@ -182,7 +193,9 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_initial_conditions_attach", "sb_initial_conditions_detach", "sb_initial_conditions_episodes_get",
            "sb_initial_conditions_episodes_set",
            "sb_randomization_attach", "sb_randomization_detach", "sb_randomization_episodes_get",
-           "sb_randomization_episodes_set", "sb_get_building_params", "sb_get_building_materials")
+           "sb_randomization_episodes_set", "sb_get_building_params", "sb_get_building_materials",
+           "sb_episode_starts_attach", "sb_episode_starts_detach", "sb_episode_starts_episodes_get",
+           "sb_episode_starts_episodes_set", "sb_episode_starts_values_get", "sb_clock_set_offsets")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
@@ -206,6 +219,13 @@ SB_RAND_MATERIAL = 0x100                 # id of material field f: SB_RAND_MATER
 SB_RAND_MAX_CHOICES = 65536
 SB_RAND_UNIFORM, SB_RAND_CHOICE = 0, 1   # sb_rand_kind
 SB_RAND_BLOCKS_PER_CU, SB_RAND_THREADS = 8, 256   # k_randomize's grid cap (randomize.hip): work beyond it takes the grid stride
+EPISODE_STARTS_ENTRIES = ("sb_episode_starts_attach", "sb_episode_starts_detach", "sb_episode_starts_episodes_get",
+                          "sb_episode_starts_episodes_set", "sb_episode_starts_values_get", "sb_clock_set_offsets")
+SB_EPISODE_STARTS_TAG = 0xE5A70000       # include/sbsim_amd.h: the starts' last counter word is this | sb_start_field_id
+SB_RAND_UNIFORM_INT = 2                  # sb_start_field's third kind
+SB_START_MAX_K = 1 << 22
+SB_START_OFFSET, SB_START_WEATHER_LOW, SB_START_WEATHER_HIGH, SB_START_WEATHER_SHIFT = range(4)   # sb_start_field_id
+SB_STARTS_BLOCKS_PER_CU, SB_STARTS_THREADS = 8, 256   # k_episode_starts' grid cap (episode_starts.hip)
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -326,6 +346,13 @@ def load():
     L.sb_randomization_detach.argtypes = [vp]
     for name in RANDOMIZATION_ENTRIES[2:]:
       getattr(L, name).argtypes = [vp, vp, vp]
+  if all(hasattr(L, name) for name in EPISODE_STARTS_ENTRIES):
+    L.sb_episode_starts_attach.argtypes = [vp, C.POINTER(EpisodeStartsDesc)]
+    L.sb_episode_starts_detach.argtypes = [vp]
+    L.sb_episode_starts_episodes_get.argtypes = [vp, vp, vp]
+    L.sb_episode_starts_episodes_set.argtypes = [vp, vp, vp]
+    L.sb_episode_starts_values_get.argtypes = [vp, vp, vp, vp]
+    L.sb_clock_set_offsets.argtypes = [vp, vp, vp]
   if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
     L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
@@ -399,6 +426,12 @@ def randomization_entry(name: str):
   """The episode-randomisation entry `name` (sb_randomization_attach, sb_randomization_detach,
   sb_randomization_episodes_get, sb_randomization_episodes_set, sb_get_building_params, sb_get_building_materials): see
   entry()."""
+  return entry(name)
+
+
+def episode_starts_entry(name: str):
+  """The episode-starts entry `name` (sb_episode_starts_attach, sb_episode_starts_detach, sb_episode_starts_episodes_get,
+  sb_episode_starts_episodes_set, sb_episode_starts_values_get, sb_clock_set_offsets): see entry()."""
   return entry(name)
 
 

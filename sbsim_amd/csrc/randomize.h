@@ -22,13 +22,19 @@ struct RandField {
   double lo, hi;      // SB_RAND_UNIFORM
 };
 
-// d of field `f` for global building gb in its episode e.  choices: the concatenated choice tables.
-__host__ __device__ inline double rand_draw(const RandField &f, const double *choices, uint64_t seed, uint64_t gb, uint32_t e) {
-  uint32_t c[4] = {(uint32_t)gb, (uint32_t)(gb >> 32), e, SB_RANDOMIZATION_TAG | (uint32_t)f.id};
-  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+// d of field `f` from the four words of its Philox block (SB_RAND_UNIFORM / SB_RAND_CHOICE; episode_starts.h draws with
+// the same formulas under its own tag).  choices: the concatenated choice tables.
+__host__ __device__ inline double rand_of_block(const RandField &f, const double *choices, const uint32_t c[4]) {
   if (f.kind == SB_RAND_CHOICE) return choices[f.choice_off + (int)(((uint64_t)c[0] * (uint64_t)f.choice_len) >> 32)];
   const uint64_t r = ((uint64_t)c[1] << 32) | c[0];
   return f.lo + (f.hi - f.lo) * ((double)(r >> 11) * 0x1p-53);
+}
+
+// d of field `f` for global building gb in its episode e.
+__host__ __device__ inline double rand_draw(const RandField &f, const double *choices, uint64_t seed, uint64_t gb, uint32_t e) {
+  uint32_t c[4] = {(uint32_t)gb, (uint32_t)(gb >> 32), e, SB_RANDOMIZATION_TAG | (uint32_t)f.id};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return rand_of_block(f, choices, c);
 }
 
 // The field's value from its draw and the building's base row.

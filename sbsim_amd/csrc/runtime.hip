@@ -596,6 +596,18 @@ int apply_building_materials(sb_handle *h, const std::vector<double> &tab, hipSt
   return SB_OK;
 }
 
+// The bounds sb_clock_seek checks, from the host shadow of the restart positions (episode_starts.hip calls it too).
+void episode_bounds(sb_handle *h) {
+  int max_eff = INT32_MIN, max_restart = 0;
+  for (size_t b = 0; b < h->h_clock_offs.size(); ++b) {
+    const int r = h->restart_pos.empty() ? 0 : h->restart_pos[b];
+    max_eff = std::max(max_eff, h->h_clock_offs[b] - r);
+    max_restart = std::max(max_restart, r);
+  }
+  h->clock_max_off = h->h_clock_offs.empty() ? 0 : max_eff;
+  h->max_restart = max_restart;
+}
+
 extern "C" {
 
 int sb_abi_version(void) { return SB_ABI_VERSION; }
@@ -635,29 +647,24 @@ static void launch_reset(sb_handle *h, const EpisodeArgs &ep, double initial_tem
                        temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset, 0);
 }
 
-// The bounds sb_clock_seek checks, from the host shadow of the restart positions.
-static void episode_bounds(sb_handle *h) {
-  int max_eff = INT32_MIN, max_restart = 0;
-  for (size_t b = 0; b < h->h_clock_offs.size(); ++b) {
-    const int r = h->restart_pos.empty() ? 0 : h->restart_pos[b];
-    max_eff = std::max(max_eff, h->h_clock_offs[b] - r);
-    max_restart = std::max(max_restart, r);
-  }
-  h->clock_max_off = h->h_clock_offs.empty() ? 0 : max_eff;
-  h->max_restart = max_restart;
-}
-
 int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *stream) {
   if (!h) return fail(SB_ERR_INVALID, "sb_reset: null handle");
   SB_ON_DEVICE(h->device);
   if (h->rz_attached) SB_CHECK(sb_randomization_redraw(h, nullptr, (hipStream_t)stream)); // the new episode's rows, before the reset reads them
+  if (h->es_attached) SB_CHECK(sb_episode_starts_redraw(h, nullptr, (hipStream_t)stream)); // ... its start and weather
   launch_reset(h, EpisodeArgs{nullptr, h->ep_start.p, nullptr, nullptr, 0}, initial_temp, temps_dev, (hipStream_t)stream);
   h->was_reset = true;
   h->steps_since_reset = 0;
   h->counters_zeroed_on = (void *)(uintptr_t)1; // (whatever came before a reset is no promise about the draw counters)
   SB_HIP(hipGetLastError());
   h->ep_dirty = false; // (the kernel above zeroes ep_start)
-  if (!h->restart_pos.empty() || h->own_prev) { // episodes per building: every building back on the attached calendar
+  const bool new_offs = !h->h_clock_next.empty(); // sb_clock_set_offsets: every building takes its new offset now
+  if (new_offs) {
+    h->h_clock_offs = std::move(h->h_clock_next);
+    h->h_clock_next.clear();
+  }
+  if (h->es_attached) sb_episode_starts_after_reset(h, nullptr);
+  if (!h->restart_pos.empty() || h->own_prev || new_offs) { // episodes per building: every building back on the attached calendar
     if (h->clock_eff.p)
       SB_HIP(hipMemcpyAsync(h->clock_eff.p, h->clock_offs.p, (size_t)h->d.B * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     h->restart_pos.clear();
@@ -696,7 +703,8 @@ int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host, int32_t restart_p
     // the rows of the building's next launch: at the position sought now, or at restart_pos once the caller has sought
     // there (sb_clock_seek refuses a position below it)
     if (!clk) continue;
-    const long long now = (long long)h->h_clock_offs[b] + std::max(0LL, (long long)h->clock_pos - restart_pos);
+    const int off = h->h_clock_next.empty() ? h->h_clock_offs[b] : h->h_clock_next[b]; // (sb_clock_set_offsets: its next offset)
+    const long long now = (long long)off + std::max(0LL, (long long)h->clock_pos - restart_pos);
     if (now > (long long)h->clock_n_rows - 2)
       return fail(SB_ERR_INVALID, "sb_reset_buildings: building " + std::to_string(b) + ": restarting at position " +
                                       std::to_string(restart_pos) + " with the clock at " + std::to_string(h->clock_pos) +
@@ -707,6 +715,7 @@ int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host, int32_t restart_p
   SB_CHECK(upload_mask(h, mask_host, "sb_reset_buildings", (hipStream_t)stream));
   if (!h->ep_start.p) SB_CHECK(alloc_zero(h->ep_start, (size_t)B));
   if (h->rz_attached) SB_CHECK(sb_randomization_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // the masked buildings' new rows
+  if (h->es_attached) SB_CHECK(sb_episode_starts_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // ... their starts and weather
   launch_reset(h, EpisodeArgs{h->ep_mask.p, h->ep_start.p, clk ? h->clock_eff.p : nullptr, h->clock_offs.p, restart_pos},
                initial_temp, temps_dev, (hipStream_t)stream);
   SB_HIP(hipGetLastError());
@@ -714,8 +723,14 @@ int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host, int32_t restart_p
   if (clk) {
     if (h->restart_pos.empty()) h->restart_pos.assign((size_t)B, 0);
     for (int b = 0; b < B; ++b)
-      if (mask_host[b]) h->restart_pos[b] = restart_pos;
+      if (mask_host[b]) {
+        h->restart_pos[b] = restart_pos;
+        if (!h->h_clock_next.empty()) h->h_clock_offs[b] = h->h_clock_next[b];
+      }
+    if (h->es_attached) sb_episode_starts_after_reset(h, mask_host);
     episode_bounds(h);
+  } else if (h->es_attached) {
+    sb_episode_starts_after_reset(h, mask_host);
   }
   return SB_OK;
 }
@@ -1083,6 +1098,8 @@ static int drop_clock(sb_handle *h) { // the kernels in flight read the table: i
   if (h->clock_eff.p) SB_HIP(hipFree(h->clock_eff.p));
   h->clock_eff.p = nullptr;
   h->h_clock_offs.clear();
+  h->h_clock_next.clear();
+  sb_episode_starts_forget(h);
   h->restart_pos.clear(); // a clock attached later starts from its own offsets and reads its own previous row
   h->own_prev = false;
   h->max_restart = 0;

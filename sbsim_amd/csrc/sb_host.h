@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "episode_starts.h"
 #include "planner.h"
 #include "sb_device.h"
 
@@ -231,6 +232,25 @@ struct sb_handle {
   std::vector<double> rz_base_mat;  // host: [3 M + 1][B] likewise; empty on a handle without materials
   uint64_t rz_seed = 0;
   long long rz_first = 0;
+  // sb_clock_set_offsets: the offsets a building takes at its next reset where they differ from h_clock_offs, which then
+  // holds the larger of the two (empty: none pending)
+  std::vector<int> h_clock_next;
+  // sb_episode_starts_attach (episode_starts.hip): the fields, their choice tables, the base values, the counters
+  bool es_attached = false;         // a reset launches k_episode_starts ...
+  bool es_restoring = false;        // ... which writes the base values: detached, until every building was reset once
+  bool es_offsets = false;          // SB_START_OFFSET is (or, restoring, was) drawn: h_clock_offs holds the largest possible offsets
+  sb::StartField es_field[SB_START_FIELDS] = {};
+  int es_relative = 0;
+  DevBuf<double> es_choices;        // the fields' choice tables, one after the other
+  DevBuf<int> es_episode;           // [B] the number of the building's next episode
+  DevBuf<int> es_base_offs;         // [B] the offsets given to sb_clock_attach
+  DevBuf<double> es_base_lohi;      // [B][2] the caller's weather array at attach
+  DevBuf<double> es_base_shift;     // [B] likewise
+  std::vector<int> es_h_base_offs;  // host copy of es_base_offs
+  std::vector<uint8_t> es_pending;  // restoring: the buildings not reset since the detach
+  double *es_lohi = nullptr, *es_shift = nullptr; // the caller's arrays
+  uint64_t es_seed = 0;
+  long long es_first = 0;
   // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
   DevBuf<float> jgrid, jtab, jscratch; // (jscratch: k_sweep_jacobi_g's per-workgroup grids)
   DevBuf<double> jrden;
@@ -249,7 +269,9 @@ inline int handle_clock_view(const sb_handle *h, const char *who, sb::ClockView 
   if (h->clock_pos < h->max_restart)
     return fail(SB_ERR_INVALID, std::string(who) + ": a building restarts at position " + std::to_string(h->max_restart) +
                                     " (sb_reset_buildings), the clock is at " + std::to_string(h->clock_pos) + ": sb_clock_seek first");
-  *out = sb::ClockView{h->clock_rows.p, h->clock_eff.p, h->clock_pos, h->clock_prev, h->clock_n_rows, h->own_prev ? 1 : 0};
+  // (drawn offsets, sb_episode_starts_attach: a reset moves the building's rows, as a reset of its own does)
+  const bool own_prev = h->own_prev || (h->es_attached && h->es_offsets);
+  *out = sb::ClockView{h->clock_rows.p, h->clock_eff.p, h->clock_pos, h->clock_prev, h->clock_n_rows, own_prev ? 1 : 0};
   return SB_OK;
 }
 
@@ -271,6 +293,15 @@ std::string material_field_name(int f, int M);
 // randomize.hip: the redraw at the top of a reset (sb_reset: mask_dev NULL, every building; sb_reset_buildings: its
 // device mask), stream-ordered launches only.  Only called while a randomisation is attached.
 int sb_randomization_redraw(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream);
+
+// runtime.hip: the bounds sb_clock_seek checks (clock_max_off, max_restart), from the host shadows
+void episode_bounds(sb_handle *h);
+// episode_starts.hip: the draw at the top of a reset, after sb_randomization_redraw (mask_dev as there), one stream-ordered
+// launch; and the host shadow's part once the reset is queued (mask_host NULL: sb_reset).  Only called while es_attached.
+int sb_episode_starts_redraw(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream);
+void sb_episode_starts_after_reset(sb_handle *h, const uint8_t *mask_host);
+// episode_starts.hip: forgets an attachment with the clock its offsets belonged to (drop_clock; the device is idle)
+void sb_episode_starts_forget(sb_handle *h);
 
 // generators.hip: the convection shuffle between the sweep and the reward (sb_step)
 int sb_launch_convection(sb_handle *h, hipStream_t stream);

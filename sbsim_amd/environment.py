@@ -370,6 +370,7 @@ class BatchedSimulator:
     self._building_materials = None   # set_building_materials: the rows in force (None: the plan's own values)
     self._clock_offsets = None   # clock_attach: the buildings' offsets into the timeline (None: one clock for the batch)
     self._calendars = None   # clock_attach(calendar_of=...): hashes of the concatenated rows and of calendar_of
+    self._episode_starts = None   # episode_starts_attach: the host_inputs.EpisodeStarts in force
     self._spatial = (False, None)   # spatial_attach: (attached, the map's shape or None); configuration, not state
     self._initial_conditions = None   # initial_conditions_attach: the host_inputs.InitialConditions in force
     self._randomization = None   # randomization_attach: the host_inputs.EpisodeRandomization in force
@@ -703,6 +704,8 @@ class BatchedSimulator:
     if rc in (-1, -4):   # SB_ERR_INVALID, SB_ERR_TOO_LARGE
       raise ValueError((self._lib.sb_last_error() or b"").decode())
     _ffi.check(rc, "sb_clock_attach")
+    if self._clock_offsets is not None:   # (a new table: the library drops the starts with the clock it replaces)
+      self._episode_starts = None
     self._clock_offsets = offsets.copy()
     self._calendars = None if calendar_of is None else (_sha(rows), _sha(np.ascontiguousarray(calendar_of, dtype=np.int32)))
 
@@ -717,6 +720,8 @@ class BatchedSimulator:
   def clock_detach(self) -> None:
     with torch.cuda.device(self.device):
       _ffi.check(_ffi.clock_entry("sb_clock_detach")(self._h), "sb_clock_detach")
+    if self._clock_offsets is not None:   # (the library drops the starts with the clock)
+      self._episode_starts = None
     self._clock_offsets = self._calendars = None
 
   def observe_step_in(self, step_in: _ffi.StepIn, out: torch.Tensor) -> torch.Tensor:
@@ -1084,6 +1089,80 @@ class BatchedSimulator:
       raise ValueError((self._lib.sb_last_error() or b"").decode())
     _ffi.check(rc, "sb_randomization_episodes_set")
 
+  # ---- a start time and weather per building, drawn per episode (sb_episode_starts_attach) ----
+  def _starts_call(self, name: str, *args) -> None:
+    with torch.cuda.device(self.device):
+      rc = _ffi.episode_starts_entry(name)(self._h, *args)
+    if rc in (-1, -5):   # SB_ERR_INVALID, SB_ERR_UNSUPPORTED
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, name)
+
+  def episode_starts_attach(self, es: host_inputs.EpisodeStarts, weather_lohi: Optional[torch.Tensor] = None,
+                            weather_offset: Optional[torch.Tensor] = None) -> None:
+    """sb_episode_starts_attach: from now on every reset of a building -- ``reset``, ``reset_buildings``, the autoreset --
+    first writes ``es.values(b, e, base_offsets)`` into the building's clock offset and its entries of the two weather
+    arrays, e the building's own episode number: 0 now, incremented by every reset of the building.  ``weather_lohi``
+    (float64 [B, 2]) / ``weather_offset`` (float64 [B]): the device tensors passed in every StepIn, which the library
+    writes in place; the caller keeps them alive.  Offsets need a clock (``clock_attach`` first).  The call synchronises
+    the device, not under stream capture."""
+    if not isinstance(es, host_inputs.EpisodeStarts):
+      raise ValueError("episode_starts_attach needs a host_inputs.EpisodeStarts (episode_starts_detach clears it)")
+    if torch.cuda.is_current_stream_capturing():   # (the library's hipDeviceSynchronize would refuse, and invalidate the capture)
+      raise ValueError("episode_starts_attach: not while the stream is being captured into a graph (the call synchronises the device)")
+    for name, t, shape in (("weather_lohi", weather_lohi, (self.B, 2)), ("weather_offset", weather_offset, (self.B,))):
+      if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != shape
+                            or t.device != self.tdev or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous float64 {list(shape)} tensor on {self.tdev}")
+    desc, keep = es.c_desc(0 if weather_lohi is None else weather_lohi.data_ptr(),
+                           0 if weather_offset is None else weather_offset.data_ptr())
+    self._starts_call("sb_episode_starts_attach", C.byref(desc))
+    del keep
+    self._episode_starts = es
+
+  def episode_starts_detach(self) -> None:
+    """sb_episode_starts_detach: from its next reset on, every building is back on its attached offset and the weather
+    entries of the attach, bit for bit; the episode in progress finishes where it is."""
+    self._starts_call("sb_episode_starts_detach")
+    self._episode_starts = None
+
+  @property
+  def episode_starts(self) -> Optional[host_inputs.EpisodeStarts]:
+    return self._episode_starts
+
+  def episode_start_episodes(self) -> torch.Tensor:
+    """sb_episode_starts_episodes_get: int32 [B] on the device, the number of every building's NEXT episode (this
+    feature's own counter).  Snapshots carry neither the values nor the counters: a checkpoint keeps the counters with
+    this pair."""
+    out = torch.empty((self.B,), dtype=torch.int32, device=self.tdev)
+    self._starts_call("sb_episode_starts_episodes_get", C.c_void_p(out.data_ptr()), self._stream())
+    return out
+
+  def set_episode_start_episodes(self, t: torch.Tensor) -> None:
+    """sb_episode_starts_episodes_set: the counters <- t (int32 [B] on the device, contiguous), and the values in force
+    <- ``values(b, t[b] - 1)`` (the attached values where t[b] == 0)."""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (self.B,) or t.device != self.tdev
+        or not t.is_contiguous()):
+      raise ValueError(f"the episode numbers must be a contiguous int32 [{self.B}] tensor on {self.tdev}")
+    self._starts_call("sb_episode_starts_episodes_set", C.c_void_p(t.data_ptr()), self._stream())
+
+  def clock_offsets_in_force(self) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sb_episode_starts_values_get: (offsets, effective offsets), int32 [B] each, stream-ordered copies -- the buildings'
+    attached offsets as the last draw or ``clock_set_offsets`` left them, and what the kernels index (offset minus the
+    building's restart position)."""
+    offs = torch.empty((self.B,), dtype=torch.int32, device=self.tdev)
+    eff = torch.empty_like(offs)
+    self._starts_call("sb_episode_starts_values_get", C.c_void_p(offs.data_ptr()), C.c_void_p(eff.data_ptr()), self._stream())
+    return offs, eff
+
+  def clock_set_offsets(self, offsets: np.ndarray) -> None:
+    """sb_clock_set_offsets: new attached offsets (int32 [B], inside the table), each taken by its building at its next
+    reset; the episodes in progress keep their rows.  Refused while attached episode starts draw the offsets."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    if offsets.shape != (self.B,):
+      raise ValueError(f"clock_set_offsets needs offsets [{self.B}]")
+    self._starts_call("sb_clock_set_offsets", offsets.ctypes.data_as(C.c_void_p), self._stream())
+    self._clock_offsets = offsets.copy()
+
   # ---- state snapshots (sb_state_save / sb_state_load) ----
   def state_fingerprint(self) -> Tuple:
     """What a SimState of this simulator means: plan shape and zones, a hash of the compiled plan tables (in the
@@ -1117,6 +1196,8 @@ class BatchedSimulator:
       fp += (("initial_conditions", self._initial_conditions.digest()),)
     if self._randomization is not None:   # (likewise; the rows and the counters are not in a snapshot)
       fp += (("episode_randomization", self._randomization.digest()),)
+    if self._episode_starts is not None:   # (likewise; the values and the counters are not in a snapshot)
+      fp += (("episode_starts", self._episode_starts.digest()),)
     return fp
 
   def save_state(self, rows: Optional[torch.Tensor] = None) -> SimState:
@@ -1370,8 +1451,15 @@ class BatchedEnvironment:
                calendars: Optional[Sequence[host_inputs.Calendar]] = None, calendar_of=None,
                spatial: Optional[host_inputs.SpatialOutputs] = None,
                initial_conditions: Optional[host_inputs.InitialConditions] = None,
-               episode_randomization: Optional[host_inputs.EpisodeRandomization] = None):
-    """``episode_randomization``: a ``host_inputs.EpisodeRandomization`` -- per-building parameters and materials drawn
+               episode_randomization: Optional[host_inputs.EpisodeRandomization] = None,
+               episode_starts: Optional[host_inputs.EpisodeStarts] = None, max_start_offset: Optional[int] = None):
+    """``max_start_offset``: the largest row ``set_start_offsets`` may move a building to; the timeline is built to hold
+    an episode that starts there (and the environment runs on the device clock).  None: the largest of ``start_offsets``.
+    ``episode_starts``: a ``host_inputs.EpisodeStarts`` -- a start time (a row of the timeline) and weather per
+    building, drawn anew at every reset of a building, on the device (``set_episode_starts`` between
+    episodes, ``episode_start_values()`` the values in force).  Such an environment always runs on the device clock.
+    None (the default): nothing of this is built or launched.
+    ``episode_randomization``: a ``host_inputs.EpisodeRandomization`` -- per-building parameters and materials drawn
     anew at every reset of a building, on the device (``set_episode_randomization`` between episodes,
     ``randomized_values()`` the values in force).  None (the default): nothing of this is built or launched.
     ``initial_conditions``: a ``host_inputs.InitialConditions`` -- start temperatures per building (recorded grids,
@@ -1460,6 +1548,15 @@ class BatchedEnvironment:
           int(n_buildings), host_inputs.effective_building_params(building_params, self.config, int(n_buildings)),
           None if building_materials is None else host_inputs.effective_building_materials(
               building_materials, plan.material_slots()[1], h_conv, int(n_buildings)), solver)
+    if max_start_offset is not None and (isinstance(max_start_offset, bool) or not isinstance(max_start_offset, (int, np.integer))
+                                         or not 0 <= max_start_offset <= (1 << 22)):
+      raise ValueError(f"max_start_offset must be an integer >= 0 (and at most 2^22), got {max_start_offset!r}")
+    if episode_starts is not None:   # (likewise)
+      if not isinstance(episode_starts, host_inputs.EpisodeStarts):
+        raise ValueError("episode_starts must be a host_inputs.EpisodeStarts (or None)")
+      episode_starts.check(int(n_buildings), self.weather, calendars)
+      if start_offsets is not None and calendars is None:
+        start_offsets = host_inputs.check_start_offsets(start_offsets, int(n_buildings))
     self.sim = BatchedSimulator(plan, self.config, n_buildings, h_conv, device,
                                 observation_normalization,
                                 histogram_parameters=observation_histogram_parameters,
@@ -1505,21 +1602,29 @@ class BatchedEnvironment:
     # environment.py:427-435
     self._num_timesteps_in_episode = int(dt.timedelta(days=num_days_in_episode) / self._step_interval)
     self.start_offsets = self.timeline = self._cursor = None
+    self._offsets_moved = False   # drawn starts or set_start_offsets: the offsets in force are the device's from then on
     if self.calendars is not None:   # several calendars: their row tables one after the other, always on the clock path
       self.timeline = host_inputs.CalendarTimeline(self.calendars, self.calendar_of, self._models(), self._start_timestamp,
                                                    start_offsets, self._num_timesteps_in_episode)
       self.start_offsets = self.timeline.start_offsets
       self.sim.clock_attach(self.timeline.rows, self.timeline.offsets, calendar_of=self.calendar_of)
       self._cursor = host_inputs.ClockCursor()
-    elif start_offsets is not None:   # a calendar per building: the table of instants, built once, and the offsets into it
-      self.start_offsets = host_inputs.check_start_offsets(start_offsets, self.batch_size)
-      self.timeline = host_inputs.Timeline(self._models(), self._start_timestamp, self.start_offsets,
-                                           self._num_timesteps_in_episode)
-      self.sim.clock_attach(self.timeline.rows, self.start_offsets)
+    elif start_offsets is not None or episode_starts is not None or max_start_offset is not None:
+      # a calendar per building: the table of instants, built once, and the offsets into it (episode_starts: all zero
+      # without start_offsets, the table sized for the largest draw)
+      self.start_offsets = (None if start_offsets is None
+                            else host_inputs.check_start_offsets(start_offsets, self.batch_size))
+      offsets = np.zeros(self.batch_size, dtype=np.int32) if self.start_offsets is None else self.start_offsets
+      self.timeline = host_inputs.Timeline(self._models(), self._start_timestamp, offsets,
+                                           self._num_timesteps_in_episode, episode_starts=episode_starts,
+                                           max_offset=max_start_offset)
+      self.sim.clock_attach(self.timeline.rows, offsets)
       self._cursor = host_inputs.ClockCursor()
     self.episode_steps = self.final_observation = None
     if self.per_building_episodes:
       self._setup_episodes(episode_steps)
+    if episode_starts is not None:
+      self._attach_starts(episode_starts)
     self._action_spec = ArraySpec((self.sim.n_actions,), np.dtype(np.float32), "action", -1.0, 1.0)
     self._observation_spec = ArraySpec((self.sim.O,), np.dtype(np.float32), "observation")
     self.field_names = self.sim.field_names
@@ -1578,6 +1683,11 @@ class BatchedEnvironment:
       pos = (self._cursor.positions() if self.per_building_episodes
              else np.full(self.batch_size, int(round((self._now - self._start_timestamp) / self._step_interval))))
       return [self.timeline.instant(b, int(pos[b])) for b in range(self.batch_size)]
+    if self._offsets_moved:   # drawn, or given by set_start_offsets for the next reset: those in force live on the device
+      # (the effective offset: the episode's own offset minus the building's restart position; a building keeps it
+      # until its next reset, whatever set_start_offsets has given it for then)
+      eff = self.sim.clock_offsets_in_force()[1].cpu().numpy().astype(np.int64)
+      return [self._start_timestamp + int(r) * self._step_interval for r in eff + self._cursor.pos]
     if self.per_building_episodes:   # every building's own episode position on its own calendar
       offs = np.zeros(self.batch_size, dtype=np.int64) if self.start_offsets is None else self.start_offsets
       return [self._start_timestamp + int(r) * self._step_interval for r in self._cursor.rows(offs)["now"]]
@@ -1850,6 +1960,108 @@ class BatchedEnvironment:
   def episode_randomization(self) -> Optional[host_inputs.EpisodeRandomization]:
     return self.sim.randomization
 
+  # ---- a start time and weather per building ----
+  def _attach_starts(self, es: host_inputs.EpisodeStarts) -> None:
+    self.sim.episode_starts_attach(es, self._weather_lohi, None if self._weather_replay is None else self._weather_replay[2])
+    self._offsets_moved = self._offsets_moved or es.has_offsets
+
+  def set_episode_starts(self, episode_starts: Optional[host_inputs.EpisodeStarts]) -> None:
+    """The starts of the resets from now on (between episodes; None: every building returns to its attached offset and
+    the weather of the attach at its next reset, and stays).  New starts begin every building's episode count at 0 and
+    inherit the attached values.  The timeline was built by the constructor: an environment created without
+    ``episode_starts`` has none that is sized for draws, and new starts must fit the table there is (ValueError)."""
+    if episode_starts is None:
+      self.sim.episode_starts_detach()
+      return
+    if not isinstance(episode_starts, host_inputs.EpisodeStarts):
+      raise ValueError("episode_starts must be a host_inputs.EpisodeStarts (or None)")
+    episode_starts.check(self.batch_size, self.weather, self.calendars)
+    if self._cursor is None:
+      raise ValueError("set_episode_starts: this environment was created without a device clock; create it with "
+                       "episode_starts=... (or start_offsets / per_building_episodes)")
+    # the constructor's checks on the table there is: its size, and a replay trace over the worst draw
+    if self.calendars is None:   # (with calendars no offset is drawn, ``check`` above, and the table is not a Timeline)
+      self.timeline.check_starts(episode_starts, self.weather, self.start_offsets)
+    self._attach_starts(episode_starts)
+
+  @property
+  def episode_starts(self) -> Optional[host_inputs.EpisodeStarts]:
+    return self.sim.episode_starts
+
+  def episode_start_values(self) -> Dict[str, torch.Tensor]:
+    """The values in force, on the device: "offsets" -> int32 [B] (every building's attached offset, drawn or not; on
+    an environment with a device clock), and with the matching weather class "weather_low" / "weather_high" /
+    "weather_shift" -> float64 [B].  Copies, ordered on the current stream."""
+    out: Dict[str, torch.Tensor] = {}
+    if self._cursor is not None:
+      out["offsets"] = self.sim.clock_offsets_in_force()[0]
+    if self._weather_lohi is not None:
+      out["weather_low"], out["weather_high"] = self._weather_lohi[:, 0].clone(), self._weather_lohi[:, 1].clone()
+    if self._weather_replay is not None:
+      out["weather_shift"] = self._weather_replay[2].clone()
+    return out
+
+  def _refuse_owned(self, what: str, *fields: str) -> None:
+    es = self.sim.episode_starts
+    owned = [] if es is None else [f for f in fields if f in es.fields]
+    if owned:
+      raise ValueError(f"{what}: the attached episode_starts draw {owned[0]} (set_episode_starts(None) first)")
+
+  def set_start_offsets(self, start_offsets) -> None:
+    """The host route to a new start time: integer rows [B] (>= 0, inside the timeline), building b's from its next
+    reset on; the episodes in progress keep their rows.  ValueError on an environment without a device clock, and while
+    attached ``episode_starts`` draw the offsets."""
+    self._refuse_owned("set_start_offsets", "offsets")
+    if self._cursor is None or self.calendars is not None:
+      raise ValueError("set_start_offsets needs an environment with one timeline on the device clock (start_offsets, "
+                       "per_building_episodes or episode_starts; not calendars)")
+    offs = host_inputs.check_start_offsets(start_offsets, self.batch_size)
+    self.sim.clock_set_offsets(offs)
+    self.start_offsets = offs   # (the attached offsets; ``current_simulation_timestamps`` asks the device for those in force)
+    self._offsets_moved = True
+
+  def set_weather(self, low_temps=None, high_temps=None, offsets_sec=None) -> None:
+    """The host route to new weather per building, from the next step on: ``low_temps`` / ``high_temps`` (float [B]
+    each, either may be left out) of a ``BatchedSinusoidWeather``, ``offsets_sec`` of a ``BatchedReplayWeather``.  The
+    host model and the device array both take the values.  ValueError for the wrong weather class, low > high, values
+    that are not finite, and while attached ``episode_starts`` draw that field.  (After ``set_episode_starts(None)`` a
+    building's next reset still writes the weather of the attach: call this once every building has been reset.)"""
+    def arr(name, a):
+      a = np.ascontiguousarray(a, dtype=np.float64)
+      if a.shape != (self.batch_size,):
+        raise ValueError(f"{name} must have shape [{self.batch_size}], got {a.shape}")
+      if not np.isfinite(a).all():
+        raise ValueError(f"{name}: building {int(np.argmin(np.isfinite(a)))} is not finite")
+      return a
+    if offsets_sec is not None:
+      if self._weather_replay is None or low_temps is not None or high_temps is not None:
+        raise ValueError("set_weather(offsets_sec=...) needs weather=BatchedReplayWeather(...), and no low_temps / high_temps")
+      self._refuse_owned("set_weather", "weather_shift")
+      a = arr("offsets_sec", offsets_sec)
+      self.weather.offsets_sec = a
+      self._weather_replay[2].copy_(torch.from_numpy(a))
+      return
+    if self._weather_lohi is None or (low_temps is None and high_temps is None):
+      raise ValueError("set_weather(low_temps=..., high_temps=...) needs weather=BatchedSinusoidWeather(...)")
+    self._refuse_owned("set_weather", *(f for f, v in (("weather_low", low_temps), ("weather_high", high_temps)) if v is not None))
+    low = self.weather.low if low_temps is None else arr("low_temps", low_temps)
+    high = self.weather.high if high_temps is None else arr("high_temps", high_temps)
+    lo_now, hi_now = low, high
+    es = self.sim.episode_starts
+    if es is not None and (low_temps is None or high_temps is None) and {"weather_low", "weather_high"} & set(es.fields):
+      # the other value in force may be a drawn one, which only the device has (a copy that waits for the stream; with
+      # both values given, or nothing drawn, the host model answers)
+      column = 1 if high_temps is None else 0
+      other = self._weather_lohi[:, column].cpu().numpy()
+      lo_now, hi_now = (low, other) if column == 1 else (other, high)
+    if (lo_now > hi_now).any():
+      raise ValueError(f"set_weather: building {int(np.argmax(lo_now > hi_now))}: low above high")
+    self.weather.low, self.weather.high = low, high
+    if low_temps is not None:
+      self._weather_lohi[:, 0].copy_(torch.from_numpy(low))
+    if high_temps is not None:
+      self._weather_lohi[:, 1].copy_(torch.from_numpy(high))
+
   def randomized_values(self) -> Dict[str, torch.Tensor]:
     """The values in force of the randomised fields, on the device (e.g. as privileged input of a critic): SimConfig
     field -> float64 [B] ([B, 2] for a window), material kind -> [B, M], "convection_coefficient" -> [B].  Copies,
@@ -2068,6 +2280,8 @@ class MixedBatchedEnvironment:
     if env_kwargs.get("calendars") is not None or env_kwargs.get("calendar_of") is not None:
       raise ValueError("calendars is not implemented for MixedBatchedEnvironment: calendar_of indexes the buildings of one "
                        "BatchedEnvironment, and the classes of a mixed batch are block-partitioned over classes and ranks")
+    if env_kwargs.get("episode_starts") is not None:
+      raise ValueError("episode_starts is not implemented for MixedBatchedEnvironment (its classes share one simulator clock)")
     if isinstance(env_kwargs.get("convection_simulator"), host_inputs.SeededStochasticConvectionSimulator):
       raise ValueError("SeededStochasticConvectionSimulator is not implemented for MixedBatchedEnvironment (its seeds belong "
                        "to the buildings of one BatchedEnvironment); use host_inputs.StochasticConvectionSimulator")

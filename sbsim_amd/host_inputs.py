@@ -798,37 +798,92 @@ class Timeline:
   instant per query; ``BatchedRandomizedArrivalDepartureOccupancy``, the device generator, is the supported form), and a
   replay weather whose trace ends before the latest building's episode does -- the message names that building."""
 
-  def __init__(self, models: StepModels, start_timestamp, offsets, steps_per_episode: int):
+  def __init__(self, models: StepModels, start_timestamp, offsets, steps_per_episode: int, episode_starts=None,
+               max_offset: Optional[int] = None):
+    """``max_offset``: the table also holds an episode that starts at this row (``BatchedEnvironment.set_start_offsets``).
+    ``episode_starts``: an ``EpisodeStarts`` -- the table is sized for the largest offset a building may draw (with
+    ``relative``: its own offset plus the largest draw), and a replay weather's trace is checked over the worst possible
+    draw of offset and shift."""
     m = models
     self.offsets = check_start_offsets(offsets, len(np.atleast_1d(np.asarray(offsets))))
     self.start = as_datetime(start_timestamp)
     self.step_interval = m.step_interval
-    self.n_rows = int(self.offsets.max()) + int(steps_per_episode) + 2
+    self.episode_starts = episode_starts
+    self._span = int(steps_per_episode) + 1   # rows an episode reads beyond its first
+    top = int(self.offsets.max()) if episode_starts is None else int(episode_starts.largest_offsets(self.offsets).max())
+    if max_offset is not None:
+      if isinstance(max_offset, bool) or not isinstance(max_offset, (int, np.integer)) or max_offset < 0:
+        raise ValueError(f"max_start_offset must be an integer >= 0, got {max_offset!r}")
+      top = max(top, int(max_offset))
+    self.n_rows = top + int(steps_per_episode) + 2
     if self.n_rows > (1 << 22):
-      raise ValueError(f"start_offsets: the timeline would have {self.n_rows} rows, more than 2^22")
+      raise ValueError(("start_offsets" if episode_starts is None else "offsets")
+                       + f": the timeline would have {self.n_rows} rows, more than 2^22")
     if (isinstance(m.occupancy, RandomizedArrivalDepartureOccupancy)
         and not isinstance(m.occupancy, BatchedRandomizedArrivalDepartureOccupancy)):
       raise ValueError("start_offsets: a host-side RandomizedArrivalDepartureOccupancy is one stateful instance queried at "
                        "one instant per step; use BatchedRandomizedArrivalDepartureOccupancy (the device generator)")
     if isinstance(m.weather, ReplayWeatherController):
       self._check_trace(m.weather)
+    if episode_starts is not None and isinstance(m.weather, BatchedReplayWeather):
+      # (the rows hold the query time alone; which rows and shifts a building can reach was checked just above)
+      w0 = copy.copy(m.weather)
+      w0.offsets_sec = np.zeros(1)
+      m = m._replace(weather=w0)
     self.rows = np.array([instant_row(m, self.instant(r)) for r in range(self.n_rows)], dtype=np.float64)
     self.rows.setflags(write=False)
 
   def instant(self, row: int) -> dt.datetime:
     return self.start + row * self.step_interval
 
-  def _check_trace(self, weather) -> None:
-    """Every building's last query (the row after its terminal step, plus its own replay offset) inside the trace."""
+  def check_starts(self, es, weather, base_offsets=None) -> None:
+    """New starts on the table there is (``BatchedEnvironment.set_episode_starts``): the largest offset ``es`` may draw
+    over ``base_offsets`` (None: the offsets of the constructor) leaves an episode's rows, and a replay weather's trace
+    holds the worst possible draw of offset and shift -- what the constructor checks for its own ``episode_starts``.
+    ValueError naming the building and the draw."""
+    base = self.offsets if base_offsets is None else check_start_offsets(base_offsets, len(self.offsets))
+    top = es.largest_offsets(base)
+    b = int(np.argmax(top))
+    if int(top[b]) + self._span + 1 > self.n_rows:
+      raise ValueError(f"offsets: building {b}: an episode that starts at the largest possible offset {int(top[b])} needs "
+                       f"{int(top[b]) + self._span + 1} rows, the timeline has {self.n_rows} (create the environment with "
+                       "these episode_starts, or with max_start_offset)")
+    if isinstance(weather, ReplayWeatherController):
+      self._check_trace(weather, es, base)
+
+  def _check_trace(self, weather, es=None, offsets=None) -> None:
+    """Every building's last query (the row after its terminal step, plus its own replay offset) inside the trace.
+    ``es`` / ``offsets``: these starts over these attached offsets (None: the constructor's)."""
     if self.start.tzinfo is None:
       raise TypeError("ReplayWeatherController needs a tz-aware timestamp (reference: tz_convert)")
     shift = getattr(weather, "offsets_sec", None)
     if shift is not None and shift.shape != self.offsets.shape:
       raise ValueError("BatchedReplayWeather needs one offset per building")
+    t_min, t_max = float(weather._times.min()), float(weather._times.max())
+    es = self.episode_starts if es is None else es
+    if es is not None:   # the worst possible draw of offset and shift, per building
+      offsets = self.offsets if offsets is None else offsets
+      hi_off, lo_off = es.largest_offsets(offsets), es.smallest_offsets(offsets)
+      base = np.zeros(self.offsets.shape) if shift is None else shift
+      s_lo, s_hi = es.fields["weather_shift"].span() if "weather_shift" in es.fields else (None, None)
+      hi_shift = base if s_hi is None else np.maximum(base, s_hi)
+      lo_shift = base if s_lo is None else np.minimum(base, s_lo)
+      dt_sec = self.step_interval.total_seconds()
+      last = self.start.timestamp() + (hi_off + self._span) * dt_sec + hi_shift
+      first = self.start.timestamp() + lo_off * dt_sec + lo_shift
+      if (last > t_max).any():
+        b = int(np.argmax(last))
+        raise ValueError(f"episode_starts: building {b}: with offset {int(hi_off[b])} and weather shift {float(hi_shift[b])} s "
+                         f"drawn, its episode ends at {dt.datetime.fromtimestamp(float(last[b]), tz=UTC)}, after the weather "
+                         f"trace's last time stamp {dt.datetime.fromtimestamp(t_max, tz=UTC)}")
+      if (first < t_min).any():
+        b = int(np.argmin(first))
+        raise ValueError(f"episode_starts: building {b}: with offset {int(lo_off[b])} and weather shift {float(lo_shift[b])} s "
+                         "drawn, its episode starts before the weather trace's first time stamp")
+      return
     last_row = self.offsets.astype(np.int64) + (self.n_rows - 1 - int(self.offsets.max()))
     last = self.start.timestamp() + last_row * self.step_interval.total_seconds() + (0.0 if shift is None else shift)
     first = self.start.timestamp() + self.offsets * self.step_interval.total_seconds() + (0.0 if shift is None else shift)
-    t_min, t_max = float(weather._times.min()), float(weather._times.max())
     if (last > t_max).any():
       b = int(np.argmax(last))
       raise ValueError(f"start_offsets: building {b}: its episode ends at "
@@ -1894,3 +1949,241 @@ class EpisodeRandomization:
     rows = sorted((f.param is None, f.param, f.material, f.choice, f.scale, f.lo.hex(), f.hi.hex(),
                    tuple(v.hex() for v in f.values)) for f in self.fields)
     return hashlib.sha256(repr((rows, self.seed, self.first_building)).encode()).hexdigest()
+
+
+# ---------------------------------------------------------------- a start time and weather per building drawn per episode
+EPISODE_STARTS_TAG = 0xE5A70000   # SB_EPISODE_STARTS_TAG (include/sbsim_amd.h): the draws' last counter word is this | id
+START_MAX_K = 1 << 22             # SB_START_MAX_K
+START_FIELDS = ("offsets", "weather_low", "weather_high", "weather_shift")   # sb_start_field_id, in order
+
+
+class UniformInt:
+  """d = lo + step * ((c0 * K) >> 32), K = (hi - lo) // step + 1, c0 the first word of the field's Philox block: one of
+  the K <= 2^22 whole numbers lo, lo + step, ... <= hi, integer arithmetic only (``EpisodeStarts(offsets=...)``)."""
+
+  def __init__(self, lo, hi, step=1):
+    self.lo, self.hi, self.step = lo, hi, step
+
+  def __repr__(self) -> str:
+    return f"UniformInt({self.lo!r}, {self.hi!r}, step={self.step!r})"
+
+
+class _StartField(NamedTuple):
+  kind: int                    # 0 Uniform, 1 Choice, 2 UniformInt (sb_rand_kind, SB_RAND_UNIFORM_INT)
+  lo: float
+  hi: float
+  step: int
+  values: Tuple[float, ...]
+
+  @property
+  def k(self) -> int:
+    return (int(self.hi) - int(self.lo)) // self.step + 1
+
+  def span(self) -> Tuple[float, float]:
+    """The smallest and the largest possible draw."""
+    if self.kind == 1:
+      return min(self.values), max(self.values)
+    if self.kind == 2:
+      return self.lo, float(int(self.lo) + self.step * (self.k - 1))
+    return self.lo, self.hi
+
+
+def _whole(v) -> bool:
+  if isinstance(v, (bool, np.bool_)):
+    return False
+  if isinstance(v, (int, np.integer)):
+    return True
+  return isinstance(v, (float, np.floating)) and math.isfinite(v) and float(v) == math.floor(v)
+
+
+def _start_field(name: str, dist, offset: bool) -> _StartField:
+  if isinstance(dist, UniformInt) and offset:
+    if not (_whole(dist.lo) and _whole(dist.hi)):
+      raise ValueError(f"{name}: UniformInt needs whole numbers of rows, got ({dist.lo!r}, {dist.hi!r})")
+    lo, hi = int(dist.lo), int(dist.hi)
+    if lo < 0:
+      raise ValueError(f"{name}: negative offset {lo}")
+    if lo > hi:
+      raise ValueError(f"{name}: lo {lo} > hi {hi}")
+    if not _whole(dist.step) or int(dist.step) < 1:
+      raise ValueError(f"{name}: step must be an integer >= 1, got {dist.step!r}")
+    if hi > (1 << 22):
+      raise ValueError(f"{name}: offset {hi} is beyond the 2^22 rows a timeline may have")
+    f = _StartField(2, float(lo), float(hi), int(dist.step), ())
+    if f.k > START_MAX_K:
+      raise ValueError(f"{name}: K == {f.k} is more than 2^22")
+    return f
+  if isinstance(dist, Choice):
+    if dist.scale:
+      raise ValueError(f"{name}: scale is not supported here" + (" (relative=True adds the draw to the attached offset)" if offset else ""))
+    try:
+      v = np.array(dist.values, dtype=np.float64)
+    except (TypeError, ValueError):
+      raise ValueError(f"{name}: Choice needs a list of numbers, got {dist.values!r}") from None
+    if v.ndim != 1:
+      raise ValueError(f"{name}: Choice needs a list of values, got shape {v.shape}")
+    if v.size == 0 or v.size > RAND_MAX_CHOICES:
+      raise ValueError(f"{name}: a Choice needs 1 .. 65,536 values, got K == {v.size}")
+    if not np.isfinite(v).all():
+      raise ValueError(f"{name}: choice {int(np.argmin(np.isfinite(v)))} is not finite")
+    if offset:
+      for j, x in enumerate(np.asarray(dist.values).tolist()):
+        if not _whole(x):
+          raise ValueError(f"{name}: choice {j} must be a whole number of rows, got {x!r}")
+        if x < 0:
+          raise ValueError(f"{name}: choice {j}: negative offset {x}")
+        if x > (1 << 22):
+          raise ValueError(f"{name}: choice {j}: offset {x} is beyond the 2^22 rows a timeline may have")
+    return _StartField(1, 0.0, 0.0, 1, tuple(float(x) for x in v))
+  if isinstance(dist, Uniform) and not offset:
+    if dist.scale:
+      raise ValueError(f"{name}: scale is not supported here")
+    try:
+      lo, hi = float(dist.lo), float(dist.hi)
+    except (TypeError, ValueError):
+      raise ValueError(f"{name}: Uniform needs one lo and one hi, got ({dist.lo!r}, {dist.hi!r})") from None
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+      raise ValueError(f"{name}: lo and hi must be finite, got ({lo}, {hi})")
+    if lo > hi:
+      raise ValueError(f"{name}: lo {lo} > hi {hi}")
+    return _StartField(0, lo, hi, 1, ())
+  raise ValueError(f"{name}: the distribution must be " + ("a UniformInt or a Choice of integer rows" if offset else "a Uniform or a Choice")
+                   + f", got {dist!r}")
+
+
+class EpisodeStarts:
+  """A start time and weather per building, drawn anew at every episode start, on the device (sb_episode_starts_attach;
+  INTEGRATION.md 4q): every reset of a building moves it to a new row of the timeline under new weather.
+
+      es = EpisodeStarts(offsets=UniformInt(0, 364 * 288, step=288),      # rows of the timeline (whole step intervals)
+                         weather_low=Uniform(268.0, 285.0), weather_high=Uniform(286.0, 305.0), seed=11)
+      env = BatchedEnvironment(plan, B, weather=BatchedSinusoidWeather(low, high), episode_steps=lengths, episode_starts=es)
+
+  ``offsets``: ``UniformInt`` or a ``Choice`` of integer rows; ``relative=True`` adds the draw to the building's attached
+  offset (``start_offsets``).  ``weather_low`` / ``weather_high``: ``Uniform`` / ``Choice``, ``BatchedSinusoidWeather``
+  only.  ``weather_shift``: likewise, ``BatchedReplayWeather``'s ``offsets_sec``.  A field left out stays what it is.
+  ``values`` states every field of building b in its episode e; a draw depends on (seed, global building, e, field)
+  alone.  ValueError, naming the field: offsets that are negative or no whole numbers, lo > hi, step < 1, K > 2^22, a
+  bound or choice that is not finite, no field at all, a seed outside uint64, first_building < 0; ``check`` adds what
+  needs the batch."""
+
+  def __init__(self, offsets=None, relative: bool = False, weather_low=None, weather_high=None, weather_shift=None,
+               seed: int = 0, first_building: int = 0):
+    given = dict(zip(START_FIELDS, (offsets, weather_low, weather_high, weather_shift)))
+    self.fields: Dict[str, _StartField] = {name: _start_field(name, dist, name == "offsets")
+                                           for name, dist in given.items() if dist is not None}
+    if not self.fields:
+      raise ValueError("EpisodeStarts needs at least one field (pass None instead of one to clear it)")
+    if "weather_low" in self.fields and "weather_high" in self.fields:
+      lo_max, hi_min = self.fields["weather_low"].span()[1], self.fields["weather_high"].span()[0]
+      if lo_max > hi_min:
+        raise ValueError(f"weather_low: low can be drawn as {lo_max}, above a high of {hi_min}")
+    if isinstance(seed, (bool, float)) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+      raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    if isinstance(first_building, (bool, float)) or int(first_building) != first_building or first_building < 0:
+      raise ValueError(f"first_building must be an integer >= 0, got {first_building!r}")
+    self.relative = bool(relative)
+    self.seed, self.first_building = int(seed), int(first_building)
+
+  @property
+  def has_offsets(self) -> bool:
+    return "offsets" in self.fields
+
+  def rows(self, lo: int, hi: int = None) -> "EpisodeStarts":
+    """The same starts for buildings lo .. of a larger batch: ``first_building`` moved so that they draw what they drew
+    in the whole batch."""
+    if lo < 0:
+      raise ValueError(f"rows: lo must be >= 0, got {lo}")
+    out = copy.copy(self)
+    out.first_building = self.first_building + int(lo)
+    return out
+
+  def draw(self, name: str, b: int, e: int):
+    """d of field ``name`` for building b in its episode number e (the formula of include/sbsim_amd.h, on Python integers
+    and IEEE doubles: one rounding per operation); an int for the offsets."""
+    f = self.fields[name]
+    gb = self.first_building + int(b)
+    c = _philox_block((gb & _M32, gb >> 32, int(e) & _M32, EPISODE_STARTS_TAG | START_FIELDS.index(name)),
+                      (self.seed & _M32, self.seed >> 32))
+    if f.kind == 2:
+      return int(f.lo) + f.step * ((c[0] * f.k) >> 32)
+    if f.kind == 1:
+      v = f.values[(c[0] * len(f.values)) >> 32]
+      return int(v) if name == "offsets" else v
+    r = (c[1] << 32) | c[0]
+    return f.lo + (f.hi - f.lo) * (float(r >> 11) * 2.0 ** -53)
+
+  def values(self, b: int, e: int, base_offsets=None) -> Dict[str, object]:
+    """The value of every drawn field of building b in its episode number e -- what the device writes: "offsets" -> int
+    (with ``relative``: ``base_offsets[b]`` + the draw; ``base_offsets`` None: zeros), the weather fields -> float."""
+    out: Dict[str, object] = {}
+    for name in self.fields:
+      d = self.draw(name, b, e)
+      if name == "offsets" and self.relative and base_offsets is not None:
+        d = int(np.asarray(base_offsets)[b]) + d
+      out[name] = d
+    return out
+
+  def largest_offsets(self, base_offsets) -> np.ndarray:
+    """int64 [B]: the largest offset building b may have while this is attached -- its attached offset, or the largest
+    possible draw (added to it with ``relative``)."""
+    base = np.asarray(base_offsets, dtype=np.int64)
+    if not self.has_offsets:
+      return base
+    top = int(self.fields["offsets"].span()[1])
+    return base + top if self.relative else np.maximum(base, top)
+
+  def smallest_offsets(self, base_offsets) -> np.ndarray:
+    base = np.asarray(base_offsets, dtype=np.int64)
+    if not self.has_offsets:
+      return base
+    low = int(self.fields["offsets"].span()[0])
+    return base + low if self.relative else np.minimum(base, low)
+
+  def check(self, n_buildings: int, weather, calendars=None) -> None:
+    """What needs the batch, as sb_episode_starts_attach checks it: weather fields need the matching per-building weather
+    class; a drawn low must not exceed the building's own high (and the other way round) where only one of the two is
+    drawn; ``calendars`` together with drawn offsets.  ValueError naming the field and, where it depends on one, the
+    building."""
+    if calendars is not None and self.has_offsets:
+      raise ValueError("offsets: episode_starts is not supported together with calendars (the calendars' tables lie one "
+                       "after the other: a drawn offset would walk from one into the next)")
+    for name in ("weather_low", "weather_high"):
+      if name in self.fields and not isinstance(weather, BatchedSinusoidWeather):
+        raise ValueError(f"{name}: needs weather=BatchedSinusoidWeather(...) (one (low, high) pair per building on the device)")
+    if "weather_shift" in self.fields and not isinstance(weather, BatchedReplayWeather):
+      raise ValueError("weather_shift: needs weather=BatchedReplayWeather(...) (one offset into the trace per building)")
+    if "weather_low" in self.fields and "weather_high" not in self.fields:
+      bad = self.fields["weather_low"].span()[1] > weather.high
+      if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError(f"weather_low: building {b}: low can be drawn as {self.fields['weather_low'].span()[1]}, above its high of {weather.high[b]}")
+    if "weather_high" in self.fields and "weather_low" not in self.fields:
+      bad = weather.low > self.fields["weather_high"].span()[0]
+      if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError(f"weather_high: building {b}: high can be drawn as {self.fields['weather_high'].span()[0]}, below its low of {weather.low[b]}")
+
+  def c_desc(self, weather_lohi_ptr: int = 0, weather_offset_ptr: int = 0):
+    """sb_episode_starts_attach's descriptor: the ctypes struct and what it points into."""
+    from . import _ffi
+    d = _ffi.EpisodeStartsDesc()
+    keep = []
+    for name, f in self.fields.items():
+      cf = d.field[START_FIELDS.index(name)]
+      cf.present, cf.kind, cf.step = 1, f.kind, f.step
+      if f.kind == 1:
+        v = np.ascontiguousarray(f.values, dtype=np.float64)
+        keep.append(v)
+        cf.n_choices, cf.choices = len(f.values), v.ctypes.data_as(_ffi._dp)
+      else:
+        cf.lo, cf.hi = f.lo, f.hi
+    d.relative = int(self.relative)
+    d.weather_lohi_dev, d.weather_offset_dev = weather_lohi_ptr or None, weather_offset_ptr or None
+    d.seed, d.first_building = self.seed, self.first_building
+    return d, keep
+
+  def digest(self) -> str:
+    """A hash of everything attached (``BatchedSimulator.state_fingerprint``)."""
+    rows = [(name, f.kind, f.lo.hex(), f.hi.hex(), f.step, tuple(v.hex() for v in f.values)) for name, f in sorted(self.fields.items())]
+    return hashlib.sha256(repr((rows, self.relative, self.seed, self.first_building)).encode()).hexdigest()
