@@ -261,7 +261,13 @@ int sb_observe_occupancy(sb_handle *h, const float aux[SB_NUM_AUX], double t_amb
  * carbon_cost (0), the three weights, person_productivity, total_occupancy, reward_scale (1),
  * reward_shift (0), productivity_regret, normalized productivity regret / energy cost / carbon}.
  * That is the default reward function (SB_REWARD_REGRET); sb_set_reward_function documents columns 7..23 under the
- * other one. */
+ * other one.
+ * Stated departure from the reference -- a damper command of exactly 0 (+0 or -0: a normalised -1 under a (0, 1)
+ * range, what a clipped policy emits).  The setter accepts it (vav.py:125-129) and the reference's step then dies on
+ * `assert self.damper_setting > 0` (vav.py:177).  Here the step goes on: a zone whose air flow is 0 gets q_zone = 0
+ * (the reference's own guard, vav.py:207-208), adds no air demand, and its zone supply temperature is the air
+ * handler's (no air passes the coil) -- that is what enters the boiler's return-water average; its reheat demand
+ * still counts.  Nothing non-finite is stored.  The oracle (oracle/sb_oracle.c) does the same. */
 int sb_step(sb_handle *h, const float *actions_dev, const sb_step_in *in, float *obs_dev,
             float *reward_dev, float *info_dev, void *stream);
 

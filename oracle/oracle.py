@@ -389,9 +389,11 @@ class OracleBuilding:
            e_price: float, e_carbon: float, g_price: float, g_carbon: float,
            action: Optional[Sequence[float]] = None, observe: bool = True, reject: bool = False,
            cool_sp: Optional[float] = None, damper_cmd: Optional[Sequence[float]] = None,
-           trace: bool = False) -> dict:
+           trace: bool = False, round_action: bool = True) -> dict:
     """One Environment._step (H2 ordering).  ``action`` = (boiler supply-water setpoint,
-    AHU heating setpoint) in native units as the proto would carry them (fp32).  ``trace``: the
+    AHU heating setpoint) in native units as the proto would carry them (fp32); ``round_action=False`` hands the
+    action, ``cool_sp`` included, to the step as the doubles they are (a caller that did the proto's rounding itself,
+    or that repeats a setpoint in force -- a double -- for a field the request leaves out).  ``trace``: the
     result also holds ``max_delta``, the max|delta| of every Gauss-Seidel sweep of the step (the
     values compared with the convergence threshold)."""
     Z = self.plan.Z
@@ -400,16 +402,17 @@ class OracleBuilding:
     si = _StepIn()
     si.now_ts = now_ts
     si.has_action = 0 if action is None else 1
+    proto = (lambda v: float(np.float32(v))) if round_action else float
     if action is not None:
-      si.blr_setpoint = float(np.float32(action[0]))
-      si.ahu_heat_sp = float(np.float32(action[1]))
+      si.blr_setpoint = proto(action[0])
+      si.ahu_heat_sp = proto(action[1])
     si.t_amb_now, si.h_conv, si.t_amb_next = t_amb_now, h_conv, t_amb_next
     si.comfort_now, si.comfort_prev, si.comfort_next = int(comfort_now), int(comfort_prev), int(comfort_next)
     si.occupancy = _d(occ)
     si.observe = int(observe)
     si.reject = int(reject)   # rejection_simulator_building.py:52-60
     if cool_sp is not None:
-      si.has_cool_sp, si.ahu_cool_sp = 1, float(np.float32(cool_sp))
+      si.has_cool_sp, si.ahu_cool_sp = 1, proto(cool_sp)
     if damper_cmd is not None:
       dc = np.ascontiguousarray(damper_cmd, dtype=np.float64)
       si.damper_cmd = _d(dc)
@@ -435,7 +438,8 @@ class OracleBuilding:
         norm_energy_cost=so.norm_energy_cost, norm_carbon=so.norm_carbon,
         ahu_flow=s.ahu_flow, ahu_count=s.ahu_count, blr_flow=s.blr_flow,
         blr_count=s.blr_count, blr_return_temp=s.blr_return_temp,
-        blr_tank_temp=s.blr_tank_temp, blr_setpoint=s.blr_setpoint,
+        blr_tank_temp=s.blr_tank_temp, blr_tank_change=s.blr_tank_change, blr_last_duration=s.blr_last_duration,
+        blr_setpoint=s.blr_setpoint,
         ahu_heat_sp=s.ahu_heat_sp, ahu_cool_sp=s.ahu_cool_sp,
         damper=self.damper.copy(), valve=self.valve.copy(), mode=self.mode.copy(),
         zone_air_temp=self.zone_air_temp.copy())

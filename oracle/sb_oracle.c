@@ -449,10 +449,15 @@ void sbo_step_trace(const sbo_plan *p, const sbo_params *prm, sbo_state *s, cons
     double tw = s->blr_setpoint;
     double reheat_flow = valve * prm->vav_max_water_flow;
     double air_flow = damper * prm->vav_max_air_flow;
-    double t_zs = sbo_dev_vav_supply_temp(t_sa, tw, air_flow, reheat_flow);
-    double qz;
-    if (damper == 0 || prm->vav_max_air_flow == 0) qz = 0;
-    else qz = sbo_dev_vav_energy(air_flow, t_zs, tz_pre[z]);
+    double t_zs, qz;
+    /* vav.py:207-208: no air, no power.  (The reference asserts damper > 0 before it gets there, vav.py:177; a
+     * command of exactly 0 is accepted by the setter, vav.py:125-129.)  No air passes the coil: the zone supply
+     * temperature that enters the return-water average is the air handler's. */
+    if (air_flow == 0) { t_zs = t_sa; qz = 0; }
+    else {
+      t_zs = sbo_dev_vav_supply_temp(t_sa, tw, air_flow, reheat_flow);
+      qz = sbo_dev_vav_energy(air_flow, t_zs, tz_pre[z]);
+    }
     tzs[z] = t_zs;
     if (air_flow > 0) { /* air_handler.py:254-268 */
       s->ahu_flow += air_flow;

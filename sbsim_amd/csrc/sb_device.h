@@ -658,7 +658,12 @@ __device__ inline void pre_building(const Dev &a, const StepArgs &s, int b, int 
     const double air = damper * vav_max_air_flow;
     const double heat_diff = kCAir * air - kCWater * reheat;     // vav.py:181-195
     const double water_heat = v.blr_sp * kCWater * reheat;
-    const double tzs = (v.t_sa * heat_diff + water_heat) / air / kCAir;
+    // A damper command of exactly 0 (normalised -1 under a (0, 1) range) is accepted, and the reference then dies on its
+    // assert (vav.py:177).  Here no air passes the coil: the zone supply temperature is t_sa, the power applied to the
+    // zone is 0 (the reference's own guard, vav.py:207-208) and nothing non-finite is formed -- the division is by 1.
+    const bool no_air = air == 0.0;
+    const double tzs_air = (v.t_sa * heat_diff + water_heat) / (no_air ? 1.0 : air) / kCAir;
+    const double tzs = no_air ? v.t_sa : tzs_air;
     if (on) {
       a.qz[zi] = air * kCAir * (tzs - tz);                       // vav.py:211-217
       a.zair[zi] = tz;

@@ -324,3 +324,70 @@ def test_action_vector_as_wide_as_the_building_has_setpoints():
         assert r[b] == ACTION_REJECTION_REWARD and abs(i_[b, 7] - o["reward"]) < 1e-6, (t, b)
   assert 0 < n_rejected < B * T          # the overshooting normaliser rejected some steps, not all
   sim.close()
+
+
+@pytest.mark.gpu
+def test_damper_commands_of_exactly_zero_keep_the_grid_finite():
+  """A normalised command of -1 under a (0, 1) range is a damper of exactly 0, which vav.py:125-129 accepts and vav.py:177
+  asserts on.  Stated departure (sb_step's header comment): such a zone gets no air -- q_zone = 0 (the reference's own
+  guard, vav.py:207-208), no air demand, the air handler's supply temperature in the return-water average -- and its
+  reheat demand still counts.  The 129-column test's plan; some dampers held at -1 for every step, against oracle twins
+  at the rollouts' tolerances, the sweep counts EQUAL and every stored value finite."""
+  torch = pytest.importorskip("torch")
+  if not torch.cuda.is_available():
+    pytest.skip("no GPU")
+  from oracle import oracle as orc   # checker only
+  from sbsim_amd.environment import BatchedSimulator, SimConfig
+  from sbsim_amd.floorplan import FloorPlan, Materials, rectangular_floor_plan
+  from tests.parity import step_buffers
+  from tests.twins import REWARD_TOL
+  plan = FloorPlan.from_file_input(rectangular_floor_plan((14, 9), (8, 7)), Materials.sb1(), 10.0, 300.0)
+  Z = len(plan.zone_cell_lists())
+  assert Z == 126
+  cfg = SimConfig.sb1()
+  cfg.action_names = ("supply_water_setpoint", "supply_air_heating_temperature_setpoint",
+                      "supply_air_cooling_temperature_setpoint") + ("supply_air_damper_percentage_command",) * Z
+  cfg.action_zones = (0, 0, 0) + tuple(range(Z - 1, -1, -1))
+  cfg.action_ranges = ((310.0, 355.0), (285.0, 295.0), (296.0, 305.0)) + ((0.0, 1.0),) * Z
+  g = load("h2_sb1_r9_random.npz")
+  B, T = 6, 5
+  sim = BatchedSimulator(plan, cfg, B, float(g["h_conv"]))
+  rs = np.random.RandomState(11)
+  H, W = plan.shape
+  init = np.clip(292.0 + 2.0 * rs.randn(B, 1) + np.zeros((B, H * W)), 285.0, 305.0)   # some buildings heat: valves open
+  sim.reset(temps=torch.tensor(init, dtype=torch.float64, device="cuda"))
+  oplan, oprm = oracle_plan_of(plan), oracle_params_of(cfg)
+  twins = [orc.OracleBuilding(oplan, oprm, 0.0, reset_temps=init[b]) for b in range(B)]
+  obs, rew, info = step_buffers(sim)
+  shut = rs.rand(B, Z) < 0.3            # these zones' dampers are held at 0; building 5: every one of them
+  shut[5] = True
+  shut[0] = False
+  n_heating_without_air = 0
+  for t in range(T):
+    norm = rs.uniform(-1, 1, size=(B, 3 + Z)).astype(np.float32)
+    for b in range(B):
+      for z in np.nonzero(shut[b])[0]:
+        norm[b, 3 + (Z - 1 - z)] = np.float32(-1.0)
+    sim.step(torch.tensor(norm, device="cuda"), step_in(g, t + 100), obs, rew, info)
+    i_ = info.cpu().numpy().astype(np.float64)
+    zt, r = sim.zone_temps().cpu().numpy(), rew.cpu().numpy()
+    dm = sim.zone_power().cpu().numpy()
+    sc = sim.scalars().cpu().numpy()
+    assert np.isfinite(dm).all() and np.isfinite(sc).all() and np.isfinite(i_).all() and np.isfinite(r).all(), t
+    assert np.isfinite(sim.temps().cpu().numpy()).all(), t
+    for b in range(B):
+      cmd = np.array([float(native_value(norm[b, 3 + (Z - 1 - z)], 0.0, 1.0)) for z in range(Z)])
+      assert (cmd[shut[b]] == 0.0).all()
+      o = twins[b].step(**step_kwargs(g, t + 100, t, cfg, norm[b, :2]), cool_sp=float(native_value(norm[b, 2], 296.0, 305.0)),
+                        damper_cmd=cmd)
+      assert o["action_accepted"] and i_[b, 4] == o["n_sweeps"], (t, b, i_[b, 4], o["n_sweeps"])
+      assert np.abs(zt[b] - o["zone_temp_post"]).max() < T_TOL, (t, b)
+      assert np.allclose(dm[b], o["q_zone"], rtol=1e-12, atol=1e-9) and not dm[b][shut[b]].any(), (t, b)
+      assert rates_match(i_[b, :4], np.array([o["blower_rate"], o["ac_rate"], o["gas_rate"], o["pump_rate"]], np.float64)), (t, b)
+      assert abs(float(r[b]) - o["reward"]) < REWARD_TOL, (t, b)
+      assert sc[b, 3] == o["ahu_count"] == int((~shut[b]).sum()) and sc[b, 6] == o["blr_count"], (t, b)
+      assert sc[b, 7] == pytest.approx(o["blr_return_temp"], rel=1e-12), (t, b)
+      n_heating_without_air += int(((o["valve"] == 1) & shut[b]).sum())
+  assert n_heating_without_air > 0      # the 0/0 of the unguarded formula: a shut damper on an open reheat valve
+  assert np.abs(sim.temps().cpu().numpy().reshape(B, -1) - np.stack([tw.temp for tw in twins])).max() < T_TOL
+  sim.close()
