@@ -218,14 +218,14 @@ SB_RANDOMIZATION_TAG = 0xE9150000        # include/sbsim_amd.h: the redraws' las
 SB_RAND_MATERIAL = 0x100                 # id of material field f: SB_RAND_MATERIAL + f
 SB_RAND_MAX_CHOICES = 65536
 SB_RAND_UNIFORM, SB_RAND_CHOICE = 0, 1   # sb_rand_kind
-SB_RAND_BLOCKS_PER_CU, SB_RAND_THREADS = 8, 256   # k_randomize's grid cap (randomize.hip): work beyond it takes the grid stride
+SB_RAND_BLOCKS_PER_CU, SB_RAND_THREADS = 8, 256   # the draw kernels' grid cap (sb_host.h: draw_blocks): work beyond it takes the grid stride
 EPISODE_STARTS_ENTRIES = ("sb_episode_starts_attach", "sb_episode_starts_detach", "sb_episode_starts_episodes_get",
                           "sb_episode_starts_episodes_set", "sb_episode_starts_values_get", "sb_clock_set_offsets")
 SB_EPISODE_STARTS_TAG = 0xE5A70000       # include/sbsim_amd.h: the starts' last counter word is this | sb_start_field_id
 SB_RAND_UNIFORM_INT = 2                  # sb_start_field's third kind
 SB_START_MAX_K = 1 << 22
 SB_START_OFFSET, SB_START_WEATHER_LOW, SB_START_WEATHER_HIGH, SB_START_WEATHER_SHIFT = range(4)   # sb_start_field_id
-SB_STARTS_BLOCKS_PER_CU, SB_STARTS_THREADS = 8, 256   # k_episode_starts' grid cap (episode_starts.hip)
+SB_STARTS_BLOCKS_PER_CU, SB_STARTS_THREADS = SB_RAND_BLOCKS_PER_CU, SB_RAND_THREADS   # k_episode_starts' grid: the same rule
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None

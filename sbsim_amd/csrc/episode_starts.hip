@@ -1,5 +1,5 @@
 // episode_starts.hip -- sb_episode_starts_attach: a start time and weather per building, drawn at every episode start, on
-// the device (include/sbsim_amd.h states the semantics; episode_starts.h the draw).  A reset of a handle with the
+// the device (include/sbsim_amd.h states the semantics; episode_draw.h the draw).  A reset of a handle with the
 // attachment launches k_episode_starts before its reset kernel: the drawn offset into the buffer the reset kernel reads
 // as the attached offsets, the weather values into the caller's arrays, the counter advanced, all by the one thread
 // that owns the building.
@@ -13,15 +13,12 @@
 #include <string>
 #include <vector>
 
-#include "episode_starts.h"
+#include "episode_draw.h"
 #include "sb_host.h"
 
 using namespace sb;
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kBlocksPerCu = 8; // the grid's cap, as randomize.hip's: beyond it the grid stride
 
 // StartField::present beyond 0 / 1: a field an earlier attachment drew and this one does not -- every reset writes its
 // base value, so the building returns to it at its next reset.
@@ -50,13 +47,13 @@ struct StartArgs {
 };
 
 // One thread per building, the building the fast index: a wavefront writes 64 neighbours of every array.
-__global__ void __launch_bounds__(kThreads) k_episode_starts(StartArgs a) {
+__global__ void __launch_bounds__(kDrawThreads) k_episode_starts(StartArgs a) {
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.B; b += gridDim.x * blockDim.x) {
     if (a.mask && !a.mask[b]) continue;
     int e = a.mode == kRestore ? 0 : a.episode[b];
-    const bool base = a.mode == kRestore || (a.mode == kMaterialise && e < 1);
+    const bool base = a.mode == kRestore || (a.mode == kMaterialise && before_first_episode(e));
     auto based = [&](int i) { return base || a.f[i].present == kPresentBase; };
-    if (a.mode == kMaterialise) e -= 1;
+    if (a.mode == kMaterialise) e = episode_in_force(e);
     const uint64_t gb = (uint64_t)(a.first + b);
     if (a.f[SB_START_OFFSET].present) {
       int off = a.base_offs[b];
@@ -78,7 +75,7 @@ __global__ void __launch_bounds__(kThreads) k_episode_starts(StartArgs a) {
                                        : start_draw(a.f[SB_START_WEATHER_HIGH], a.choices, a.seed, gb, (uint32_t)e);
     if (a.f[SB_START_WEATHER_SHIFT].present)
       a.shift[b] = based(SB_START_WEATHER_SHIFT) ? a.base_shift[b] : start_draw(a.f[SB_START_WEATHER_SHIFT], a.choices, a.seed, gb, (uint32_t)e);
-    if (a.mode == kDraw) a.episode[b] = (int)((unsigned)e + 1u);
+    if (a.mode == kDraw) a.episode[b] = next_episode(e);
   }
 }
 
@@ -93,37 +90,24 @@ int launch_starts(sb_handle *h, const uint8_t *mask, int mode, hipStream_t strea
   a.eff = h->clock_eff.p;
   a.lohi = h->es_lohi;
   a.shift = h->es_shift;
-  a.episode = h->es_episode.p;
+  a.episode = h->es_draws.episode.p;
   a.mask = mask;
-  a.seed = h->es_seed;
-  a.first = h->es_first;
+  a.seed = h->es_draws.seed;
+  a.first = h->es_draws.first;
   a.B = h->d.B;
   a.relative = h->es_relative;
   a.mode = mode;
-  const int B = h->d.B;
-  const int blocks = std::max(1, std::min((B + kThreads - 1) / kThreads, h->cus * kBlocksPerCu));
-  hipLaunchKernelGGL(k_episode_starts, dim3(blocks), dim3(kThreads), 0, stream, a);
+  hipLaunchKernelGGL(k_episode_starts, dim3(draw_blocks(h, (size_t)h->d.B)), dim3(kDrawThreads), 0, stream, a);
   SB_HIP(hipGetLastError());
   return SB_OK;
 }
 
 const char *const kFieldNames[SB_START_FIELDS] = {"offsets", "weather_low", "weather_high", "weather_shift"};
 
-// The device is idle on return; a capture in progress refuses the synchronisation.
-int idle_device(const std::string &who) {
-  if (const hipError_t e = hipDeviceSynchronize(); e != hipSuccess) {
-    const bool capturing = e == hipErrorStreamCaptureUnsupported || e == hipErrorStreamCaptureImplicit;
-    return fail(capturing ? SB_ERR_INVALID : SB_ERR_HIP, who + (capturing ? "not while a stream is being captured into a graph"
-                                                                          : hipGetErrorString(e)));
-  }
-  return SB_OK;
-}
+// An offset, bound or choice: a whole number of rows a timeline may have.
+bool whole_rows(double v) { return v >= 0.0 && v <= (double)SB_CLOCK_MAX_ROWS && v == std::floor(v); }
 
-template <typename Buf>
-void drop(Buf &buf) {
-  if (buf.p) (void)hipFree(buf.p);
-  buf.p = nullptr;
-}
+const char *const kNoStarts = "the handle has no episode starts (sb_episode_starts_attach)";
 
 // Largest offset building b may have while the attachment draws: the attached one, or the largest draw.
 int largest_offset(const sb_handle *h, int b, int max_draw, int relative) {
@@ -149,12 +133,12 @@ void sb_episode_starts_after_reset(sb_handle *h, const uint8_t *mask_host) {
     left = left || h->es_pending[b];
   }
   if (h->es_offsets) episode_bounds(h);
-  if (!left) h->es_attached = h->es_restoring = h->es_offsets = false; // (the buffers go with the next attach or the handle)
+  if (!left) h->es_draws.attached = h->es_restoring = h->es_offsets = false; // (the buffers go with the next attach or the handle)
 }
 
 void sb_episode_starts_forget(sb_handle *h) {
-  h->es_attached = h->es_restoring = h->es_offsets = false;
-  drop(h->es_choices); drop(h->es_episode); drop(h->es_base_offs); drop(h->es_base_lohi); drop(h->es_base_shift);
+  h->es_draws.attached = h->es_restoring = h->es_offsets = false;
+  drop(h->es_choices); drop(h->es_draws.episode); drop(h->es_base_offs); drop(h->es_base_lohi); drop(h->es_base_shift);
   h->es_h_base_offs.clear();
   h->es_pending.clear();
   h->es_lohi = h->es_shift = nullptr;
@@ -181,44 +165,18 @@ int sb_episode_starts_attach(sb_handle *h, const sb_episode_starts *es) {
     d.present = 1;
     d.d = RandField{i, 0, 0, f.kind, 0, 0, 0, 0, 0.0, 0.0};
     const bool offset = i == SB_START_OFFSET;
-    auto whole = [](double v) { return v >= 0.0 && v <= (double)SB_CLOCK_MAX_ROWS && v == std::floor(v); };
-    if (f.kind == SB_RAND_UNIFORM_INT && offset) {
-      if (!(std::isfinite(f.lo) && std::isfinite(f.hi))) return fail(SB_ERR_INVALID, who + name + ": lo and hi must be finite");
-      if (f.lo > f.hi) return fail(SB_ERR_INVALID, who + name + ": lo " + std::to_string(f.lo) + " > hi " + std::to_string(f.hi));
-      if (!whole(f.lo) || !whole(f.hi))
-        return fail(SB_ERR_INVALID, who + name + ": lo and hi must be whole numbers of rows in 0 .. 2^22");
-      if (f.step < 1) return fail(SB_ERR_INVALID, who + name + ": step must be >= 1, got " + std::to_string(f.step));
-      const long long k = ((long long)f.hi - (long long)f.lo) / f.step + 1;
-      if (k > SB_START_MAX_K) return fail(SB_ERR_INVALID, who + name + ": K = " + std::to_string(k) + " is more than 2^22");
-      d.ilo = (int)f.lo;
-      d.step = f.step;
-      d.k = (int)k;
-      dmin[i] = f.lo;
-      dmax[i] = (double)(d.ilo + d.step * (d.k - 1));
-    } else if (f.kind == SB_RAND_UNIFORM && !offset) {
-      if (!(std::isfinite(f.lo) && std::isfinite(f.hi))) return fail(SB_ERR_INVALID, who + name + ": lo and hi must be finite");
-      if (f.lo > f.hi) return fail(SB_ERR_INVALID, who + name + ": lo " + std::to_string(f.lo) + " > hi " + std::to_string(f.hi));
-      d.d.lo = dmin[i] = f.lo;
-      d.d.hi = dmax[i] = f.hi;
-    } else if (f.kind == SB_RAND_CHOICE) {
-      if (f.n_choices < 1 || f.n_choices > SB_RAND_MAX_CHOICES || !f.choices)
-        return fail(SB_ERR_INVALID, who + name + ": a choice needs 1 .. 65,536 values, got " + std::to_string(f.n_choices));
-      for (int j = 0; j < f.n_choices; ++j) {
-        if (!std::isfinite(f.choices[j])) return fail(SB_ERR_INVALID, who + name + ": choice " + std::to_string(j) + " is not finite");
-        if (offset && !whole(f.choices[j]))
-          return fail(SB_ERR_INVALID, who + name + ": choice " + std::to_string(j) + " must be a whole number of rows in 0 .. 2^22");
-      }
-      d.d.choice_off = (int)choices.size();
-      d.d.choice_len = f.n_choices;
-      choices.insert(choices.end(), f.choices, f.choices + f.n_choices);
-      dmin[i] = *std::min_element(f.choices, f.choices + f.n_choices);
-      dmax[i] = *std::max_element(f.choices, f.choices + f.n_choices);
-    } else {
-      return fail(SB_ERR_INVALID, who + name + ": distribution " + std::to_string(f.kind) + " is unknown or not one this field takes");
-    }
+    DistOut o;
+    SB_CHECK(parse_dist(who + name, DistIn{f.kind, f.lo, f.hi, f.step, f.n_choices, f.choices},
+                        1u << (offset ? SB_RAND_UNIFORM_INT : SB_RAND_UNIFORM) | 1u << SB_RAND_CHOICE,
+                        DistWords{"distribution ", " is unknown or not one this field takes", offset ? whole_rows : nullptr,
+                                  "lo and hi must be whole numbers of rows in 0 .. 2^22", "must be a whole number of rows in 0 .. 2^22"},
+                        choices, &o));
+    d.d.lo = o.lo; d.d.hi = o.hi; d.d.choice_off = o.choice_off; d.d.choice_len = o.choice_len;
+    d.ilo = o.ilo; d.step = o.step; d.k = o.k;
+    dmin[i] = o.dmin; dmax[i] = o.dmax;
   }
   if (!any) return fail(SB_ERR_INVALID, who + "no field is present (sb_episode_starts_detach returns to the handle without)");
-  const bool inherit = h->es_attached;
+  const bool inherit = h->es_draws.attached;
   double *const lohi_dev = es->weather_lohi_dev ? es->weather_lohi_dev : inherit ? h->es_lohi : nullptr;
   double *const shift_dev = es->weather_offset_dev ? es->weather_offset_dev : inherit ? h->es_shift : nullptr;
   if (inherit)
@@ -268,9 +226,9 @@ int sb_episode_starts_attach(sb_handle *h, const sb_episode_starts *es) {
     SB_HIP(hipMemcpy(base_shift.data(), src, base_shift.size() * sizeof(double), hipMemcpyDeviceToHost));
   }
   // nothing refused: from here on the handle changes
-  drop(h->es_choices); drop(h->es_episode); drop(h->es_base_offs); drop(h->es_base_lohi); drop(h->es_base_shift);
+  drop(h->es_choices); drop(h->es_draws.episode); drop(h->es_base_offs); drop(h->es_base_lohi); drop(h->es_base_shift);
   SB_CHECK(upload(h->es_choices, choices.data(), choices.size()));
-  SB_CHECK(alloc_zero(h->es_episode, (size_t)B));
+  SB_CHECK(alloc_zero(h->es_draws.episode, (size_t)B));
   if (!base_offs.empty()) SB_CHECK(upload(h->es_base_offs, base_offs.data(), base_offs.size()));
   if (!base_lohi.empty()) SB_CHECK(upload(h->es_base_lohi, base_lohi.data(), base_lohi.size()));
   if (!base_shift.empty()) SB_CHECK(upload(h->es_base_shift, base_shift.data(), base_shift.size()));
@@ -278,13 +236,13 @@ int sb_episode_starts_attach(sb_handle *h, const sb_episode_starts *es) {
   h->es_relative = es->relative ? 1 : 0;
   h->es_lohi = lohi_dev;
   h->es_shift = shift_dev;
-  h->es_seed = es->seed;
-  h->es_first = es->first_building;
+  h->es_draws.seed = es->seed;
+  h->es_draws.first = es->first_building;
   h->es_h_base_offs = base_offs;
   h->es_pending.clear();
   h->es_offsets = fld[SB_START_OFFSET].present != 0;
   h->es_restoring = false;
-  h->es_attached = true;
+  h->es_draws.attached = true;
   if (h->es_offsets) { // the host shadow: the largest offset every building may have from here on
     h->h_clock_next.clear();
     const int max_draw = (int)dmax[SB_START_OFFSET];
@@ -296,27 +254,24 @@ int sb_episode_starts_attach(sb_handle *h, const sb_episode_starts *es) {
 
 int sb_episode_starts_detach(sb_handle *h) {
   if (!h) return fail(SB_ERR_INVALID, "sb_episode_starts_detach: null handle");
-  if (!h->es_attached || h->es_restoring) return SB_OK;
+  if (!h->es_draws.attached || h->es_restoring) return SB_OK;
   h->es_restoring = true; // every building's next reset writes its base values; the counters mean nothing from here on
   h->es_pending.assign((size_t)h->d.B, 1);
   return SB_OK;
 }
 
+// (restoring: detached, the counters mean nothing)
 int sb_episode_starts_episodes_get(sb_handle *h, int32_t *out_dev, void *stream) {
-  if (!h || !out_dev) return fail(SB_ERR_INVALID, "sb_episode_starts_episodes_get: null argument");
-  if (!h->es_attached || h->es_restoring)
-    return fail(SB_ERR_UNSUPPORTED, "sb_episode_starts_episodes_get: the handle has no episode starts (sb_episode_starts_attach)");
-  SB_ON_DEVICE(h->device);
-  SB_HIP(hipMemcpyAsync(out_dev, h->es_episode.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return SB_OK;
+  const char *who = "sb_episode_starts_episodes_get";
+  if (h && out_dev && h->es_restoring) return fail(SB_ERR_UNSUPPORTED, std::string(who) + ": " + kNoStarts);
+  return episodes_get(h, &sb_handle::es_draws, who, kNoStarts, out_dev, (hipStream_t)stream);
 }
 
 int sb_episode_starts_episodes_set(sb_handle *h, const int32_t *in_dev, void *stream) {
-  if (!h || !in_dev) return fail(SB_ERR_INVALID, "sb_episode_starts_episodes_set: null argument");
-  if (!h->es_attached || h->es_restoring)
-    return fail(SB_ERR_UNSUPPORTED, "sb_episode_starts_episodes_set: the handle has no episode starts (sb_episode_starts_attach)");
+  const char *who = "sb_episode_starts_episodes_set";
+  if (h && in_dev && h->es_restoring) return fail(SB_ERR_UNSUPPORTED, std::string(who) + ": " + kNoStarts);
+  SB_CHECK(episodes_set(h, &sb_handle::es_draws, who, kNoStarts, in_dev, (hipStream_t)stream));
   SB_ON_DEVICE(h->device);
-  SB_HIP(hipMemcpyAsync(h->es_episode.p, in_dev, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return launch_starts(h, nullptr, kMaterialise, (hipStream_t)stream); // the values in force for these counters
 }
 
@@ -334,7 +289,7 @@ int sb_clock_set_offsets(sb_handle *h, const int32_t *offsets_host, void *stream
   const std::string who = "sb_clock_set_offsets: ";
   if (!h || !offsets_host) return fail(SB_ERR_INVALID, who + "null argument");
   if (!h->clock_rows.p) return fail(SB_ERR_UNSUPPORTED, who + "the handle has no clock (sb_clock_attach first)");
-  if (h->es_attached && h->es_offsets)
+  if (h->es_draws.attached && h->es_offsets)
     return fail(SB_ERR_INVALID, who + "the attached episode starts draw the offsets (sb_episode_starts_detach, then a reset of every building, first)");
   const int B = h->d.B;
   for (int b = 0; b < B; ++b) {

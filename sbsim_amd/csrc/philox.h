@@ -1,10 +1,10 @@
 // philox.h -- the counter-based generator the device generators share (generators.hip: occupancy, convection;
-// runtime.hip: the start temperatures' jitter; randomize.h: the redraw of per-building parameters and materials).
+// episode_draw.h: the per-episode draws -- start temperatures, per-building parameters and materials, episode starts).
 #ifndef SBSIM_AMD_PHILOX_H_
 #define SBSIM_AMD_PHILOX_H_
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
-#elif !defined(__host__) // a host-only program built by a plain C++ compiler (randomize.h's users): the qualifiers mean nothing
+#elif !defined(__host__) // a host-only program built by a plain C++ compiler (episode_draw.h's users): the qualifiers mean nothing
 #define __host__
 #define __device__
 #endif

@@ -1,5 +1,5 @@
 // randomize.hip -- sb_randomization_attach: per-building parameters and materials re-drawn at every episode start, on the
-// device (include/sbsim_amd.h states the semantics; randomize.h the draw).  A reset of a handle with a randomisation
+// device (include/sbsim_amd.h states the semantics; episode_draw.h the draw).  A reset of a handle with a randomisation
 // launches, before its reset kernel: k_randomize (the drawn values of the resetting buildings into the two tables),
 // k_rand_advance (their counters) and, with material fields, the masked k_class_coef (runtime.hip).
 //
@@ -12,21 +12,18 @@
 #include <string>
 #include <vector>
 
-#include "randomize.h"
+#include "episode_draw.h"
 #include "sb_host.h"
 
 using namespace sb;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kBlocksPerCu = 8; // the grid's cap (SB_RAND_BLOCKS_PER_CU in _ffi.py): beyond it the grid stride
-
 // One thread per (building, randomised field), the building the fast index: a wavefront writes 64 neighbours of one row.
 // materialise (sb_randomization_episodes_set): the rows in force for counters t -- values(b, t - 1), the base row at 0.
-__global__ void __launch_bounds__(kThreads) k_randomize(const RandField *fields, const double *choices, const double *base, int nf,
-                                                        int B, double *bp, double *mat, const uint8_t *mask, const int *episode,
-                                                        uint64_t seed, long long first, int materialise) {
+__global__ void __launch_bounds__(kDrawThreads) k_randomize(const RandField *fields, const double *choices, const double *base, int nf,
+                                                            int B, double *bp, double *mat, const uint8_t *mask, const int *episode,
+                                                            uint64_t seed, long long first, int materialise) {
   const size_t n = (size_t)B * nf;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int f = (int)(i / B), b = (int)(i - (size_t)f * B);
@@ -34,36 +31,31 @@ __global__ void __launch_bounds__(kThreads) k_randomize(const RandField *fields,
     const RandField fd = fields[f];
     const double b0 = base[i];
     int e = episode[b];
+    const bool drawn = !materialise || !before_first_episode(e);
+    if (materialise) e = episode_in_force(e);
     double v = b0;
-    if (!materialise || e >= 1) {
-      if (materialise) e -= 1;
-      v = rand_value(fd, rand_draw(fd, choices, seed, (uint64_t)(first + b), (uint32_t)e), b0);
-    }
+    if (drawn) v = rand_value(fd, rand_draw(fd, choices, seed, (uint64_t)(first + b), (uint32_t)e), b0);
     (fd.material ? mat : bp)[(size_t)fd.row * B + b] = v;
   }
 }
 
 // After k_randomize (whose threads of a building all read the counter): the resetting buildings' next episode.
-__global__ void __launch_bounds__(kThreads) k_rand_advance(int *episode, const uint8_t *mask, int B) {
+__global__ void __launch_bounds__(kDrawThreads) k_rand_advance(int *episode, const uint8_t *mask, int B) {
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x)
-    if (!mask || mask[b]) episode[b] = (int)((unsigned)episode[b] + 1u);
+    if (!mask || mask[b]) episode[b] = next_episode(episode[b]);
 }
 
 // sb_params' value of every field in every building's row (a handle without a table).
 struct ParamRow { double v[SB_NUM_BUILDING_PARAMS]; };
-__global__ void __launch_bounds__(kThreads) k_fill_params(ParamRow r, int B, double *out) {
+__global__ void __launch_bounds__(kDrawThreads) k_fill_params(ParamRow r, int B, double *out) {
   const size_t n = (size_t)B * SB_NUM_BUILDING_PARAMS;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = r.v[i / B];
-}
-
-int blocks_for(const sb_handle *h, size_t n) {
-  return (int)std::max<size_t>(1, std::min<size_t>((n + kThreads - 1) / kThreads, (size_t)h->cus * kBlocksPerCu));
 }
 
 int fill_params(const sb_handle *h, double *out, hipStream_t stream) {
   ParamRow r;
   for (int k = 0; k < SB_NUM_BUILDING_PARAMS; ++k) r.v[k] = param_field(h->d.p, k);
-  hipLaunchKernelGGL(k_fill_params, dim3(blocks_for(h, (size_t)h->d.B * SB_NUM_BUILDING_PARAMS)), dim3(kThreads), 0, stream, r, h->d.B, out);
+  hipLaunchKernelGGL(k_fill_params, dim3(draw_blocks(h, (size_t)h->d.B * SB_NUM_BUILDING_PARAMS)), dim3(kDrawThreads), 0, stream, r, h->d.B, out);
   SB_HIP(hipGetLastError());
   return SB_OK;
 }
@@ -71,9 +63,9 @@ int fill_params(const sb_handle *h, double *out, hipStream_t stream) {
 int launch_randomize(sb_handle *h, const uint8_t *mask, int materialise, hipStream_t stream) {
   const RandField *fields = (const RandField *)h->rz_desc.p;
   const double *choices = (const double *)(h->rz_desc.p + h->rz_choices_at);
-  hipLaunchKernelGGL(k_randomize, dim3(blocks_for(h, (size_t)h->d.B * h->rz_n_fields)), dim3(kThreads), 0, stream, fields, choices,
-                     h->rz_base.p, h->rz_n_fields, h->d.B, h->bp.p, h->mat_tab.p, mask, h->rz_episode.p, h->rz_seed, h->rz_first,
-                     materialise);
+  hipLaunchKernelGGL(k_randomize, dim3(draw_blocks(h, (size_t)h->d.B * h->rz_n_fields)), dim3(kDrawThreads), 0, stream, fields, choices,
+                     h->rz_base.p, h->rz_n_fields, h->d.B, h->bp.p, h->mat_tab.p, mask, h->rz_draws.episode.p, h->rz_draws.seed,
+                     h->rz_draws.first, materialise);
   SB_HIP(hipGetLastError());
   return SB_OK;
 }
@@ -82,19 +74,9 @@ std::string field_name(const sb_handle *h, int id) {
   return id < SB_RAND_MATERIAL ? building_param_name(id) : material_field_name(id - SB_RAND_MATERIAL, h->mat_slots);
 }
 
-// The device is idle on return; a capture in progress refuses the synchronisation.
-int idle_device(const std::string &who) {
-  if (const hipError_t e = hipDeviceSynchronize(); e != hipSuccess) {
-    const bool capturing = e == hipErrorStreamCaptureUnsupported || e == hipErrorStreamCaptureImplicit;
-    return fail(capturing ? SB_ERR_INVALID : SB_ERR_HIP, who + (capturing ? "not while a stream is being captured into a graph"
-                                                                          : hipGetErrorString(e)));
-  }
-  return SB_OK;
-}
-
 // Both tables back to the rows of the attach, the buffers dropped.  The device is idle.
 int drop_randomization(sb_handle *h) {
-  if (!h->rz_attached) return SB_OK;
+  if (!h->rz_draws.attached) return SB_OK;
   if (h->rz_own_bp) { // the handle had no table: back to sb_params' values through Dev::bp == NULL
     h->d.bp = nullptr;
     if (h->bp.p) SB_HIP(hipFree(h->bp.p));
@@ -107,14 +89,10 @@ int drop_randomization(sb_handle *h) {
     SB_CHECK(launch_class_coef(h, nullptr, nullptr));
     SB_HIP(hipDeviceSynchronize());
   }
-  auto drop = [](auto &buf) {
-    if (buf.p) (void)hipFree(buf.p);
-    buf.p = nullptr;
-  };
-  drop(h->rz_desc); drop(h->rz_base); drop(h->rz_episode);
+  drop(h->rz_desc); drop(h->rz_base); drop(h->rz_draws.episode);
   h->rz_base_bp.clear(); h->rz_base_bp.shrink_to_fit();
   h->rz_base_mat.clear(); h->rz_base_mat.shrink_to_fit();
-  h->rz_attached = h->rz_materials = h->rz_own_bp = false;
+  h->rz_draws.attached = h->rz_materials = h->rz_own_bp = false;
   h->rz_n_fields = 0;
   return SB_OK;
 }
@@ -123,7 +101,7 @@ int drop_randomization(sb_handle *h) {
 
 int sb_randomization_redraw(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream) {
   SB_CHECK(launch_randomize(h, mask_dev, 0, stream));
-  hipLaunchKernelGGL(k_rand_advance, dim3(blocks_for(h, (size_t)h->d.B)), dim3(kThreads), 0, stream, h->rz_episode.p, mask_dev, h->d.B);
+  hipLaunchKernelGGL(k_rand_advance, dim3(draw_blocks(h, (size_t)h->d.B)), dim3(kDrawThreads), 0, stream, h->rz_draws.episode.p, mask_dev, h->d.B);
   SB_HIP(hipGetLastError());
   if (h->rz_materials) SB_CHECK(launch_class_coef(h, mask_dev, stream));
   return SB_OK;
@@ -159,31 +137,18 @@ int sb_randomization_attach(sb_handle *h, const sb_rand_field *fields, int32_t n
     (material ? any_mat : any_param) = true;
     RandField &d = desc[i];
     d = RandField{f.id, row, material ? 1 : 0, f.kind, f.scale ? 1 : 0, 0, 0, 0, 0.0, 0.0};
-    if (f.kind == SB_RAND_UNIFORM) {
-      if (!(std::isfinite(f.lo) && std::isfinite(f.hi))) return fail(SB_ERR_INVALID, who + name + ": lo and hi must be finite");
-      if (f.lo > f.hi) return fail(SB_ERR_INVALID, who + name + ": lo " + std::to_string(f.lo) + " > hi " + std::to_string(f.hi));
-      d.lo = dmin[i] = f.lo;
-      d.hi = dmax[i] = f.hi;
-    } else if (f.kind == SB_RAND_CHOICE) {
-      if (f.n_choices < 1 || f.n_choices > SB_RAND_MAX_CHOICES || !f.choices)
-        return fail(SB_ERR_INVALID, who + name + ": a choice needs 1 .. 65,536 values, got " + std::to_string(f.n_choices));
-      for (int j = 0; j < f.n_choices; ++j)
-        if (!std::isfinite(f.choices[j])) return fail(SB_ERR_INVALID, who + name + ": choice " + std::to_string(j) + " is not finite");
-      d.choice_off = (int)choices.size();
-      d.choice_len = f.n_choices;
-      choices.insert(choices.end(), f.choices, f.choices + f.n_choices);
-      dmin[i] = *std::min_element(f.choices, f.choices + f.n_choices);
-      dmax[i] = *std::max_element(f.choices, f.choices + f.n_choices);
-    } else {
-      return fail(SB_ERR_INVALID, who + name + ": unknown distribution " + std::to_string(f.kind));
-    }
+    DistOut o;
+    SB_CHECK(parse_dist(who + name, DistIn{f.kind, f.lo, f.hi, 0, f.n_choices, f.choices}, 1u << SB_RAND_UNIFORM | 1u << SB_RAND_CHOICE,
+                        DistWords{"unknown distribution ", "", nullptr, nullptr, nullptr}, choices, &o));
+    d.lo = o.lo; d.hi = o.hi; d.choice_off = o.choice_off; d.choice_len = o.choice_len;
+    dmin[i] = o.dmin; dmax[i] = o.dmax;
   }
   SB_ON_DEVICE(h->device);
   SB_CHECK(idle_device(who));
   // the base rows: those of an attachment this one replaces, else the tables in force
   std::vector<double> base_bp, base_mat;
-  const bool had_table = h->rz_attached ? !h->rz_own_bp : h->bp.p != nullptr;
-  if (h->rz_attached) {
+  const bool had_table = h->rz_draws.attached ? !h->rz_own_bp : h->bp.p != nullptr;
+  if (h->rz_draws.attached) {
     base_bp = h->rz_base_bp;
     base_mat = h->rz_base_mat;
   } else {
@@ -256,39 +221,35 @@ int sb_randomization_attach(sb_handle *h, const sb_rand_field *fields, int32_t n
   if (!choices.empty()) std::memcpy(blob.data() + desc_bytes, choices.data(), choices.size() * sizeof(double));
   SB_CHECK(upload(h->rz_desc, blob.data(), blob.size()));
   SB_CHECK(upload(h->rz_base, base.data(), base.size()));
-  SB_CHECK(alloc_zero(h->rz_episode, (size_t)B));
+  SB_CHECK(alloc_zero(h->rz_draws.episode, (size_t)B));
   h->rz_choices_at = desc_bytes;
   h->rz_base_bp = std::move(base_bp);
   h->rz_base_mat = std::move(base_mat);
   h->rz_n_fields = n_fields;
   h->rz_materials = any_mat;
-  h->rz_seed = seed;
-  h->rz_first = first_building;
-  h->rz_attached = true;
+  h->rz_draws.seed = seed;
+  h->rz_draws.first = first_building;
+  h->rz_draws.attached = true;
   return SB_OK;
 }
 
 int sb_randomization_detach(sb_handle *h) {
   if (!h) return fail(SB_ERR_INVALID, "sb_randomization_detach: null handle");
-  if (!h->rz_attached) return SB_OK;
+  if (!h->rz_draws.attached) return SB_OK;
   SB_ON_DEVICE(h->device);
   SB_CHECK(idle_device("sb_randomization_detach: "));
   return drop_randomization(h);
 }
 
+static const char *const kNoRandomization = "the handle has no randomisation (sb_randomization_attach)";
+
 int sb_randomization_episodes_get(sb_handle *h, int32_t *out_dev, void *stream) {
-  if (!h || !out_dev) return fail(SB_ERR_INVALID, "sb_randomization_episodes_get: null argument");
-  if (!h->rz_attached) return fail(SB_ERR_UNSUPPORTED, "sb_randomization_episodes_get: the handle has no randomisation (sb_randomization_attach)");
-  SB_ON_DEVICE(h->device);
-  SB_HIP(hipMemcpyAsync(out_dev, h->rz_episode.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return SB_OK;
+  return episodes_get(h, &sb_handle::rz_draws, "sb_randomization_episodes_get", kNoRandomization, out_dev, (hipStream_t)stream);
 }
 
 int sb_randomization_episodes_set(sb_handle *h, const int32_t *in_dev, void *stream) {
-  if (!h || !in_dev) return fail(SB_ERR_INVALID, "sb_randomization_episodes_set: null argument");
-  if (!h->rz_attached) return fail(SB_ERR_UNSUPPORTED, "sb_randomization_episodes_set: the handle has no randomisation (sb_randomization_attach)");
+  SB_CHECK(episodes_set(h, &sb_handle::rz_draws, "sb_randomization_episodes_set", kNoRandomization, in_dev, (hipStream_t)stream));
   SB_ON_DEVICE(h->device);
-  SB_HIP(hipMemcpyAsync(h->rz_episode.p, in_dev, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   SB_CHECK(launch_randomize(h, nullptr, 1, (hipStream_t)stream)); // the rows in force for these counters
   if (h->rz_materials) SB_CHECK(launch_class_coef(h, nullptr, (hipStream_t)stream));
   return SB_OK;

@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "philox.h"
+#include "episode_draw.h"
 #include "sb_host.h"
 
 using namespace sb;
@@ -74,8 +74,8 @@ __device__ __forceinline__ double wave_first(double x) { // lane 0's value in ev
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-// The top of a building's reset with conditions attached.  The draw is one Philox block per building, in lane 0, and
-// broadcast: u = lo + (hi - lo) * ((r >> 11) * 2^-53), r the block's first two words.
+// The top of a building's reset with conditions attached.  The draw (episode_draw.h: initial_conditions_draw) is one
+// Philox block per building, in lane 0, and broadcast.
 __device__ __forceinline__ Start start_of(const StartView &ic, int b, int lane, int N, double initial_temp) {
   Start st;
   st.grid = ic.grids ? ic.grids + (size_t)(ic.grid_of ? ic.grid_of[b] : 0) * N : nullptr;
@@ -87,13 +87,7 @@ __device__ __forceinline__ Start start_of(const StartView &ic, int b, int lane, 
   st.u = 0.0;
   if (st.has_jitter) {
     double u = 0.0;
-    if (lane == 0) {
-      const unsigned long long gb = (unsigned long long)(ic.first + b);
-      uint32_t c[4] = {(uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)st.e, SB_INITIAL_CONDITIONS_TAG};
-      philox4x32_10(c, (uint32_t)ic.seed, (uint32_t)(ic.seed >> 32));
-      const uint64_t r = ((uint64_t)c[1] << 32) | c[0];
-      u = ic.lo + (ic.hi - ic.lo) * ((double)(r >> 11) * 0x1p-53);
-    }
+    if (lane == 0) u = initial_conditions_draw(ic.lo, ic.hi, ic.seed, (uint64_t)(ic.first + b), (uint32_t)st.e);
     st.u = wave_first(u);
   }
   return st;
@@ -178,7 +172,7 @@ __device__ __forceinline__ void reset_grid(Dev a, EpisodeArgs ep, StartView ic, 
       S[16] = a.reg && a.n_ring > 0 ? rlo : 0.0; // extremes of the exterior-space ring (register path)
       S[17] = a.reg && a.n_ring > 0 ? rhi : 0.0;
       reset_episode(S, ep, b, first, steps_since_reset);
-      if (IC) ic.episode[b] = st.e + 1;
+      if (IC) ic.episode[b] = next_episode(st.e);
     }
   }
 }
@@ -398,7 +392,7 @@ __device__ __forceinline__ void reset_jacobi(Dev a, EpisodeArgs ep, StartView ic
       S[12] = S[13] = S[14] = S[15] = 0.0;
       S[16] = S[17] = 0.0; // (the register path's ring extremes: no ring here)
       reset_episode(S, ep, b, first, steps_since_reset);
-      if (IC) ic.episode[b] = st.e + 1;
+      if (IC) ic.episode[b] = next_episode(st.e);
     }
   }
 }
@@ -630,9 +624,9 @@ int sb_get_launch_info(const sb_handle *h, sb_launch_info *out) {
 static void launch_reset(sb_handle *h, const EpisodeArgs &ep, double initial_temp, const double *temps_dev, hipStream_t stream) {
   const int wpb = 4;
   const int blocks = std::min((h->d.B + wpb - 1) / wpb, 4096);
-  if (h->ic_attached) { // the conditions' kernels: the values without temps_dev, the episode counters either way
-    const StartView ic{h->ic_grids.p, h->ic_grid_of.p, h->ic_base.p, h->ic_offset.p, h->ic_episode.p,
-                       h->ic_lo, h->ic_hi, h->ic_seed, h->ic_first, h->ic_jitter ? 1 : 0};
+  if (h->ic_draws.attached) { // the conditions' kernels: the values without temps_dev, the episode counters either way
+    const StartView ic{h->ic_grids.p, h->ic_grid_of.p, h->ic_base.p, h->ic_offset.p, h->ic_draws.episode.p,
+                       h->ic_lo, h->ic_hi, h->ic_draws.seed, h->ic_draws.first, h->ic_jitter ? 1 : 0};
     if (h->kernel == SB_KERNEL_JACOBI)
       hipLaunchKernelGGL(k_reset_jacobi_ic, dim3(blocks), dim3(64 * wpb), 0, stream, h->d, ep, ic, h->jgrid.p,
                          initial_temp, temps_dev, h->was_reset ? 0 : 1, h->steps_since_reset);
@@ -650,8 +644,8 @@ static void launch_reset(sb_handle *h, const EpisodeArgs &ep, double initial_tem
 int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *stream) {
   if (!h) return fail(SB_ERR_INVALID, "sb_reset: null handle");
   SB_ON_DEVICE(h->device);
-  if (h->rz_attached) SB_CHECK(sb_randomization_redraw(h, nullptr, (hipStream_t)stream)); // the new episode's rows, before the reset reads them
-  if (h->es_attached) SB_CHECK(sb_episode_starts_redraw(h, nullptr, (hipStream_t)stream)); // ... its start and weather
+  if (h->rz_draws.attached) SB_CHECK(sb_randomization_redraw(h, nullptr, (hipStream_t)stream)); // the new episode's rows, before the reset reads them
+  if (h->es_draws.attached) SB_CHECK(sb_episode_starts_redraw(h, nullptr, (hipStream_t)stream)); // ... its start and weather
   launch_reset(h, EpisodeArgs{nullptr, h->ep_start.p, nullptr, nullptr, 0}, initial_temp, temps_dev, (hipStream_t)stream);
   h->was_reset = true;
   h->steps_since_reset = 0;
@@ -663,7 +657,7 @@ int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *s
     h->h_clock_offs = std::move(h->h_clock_next);
     h->h_clock_next.clear();
   }
-  if (h->es_attached) sb_episode_starts_after_reset(h, nullptr);
+  if (h->es_draws.attached) sb_episode_starts_after_reset(h, nullptr);
   if (!h->restart_pos.empty() || h->own_prev || new_offs) { // episodes per building: every building back on the attached calendar
     if (h->clock_eff.p)
       SB_HIP(hipMemcpyAsync(h->clock_eff.p, h->clock_offs.p, (size_t)h->d.B * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -714,8 +708,8 @@ int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host, int32_t restart_p
   SB_ON_DEVICE(h->device);
   SB_CHECK(upload_mask(h, mask_host, "sb_reset_buildings", (hipStream_t)stream));
   if (!h->ep_start.p) SB_CHECK(alloc_zero(h->ep_start, (size_t)B));
-  if (h->rz_attached) SB_CHECK(sb_randomization_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // the masked buildings' new rows
-  if (h->es_attached) SB_CHECK(sb_episode_starts_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // ... their starts and weather
+  if (h->rz_draws.attached) SB_CHECK(sb_randomization_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // the masked buildings' new rows
+  if (h->es_draws.attached) SB_CHECK(sb_episode_starts_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // ... their starts and weather
   launch_reset(h, EpisodeArgs{h->ep_mask.p, h->ep_start.p, clk ? h->clock_eff.p : nullptr, h->clock_offs.p, restart_pos},
                initial_temp, temps_dev, (hipStream_t)stream);
   SB_HIP(hipGetLastError());
@@ -727,9 +721,9 @@ int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host, int32_t restart_p
         h->restart_pos[b] = restart_pos;
         if (!h->h_clock_next.empty()) h->h_clock_offs[b] = h->h_clock_next[b];
       }
-    if (h->es_attached) sb_episode_starts_after_reset(h, mask_host);
+    if (h->es_draws.attached) sb_episode_starts_after_reset(h, mask_host);
     episode_bounds(h);
-  } else if (h->es_attached) {
+  } else if (h->es_draws.attached) {
     sb_episode_starts_after_reset(h, mask_host);
   }
   return SB_OK;
@@ -979,7 +973,7 @@ int sb_set_building_params(sb_handle *h, int32_t n_fields, const int32_t *fields
   if (n_fields < 0 || n_fields > SB_NUM_BUILDING_PARAMS)
     return fail(SB_ERR_INVALID, "sb_set_building_params: n_fields must be in 0 .. SB_NUM_BUILDING_PARAMS");
   if (n_fields > 0 && (!fields || !values)) return fail(SB_ERR_INVALID, "sb_set_building_params: null argument");
-  if (h->rz_attached)
+  if (h->rz_draws.attached)
     return fail(SB_ERR_INVALID, "sb_set_building_params: a randomisation is attached, which owns the rows (sb_randomization_detach first)");
   const int B = h->d.B;
   std::vector<double> tab;
@@ -1034,7 +1028,7 @@ int sb_set_building_materials(sb_handle *h, int32_t n_fields, const int32_t *fie
   if (!h->materials)
     return fail(SB_ERR_UNSUPPORTED, "sb_set_building_materials: the handle has one coefficient table for every building "
                                     "(sb_create / sb_create_jacobi); create it with sb_create_materials");
-  if (h->rz_attached)
+  if (h->rz_draws.attached)
     return fail(SB_ERR_INVALID, "sb_set_building_materials: a randomisation is attached, which owns the rows (sb_randomization_detach first)");
   const int M = h->mat_slots, F = 3 * M + 1, B = h->d.B;
   if (n_fields < 0 || n_fields > F)
@@ -1166,14 +1160,10 @@ int sb_clock_detach(sb_handle *h) {
 
 /* ---- start temperatures per building ---- */
 static int drop_initial_conditions(sb_handle *h) { // the kernels in flight read the arrays: they go once the device is idle
-  if (!h->ic_attached) return SB_OK;
+  if (!h->ic_draws.attached) return SB_OK;
   SB_HIP(hipDeviceSynchronize());
-  h->ic_attached = false; // (launch_reset: the kernels of the handle without, from here on)
-  auto drop = [](auto &buf) {
-    if (buf.p) (void)hipFree(buf.p);
-    buf.p = nullptr;
-  };
-  drop(h->ic_grids); drop(h->ic_grid_of); drop(h->ic_base); drop(h->ic_offset); drop(h->ic_episode);
+  h->ic_draws.attached = false; // (launch_reset: the kernels of the handle without, from here on)
+  drop(h->ic_grids); drop(h->ic_grid_of); drop(h->ic_base); drop(h->ic_offset); drop(h->ic_draws.episode);
   h->ic_n_grids = 0;
   h->ic_jitter = false;
   return SB_OK;
@@ -1208,23 +1198,19 @@ int sb_initial_conditions_attach(sb_handle *h, const sb_initial_conditions *ic) 
   if (ic->has_jitter && !(std::isfinite(ic->jitter_lo) && std::isfinite(ic->jitter_hi) && ic->jitter_lo <= ic->jitter_hi))
     return fail(SB_ERR_INVALID, who + "jitter: needs finite lo <= hi");
   SB_ON_DEVICE(h->device);
-  if (const hipError_t e = hipDeviceSynchronize(); e != hipSuccess) { // (also what a capture in progress refuses)
-    const bool capturing = e == hipErrorStreamCaptureUnsupported || e == hipErrorStreamCaptureImplicit;
-    return fail(capturing ? SB_ERR_INVALID : SB_ERR_HIP, who + (capturing ? "not while a stream is being captured into a graph"
-                                                                          : hipGetErrorString(e)));
-  }
+  SB_CHECK(idle_device(who));
   SB_CHECK(drop_initial_conditions(h));
   if (ic->grids) SB_CHECK(upload(h->ic_grids, ic->grids, (size_t)ic->n_grids * N));
   if (ic->grid_of) SB_CHECK(upload(h->ic_grid_of, ic->grid_of, (size_t)B));
   if (ic->initial_temp) SB_CHECK(upload(h->ic_base, ic->initial_temp, (size_t)B));
   if (ic->offset) SB_CHECK(upload(h->ic_offset, ic->offset, (size_t)B));
-  SB_CHECK(alloc_zero(h->ic_episode, (size_t)B));
+  SB_CHECK(alloc_zero(h->ic_draws.episode, (size_t)B));
   h->ic_n_grids = ic->n_grids;
   h->ic_jitter = ic->has_jitter != 0;
   h->ic_lo = ic->jitter_lo; h->ic_hi = ic->jitter_hi;
-  h->ic_seed = ic->seed;
-  h->ic_first = ic->first_building;
-  h->ic_attached = true;
+  h->ic_draws.seed = ic->seed;
+  h->ic_draws.first = ic->first_building;
+  h->ic_draws.attached = true;
   return SB_OK;
 }
 
@@ -1234,20 +1220,14 @@ int sb_initial_conditions_detach(sb_handle *h) {
   return drop_initial_conditions(h);
 }
 
+static const char *const kNoInitialConditions = "the handle has no initial conditions (sb_initial_conditions_attach)";
+
 int sb_initial_conditions_episodes_get(sb_handle *h, int32_t *out_dev, void *stream) {
-  if (!h || !out_dev) return fail(SB_ERR_INVALID, "sb_initial_conditions_episodes_get: null argument");
-  if (!h->ic_attached) return fail(SB_ERR_UNSUPPORTED, "sb_initial_conditions_episodes_get: the handle has no initial conditions (sb_initial_conditions_attach)");
-  SB_ON_DEVICE(h->device);
-  SB_HIP(hipMemcpyAsync(out_dev, h->ic_episode.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return SB_OK;
+  return episodes_get(h, &sb_handle::ic_draws, "sb_initial_conditions_episodes_get", kNoInitialConditions, out_dev, (hipStream_t)stream);
 }
 
 int sb_initial_conditions_episodes_set(sb_handle *h, const int32_t *in_dev, void *stream) {
-  if (!h || !in_dev) return fail(SB_ERR_INVALID, "sb_initial_conditions_episodes_set: null argument");
-  if (!h->ic_attached) return fail(SB_ERR_UNSUPPORTED, "sb_initial_conditions_episodes_set: the handle has no initial conditions (sb_initial_conditions_attach)");
-  SB_ON_DEVICE(h->device);
-  SB_HIP(hipMemcpyAsync(h->ic_episode.p, in_dev, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return SB_OK;
+  return episodes_set(h, &sb_handle::ic_draws, "sb_initial_conditions_episodes_set", kNoInitialConditions, in_dev, (hipStream_t)stream);
 }
 
 /* ---- the reward function ---- */

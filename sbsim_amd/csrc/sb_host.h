@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "episode_starts.h"
+#include "episode_draw.h"
 #include "planner.h"
 #include "sb_device.h"
 
@@ -91,6 +91,12 @@ struct DevBuf {
 };
 
 template <typename Tp>
+inline void drop(DevBuf<Tp> &buf) { // (the caller has made the device idle where a kernel may still read the buffer)
+  if (buf.p) (void)hipFree(buf.p);
+  buf.p = nullptr;
+}
+
+template <typename Tp>
 inline int upload(DevBuf<Tp> &buf, const Tp *src, size_t n) {
   SB_HIP(hipMalloc((void **)&buf.p, std::max<size_t>(n, 1) * sizeof(Tp)));
   if (n) SB_HIP(hipMemcpy(buf.p, src, n * sizeof(Tp), hipMemcpyHostToDevice));
@@ -118,6 +124,16 @@ struct ConvCell {
 struct OccGroup {
   int e_arr, l_arr, e_dep, n_occ;
   double p_arr, p_dep;
+};
+
+// What the three per-episode attachments (sb_initial_conditions_attach, sb_randomization_attach,
+// sb_episode_starts_attach) each keep for their draws (episode_draw.h): one Philox block per (seed, global building,
+// episode, tag | field).
+struct EpisodeDraws {
+  bool attached = false;
+  DevBuf<int> episode;  // [B] the number of the building's next episode: 0 at attach, advanced by every reset of the building
+  uint64_t seed = 0;
+  long long first = 0;  // global index of building 0
 };
 
 struct sb_handle {
@@ -209,48 +225,39 @@ struct sb_handle {
   int sp_stage_bytes = 0;           // > 0: the state is staged in this much LDS per workgroup; 0: gathered from global memory
   DevBuf<int> sp_tile_src, sp_tile_off, sp_tile_cnt, sp_zone_off, sp_zone_src;
   // sb_initial_conditions_attach (runtime.hip): the start temperatures' arrays and the buildings' episode counters
-  bool ic_attached = false;
+  EpisodeDraws ic_draws;            // (attached: launch_reset runs the conditions' kernels)
   int ic_n_grids = 0;               // K; 0: no grids
   DevBuf<double> ic_grids;          // [K][N] in the handle's orientation
   DevBuf<int> ic_grid_of;           // [B]; NULL: every building grid 0
   DevBuf<double> ic_base, ic_offset; // [B] initial_temp, offset; NULL: absent
-  DevBuf<int> ic_episode;           // [B] the number of the building's next episode
   bool ic_jitter = false;
   double ic_lo = 0.0, ic_hi = 0.0;
-  uint64_t ic_seed = 0;
-  long long ic_first = 0;
   // sb_randomization_attach (randomize.hip): the fields' descriptors and choice tables, their base rows, the counters
-  bool rz_attached = false;
+  EpisodeDraws rz_draws;
   int rz_n_fields = 0;
   bool rz_materials = false;        // some field is a material field: a redraw re-folds the coefficient rows
   bool rz_own_bp = false;           // the attach allocated the parameter table (the handle had none): detach drops it
   DevBuf<unsigned char> rz_desc;    // [n_fields] sb::RandField, then the choice tables (doubles)
   size_t rz_choices_at = 0;         // byte offset of the choice tables in rz_desc
   DevBuf<double> rz_base;           // [n_fields][B] the rows in force at attach
-  DevBuf<int> rz_episode;           // [B] the number of the building's next episode
   std::vector<double> rz_base_bp;   // host: [SB_NUM_BUILDING_PARAMS][B] the whole table at attach (sb_params' values without one)
   std::vector<double> rz_base_mat;  // host: [3 M + 1][B] likewise; empty on a handle without materials
-  uint64_t rz_seed = 0;
-  long long rz_first = 0;
   // sb_clock_set_offsets: the offsets a building takes at its next reset where they differ from h_clock_offs, which then
   // holds the larger of the two (empty: none pending)
   std::vector<int> h_clock_next;
   // sb_episode_starts_attach (episode_starts.hip): the fields, their choice tables, the base values, the counters
-  bool es_attached = false;         // a reset launches k_episode_starts ...
+  EpisodeDraws es_draws;            // attached: a reset launches k_episode_starts ...
   bool es_restoring = false;        // ... which writes the base values: detached, until every building was reset once
   bool es_offsets = false;          // SB_START_OFFSET is (or, restoring, was) drawn: h_clock_offs holds the largest possible offsets
   sb::StartField es_field[SB_START_FIELDS] = {};
   int es_relative = 0;
   DevBuf<double> es_choices;        // the fields' choice tables, one after the other
-  DevBuf<int> es_episode;           // [B] the number of the building's next episode
   DevBuf<int> es_base_offs;         // [B] the offsets given to sb_clock_attach
   DevBuf<double> es_base_lohi;      // [B][2] the caller's weather array at attach
   DevBuf<double> es_base_shift;     // [B] likewise
   std::vector<int> es_h_base_offs;  // host copy of es_base_offs
   std::vector<uint8_t> es_pending;  // restoring: the buildings not reset since the detach
   double *es_lohi = nullptr, *es_shift = nullptr; // the caller's arrays
-  uint64_t es_seed = 0;
-  long long es_first = 0;
   // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
   DevBuf<float> jgrid, jtab, jscratch; // (jscratch: k_sweep_jacobi_g's per-workgroup grids)
   DevBuf<double> jrden;
@@ -270,7 +277,7 @@ inline int handle_clock_view(const sb_handle *h, const char *who, sb::ClockView 
     return fail(SB_ERR_INVALID, std::string(who) + ": a building restarts at position " + std::to_string(h->max_restart) +
                                     " (sb_reset_buildings), the clock is at " + std::to_string(h->clock_pos) + ": sb_clock_seek first");
   // (drawn offsets, sb_episode_starts_attach: a reset moves the building's rows, as a reset of its own does)
-  const bool own_prev = h->own_prev || (h->es_attached && h->es_offsets);
+  const bool own_prev = h->own_prev || (h->es_draws.attached && h->es_offsets);
   *out = sb::ClockView{h->clock_rows.p, h->clock_eff.p, h->clock_pos, h->clock_prev, h->clock_n_rows, own_prev ? 1 : 0};
   return SB_OK;
 }
@@ -290,6 +297,38 @@ int launch_class_coef(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream)
 const char *building_param_name(int k);
 std::string material_field_name(int f, int M);
 
+// episode_draw.hip: what the per-episode attachments share on the host.
+// The device is idle on return; a capture in progress refuses the synchronisation (SB_ERR_INVALID, `who` in front).
+int idle_device(const std::string &who);
+// The grid of a draw kernel over n items: kDrawThreads per workgroup, at most kDrawBlocksPerCu workgroups per CU (the
+// kernels take the grid stride beyond), at least one.
+constexpr int kDrawThreads = 256, kDrawBlocksPerCu = 8; // (_ffi.py: SB_RAND_THREADS, SB_RAND_BLOCKS_PER_CU)
+int draw_blocks(const sb_handle *h, size_t n);
+// One distribution of a sb_rand_field / sb_start_field, checked and taken apart.
+struct DistIn {
+  int kind;                     // sb_rand_kind, or SB_RAND_UNIFORM_INT
+  double lo, hi;
+  int step, n_choices;
+  const double *choices;
+};
+struct DistWords {              // where the callers' messages differ, and what one of them checks beyond the other
+  const char *unknown_head, *unknown_tail; // a kind outside `kinds`: "<field>: <head><kind><tail>"
+  bool (*value_ok)(double);     // a further check on SB_RAND_UNIFORM_INT's bounds and on every choice; NULL: none
+  const char *bounds_text, *choice_text; // ... "<field>: <bounds_text>", "<field>: choice <j> <choice_text>"
+};
+struct DistOut {
+  double lo, hi;                // SB_RAND_UNIFORM
+  int choice_off, choice_len;   // SB_RAND_CHOICE: the field's entries of `choices`, which parse_dist appended
+  int ilo, step, k;             // SB_RAND_UNIFORM_INT
+  double dmin, dmax;            // the smallest and the largest possible draw
+};
+// `at`: the entry point and the field's name, in front of every message; kinds: bit k set -- the field takes kind k.
+int parse_dist(const std::string &at, const DistIn &in, unsigned kinds, const DistWords &w, std::vector<double> &choices, DistOut *out);
+// The *_episodes_get / *_episodes_set entry points: the null checks, SB_ERR_UNSUPPORTED ("<who>: <missing_text>") when
+// `draws` is not attached, and the stream-ordered device-to-device copy of the [B] counters.
+int episodes_get(sb_handle *h, EpisodeDraws sb_handle::*draws, const char *who, const char *missing_text, int32_t *out_dev, hipStream_t stream);
+int episodes_set(sb_handle *h, EpisodeDraws sb_handle::*draws, const char *who, const char *missing_text, const int32_t *in_dev, hipStream_t stream);
+
 // randomize.hip: the redraw at the top of a reset (sb_reset: mask_dev NULL, every building; sb_reset_buildings: its
 // device mask), stream-ordered launches only.  Only called while a randomisation is attached.
 int sb_randomization_redraw(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream);
@@ -297,7 +336,7 @@ int sb_randomization_redraw(sb_handle *h, const uint8_t *mask_dev, hipStream_t s
 // runtime.hip: the bounds sb_clock_seek checks (clock_max_off, max_restart), from the host shadows
 void episode_bounds(sb_handle *h);
 // episode_starts.hip: the draw at the top of a reset, after sb_randomization_redraw (mask_dev as there), one stream-ordered
-// launch; and the host shadow's part once the reset is queued (mask_host NULL: sb_reset).  Only called while es_attached.
+// launch; and the host shadow's part once the reset is queued (mask_host NULL: sb_reset).  Only called while es_draws.attached.
 int sb_episode_starts_redraw(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream);
 void sb_episode_starts_after_reset(sb_handle *h, const uint8_t *mask_host);
 // episode_starts.hip: forgets an attachment with the clock its offsets belonged to (drop_clock; the device is idle)

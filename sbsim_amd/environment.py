@@ -928,6 +928,27 @@ class BatchedSimulator:
     """The reward function in force (None: the default regret function)."""
     return self._reward_function
 
+  # ---- the three per-episode attachments: one path into the library ----
+  def _draws_call(self, name: str, *args, value_errors=(-1, -5)) -> None:
+    """The library's entry ``name`` on this simulator's device.  A return code in ``value_errors`` (-1 SB_ERR_INVALID,
+    -5 SB_ERR_UNSUPPORTED) raises ValueError with the library's message, any other failure ``_ffi.SbsimError``."""
+    with torch.cuda.device(self.device):
+      rc = _ffi.entry(name)(self._h, *args)
+    if rc in value_errors:
+      raise ValueError((self._lib.sb_last_error() or b"").decode())
+    _ffi.check(rc, name)
+
+  def _episodes_get(self, name: str, value_errors=(-5,)) -> torch.Tensor:
+    out = torch.empty((self.B,), dtype=torch.int32, device=self.tdev)
+    self._draws_call(name, C.c_void_p(out.data_ptr()), self._stream(), value_errors=value_errors)
+    return out
+
+  def _episodes_set(self, name: str, t: torch.Tensor, value_errors=(-5,)) -> None:
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (self.B,) or t.device != self.tdev
+        or not t.is_contiguous()):
+      raise ValueError(f"the episode numbers must be a contiguous int32 [{self.B}] tensor on {self.tdev}")
+    self._draws_call(name, C.c_void_p(t.data_ptr()), self._stream(), value_errors=value_errors)
+
   # ---- start temperatures per building (sb_initial_conditions_attach) ----
   def initial_conditions_attach(self, ic: host_inputs.InitialConditions) -> None:
     """sb_initial_conditions_attach: from now on every reset without ``temps`` -- ``reset``, ``reset_buildings`` -- takes
@@ -938,7 +959,6 @@ class BatchedSimulator:
     if not isinstance(ic, host_inputs.InitialConditions):
       raise ValueError("initial_conditions_attach needs a host_inputs.InitialConditions (initial_conditions_detach clears them)")
     ic.check(self.B, (self.H, self.W))
-    fn = _ffi.initial_conditions_entry("sb_initial_conditions_attach")
     d = _ffi.InitialConditionsDesc()
     keep = []
     if ic.reset_temp_values is not None:
@@ -956,18 +976,13 @@ class BatchedSimulator:
     if ic.jitter is not None:
       d.has_jitter, d.jitter_lo, d.jitter_hi, d.seed = 1, ic.jitter[0], ic.jitter[1], ic.jitter[2]
     d.first_building = ic.first_building
-    with torch.cuda.device(self.device):
-      rc = fn(self._h, C.byref(d))
-    if rc == -1:   # SB_ERR_INVALID
-      raise ValueError((self._lib.sb_last_error() or b"").decode())
-    _ffi.check(rc, "sb_initial_conditions_attach")
+    self._draws_call("sb_initial_conditions_attach", C.byref(d), value_errors=(-1,))
     self._initial_conditions = ic
 
   def initial_conditions_detach(self) -> None:
     """sb_initial_conditions_detach: the resets fill from ``initial_temp`` again, with the kernels of a handle that never
     had conditions."""
-    with torch.cuda.device(self.device):
-      _ffi.check(_ffi.initial_conditions_entry("sb_initial_conditions_detach")(self._h), "sb_initial_conditions_detach")
+    self._draws_call("sb_initial_conditions_detach", value_errors=())
     self._initial_conditions = None
 
   @property
@@ -977,22 +992,11 @@ class BatchedSimulator:
   def initial_condition_episodes(self) -> torch.Tensor:
     """sb_initial_conditions_episodes_get: int32 [B] on the device, the number of every building's NEXT episode.
     ``save_state`` / ``load_state`` leave the counters alone; a checkpoint keeps them with this pair."""
-    out = torch.empty((self.B,), dtype=torch.int32, device=self.tdev)
-    rc = _ffi.initial_conditions_entry("sb_initial_conditions_episodes_get")(self._h, C.c_void_p(out.data_ptr()), self._stream())
-    if rc == -5:   # SB_ERR_UNSUPPORTED
-      raise ValueError((self._lib.sb_last_error() or b"").decode())
-    _ffi.check(rc, "sb_initial_conditions_episodes_get")
-    return out
+    return self._episodes_get("sb_initial_conditions_episodes_get")
 
   def set_initial_condition_episodes(self, t: torch.Tensor) -> None:
     """sb_initial_conditions_episodes_set: the counters <- t (int32 [B] on the device, contiguous)."""
-    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (self.B,) or t.device != self.tdev
-        or not t.is_contiguous()):
-      raise ValueError(f"the episode numbers must be a contiguous int32 [{self.B}] tensor on {self.tdev}")
-    rc = _ffi.initial_conditions_entry("sb_initial_conditions_episodes_set")(self._h, C.c_void_p(t.data_ptr()), self._stream())
-    if rc == -5:
-      raise ValueError((self._lib.sb_last_error() or b"").decode())
-    _ffi.check(rc, "sb_initial_conditions_episodes_set")
+    self._episodes_set("sb_initial_conditions_episodes_set", t)
 
   # ---- parameters and materials re-drawn per episode (sb_randomization_attach) ----
   def _randomization_bases(self):
@@ -1016,14 +1020,9 @@ class BatchedSimulator:
       raise ValueError("randomization_attach: not while the stream is being captured into a graph (the call synchronises the device)")
     bases = self._randomization_bases()
     er.check(self.B, bases[0], bases[1], self.solver)
-    fn = _ffi.randomization_entry("sb_randomization_attach")
     arr, keep = er.c_fields(len(self._slot_table) if self._materials_handle else None)
-    with torch.cuda.device(self.device):
-      rc = fn(self._h, arr, len(er.fields), er.seed, er.first_building)
+    self._draws_call("sb_randomization_attach", arr, len(er.fields), er.seed, er.first_building)
     del keep
-    if rc in (-1, -5):   # SB_ERR_INVALID, SB_ERR_UNSUPPORTED
-      raise ValueError((self._lib.sb_last_error() or b"").decode())
-    _ffi.check(rc, "sb_randomization_attach")
     self._randomization, self._randomization_base = er, bases
 
   def randomization_detach(self) -> None:
@@ -1031,8 +1030,7 @@ class BatchedSimulator:
     the resets launch what they launched before."""
     if torch.cuda.is_current_stream_capturing():
       raise ValueError("randomization_detach: not while the stream is being captured into a graph (the call synchronises the device)")
-    with torch.cuda.device(self.device):
-      _ffi.check(_ffi.randomization_entry("sb_randomization_detach")(self._h), "sb_randomization_detach")
+    self._draws_call("sb_randomization_detach", value_errors=())
     self._randomization = self._randomization_base = None
 
   @property
@@ -1048,11 +1046,7 @@ class BatchedSimulator:
 
   def _rows_out(self, name: str, n_rows: int) -> torch.Tensor:
     out = torch.empty((n_rows, self.B), dtype=torch.float64, device=self.tdev)
-    with torch.cuda.device(self.device):
-      rc = _ffi.randomization_entry(name)(self._h, C.c_void_p(out.data_ptr()), self._stream())
-    if rc == -5:   # SB_ERR_UNSUPPORTED
-      raise ValueError((self._lib.sb_last_error() or b"").decode())
-    _ffi.check(rc, name)
+    self._draws_call(name, C.c_void_p(out.data_ptr()), self._stream(), value_errors=(-5,))
     return out
 
   def building_param_rows(self) -> torch.Tensor:
@@ -1070,33 +1064,14 @@ class BatchedSimulator:
   def randomization_episodes(self) -> torch.Tensor:
     """sb_randomization_episodes_get: int32 [B] on the device, the number of every building's NEXT episode.  Snapshots
     carry neither the rows nor the counters: a checkpoint keeps the counters with this pair."""
-    out = torch.empty((self.B,), dtype=torch.int32, device=self.tdev)
-    rc = _ffi.randomization_entry("sb_randomization_episodes_get")(self._h, C.c_void_p(out.data_ptr()), self._stream())
-    if rc == -5:   # SB_ERR_UNSUPPORTED
-      raise ValueError((self._lib.sb_last_error() or b"").decode())
-    _ffi.check(rc, "sb_randomization_episodes_get")
-    return out
+    return self._episodes_get("sb_randomization_episodes_get")
 
   def set_randomization_episodes(self, t: torch.Tensor) -> None:
     """sb_randomization_episodes_set: the counters <- t (int32 [B] on the device, contiguous), and the rows in force
     <- ``values(b, t[b] - 1)`` (the base row where t[b] == 0), coefficient rows included."""
-    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (self.B,) or t.device != self.tdev
-        or not t.is_contiguous()):
-      raise ValueError(f"the episode numbers must be a contiguous int32 [{self.B}] tensor on {self.tdev}")
-    with torch.cuda.device(self.device):
-      rc = _ffi.randomization_entry("sb_randomization_episodes_set")(self._h, C.c_void_p(t.data_ptr()), self._stream())
-    if rc == -5:
-      raise ValueError((self._lib.sb_last_error() or b"").decode())
-    _ffi.check(rc, "sb_randomization_episodes_set")
+    self._episodes_set("sb_randomization_episodes_set", t)
 
   # ---- a start time and weather per building, drawn per episode (sb_episode_starts_attach) ----
-  def _starts_call(self, name: str, *args) -> None:
-    with torch.cuda.device(self.device):
-      rc = _ffi.episode_starts_entry(name)(self._h, *args)
-    if rc in (-1, -5):   # SB_ERR_INVALID, SB_ERR_UNSUPPORTED
-      raise ValueError((self._lib.sb_last_error() or b"").decode())
-    _ffi.check(rc, name)
-
   def episode_starts_attach(self, es: host_inputs.EpisodeStarts, weather_lohi: Optional[torch.Tensor] = None,
                             weather_offset: Optional[torch.Tensor] = None) -> None:
     """sb_episode_starts_attach: from now on every reset of a building -- ``reset``, ``reset_buildings``, the autoreset --
@@ -1115,14 +1090,14 @@ class BatchedSimulator:
         raise ValueError(f"{name} must be a contiguous float64 {list(shape)} tensor on {self.tdev}")
     desc, keep = es.c_desc(0 if weather_lohi is None else weather_lohi.data_ptr(),
                            0 if weather_offset is None else weather_offset.data_ptr())
-    self._starts_call("sb_episode_starts_attach", C.byref(desc))
+    self._draws_call("sb_episode_starts_attach", C.byref(desc))
     del keep
     self._episode_starts = es
 
   def episode_starts_detach(self) -> None:
     """sb_episode_starts_detach: from its next reset on, every building is back on its attached offset and the weather
     entries of the attach, bit for bit; the episode in progress finishes where it is."""
-    self._starts_call("sb_episode_starts_detach")
+    self._draws_call("sb_episode_starts_detach")
     self._episode_starts = None
 
   @property
@@ -1133,17 +1108,12 @@ class BatchedSimulator:
     """sb_episode_starts_episodes_get: int32 [B] on the device, the number of every building's NEXT episode (this
     feature's own counter).  Snapshots carry neither the values nor the counters: a checkpoint keeps the counters with
     this pair."""
-    out = torch.empty((self.B,), dtype=torch.int32, device=self.tdev)
-    self._starts_call("sb_episode_starts_episodes_get", C.c_void_p(out.data_ptr()), self._stream())
-    return out
+    return self._episodes_get("sb_episode_starts_episodes_get", value_errors=(-1, -5))
 
   def set_episode_start_episodes(self, t: torch.Tensor) -> None:
     """sb_episode_starts_episodes_set: the counters <- t (int32 [B] on the device, contiguous), and the values in force
     <- ``values(b, t[b] - 1)`` (the attached values where t[b] == 0)."""
-    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (self.B,) or t.device != self.tdev
-        or not t.is_contiguous()):
-      raise ValueError(f"the episode numbers must be a contiguous int32 [{self.B}] tensor on {self.tdev}")
-    self._starts_call("sb_episode_starts_episodes_set", C.c_void_p(t.data_ptr()), self._stream())
+    self._episodes_set("sb_episode_starts_episodes_set", t, value_errors=(-1, -5))
 
   def clock_offsets_in_force(self) -> Tuple[torch.Tensor, torch.Tensor]:
     """sb_episode_starts_values_get: (offsets, effective offsets), int32 [B] each, stream-ordered copies -- the buildings'
@@ -1151,7 +1121,7 @@ class BatchedSimulator:
     building's restart position)."""
     offs = torch.empty((self.B,), dtype=torch.int32, device=self.tdev)
     eff = torch.empty_like(offs)
-    self._starts_call("sb_episode_starts_values_get", C.c_void_p(offs.data_ptr()), C.c_void_p(eff.data_ptr()), self._stream())
+    self._draws_call("sb_episode_starts_values_get", C.c_void_p(offs.data_ptr()), C.c_void_p(eff.data_ptr()), self._stream())
     return offs, eff
 
   def clock_set_offsets(self, offsets: np.ndarray) -> None:
@@ -1160,7 +1130,7 @@ class BatchedSimulator:
     offsets = np.ascontiguousarray(offsets, dtype=np.int32)
     if offsets.shape != (self.B,):
       raise ValueError(f"clock_set_offsets needs offsets [{self.B}]")
-    self._starts_call("sb_clock_set_offsets", offsets.ctypes.data_as(C.c_void_p), self._stream())
+    self._draws_call("sb_clock_set_offsets", offsets.ctypes.data_as(C.c_void_p), self._stream())
     self._clock_offsets = offsets.copy()
 
   # ---- state snapshots (sb_state_save / sb_state_load) ----

@@ -23,6 +23,8 @@ from zoneinfo import ZoneInfo
 
 import numpy as np
 
+from . import _ffi
+
 UTC = dt.timezone.utc
 _SECONDS_IN_A_DAY = 24 * 3600
 _DAYS_IN_A_YEAR = 365
@@ -1418,7 +1420,12 @@ def effective_building_materials(materials: Optional[BuildingMaterials], slot_ta
 
 
 # ---------------------------------------------------------------- start temperatures per building
-INITIAL_CONDITIONS_TAG = 0xC1C00000   # SB_INITIAL_CONDITIONS_TAG (include/sbsim_amd.h): the draws' last counter word
+# the three attachments' draws: the last counter word is the tag (| the field's number); _ffi states them from include/sbsim_amd.h
+INITIAL_CONDITIONS_TAG, RANDOMIZATION_TAG, EPISODE_STARTS_TAG = (
+    _ffi.SB_INITIAL_CONDITIONS_TAG, _ffi.SB_RANDOMIZATION_TAG, _ffi.SB_EPISODE_STARTS_TAG)
+RAND_MATERIAL = _ffi.SB_RAND_MATERIAL            # id of material field f
+RAND_MAX_CHOICES = _ffi.SB_RAND_MAX_CHOICES
+START_MAX_K = _ffi.SB_START_MAX_K
 _M32 = 0xFFFFFFFF
 
 
@@ -1433,6 +1440,169 @@ def _philox_block(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int,
     c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
     k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
   return c0, c1, c2, c3
+
+
+class Uniform:
+  """d = lo + (hi - lo) * u, u the 53-bit uniform of the field's Philox block: a value in [lo, hi].  ``scale``: the
+  field's value is the building's own base row times d.  For a window field (``comfort_temp_window``,
+  ``eco_temp_window``) lo and hi are pairs, one interval per edge: ``Uniform((293.0, 296.5), (295.0, 299.0))`` draws
+  edge 0 in [293, 295] and edge 1 in [296.5, 299]."""
+
+  def __init__(self, lo, hi, scale: bool = False):
+    self.lo, self.hi, self.scale = lo, hi, bool(scale)
+
+  def __repr__(self) -> str:
+    return f"Uniform({self.lo!r}, {self.hi!r}, scale={self.scale})"
+
+
+class Choice:
+  """d = values[(c0 * K) >> 32], c0 the first word of the field's Philox block: one of K <= 65,536 values, integer
+  arithmetic only (a log-spaced table is how a log-uniform draw stays bit for bit).  ``scale`` as ``Uniform``'s."""
+
+  def __init__(self, values, scale: bool = False):
+    self.values, self.scale = values, bool(scale)
+
+  def __repr__(self) -> str:
+    return f"Choice({self.values!r}, scale={self.scale})"
+
+
+class UniformInt:
+  """d = lo + step * ((c0 * K) >> 32), K = (hi - lo) // step + 1, c0 the first word of the field's Philox block: one of
+  the K <= 2^22 whole numbers lo, lo + step, ... <= hi, integer arithmetic only (``EpisodeStarts(offsets=...)``)."""
+
+  def __init__(self, lo, hi, step=1):
+    self.lo, self.hi, self.step = lo, hi, step
+
+  def __repr__(self) -> str:
+    return f"UniformInt({self.lo!r}, {self.hi!r}, step={self.step!r})"
+
+
+class _Dist(NamedTuple):
+  """One parsed distribution, as the three per-episode attachments keep it."""
+  kind: int                    # sb_rand_kind: 0 Uniform, 1 Choice, 2 UniformInt
+  lo: float
+  hi: float
+  step: int
+  values: Tuple[float, ...]
+  scale: bool
+
+  @property
+  def k(self) -> int:
+    return len(self.values) if self.kind == _ffi.SB_RAND_CHOICE else (int(self.hi) - int(self.lo)) // self.step + 1
+
+  def span(self) -> Tuple[float, float]:
+    """The smallest and the largest possible draw."""
+    if self.kind == _ffi.SB_RAND_CHOICE:
+      return min(self.values), max(self.values)
+    if self.kind == _ffi.SB_RAND_UNIFORM_INT:
+      return self.lo, float(int(self.lo) + self.step * (self.k - 1))
+    return self.lo, self.hi
+
+
+def _whole(v) -> bool:
+  if isinstance(v, (bool, np.bool_)):
+    return False
+  if isinstance(v, (int, np.integer)):
+    return True
+  return isinstance(v, (float, np.floating)) and math.isfinite(v) and float(v) == math.floor(v)
+
+
+def _parse_dist(name: str, dist, *, offset: bool = False, allow_scale: bool = True) -> _Dist:
+  """``dist`` of field ``name`` checked: a ``Uniform`` or a ``Choice``; ``offset`` (rows of a timeline): a ``UniformInt``
+  or a ``Choice`` of whole numbers in 0 .. 2^22.  ValueError naming the field."""
+  if isinstance(dist, UniformInt) and offset:
+    if not (_whole(dist.lo) and _whole(dist.hi)):
+      raise ValueError(f"{name}: UniformInt needs whole numbers of rows, got ({dist.lo!r}, {dist.hi!r})")
+    lo, hi = int(dist.lo), int(dist.hi)
+    if lo < 0:
+      raise ValueError(f"{name}: negative offset {lo}")
+    if lo > hi:
+      raise ValueError(f"{name}: lo {lo} > hi {hi}")
+    if not _whole(dist.step) or int(dist.step) < 1:
+      raise ValueError(f"{name}: step must be an integer >= 1, got {dist.step!r}")
+    if hi > (1 << 22):
+      raise ValueError(f"{name}: offset {hi} is beyond the 2^22 rows a timeline may have")
+    d = _Dist(_ffi.SB_RAND_UNIFORM_INT, float(lo), float(hi), int(dist.step), (), False)
+    if d.k > START_MAX_K:
+      raise ValueError(f"{name}: K == {d.k} is more than 2^22")
+    return d
+  if isinstance(dist, Choice):
+    if dist.scale and not allow_scale:
+      raise ValueError(f"{name}: scale is not supported here" + (" (relative=True adds the draw to the attached offset)" if offset else ""))
+    try:
+      v = np.array(dist.values, dtype=np.float64)
+    except (TypeError, ValueError):
+      raise ValueError(f"{name}: Choice needs a list of numbers, got {dist.values!r}") from None
+    if v.ndim != 1:
+      raise ValueError(f"{name}: Choice needs a list of values, got shape {v.shape}")
+    if v.size == 0 or v.size > RAND_MAX_CHOICES:
+      raise ValueError(f"{name}: a Choice needs 1 .. 65,536 values, got K == {v.size}")
+    if not np.isfinite(v).all():
+      raise ValueError(f"{name}: choice {int(np.argmin(np.isfinite(v)))} is not finite")
+    if offset:
+      for j, x in enumerate(np.asarray(dist.values).tolist()):
+        if not _whole(x):
+          raise ValueError(f"{name}: choice {j} must be a whole number of rows, got {x!r}")
+        if x < 0:
+          raise ValueError(f"{name}: choice {j}: negative offset {x}")
+        if x > (1 << 22):
+          raise ValueError(f"{name}: choice {j}: offset {x} is beyond the 2^22 rows a timeline may have")
+    return _Dist(_ffi.SB_RAND_CHOICE, 0.0, 0.0, 1, tuple(float(x) for x in v), dist.scale)
+  if isinstance(dist, Uniform) and not offset:
+    if dist.scale and not allow_scale:
+      raise ValueError(f"{name}: scale is not supported here")
+    try:
+      lo, hi = float(dist.lo), float(dist.hi)
+    except (TypeError, ValueError):
+      raise ValueError(f"{name}: Uniform needs one lo and one hi, got ({dist.lo!r}, {dist.hi!r})") from None
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+      raise ValueError(f"{name}: lo and hi must be finite, got ({lo}, {hi})")
+    if lo > hi:
+      raise ValueError(f"{name}: lo {lo} > hi {hi}")
+    return _Dist(_ffi.SB_RAND_UNIFORM, lo, hi, 1, (), dist.scale)
+  raise ValueError(f"{name}: the distribution must be " + ("a UniformInt or a Choice of integer rows" if offset else "a Uniform or a Choice")
+                   + f", got {dist!r}")
+
+
+def _episode_draw(dist: _Dist, tag_word: int, seed: int, gb: int, e: int):
+  """d of one field for global building gb in its episode number e (the formulas of include/sbsim_amd.h, on Python integers
+  and IEEE doubles: one rounding per operation): from the Philox4x32-10 block keyed by the seed with counter (gb lo, gb hi,
+  e, tag_word).  An int for a ``UniformInt``."""
+  c = _philox_block((gb & _M32, gb >> 32, int(e) & _M32, tag_word), (seed & _M32, seed >> 32))
+  if dist.kind == _ffi.SB_RAND_UNIFORM:
+    r = (c[1] << 32) | c[0]
+    return dist.lo + (dist.hi - dist.lo) * (float(r >> 11) * 2.0 ** -53)
+  i = (c[0] * dist.k) >> 32
+  return dist.values[i] if dist.kind == _ffi.SB_RAND_CHOICE else int(dist.lo) + dist.step * i
+
+
+def _fill_c_dist(cf, dist: _Dist, keep: list) -> None:
+  """kind and lo / hi or choices / n_choices of a sb_rand_field or a sb_start_field; ``keep`` gets what ``choices`` points into."""
+  cf.kind = dist.kind
+  if dist.kind == _ffi.SB_RAND_CHOICE:
+    v = np.ascontiguousarray(dist.values, dtype=np.float64)
+    keep.append(v)
+    cf.n_choices, cf.choices = len(dist.values), v.ctypes.data_as(_ffi._dp)
+  else:
+    cf.lo, cf.hi = dist.lo, dist.hi
+
+
+def _check_seed_first(seed, first_building) -> Tuple[int, int]:
+  if isinstance(seed, (bool, float)) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+    raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+  if isinstance(first_building, (bool, float)) or int(first_building) != first_building or first_building < 0:
+    raise ValueError(f"first_building must be an integer >= 0, got {first_building!r}")
+  return int(seed), int(first_building)
+
+
+def _moved_first(self, lo: int):
+  """``rows(lo)`` of an attachment without [B] arrays: a copy with ``first_building`` moved, so that buildings lo .. of a
+  larger batch draw what they drew in the whole batch."""
+  if lo < 0:
+    raise ValueError(f"rows: lo must be >= 0, got {lo}")
+  out = copy.copy(self)
+  out.first_building = self.first_building + int(lo)
+  return out
 
 
 def _per_building(name: str, arr, dtype) -> np.ndarray:
@@ -1574,10 +1744,7 @@ class InitialConditions:
     """u(b, e): the jitter of building b's episode number e -- lo + (hi - lo) * ((r >> 11) * 2^-53), r the first two
     words of the Philox4x32-10 block keyed by the seed with counter (global building lo, hi, e, INITIAL_CONDITIONS_TAG)."""
     lo, hi, seed = self.jitter
-    gb = self.first_building + int(b)
-    c = _philox_block((gb & _M32, gb >> 32, int(e) & _M32, INITIAL_CONDITIONS_TAG), (seed & _M32, seed >> 32))
-    r = (c[1] << 32) | c[0]
-    return lo + (hi - lo) * (float(r >> 11) * 2.0 ** -53)
+    return _episode_draw(_Dist(_ffi.SB_RAND_UNIFORM, lo, hi, 1, (), False), INITIAL_CONDITIONS_TAG, seed, self.first_building + int(b), e)
 
   def start_temps(self, b: int, e: int, initial_temp: Optional[float] = None, shape: Optional[Tuple[int, int]] = None) -> np.ndarray:
     """The grid [H, W] (caller's orientation) building b starts its episode number e from, in float64 with one rounding
@@ -1609,44 +1776,11 @@ class InitialConditions:
 
 
 # ---------------------------------------------------------------- parameters and materials re-drawn per episode
-RANDOMIZATION_TAG = 0xE9150000   # SB_RANDOMIZATION_TAG (include/sbsim_amd.h): the draws' last counter word is this | id
-RAND_MATERIAL = 0x100            # SB_RAND_MATERIAL: id of material field f
-RAND_MAX_CHOICES = 65536
-
-
-class Uniform:
-  """d = lo + (hi - lo) * u, u the 53-bit uniform of the field's Philox block: a value in [lo, hi].  ``scale``: the
-  field's value is the building's own base row times d.  For a window field (``comfort_temp_window``,
-  ``eco_temp_window``) lo and hi are pairs, one interval per edge: ``Uniform((293.0, 296.5), (295.0, 299.0))`` draws
-  edge 0 in [293, 295] and edge 1 in [296.5, 299]."""
-
-  def __init__(self, lo, hi, scale: bool = False):
-    self.lo, self.hi, self.scale = lo, hi, bool(scale)
-
-  def __repr__(self) -> str:
-    return f"Uniform({self.lo!r}, {self.hi!r}, scale={self.scale})"
-
-
-class Choice:
-  """d = values[(c0 * K) >> 32], c0 the first word of the field's Philox block: one of K <= 65,536 values, integer
-  arithmetic only (a log-spaced table is how a log-uniform draw stays bit for bit).  ``scale`` as ``Uniform``'s."""
-
-  def __init__(self, values, scale: bool = False):
-    self.values, self.scale = values, bool(scale)
-
-  def __repr__(self) -> str:
-    return f"Choice({self.values!r}, scale={self.scale})"
-
-
 class _RandField(NamedTuple):
   name: str        # as messages and ``values`` name it: the SimConfig field (with [edge]), kind[slot], convection_coefficient
   param: Optional[int]                  # sb_building_param, or None for a material field
   material: Optional[Tuple[int, int]]   # (kind, slot); kind 3: the convection coefficient
-  choice: bool
-  scale: bool
-  lo: float
-  hi: float
-  values: Tuple[float, ...]
+  dist: _Dist
 
   def ident(self, n_slots: Optional[int]) -> int:
     if self.param is not None:
@@ -1655,9 +1789,6 @@ class _RandField(NamedTuple):
       raise ValueError(f"{self.name}: a material field's number needs the plan's slot count (n_slots)")
     kind, slot = self.material
     return RAND_MATERIAL + (3 * n_slots if kind == 3 else kind * n_slots + slot)
-
-  def span(self) -> Tuple[float, float]:
-    return (min(self.values), max(self.values)) if self.choice else (self.lo, self.hi)
 
 
 def _items(table, what: str):
@@ -1692,7 +1823,6 @@ class EpisodeRandomization:
   the batch."""
 
   def __init__(self, params=None, materials=None, seed: int = 0, first_building: int = 0):
-    from . import _ffi
     index = {name: k for k, name in enumerate(_ffi.BUILDING_PARAM_FIELDS)}
     fields: List[_RandField] = []
     seen = set()
@@ -1702,27 +1832,7 @@ class EpisodeRandomization:
       if key in seen:
         raise ValueError(f"{name} is named twice")
       seen.add(key)
-      if isinstance(dist, Uniform):
-        try:
-          lo, hi = float(dist.lo), float(dist.hi)
-        except (TypeError, ValueError):
-          raise ValueError(f"{name}: Uniform needs one lo and one hi, got ({dist.lo!r}, {dist.hi!r})") from None
-        if not (math.isfinite(lo) and math.isfinite(hi)):
-          raise ValueError(f"{name}: lo and hi must be finite, got ({lo}, {hi})")
-        if lo > hi:
-          raise ValueError(f"{name}: lo {lo} > hi {hi}")
-        fields.append(_RandField(name, param, material, False, dist.scale, lo, hi, ()))
-      elif isinstance(dist, Choice):
-        v = np.array(dist.values, dtype=np.float64)
-        if v.ndim != 1:
-          raise ValueError(f"{name}: Choice needs a list of values, got shape {v.shape}")
-        if v.size == 0 or v.size > RAND_MAX_CHOICES:
-          raise ValueError(f"{name}: a Choice needs 1 .. 65,536 values, got K == {v.size}")
-        if not np.isfinite(v).all():
-          raise ValueError(f"{name}: choice {int(np.argmin(np.isfinite(v)))} is not finite")
-        fields.append(_RandField(name, param, material, True, dist.scale, 0.0, 0.0, tuple(float(x) for x in v)))
-      else:
-        raise ValueError(f"{name}: the distribution must be a Uniform or a Choice, got {dist!r}")
+      fields.append(_RandField(name, param, material, _parse_dist(name, dist)))
 
     for name, dist in _items(params, "params"):
       if name in PER_BATCH_CONFIG_FIELDS:
@@ -1758,12 +1868,8 @@ class EpisodeRandomization:
         raise ValueError(f"unknown material field {kind!r}; allowed: {', '.join(_MATERIAL_KINDS)}, convection_coefficient")
     if not fields:
       raise ValueError("EpisodeRandomization needs at least one field (pass None instead of one to clear it)")
-    if isinstance(seed, (bool, float)) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
-      raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
-    if isinstance(first_building, (bool, float)) or int(first_building) != first_building or first_building < 0:
-      raise ValueError(f"first_building must be an integer >= 0, got {first_building!r}")
+    self.seed, self.first_building = _check_seed_first(seed, first_building)
     self.fields = tuple(fields)
-    self.seed, self.first_building = int(seed), int(first_building)
 
   @property
   def has_materials(self) -> bool:
@@ -1776,22 +1882,12 @@ class EpisodeRandomization:
   def rows(self, lo: int, hi: int = None) -> "EpisodeRandomization":
     """The same randomisation for buildings lo .. of a larger batch: ``first_building`` moved so that they draw what they
     drew in the whole batch."""
-    if lo < 0:
-      raise ValueError(f"rows: lo must be >= 0, got {lo}")
-    out = copy.copy(self)
-    out.first_building = self.first_building + int(lo)
-    return out
+    return _moved_first(self, lo)
 
   def draw(self, field: _RandField, b: int, e: int, n_slots: Optional[int] = None) -> float:
     """d of ``field`` for building b in its episode number e (the formula of include/sbsim_amd.h, on Python integers and
     IEEE doubles: one rounding per operation)."""
-    gb = self.first_building + int(b)
-    c = _philox_block((gb & _M32, gb >> 32, int(e) & _M32, RANDOMIZATION_TAG | field.ident(n_slots)),
-                      (self.seed & _M32, self.seed >> 32))
-    if field.choice:
-      return field.values[(c[0] * len(field.values)) >> 32]
-    r = (c[1] << 32) | c[0]
-    return field.lo + (field.hi - field.lo) * (float(r >> 11) * 2.0 ** -53)
+    return _episode_draw(field.dist, RANDOMIZATION_TAG | field.ident(n_slots), self.seed, self.first_building + int(b), e)
 
   @staticmethod
   def _base_of(field: _RandField, base, b: int) -> float:
@@ -1824,7 +1920,7 @@ class EpisodeRandomization:
     out: Dict[str, object] = {}
     for f in self.fields:
       d = self.draw(f, b, e, n_slots)
-      if f.scale:
+      if f.dist.scale:
         if base is None:
           raise ValueError(f"{f.name}: a scale field needs the base rows")
         d = self._base_of(f, base, b) * d
@@ -1877,10 +1973,11 @@ class EpisodeRandomization:
     for f in self.fields:
       if f.material is not None and f.material[0] != 3 and f.material[1] >= M:
         raise ValueError(f"{f.name}: the floor plan has {M} material slots (FloorPlan.material_slots())")
-      lo, hi = f.span()
-      b0 = self._base_column(f, base) if f.scale else None
+      lo, hi = f.dist.span()
+      scale = f.dist.scale
+      b0 = self._base_column(f, base) if scale else None
       with np.errstate(over="ignore", invalid="ignore"):   # (an overflow is what the next lines refuse)
-        x, y = (b0 * lo, b0 * hi) if f.scale else (np.full(B, lo), np.full(B, hi))
+        x, y = (b0 * lo, b0 * hi) if scale else (np.full(B, lo), np.full(B, hi))
       ok = np.isfinite(x) & np.isfinite(y)
       if not ok.all():
         raise ValueError(f"building {first_bad(ok)}: {f.name} can be drawn not finite")
@@ -1897,7 +1994,6 @@ class EpisodeRandomization:
         raise ValueError(f"building {b}: {f.name} must be positive, and can be drawn as {mn[b]}")
     if not self.has_params:
       return
-    from . import _ffi
     index = {name: k for k, name in enumerate(_ffi.BUILDING_PARAM_FIELDS)}
 
     def rng(name: str, edge: Optional[int] = None):
@@ -1930,125 +2026,22 @@ class EpisodeRandomization:
 
   def c_fields(self, n_slots: Optional[int]):
     """sb_randomization_attach's ``fields`` for a plan of n_slots material slots: the ctypes array and what it points into."""
-    import ctypes as C
-    from . import _ffi
     arr = (_ffi.RandField * len(self.fields))()
     keep = []
     for i, f in enumerate(self.fields):
-      arr[i].id, arr[i].scale = f.ident(n_slots), int(f.scale)
-      if f.choice:
-        v = np.ascontiguousarray(f.values, dtype=np.float64)
-        keep.append(v)
-        arr[i].kind, arr[i].n_choices, arr[i].choices = _ffi.SB_RAND_CHOICE, len(f.values), v.ctypes.data_as(_ffi._dp)
-      else:
-        arr[i].kind, arr[i].lo, arr[i].hi = _ffi.SB_RAND_UNIFORM, f.lo, f.hi
+      arr[i].id, arr[i].scale = f.ident(n_slots), int(f.dist.scale)
+      _fill_c_dist(arr[i], f.dist, keep)
     return arr, keep
 
   def digest(self) -> str:
     """A hash of everything attached (``BatchedSimulator.state_fingerprint``): the fields in the order of their numbers."""
-    rows = sorted((f.param is None, f.param, f.material, f.choice, f.scale, f.lo.hex(), f.hi.hex(),
-                   tuple(v.hex() for v in f.values)) for f in self.fields)
+    rows = sorted((f.param is None, f.param, f.material, d.kind == _ffi.SB_RAND_CHOICE, d.scale, d.lo.hex(), d.hi.hex(),
+                   tuple(v.hex() for v in d.values)) for f, d in ((f, f.dist) for f in self.fields))
     return hashlib.sha256(repr((rows, self.seed, self.first_building)).encode()).hexdigest()
 
 
 # ---------------------------------------------------------------- a start time and weather per building drawn per episode
-EPISODE_STARTS_TAG = 0xE5A70000   # SB_EPISODE_STARTS_TAG (include/sbsim_amd.h): the draws' last counter word is this | id
-START_MAX_K = 1 << 22             # SB_START_MAX_K
 START_FIELDS = ("offsets", "weather_low", "weather_high", "weather_shift")   # sb_start_field_id, in order
-
-
-class UniformInt:
-  """d = lo + step * ((c0 * K) >> 32), K = (hi - lo) // step + 1, c0 the first word of the field's Philox block: one of
-  the K <= 2^22 whole numbers lo, lo + step, ... <= hi, integer arithmetic only (``EpisodeStarts(offsets=...)``)."""
-
-  def __init__(self, lo, hi, step=1):
-    self.lo, self.hi, self.step = lo, hi, step
-
-  def __repr__(self) -> str:
-    return f"UniformInt({self.lo!r}, {self.hi!r}, step={self.step!r})"
-
-
-class _StartField(NamedTuple):
-  kind: int                    # 0 Uniform, 1 Choice, 2 UniformInt (sb_rand_kind, SB_RAND_UNIFORM_INT)
-  lo: float
-  hi: float
-  step: int
-  values: Tuple[float, ...]
-
-  @property
-  def k(self) -> int:
-    return (int(self.hi) - int(self.lo)) // self.step + 1
-
-  def span(self) -> Tuple[float, float]:
-    """The smallest and the largest possible draw."""
-    if self.kind == 1:
-      return min(self.values), max(self.values)
-    if self.kind == 2:
-      return self.lo, float(int(self.lo) + self.step * (self.k - 1))
-    return self.lo, self.hi
-
-
-def _whole(v) -> bool:
-  if isinstance(v, (bool, np.bool_)):
-    return False
-  if isinstance(v, (int, np.integer)):
-    return True
-  return isinstance(v, (float, np.floating)) and math.isfinite(v) and float(v) == math.floor(v)
-
-
-def _start_field(name: str, dist, offset: bool) -> _StartField:
-  if isinstance(dist, UniformInt) and offset:
-    if not (_whole(dist.lo) and _whole(dist.hi)):
-      raise ValueError(f"{name}: UniformInt needs whole numbers of rows, got ({dist.lo!r}, {dist.hi!r})")
-    lo, hi = int(dist.lo), int(dist.hi)
-    if lo < 0:
-      raise ValueError(f"{name}: negative offset {lo}")
-    if lo > hi:
-      raise ValueError(f"{name}: lo {lo} > hi {hi}")
-    if not _whole(dist.step) or int(dist.step) < 1:
-      raise ValueError(f"{name}: step must be an integer >= 1, got {dist.step!r}")
-    if hi > (1 << 22):
-      raise ValueError(f"{name}: offset {hi} is beyond the 2^22 rows a timeline may have")
-    f = _StartField(2, float(lo), float(hi), int(dist.step), ())
-    if f.k > START_MAX_K:
-      raise ValueError(f"{name}: K == {f.k} is more than 2^22")
-    return f
-  if isinstance(dist, Choice):
-    if dist.scale:
-      raise ValueError(f"{name}: scale is not supported here" + (" (relative=True adds the draw to the attached offset)" if offset else ""))
-    try:
-      v = np.array(dist.values, dtype=np.float64)
-    except (TypeError, ValueError):
-      raise ValueError(f"{name}: Choice needs a list of numbers, got {dist.values!r}") from None
-    if v.ndim != 1:
-      raise ValueError(f"{name}: Choice needs a list of values, got shape {v.shape}")
-    if v.size == 0 or v.size > RAND_MAX_CHOICES:
-      raise ValueError(f"{name}: a Choice needs 1 .. 65,536 values, got K == {v.size}")
-    if not np.isfinite(v).all():
-      raise ValueError(f"{name}: choice {int(np.argmin(np.isfinite(v)))} is not finite")
-    if offset:
-      for j, x in enumerate(np.asarray(dist.values).tolist()):
-        if not _whole(x):
-          raise ValueError(f"{name}: choice {j} must be a whole number of rows, got {x!r}")
-        if x < 0:
-          raise ValueError(f"{name}: choice {j}: negative offset {x}")
-        if x > (1 << 22):
-          raise ValueError(f"{name}: choice {j}: offset {x} is beyond the 2^22 rows a timeline may have")
-    return _StartField(1, 0.0, 0.0, 1, tuple(float(x) for x in v))
-  if isinstance(dist, Uniform) and not offset:
-    if dist.scale:
-      raise ValueError(f"{name}: scale is not supported here")
-    try:
-      lo, hi = float(dist.lo), float(dist.hi)
-    except (TypeError, ValueError):
-      raise ValueError(f"{name}: Uniform needs one lo and one hi, got ({dist.lo!r}, {dist.hi!r})") from None
-    if not (math.isfinite(lo) and math.isfinite(hi)):
-      raise ValueError(f"{name}: lo and hi must be finite, got ({lo}, {hi})")
-    if lo > hi:
-      raise ValueError(f"{name}: lo {lo} > hi {hi}")
-    return _StartField(0, lo, hi, 1, ())
-  raise ValueError(f"{name}: the distribution must be " + ("a UniformInt or a Choice of integer rows" if offset else "a Uniform or a Choice")
-                   + f", got {dist!r}")
 
 
 class EpisodeStarts:
@@ -2070,20 +2063,16 @@ class EpisodeStarts:
   def __init__(self, offsets=None, relative: bool = False, weather_low=None, weather_high=None, weather_shift=None,
                seed: int = 0, first_building: int = 0):
     given = dict(zip(START_FIELDS, (offsets, weather_low, weather_high, weather_shift)))
-    self.fields: Dict[str, _StartField] = {name: _start_field(name, dist, name == "offsets")
-                                           for name, dist in given.items() if dist is not None}
+    self.fields: Dict[str, _Dist] = {name: _parse_dist(name, dist, offset=name == "offsets", allow_scale=False)
+                                     for name, dist in given.items() if dist is not None}
     if not self.fields:
       raise ValueError("EpisodeStarts needs at least one field (pass None instead of one to clear it)")
     if "weather_low" in self.fields and "weather_high" in self.fields:
       lo_max, hi_min = self.fields["weather_low"].span()[1], self.fields["weather_high"].span()[0]
       if lo_max > hi_min:
         raise ValueError(f"weather_low: low can be drawn as {lo_max}, above a high of {hi_min}")
-    if isinstance(seed, (bool, float)) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
-      raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
-    if isinstance(first_building, (bool, float)) or int(first_building) != first_building or first_building < 0:
-      raise ValueError(f"first_building must be an integer >= 0, got {first_building!r}")
+    self.seed, self.first_building = _check_seed_first(seed, first_building)
     self.relative = bool(relative)
-    self.seed, self.first_building = int(seed), int(first_building)
 
   @property
   def has_offsets(self) -> bool:
@@ -2092,26 +2081,13 @@ class EpisodeStarts:
   def rows(self, lo: int, hi: int = None) -> "EpisodeStarts":
     """The same starts for buildings lo .. of a larger batch: ``first_building`` moved so that they draw what they drew
     in the whole batch."""
-    if lo < 0:
-      raise ValueError(f"rows: lo must be >= 0, got {lo}")
-    out = copy.copy(self)
-    out.first_building = self.first_building + int(lo)
-    return out
+    return _moved_first(self, lo)
 
   def draw(self, name: str, b: int, e: int):
     """d of field ``name`` for building b in its episode number e (the formula of include/sbsim_amd.h, on Python integers
     and IEEE doubles: one rounding per operation); an int for the offsets."""
-    f = self.fields[name]
-    gb = self.first_building + int(b)
-    c = _philox_block((gb & _M32, gb >> 32, int(e) & _M32, EPISODE_STARTS_TAG | START_FIELDS.index(name)),
-                      (self.seed & _M32, self.seed >> 32))
-    if f.kind == 2:
-      return int(f.lo) + f.step * ((c[0] * f.k) >> 32)
-    if f.kind == 1:
-      v = f.values[(c[0] * len(f.values)) >> 32]
-      return int(v) if name == "offsets" else v
-    r = (c[1] << 32) | c[0]
-    return f.lo + (f.hi - f.lo) * (float(r >> 11) * 2.0 ** -53)
+    d = _episode_draw(self.fields[name], EPISODE_STARTS_TAG | START_FIELDS.index(name), self.seed, self.first_building + int(b), e)
+    return int(d) if name == "offsets" else d
 
   def values(self, b: int, e: int, base_offsets=None) -> Dict[str, object]:
     """The value of every drawn field of building b in its episode number e -- what the device writes: "offsets" -> int
@@ -2166,18 +2142,12 @@ class EpisodeStarts:
 
   def c_desc(self, weather_lohi_ptr: int = 0, weather_offset_ptr: int = 0):
     """sb_episode_starts_attach's descriptor: the ctypes struct and what it points into."""
-    from . import _ffi
     d = _ffi.EpisodeStartsDesc()
     keep = []
     for name, f in self.fields.items():
       cf = d.field[START_FIELDS.index(name)]
-      cf.present, cf.kind, cf.step = 1, f.kind, f.step
-      if f.kind == 1:
-        v = np.ascontiguousarray(f.values, dtype=np.float64)
-        keep.append(v)
-        cf.n_choices, cf.choices = len(f.values), v.ctypes.data_as(_ffi._dp)
-      else:
-        cf.lo, cf.hi = f.lo, f.hi
+      cf.present, cf.step = 1, f.step
+      _fill_c_dist(cf, f, keep)
     d.relative = int(self.relative)
     d.weather_lohi_dev, d.weather_offset_dev = weather_lohi_ptr or None, weather_offset_ptr or None
     d.seed, d.first_building = self.seed, self.first_building

@@ -1,4 +1,4 @@
-"""Episode randomisation without a device: the draw of csrc/randomize.h (compiled for the host into a small program)
+"""Episode randomisation without a device: the draw of csrc/episode_draw.h (compiled for the host into a small program)
 against its NumPy restatement ``EpisodeRandomization.values``, bit for bit; pinned draws; ranges and independence of the
 field list; the refusals of host_inputs and of BatchedEnvironment, raised before anything is created."""
 import os
@@ -22,7 +22,7 @@ PROGRAM = textwrap.dedent("""
     #include <cstdio>
     #include <cstring>
     #include <vector>
-    #include "randomize.h"
+    #include "episode_draw.h"
     int main() {
       unsigned long long seed, gb;
       unsigned e;

@@ -1,4 +1,4 @@
-"""Episode starts without a device: the draw of csrc/episode_starts.h (compiled for the host into a small program) against
+"""Episode starts without a device: the draw of csrc/episode_draw.h (compiled for the host into a small program) against
 its restatement ``EpisodeStarts.values``, bit for bit; pinned draws; UniformInt's range; independence of the field list and
 of the shard; that the seeds of the GPU tests can show a failure; the Timeline's size and trace check; the refusals of
 host_inputs and of BatchedEnvironment, raised before anything is created."""
@@ -24,7 +24,7 @@ PROGRAM = textwrap.dedent("""
     #include <cstdio>
     #include <cstring>
     #include <vector>
-    #include "episode_starts.h"
+    #include "episode_draw.h"
     int main() {
       unsigned long long seed, gb;
       unsigned e;

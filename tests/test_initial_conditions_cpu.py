@@ -5,13 +5,15 @@ answers, the symbols of the library -- and the reference's own FloorPlanBasedBui
 margins that make equal sweep counts a legitimate demand."""
 import ctypes as C
 import os
+import subprocess
+import textwrap
 
 import numpy as np
 import pytest
 
 from oracle.occupancy_oracle import philox4x32_10
 from sbsim_amd import _ffi, build, host_inputs
-from sbsim_amd.host_inputs import InitialConditions
+from sbsim_amd.host_inputs import Choice, EpisodeRandomization, EpisodeStarts, InitialConditions, Uniform, UniformInt
 from tests import initial_conditions_cases as icc
 from tests.golden_util import load
 from tests.twins import oracle_twin
@@ -199,6 +201,85 @@ def test_the_tag_keeps_the_counters_apart():
   assert tag // 8 > 400_000_000   # occupancy queries of one handle before its counters reach the tag
   text = open(os.path.join(ROOT, "include", "sbsim_amd.h")).read()
   assert "#define SB_INITIAL_CONDITIONS_TAG 0xC1C00000u" in text
+
+
+# ---------------------------------------------------------------- the device's draw, built for the host
+# stdin: one draw per line -- seed gb e lo hi; stdout: the bits of csrc/episode_draw.h's initial_conditions_draw
+DRAW_PROGRAM = textwrap.dedent("""
+    #include <cinttypes>
+    #include <cstdio>
+    #include <cstring>
+    #include "episode_draw.h"
+    int main() {
+      unsigned long long seed, gb;
+      unsigned e;
+      double lo, hi;
+      while (std::scanf("%llu %llu %u %la %la", &seed, &gb, &e, &lo, &hi) == 5) {
+        const double u = sb::initial_conditions_draw(lo, hi, seed, gb, e);
+        uint64_t bits;
+        std::memcpy(&bits, &u, 8);
+        std::printf("%016" PRIx64 "\\n", bits);
+      }
+      return 0;
+    }
+""")
+
+
+def test_the_host_build_of_the_draw_equals_the_restatement_and_the_oracles_philox(tmp_path):
+  """The one draw of the three that k_reset_ic / k_reset_jacobi_ic call, compiled by a plain C++ compiler with one
+  rounding per operation, against ``InitialConditions.draw`` and against the formula on the oracle's Philox, bit for bit."""
+  src, exe = os.path.join(tmp_path, "draw.cpp"), os.path.join(tmp_path, "draw")
+  open(src, "w").write(DRAW_PROGRAM)
+  subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "sbsim_amd", "csrc"),
+                  "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
+  seeds = (0, 1, 2 ** 32 - 1, 2 ** 32, 0x9E3779B97F4A7C15, 2 ** 63 + 5, 2 ** 64 - 1)
+  buildings = (0, 1, 69, 2 ** 32 - 1, 2 ** 32, 2 ** 40 + 17)
+  episodes = (0, 1, 2, 1000, 2 ** 31, 2 ** 32 - 1)
+  intervals = ((-0.5, 0.5), (0.25, 0.25), (-3.0, -1.0 / 3.0), (288.15, 301.0))   # lo == hi; a negative lo
+  cases = [(s, gb, e, lo, hi) for s in seeds for gb in buildings for e in episodes for lo, hi in intervals]
+  text = "".join(f"{s} {gb} {e} {float(lo).hex()} {float(hi).hex()}\n" for s, gb, e, lo, hi in cases)
+  out = subprocess.run([exe], input=text, check=True, capture_output=True, text=True).stdout.split()
+  assert len(out) == len(cases)
+  for (seed, gb, e, lo, hi), bits in zip(cases, out):
+    got = np.array([int(bits, 16)], dtype=np.uint64).view(np.float64)[0]
+    restated = InitialConditions(jitter=(lo, hi, seed), first_building=gb).draw(0, e)
+    c = philox4x32_10(gb & 0xFFFFFFFF, gb >> 32, e & 0xFFFFFFFF, _ffi.SB_INITIAL_CONDITIONS_TAG, seed & 0xFFFFFFFF, seed >> 32)
+    r = (int(c[1]) << 32) | int(c[0])
+    spelled = lo + (hi - lo) * ((r >> 11) * 2.0 ** -53)
+    assert float(got).hex() == float(restated).hex() == float(spelled).hex(), (seed, gb, e, lo, hi)
+    assert lo <= got <= hi
+
+
+# ---------------------------------------------------------------- the digests snapshots compare
+def test_the_digests_of_the_three_attachments_are_those_of_the_commit_before_their_shared_core():
+  """``digest()`` goes into ``BatchedSimulator.state_fingerprint``: a snapshot taken before the three classes shared one
+  parsed distribution must still load.  The strings were recorded by running that commit's classes on these inputs."""
+  grids = np.arange(24, dtype=np.float64).reshape(2, 3, 4) * 0.125 + 290.0
+  cases = {
+      "ic_grids_jitter": InitialConditions(reset_temp_values=grids, grid_of=np.array([1, 0, 1], dtype=np.int32),
+                                           offset=np.array([-0.5, 0.0, 1.25]), jitter=(-0.5, 0.25, 2 ** 63 + 5), first_building=3),
+      "ic_base_jitter": InitialConditions(initial_temp=np.array([291.0, 294.5]), jitter=(0.0, 0.0, 7)),
+      "er_mixed": EpisodeRandomization(
+          params={"ahu_fan_efficiency": Uniform(0.7, 0.95), "vav_max_air_flow_rate": Uniform(0.8, 1.2, scale=True),
+                  "comfort_temp_window": Uniform((293.0, 296.5), (295.0, 299.0)),
+                  "boiler_reheat_water_setpoint": Choice([340.0, 350.0, 360.5])},
+          materials={"conductivity": {0: Choice([0.5, 1.0, 2.0], scale=True)}, "convection_coefficient": Uniform(6.0, 25.0)},
+          seed=2 ** 64 - 3, first_building=2 ** 32 + 1),
+      "er_pair": EpisodeRandomization(params={"eco_temp_window": (Choice([285.0, 287.0]), Uniform(300.0, 303.0))}, seed=7),
+      "es_int_step": EpisodeStarts(offsets=UniformInt(0, 364 * 288, step=288), weather_low=Uniform(268.0, 285.0),
+                                   weather_high=Choice([286.0, 290.5, 305.0]), seed=11),
+      "es_choice_relative": EpisodeStarts(offsets=Choice([0, 12, 288]), relative=True, weather_shift=Uniform(-3600.0, 7200.0),
+                                          seed=2 ** 40 + 17, first_building=69),
+  }
+  recorded = {
+      "ic_grids_jitter": "59f3c0f2f57640967ee912f8b19485e2fcb19e6c6df396e1ff89726c61da0190",
+      "ic_base_jitter": "b9cb79a576f628f69f22bac0ee77933d38a15a25748c8c8572c2acc2412b786e",
+      "er_mixed": "61a6f46bac90e706314705fb4571a099245a3141a8df619e866a740db2b3ddd1",
+      "er_pair": "38078404a1df9322ef39187a0bba05844f02c4826a4cb841c90925e3b35dd7ee",
+      "es_int_step": "d1dff216a04774e1b152256520e750e623a3126293b5f32e033eb9122bd38683",
+      "es_choice_relative": "b1d1653bada6c70dbcf3bc9b4d4ee4eb9e092b5b47092511e48446788c6ee6f2",
+  }
+  assert {name: a.digest() for name, a in cases.items()} == recorded
 
 
 # ---------------------------------------------------------------- the library, without a device
