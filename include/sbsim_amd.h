@@ -1023,6 +1023,73 @@ int sb_episode_starts_values_get(sb_handle *h, int32_t *offsets_dev, int32_t *ef
  * the offsets; SB_ERR_UNSUPPORTED without a clock. */
 int sb_clock_set_offsets(sb_handle *h, const int32_t *offsets_host /* [B] */, void *stream);
 
+/* Episode totals per building, on the device (the reference keeps _episode_cumulative_reward,
+ * environment/environment.py:422, 1172, 1315, and an accumulator of energy, cost, carbon, occupancy and regret series,
+ * :1099-1140, with utils/conversion_utils.py:173-213 for the kWh): what episode e of building b returned, used and cost.
+ * Off unless attached; a handle without the attachment launches exactly what it launched before.
+ *
+ * A row of SB_EM_FIELDS doubles per building (sb_episode_metric); integers are stored exactly.  Per step, with `reward`
+ * the fp32 value sb_step returned, I the building's info row as k_post wrote it (the columns are documented at sb_step),
+ * dt = sb_params.dt and K = 1.0 / 3600.0 / 1000.0, every product evaluated left to right with one rounding each:
+ *    0 episode                          the index of the building's current episode: the number of its episodes closed
+ *                                       since the attach
+ *    1 steps                            += 1
+ *    2 rejected_steps                   += 1 when reward is the rejection reward (-inf)
+ *    3 return                           += (double)reward; a -inf makes it -inf, as the reference's += does
+ *    4 accepted_return                  the same sum over the steps that were not rejected
+ *    5 electrical_energy [kWh]          += ((double)I[0] * dt * K + (double)I[1] * dt * K) + (double)I[3] * dt * K
+ *    6 natural_gas_energy [kWh]         += (double)I[2] * dt * K
+ *    7 electricity_energy_cost          += (double)I[9]
+ *    8 natural_gas_energy_cost          += (double)I[10]
+ *    9 carbon_emitted                   += (double)I[11]
+ *   10 total_occupancy                  += (double)I[17]
+ *   11 productivity_regret              += (double)I[20]
+ *   12 normalized_productivity_regret   += (double)I[21]
+ *   13 normalized_energy_cost           += (double)I[22]
+ *   14 normalized_carbon_emission       += (double)I[23]
+ *   15 productivity_reward              += (double)I[8]
+ *   16 sweeps                           += (double)I[4]
+ *   17 unconverged_steps                += 1 when I[5] == 0
+ *   18 zone_temp_min                    min over the building's zones of the post-update zone means (sb_get_zone_temps),
+ *   19 zone_temp_max                    max likewise; +inf / -inf before the first step
+ * The fp32 values widened to double are exactly what the reference accumulates (its proto fields are float).  Rejected
+ * steps count in every sum but accepted_return: the reference calls _get_reward() on them too.  Under
+ * SB_REWARD_SETPOINT_ENERGY_CARBON the same columns are summed; several of them are 0 there.  Stated departure: the
+ * reference's accumulator appends normalized_productivity_regret under its `step_duration_sec` key
+ * (environment.py:1138-1140), the wrong field; that series is not reproduced here -- steps * dt is the duration.
+ *
+ * Two [B] tables: the RUNNING rows of the episodes in progress, and the COMPLETED rows, each building's last closed
+ * episode.  sb_step (its POST phase) launches k_episode_metrics behind k_post: one more launch, no host synchronisation,
+ * no allocation, so a captured step replays.  k_post is untouched; with info_dev == NULL it is handed a
+ * [B][SB_INFO_STRIDE] buffer of the library's own, allocated at attach.  Every reset latches in front of its redraws and
+ * its reset kernel (k_episode_metrics_close; sb_reset: every building, sb_reset_buildings: its mask): a building with
+ * steps > 0 has its running row copied to its completed row, and its running row re-initialised -- zeros, the extremes,
+ * episode + 1; a building with steps == 0 (the first sb_reset, two resets in a row) closes nothing; a building outside
+ * the mask keeps every bit of both rows.
+ * Not state: sb_state_save / sb_state_load and sb_set_temps leave the tables alone; _get / _set are the checkpoint pair.
+ *
+ * sb_episode_metrics_attach allocates both tables and initialises them (running: episode 0; completed: episode -1, no
+ * steps, the extremes at +inf / -inf); attaching again re-initialises them.  Synchronises the device: SB_ERR_INVALID
+ * while a stream is being captured, and for a null handle. */
+#define SB_EM_FIELDS 20
+typedef enum sb_episode_metric {
+  SB_EM_EPISODE = 0, SB_EM_STEPS = 1, SB_EM_REJECTED_STEPS = 2, SB_EM_RETURN = 3, SB_EM_ACCEPTED_RETURN = 4,
+  SB_EM_ELECTRICAL_ENERGY = 5, SB_EM_NATURAL_GAS_ENERGY = 6, SB_EM_ELECTRICITY_ENERGY_COST = 7,
+  SB_EM_NATURAL_GAS_ENERGY_COST = 8, SB_EM_CARBON_EMITTED = 9, SB_EM_TOTAL_OCCUPANCY = 10, SB_EM_PRODUCTIVITY_REGRET = 11,
+  SB_EM_NORMALIZED_PRODUCTIVITY_REGRET = 12, SB_EM_NORMALIZED_ENERGY_COST = 13, SB_EM_NORMALIZED_CARBON_EMISSION = 14,
+  SB_EM_PRODUCTIVITY_REWARD = 15, SB_EM_SWEEPS = 16, SB_EM_UNCONVERGED_STEPS = 17, SB_EM_ZONE_TEMP_MIN = 18,
+  SB_EM_ZONE_TEMP_MAX = 19
+} sb_episode_metric;
+int sb_episode_metrics_attach(sb_handle *h);
+/* Frees the tables (once the device is idle); the handle launches what it launched before the attach.  No-op without an
+ * attachment; SB_ERR_INVALID for a null handle or a capturing stream. */
+int sb_episode_metrics_detach(sb_handle *h);
+/* The tables, building-major DEVICE [B][SB_EM_FIELDS] doubles, stream-ordered; either pointer may be NULL, not both.
+ * _set puts back what _get returned, bit for bit (a checkpoint: get, later attach and set).  SB_ERR_INVALID for a null
+ * handle or two null pointers; SB_ERR_UNSUPPORTED without an attachment. */
+int sb_episode_metrics_get(sb_handle *h, double *running_dev, double *completed_dev, void *stream);
+int sb_episode_metrics_set(sb_handle *h, const double *running_dev, const double *completed_dev, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

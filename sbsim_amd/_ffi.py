@@ -195,7 +195,8 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_randomization_attach", "sb_randomization_detach", "sb_randomization_episodes_get",
            "sb_randomization_episodes_set", "sb_get_building_params", "sb_get_building_materials",
            "sb_episode_starts_attach", "sb_episode_starts_detach", "sb_episode_starts_episodes_get",
-           "sb_episode_starts_episodes_set", "sb_episode_starts_values_get", "sb_clock_set_offsets")
+           "sb_episode_starts_episodes_set", "sb_episode_starts_values_get", "sb_clock_set_offsets",
+           "sb_episode_metrics_attach", "sb_episode_metrics_detach", "sb_episode_metrics_get", "sb_episode_metrics_set")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
@@ -226,6 +227,14 @@ SB_RAND_UNIFORM_INT = 2                  # sb_start_field's third kind
 SB_START_MAX_K = 1 << 22
 SB_START_OFFSET, SB_START_WEATHER_LOW, SB_START_WEATHER_HIGH, SB_START_WEATHER_SHIFT = range(4)   # sb_start_field_id
 SB_STARTS_BLOCKS_PER_CU, SB_STARTS_THREADS = SB_RAND_BLOCKS_PER_CU, SB_RAND_THREADS   # k_episode_starts' grid: the same rule
+EPISODE_METRICS_ENTRIES = ("sb_episode_metrics_attach", "sb_episode_metrics_detach", "sb_episode_metrics_get",
+                           "sb_episode_metrics_set")
+SB_EM_FIELDS = 20                        # include/sbsim_amd.h: doubles per building of the episode totals (sb_episode_metric)
+EPISODE_METRIC_NAMES = (
+    "episode", "steps", "rejected_steps", "return", "accepted_return", "electrical_energy", "natural_gas_energy",
+    "electricity_energy_cost", "natural_gas_energy_cost", "carbon_emitted", "total_occupancy", "productivity_regret",
+    "normalized_productivity_regret", "normalized_energy_cost", "normalized_carbon_emission", "productivity_reward",
+    "sweeps", "unconverged_steps", "zone_temp_min", "zone_temp_max")
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -353,6 +362,11 @@ def load():
     L.sb_episode_starts_episodes_set.argtypes = [vp, vp, vp]
     L.sb_episode_starts_values_get.argtypes = [vp, vp, vp, vp]
     L.sb_clock_set_offsets.argtypes = [vp, vp, vp]
+  if all(hasattr(L, name) for name in EPISODE_METRICS_ENTRIES):
+    L.sb_episode_metrics_attach.argtypes = [vp]
+    L.sb_episode_metrics_detach.argtypes = [vp]
+    L.sb_episode_metrics_get.argtypes = [vp, vp, vp, vp]
+    L.sb_episode_metrics_set.argtypes = [vp, vp, vp, vp]
   if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
     L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
@@ -432,6 +446,12 @@ def randomization_entry(name: str):
 def episode_starts_entry(name: str):
   """The episode-starts entry `name` (sb_episode_starts_attach, sb_episode_starts_detach, sb_episode_starts_episodes_get,
   sb_episode_starts_episodes_set, sb_episode_starts_values_get, sb_clock_set_offsets): see entry()."""
+  return entry(name)
+
+
+def episode_metrics_entry(name: str):
+  """The episode-totals entry `name` (sb_episode_metrics_attach, sb_episode_metrics_detach, sb_episode_metrics_get,
+  sb_episode_metrics_set): see entry()."""
   return entry(name)
 
 

@@ -1,5 +1,6 @@
 // episode_draw.hip -- what the three per-episode attachments share on the host (sb_host.h declares it): the idle-device
-// guard of an attach, the draw kernels' grid, the check of one distribution, the copies behind *_episodes_get / _set.
+// guard of an attach, the draw kernels' grid, the check of one distribution, the copies behind *_episodes_get / _set and their
+// attachment check (which sb_episode_metrics_get / _set use too).
 // Host code only: the draws themselves are episode_draw.h's.
 #include <hip/hip_runtime.h>
 
@@ -62,13 +63,18 @@ int parse_dist(const std::string &at, const DistIn &in, unsigned kinds, const Di
   return fail(SB_ERR_INVALID, at + ": " + w.unknown_head + std::to_string(in.kind) + w.unknown_tail);
 }
 
+int draws_attached(const sb_handle *h, EpisodeDraws sb_handle::*draws, const char *who, const char *missing_text, bool have_array) {
+  if (!h || !have_array) return fail(SB_ERR_INVALID, std::string(who) + ": null argument");
+  if (!(h->*draws).attached) return fail(SB_ERR_UNSUPPORTED, std::string(who) + ": " + missing_text);
+  return SB_OK;
+}
+
 namespace {
 
 int episodes_copy(sb_handle *h, EpisodeDraws sb_handle::*draws, const char *who, const char *missing_text, int32_t *out_dev,
                   const int32_t *in_dev, hipStream_t stream) {
-  if (!h || !(out_dev || in_dev)) return fail(SB_ERR_INVALID, std::string(who) + ": null argument");
+  SB_CHECK(draws_attached(h, draws, who, missing_text, out_dev || in_dev));
   const EpisodeDraws &d = h->*draws;
-  if (!d.attached) return fail(SB_ERR_UNSUPPORTED, std::string(who) + ": " + missing_text);
   SB_ON_DEVICE(h->device);
   const size_t bytes = (size_t)h->d.B * sizeof(int32_t);
   if (out_dev) SB_HIP(hipMemcpyAsync(out_dev, d.episode.p, bytes, hipMemcpyDeviceToDevice, stream));

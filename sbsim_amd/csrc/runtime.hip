@@ -644,6 +644,7 @@ static void launch_reset(sb_handle *h, const EpisodeArgs &ep, double initial_tem
 int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *stream) {
   if (!h) return fail(SB_ERR_INVALID, "sb_reset: null handle");
   SB_ON_DEVICE(h->device);
+  if (h->em_draws.attached) SB_CHECK(sb_episode_metrics_close(h, nullptr, (hipStream_t)stream)); // the episodes that end here: their totals latched
   if (h->rz_draws.attached) SB_CHECK(sb_randomization_redraw(h, nullptr, (hipStream_t)stream)); // the new episode's rows, before the reset reads them
   if (h->es_draws.attached) SB_CHECK(sb_episode_starts_redraw(h, nullptr, (hipStream_t)stream)); // ... its start and weather
   launch_reset(h, EpisodeArgs{nullptr, h->ep_start.p, nullptr, nullptr, 0}, initial_temp, temps_dev, (hipStream_t)stream);
@@ -708,6 +709,7 @@ int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host, int32_t restart_p
   SB_ON_DEVICE(h->device);
   SB_CHECK(upload_mask(h, mask_host, "sb_reset_buildings", (hipStream_t)stream));
   if (!h->ep_start.p) SB_CHECK(alloc_zero(h->ep_start, (size_t)B));
+  if (h->em_draws.attached) SB_CHECK(sb_episode_metrics_close(h, h->ep_mask.p, (hipStream_t)stream)); // the masked buildings' totals latched
   if (h->rz_draws.attached) SB_CHECK(sb_randomization_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // the masked buildings' new rows
   if (h->es_draws.attached) SB_CHECK(sb_episode_starts_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // ... their starts and weather
   launch_reset(h, EpisodeArgs{h->ep_mask.p, h->ep_start.p, clk ? h->clock_eff.p : nullptr, h->clock_offs.p, restart_pos},
@@ -792,6 +794,7 @@ int sb_step_phases(sb_handle *h, const float *actions_dev, const sb_step_in *in,
   if (in->has_action && !actions_dev) return fail(SB_ERR_INVALID, "sb_step: has_action set but actions_dev is NULL");
   StepArgs s;
   s.actions = actions_dev; s.obs = obs_dev; s.reward = reward_dev; s.info = info_dev; s.in = *in;
+  if (!info_dev && h->em_draws.attached) s.info = h->em_info.p; // the episode metrics sum info columns: k_post writes the library's own rows
   SB_CHECK(handle_clock_view(h, "sb_step", &s.clk));
   SB_ON_DEVICE(h->device);
   const Dev &d = h->d;
@@ -824,6 +827,7 @@ int sb_step_phases(sb_handle *h, const float *actions_dev, const sb_step_in *in,
     launch_post(h, s, dim3(std::max(1, std::min((d.B + 63) / 64, h->cus * 16))), (hipStream_t)stream, -1);
     ++h->steps_since_reset;
     SB_HIP(hipGetLastError());
+    if (h->em_draws.attached) SB_CHECK(sb_episode_metrics_step(h, reward_dev, s.info, (hipStream_t)stream)); // a launch of its own: k_post is untouched
   }
   return SB_OK;
 }

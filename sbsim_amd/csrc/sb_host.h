@@ -258,6 +258,11 @@ struct sb_handle {
   std::vector<int> es_h_base_offs;  // host copy of es_base_offs
   std::vector<uint8_t> es_pending;  // restoring: the buildings not reset since the detach
   double *es_lohi = nullptr, *es_shift = nullptr; // the caller's arrays
+  // sb_episode_metrics_attach (episode_metrics.hip): the buildings' episode totals
+  EpisodeDraws em_draws;            // attached: sb_step launches k_episode_metrics, a reset k_episode_metrics_close (no draws: the flag alone)
+  DevBuf<double> em_running;        // [SB_EM_FIELDS][B] the episodes in progress
+  DevBuf<double> em_completed;      // [SB_EM_FIELDS][B] every building's last closed episode
+  DevBuf<float> em_info;            // [B][SB_INFO_STRIDE] k_post's info rows when sb_step is given none
   // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
   DevBuf<float> jgrid, jtab, jscratch; // (jscratch: k_sweep_jacobi_g's per-workgroup grids)
   DevBuf<double> jrden;
@@ -328,6 +333,15 @@ int parse_dist(const std::string &at, const DistIn &in, unsigned kinds, const Di
 // `draws` is not attached, and the stream-ordered device-to-device copy of the [B] counters.
 int episodes_get(sb_handle *h, EpisodeDraws sb_handle::*draws, const char *who, const char *missing_text, int32_t *out_dev, hipStream_t stream);
 int episodes_set(sb_handle *h, EpisodeDraws sb_handle::*draws, const char *who, const char *missing_text, const int32_t *in_dev, hipStream_t stream);
+// Their check by itself (sb_episode_metrics_get / _set share it): SB_ERR_INVALID for a null handle or !have_array,
+// SB_ERR_UNSUPPORTED when `draws` is not attached.
+int draws_attached(const sb_handle *h, EpisodeDraws sb_handle::*draws, const char *who, const char *missing_text, bool have_array);
+
+// episode_metrics.hip: k_episode_metrics behind k_post (sb_step's POST phase; info_dev: the rows k_post wrote), and the
+// latch at the top of a reset, in front of the redraws below (mask_dev NULL: every building).  Stream-ordered launches
+// only.  Only called while em_draws.attached.
+int sb_episode_metrics_step(sb_handle *h, const float *reward_dev, const float *info_dev, hipStream_t stream);
+int sb_episode_metrics_close(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream);
 
 // randomize.hip: the redraw at the top of a reset (sb_reset: mask_dev NULL, every building; sb_reset_buildings: its
 // device mask), stream-ordered launches only.  Only called while a randomisation is attached.

@@ -375,6 +375,7 @@ class BatchedSimulator:
     self._initial_conditions = None   # initial_conditions_attach: the host_inputs.InitialConditions in force
     self._randomization = None   # randomization_attach: the host_inputs.EpisodeRandomization in force
     self._randomization_base = None   # ... and the rows in force when it was attached, by name
+    self._episode_metrics = False   # episode_metrics_attach: episode totals are kept (not state: no fingerprint entry)
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -1133,6 +1134,54 @@ class BatchedSimulator:
     self._draws_call("sb_clock_set_offsets", offsets.ctypes.data_as(C.c_void_p), self._stream())
     self._clock_offsets = offsets.copy()
 
+  # ---- episode totals per building (sb_episode_metrics_attach) ----
+  EPISODE_METRIC_NAMES = _ffi.EPISODE_METRIC_NAMES
+
+  def episode_metrics_attach(self) -> None:
+    """sb_episode_metrics_attach: from now on every step adds to each building's running row of episode totals (return,
+    energy, cost, carbon, ...: ``EPISODE_METRIC_NAMES``, include/sbsim_amd.h states each), and every reset of a building
+    that has stepped closes its episode into its completed row.  One more launch per step, on tables allocated here;
+    attaching again re-initialises them.  The call synchronises the device, not under stream capture.  Not part of a
+    snapshot: ``episode_metrics`` / ``completed_episodes`` / ``episode_metrics_set`` are how a checkpoint keeps them."""
+    self._draws_call("sb_episode_metrics_attach")
+    self._episode_metrics = True
+
+  def episode_metrics_detach(self) -> None:
+    """sb_episode_metrics_detach: the tables go; the simulator launches what it launched before the attach."""
+    self._draws_call("sb_episode_metrics_detach")
+    self._episode_metrics = False
+
+  @property
+  def episode_metrics_attached(self) -> bool:
+    return self._episode_metrics
+
+  def _episode_metrics_get(self, running: bool) -> torch.Tensor:
+    out = torch.empty((self.B, _ffi.SB_EM_FIELDS), dtype=torch.float64, device=self.tdev)
+    ptr = C.c_void_p(out.data_ptr())
+    self._draws_call("sb_episode_metrics_get", ptr if running else None, None if running else ptr, self._stream())
+    return out
+
+  def episode_metrics(self) -> torch.Tensor:
+    """sb_episode_metrics_get: the running rows, float64 [B, 20] on the device (columns: ``EPISODE_METRIC_NAMES``), a
+    stream-ordered copy -- the totals of every building's episode in progress.  ValueError without an attachment."""
+    return self._episode_metrics_get(True)
+
+  def completed_episodes(self) -> torch.Tensor:
+    """sb_episode_metrics_get: the completed rows, float64 [B, 20] on the device -- the totals of every building's last
+    closed episode (``episode`` -1, no steps: none closed since the attach)."""
+    return self._episode_metrics_get(False)
+
+  def episode_metrics_set(self, running: Optional[torch.Tensor], completed: Optional[torch.Tensor]) -> None:
+    """sb_episode_metrics_set: puts back what ``episode_metrics()`` / ``completed_episodes()`` returned (either may be
+    None, not both), bit for bit."""
+    ptrs = []
+    for t in (running, completed):
+      if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self.tdev
+                            or tuple(t.shape) != (self.B, _ffi.SB_EM_FIELDS) or not t.is_contiguous()):
+        raise ValueError(f"episode metrics must be contiguous float64 [{self.B}, {_ffi.SB_EM_FIELDS}] tensors on {self.tdev}")
+      ptrs.append(C.c_void_p(t.data_ptr()) if t is not None else None)
+    self._draws_call("sb_episode_metrics_set", ptrs[0], ptrs[1], self._stream())
+
   # ---- state snapshots (sb_state_save / sb_state_load) ----
   def state_fingerprint(self) -> Tuple:
     """What a SimState of this simulator means: plan shape and zones, a hash of the compiled plan tables (in the
@@ -1422,8 +1471,13 @@ class BatchedEnvironment:
                spatial: Optional[host_inputs.SpatialOutputs] = None,
                initial_conditions: Optional[host_inputs.InitialConditions] = None,
                episode_randomization: Optional[host_inputs.EpisodeRandomization] = None,
-               episode_starts: Optional[host_inputs.EpisodeStarts] = None, max_start_offset: Optional[int] = None):
-    """``max_start_offset``: the largest row ``set_start_offsets`` may move a building to; the timeline is built to hold
+               episode_starts: Optional[host_inputs.EpisodeStarts] = None, max_start_offset: Optional[int] = None,
+               episode_metrics: bool = False):
+    """``episode_metrics``: True -- every building's episode totals are kept on the device:
+    ``episode_metrics()`` the running rows, ``completed_episodes()`` each building's last closed episode, float64
+    [B, 20] with the columns ``EPISODE_METRIC_NAMES``; works with and without ``collect_info``.  False (the default):
+    nothing of this is built or launched.
+    ``max_start_offset``: the largest row ``set_start_offsets`` may move a building to; the timeline is built to hold
     an episode that starts there (and the environment runs on the device clock).  None: the largest of ``start_offsets``.
     ``episode_starts``: a ``host_inputs.EpisodeStarts`` -- a start time (a row of the timeline) and weather per
     building, drawn anew at every reset of a building, on the device (``set_episode_starts`` between
@@ -1595,6 +1649,9 @@ class BatchedEnvironment:
       self._setup_episodes(episode_steps)
     if episode_starts is not None:
       self._attach_starts(episode_starts)
+    self.has_episode_metrics = bool(episode_metrics)
+    if self.has_episode_metrics:
+      self.sim.episode_metrics_attach()
     self._action_spec = ArraySpec((self.sim.n_actions,), np.dtype(np.float32), "action", -1.0, 1.0)
     self._observation_spec = ArraySpec((self.sim.O,), np.dtype(np.float32), "observation")
     self.field_names = self.sim.field_names
@@ -1644,6 +1701,24 @@ class BatchedEnvironment:
   @property
   def info(self) -> Optional[torch.Tensor]:
     return self._info
+
+  # ---- episode totals per building (episode_metrics=True) ----
+  EPISODE_METRIC_NAMES = _ffi.EPISODE_METRIC_NAMES
+
+  def _need_episode_metrics(self) -> None:
+    if not self.has_episode_metrics:
+      raise ValueError("the environment was built without episode_metrics=True")
+
+  def episode_metrics(self) -> torch.Tensor:
+    """The running rows: float64 [B, 20] on the device, the totals of every building's episode in progress."""
+    self._need_episode_metrics()
+    return self.sim.episode_metrics()
+
+  def completed_episodes(self) -> torch.Tensor:
+    """The completed rows: float64 [B, 20] on the device, the totals of every building's last closed episode (closed by
+    the reset that followed it: ``reset()``, the autoreset inside ``step()``, ``reset_buildings``)."""
+    self._need_episode_metrics()
+    return self.sim.completed_episodes()
 
   def current_simulation_timestamps(self) -> List[dt.datetime]:
     """Every building's own instant: ``current_simulation_timestamp`` (the batch's base clock) moved by the building's
@@ -2369,6 +2444,29 @@ class MixedBatchedEnvironment:
     """Every class's ``BatchedEnvironment.zone_temp_stats`` ([B_k, Z_k, 3] float64, or None)."""
     return [e.zone_temp_stats for e in self.envs]
 
+  # ---- episode totals per building (episode_metrics=True goes to every class) ----
+  EPISODE_METRIC_NAMES = _ffi.EPISODE_METRIC_NAMES
+
+  @property
+  def has_episode_metrics(self) -> bool:
+    return all(e.has_episode_metrics for e in self.envs)
+
+  def episode_metrics(self) -> torch.Tensor:
+    """``BatchedEnvironment.episode_metrics`` of every class, read on the class streams: float64 [B_total, 20], the
+    rows in class order."""
+    return self._cat_rows(lambda k, env: env.episode_metrics())
+
+  def completed_episodes(self) -> torch.Tensor:
+    """``BatchedEnvironment.completed_episodes`` of every class: float64 [B_total, 20], the rows in class order."""
+    return self._cat_rows(lambda k, env: env.completed_episodes())
+
+  def _cat_rows(self, fn) -> torch.Tensor:
+    cur = torch.cuda.current_stream(self.tdev)
+    parts = self._on_streams(fn)
+    for t in parts:   # allocated on a class stream, read on the caller's
+      t.record_stream(cur)
+    return torch.cat(parts)
+
   def _check_building_params(self, params: Optional[host_inputs.BuildingParams]) -> None:
     total = sum(self.class_totals)
     if params is not None and params.n_buildings != total:
@@ -2562,6 +2660,14 @@ class GymVectorEnv:
     info = {"step_type": ts.step_type, "discount": ts.discount}
     if getattr(self.env, "per_building_episodes", False):
       info.update(final_obs=self.env.final_observation, autoreset_mode="same_step")
+    if getattr(self.env, "has_episode_metrics", False):
+      # gymnasium's RecordEpisodeStatistics convention: info["episode"] counts where info["_episode"] is set.  Same-step
+      # autoreset: the reset inside step() has closed the episodes that ended, so they are the completed rows; on a
+      # shared clock the reset follows with the next step(), and the episode still is the running rows
+      rows = self.env.completed_episodes() if getattr(self.env, "per_building_episodes", False) else self.env.episode_metrics()
+      info["episode"] = {"r": rows[:, _ffi.EPISODE_METRIC_NAMES.index("return")],
+                         "l": rows[:, _ffi.EPISODE_METRIC_NAMES.index("steps")].to(torch.int64)}
+      info["_episode"] = last
     return ts.observation, ts.reward, terminated, truncated, info
 
   def close(self) -> None:

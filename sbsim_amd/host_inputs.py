@@ -2157,3 +2157,65 @@ class EpisodeStarts:
     """A hash of everything attached (``BatchedSimulator.state_fingerprint``)."""
     rows = [(name, f.kind, f.lo.hex(), f.hi.hex(), f.step, tuple(v.hex() for v in f.values)) for name, f in sorted(self.fields.items())]
     return hashlib.sha256(repr((rows, self.relative, self.seed, self.first_building)).encode()).hexdigest()
+
+
+# ---- episode totals per building (sb_episode_metrics_attach; include/sbsim_amd.h states the table) ----
+EPISODE_METRIC_NAMES = _ffi.EPISODE_METRIC_NAMES
+
+
+class EpisodeMetricsTwin:
+  """The episode totals of B buildings in NumPy, written from the table of include/sbsim_amd.h (sb_episode_metrics_attach):
+  ``running`` and ``completed``, float64 [B, 20] with the columns ``EPISODE_METRIC_NAMES``.  ``step`` is what one
+  sb_step adds, ``close`` the latch in front of a reset.  Every operation is one IEEE double operation on fp32 inputs
+  widened, in the table's order, so the device rows equal these bit for bit."""
+
+  K = 1.0 / 3600.0 / 1000.0   # W s -> kWh
+
+  def __init__(self, n_buildings: int, dt: float):
+    self.B, self.dt = int(n_buildings), np.float64(dt)
+    self.running = self._fresh(self.B, 0.0)
+    self.completed = self._fresh(self.B, -1.0)   # no episode closed yet
+
+  @staticmethod
+  def _fresh(n: int, episode) -> np.ndarray:
+    rows = np.zeros((n, _ffi.SB_EM_FIELDS), dtype=np.float64)
+    rows[:, 0] = episode
+    rows[:, 18], rows[:, 19] = np.inf, -np.inf
+    return rows
+
+  def step(self, reward, info, zone_means) -> None:
+    """reward: float32 [B] as the step returned it (-inf: rejected); info: float32 [B, 24] as k_post wrote it;
+    zone_means: float64 [B, Z], the post-update zone means."""
+    reward = np.asarray(reward)
+    info = np.asarray(info)
+    if reward.dtype != np.float32 or info.dtype != np.float32:
+      raise ValueError("reward and info are the step's float32 outputs")
+    zm = np.asarray(zone_means, dtype=np.float64).reshape(self.B, -1)
+    r = reward.astype(np.float64)
+    I = info.astype(np.float64)
+    dt, K = self.dt, np.float64(self.K)
+    rejected = np.isneginf(reward)
+    R = self.running
+    with np.errstate(invalid="ignore"):
+      R[:, 1] += 1.0
+      R[:, 2] += rejected
+      R[:, 3] += r
+      R[~rejected, 4] += r[~rejected]
+      R[:, 5] += (I[:, 0] * dt * K + I[:, 1] * dt * K) + I[:, 3] * dt * K
+      R[:, 6] += I[:, 2] * dt * K
+      for col, src in ((7, 9), (8, 10), (9, 11), (10, 17), (11, 20), (12, 21), (13, 22), (14, 23), (15, 8), (16, 4)):
+        R[:, col] += I[:, src]
+      R[:, 17] += info[:, 5] == 0
+      R[:, 18] = np.minimum(R[:, 18], zm.min(axis=1))
+      R[:, 19] = np.maximum(R[:, 19], zm.max(axis=1))
+
+  def close(self, mask=None) -> np.ndarray:
+    """The latch: every building of ``mask`` (None: all) with steps > 0 has its running row copied to its completed row
+    and its running row re-initialised with episode + 1; the others keep both rows.  Returns which buildings closed."""
+    m = np.ones(self.B, dtype=bool) if mask is None else np.asarray(mask).astype(bool)
+    closing = m & (self.running[:, 1] > 0)
+    self.completed[closing] = self.running[closing]
+    fresh = self._fresh(int(closing.sum()), 0.0)
+    fresh[:, 0] = self.running[closing, 0] + 1.0
+    self.running[closing] = fresh
+    return closing
