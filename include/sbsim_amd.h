@@ -1090,6 +1090,93 @@ int sb_episode_metrics_detach(sb_handle *h);
 int sb_episode_metrics_get(sb_handle *h, double *running_dev, double *completed_dev, void *stream);
 int sb_episode_metrics_set(sb_handle *h, const double *running_dev, const double *completed_dev, void *stream);
 
+/* Every building scored against recorded zone temperatures, on the device: how far a candidate's zones were from a
+ * recording (calibration, model validation, sim-to-real).  Off unless attached; a handle without the attachment launches
+ * exactly what it launched before.  Works on every solver's handle: only the post-update zone means (sb_get_zone_temps)
+ * are read.
+ *
+ * The recording: n_traces traces of n_rows rows of Z doubles, kelvin, [n_traces][n_rows][Z]; NaN is "no sample", +-inf
+ * is refused.  Building b is scored on trace trace_of[b] (NULL: 0), and row r of it is compared with the zone means after
+ * the building's (r - first_row[b])-th step since its last reset (first_row NULL: 0; 0 <= first_row[b] < n_rows): the
+ * building's step count is column 1 of its running row, so no clock is involved.  A row at or beyond n_rows counts Z
+ * missing samples and reads nothing.
+ *
+ * A row of SB_TL_FIELDS doubles per building (sb_telemetry_score); integers are stored exactly.  Per step, with
+ * r = first_row[b] + steps (steps before this step's += 1), and then for z = 0 .. Z-1 in that order, obs = trace[r][z],
+ * e = zmean[z] - obs, a = fabs(e), q = e * e, w = zone_weights[z], one rounding per operation:
+ *    0 episode             the index of the building's current episode: the number of its episodes closed since the attach
+ *    1 steps               += 1 per step
+ *    2 samples             += 1 per zone whose obs is not NaN
+ *    3 missing             += 1 per zone whose obs is NaN (nothing else changes for it); += Z for a row past the end
+ *    4 sum_err             += e      (the bias's numerator)
+ *    5 sum_abs_err         += a
+ *    6 sum_sq_err          += q
+ *    7 max_abs_err         a where a > max_abs_err (strict: the first occurrence wins); -1 before any sample
+ *    8 max_abs_row         the trace row r of that maximum; -1 before any sample
+ *    9 max_abs_zone        the zone z of that maximum; -1 before any sample
+ *   10 weighted_abs_err    += w * a
+ *   11 weighted_sq_err     += w * q
+ *   12 weight_sum          += w
+ * A simulated zone mean that is not finite is a sample and goes into the sums (it is not hidden; a NaN never becomes the
+ * maximum).  MAE = sum_abs_err / samples, RMSE = sqrt(sum_sq_err / samples), bias = sum_err / samples are the caller's
+ * quotients; the sums are additive, so an error-against-horizon curve is the difference of two reads.
+ * With per_zone != 0 also a [Z][4] block per building: samples, sum_err, sum_abs_err, sum_sq_err of each zone, by the
+ * same operations.
+ *
+ * Two tables each: the RUNNING rows of the episodes in progress and the COMPLETED rows, each building's last closed
+ * episode.  sb_step (its POST phase) launches k_telemetry behind k_post (behind k_episode_metrics where both are
+ * attached): one more launch, no host synchronisation, no allocation, so a captured step replays.  Every reset latches in
+ * front of its redraws and its reset kernel (k_telemetry_close; sb_reset: every building, sb_reset_buildings: its
+ * mask), as sb_episode_metrics_attach describes: a building with steps > 0 has its running rows copied to its completed
+ * rows and re-initialised with episode + 1; a building with steps == 0 closes nothing; a building outside the mask keeps
+ * every bit.  Not state: sb_state_save / sb_state_load and sb_set_temps leave the tables alone; _get / _set are the
+ * checkpoint pair.
+ *
+ * actions (NULL: none): the recorded setpoints that go with the recording, [n_traces][n_rows][n_actions] float32
+ * normalised actions; n_actions must be the handle's.  sb_telemetry_actions writes building b's row
+ * first_row[b] + steps -- the row its next step is scored on -- of trace trace_of[b]; past the end of the recording it
+ * writes the LAST row.
+ *
+ * sb_telemetry_attach checks everything before anything changes -- SB_ERR_INVALID, the message naming the building,
+ * trace or row at fault: a null handle or trace, n_traces < 1, n_rows < 1, an infinite trace value, trace_of[b] outside
+ * [0, n_traces), first_row[b] outside [0, n_rows), a weight that is negative or not finite, actions with n_actions other
+ * than the handle's, an action that is not finite, a capturing stream -- and a refused call leaves the attachment in
+ * force untouched.  The host arrays are copied and may go away on return.  Attaching again replaces the recording and
+ * re-initialises the tables (running: episode 0; completed: episode -1, no steps).  Synchronises the device. */
+#define SB_TL_FIELDS 13
+#define SB_TL_ZONE_FIELDS 4
+typedef enum sb_telemetry_score {
+  SB_TL_EPISODE = 0, SB_TL_STEPS = 1, SB_TL_SAMPLES = 2, SB_TL_MISSING = 3, SB_TL_SUM_ERR = 4, SB_TL_SUM_ABS_ERR = 5,
+  SB_TL_SUM_SQ_ERR = 6, SB_TL_MAX_ABS_ERR = 7, SB_TL_MAX_ABS_ROW = 8, SB_TL_MAX_ABS_ZONE = 9, SB_TL_WEIGHTED_ABS_ERR = 10,
+  SB_TL_WEIGHTED_SQ_ERR = 11, SB_TL_WEIGHT_SUM = 12
+} sb_telemetry_score;
+typedef struct sb_telemetry {
+  const double *traces;       /* HOST [n_traces][n_rows][Z] kelvin; NaN: no sample */
+  const int32_t *trace_of;    /* HOST [B], or NULL: trace 0 */
+  const int32_t *first_row;   /* HOST [B], or NULL: row 0 */
+  const double *zone_weights; /* HOST [Z] finite, >= 0, or NULL: all 1 */
+  const float *actions;       /* HOST [n_traces][n_rows][n_actions], or NULL: none */
+  int32_t n_traces, n_rows, n_actions;
+  int32_t per_zone;           /* != 0: the per-zone tables are kept too */
+} sb_telemetry;
+int sb_telemetry_attach(sb_handle *h, const sb_telemetry *t);
+/* Frees the tables and the recording (once the device is idle); the handle launches what it launched before the attach.
+ * No-op without an attachment; SB_ERR_INVALID for a null handle or a capturing stream. */
+int sb_telemetry_detach(sb_handle *h);
+/* The scalar tables, building-major DEVICE [B][SB_TL_FIELDS] doubles, stream-ordered; either pointer may be NULL, not
+ * both.  _set puts back what _get returned, bit for bit.  SB_ERR_INVALID for a null handle or two null pointers;
+ * SB_ERR_UNSUPPORTED without an attachment. */
+int sb_telemetry_get(sb_handle *h, double *running_dev, double *completed_dev, void *stream);
+int sb_telemetry_set(sb_handle *h, const double *running_dev, const double *completed_dev, void *stream);
+/* The per-zone tables likewise, DEVICE [B][Z][SB_TL_ZONE_FIELDS] doubles; SB_ERR_UNSUPPORTED also when the attachment
+ * was made without per_zone. */
+int sb_telemetry_zone_get(sb_handle *h, double *running_dev, double *completed_dev, void *stream);
+int sb_telemetry_zone_set(sb_handle *h, const double *running_dev, const double *completed_dev, void *stream);
+/* The recorded setpoints of every building's next step: DEVICE [B][n_actions] float32, stream-ordered (see above; past
+ * the end of the recording, the last row).  SB_ERR_INVALID for a null argument; SB_ERR_UNSUPPORTED without an attachment
+ * or without an action table. */
+int sb_telemetry_actions(sb_handle *h, float *actions_dev, void *stream);
+
 /* Developer aid: when SBSIM_PHASE_TIMING is set at sb_create, the step kernel stamps the
  * shader clock at its phase boundaries for building 0; copies 16 int64 to a HOST buffer. */
 int sb_debug_phase_cycles(sb_handle *h, long long *out_host);

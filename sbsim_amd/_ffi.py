@@ -172,6 +172,11 @@ class EpisodeStartsDesc(C.Structure):   # sb_episode_starts (the two weather arr
               ("first_building", C.c_int64)]
 
 
+class Telemetry(C.Structure):   # sb_telemetry (HOST pointers)
+  _fields_ = [("traces", _dp), ("trace_of", _ip), ("first_row", _ip), ("zone_weights", _dp), ("actions", C.POINTER(C.c_float)),
+              ("n_traces", C.c_int32), ("n_rows", C.c_int32), ("n_actions", C.c_int32), ("per_zone", C.c_int32)]
+
+
 # sb_sweep_kernel
 SWEEP_KERNELS = {0: "k_sweep_lds", 1: "k_sweep_reg", 2: "k_sweep_reg (two wavefronts)", 3: "k_sweep_roll", 4: "k_sweep_two",
                  5: "k_sweep_band", 6: "k_sweep_stream", 7: "k_sweep_jacobi"}
@@ -196,7 +201,9 @@ EXPORTS = ("sb_abi_version", "sb_has_experimental_kernels", "sb_last_error", "sb
            "sb_randomization_episodes_set", "sb_get_building_params", "sb_get_building_materials",
            "sb_episode_starts_attach", "sb_episode_starts_detach", "sb_episode_starts_episodes_get",
            "sb_episode_starts_episodes_set", "sb_episode_starts_values_get", "sb_clock_set_offsets",
-           "sb_episode_metrics_attach", "sb_episode_metrics_detach", "sb_episode_metrics_get", "sb_episode_metrics_set")
+           "sb_episode_metrics_attach", "sb_episode_metrics_detach", "sb_episode_metrics_get", "sb_episode_metrics_set",
+           "sb_telemetry_attach", "sb_telemetry_detach", "sb_telemetry_get", "sb_telemetry_set", "sb_telemetry_zone_get",
+           "sb_telemetry_zone_set", "sb_telemetry_actions")
 # entries a library of ABI 8 may predate (load() binds them when present; state_entry() / jacobi_entry() raise without them)
 STATE_ENTRIES = ("sb_state_save", "sb_state_load")
 JACOBI_ENTRIES = ("sb_create_jacobi", "sb_tap_jacobi")
@@ -235,6 +242,14 @@ EPISODE_METRIC_NAMES = (
     "electricity_energy_cost", "natural_gas_energy_cost", "carbon_emitted", "total_occupancy", "productivity_regret",
     "normalized_productivity_regret", "normalized_energy_cost", "normalized_carbon_emission", "productivity_reward",
     "sweeps", "unconverged_steps", "zone_temp_min", "zone_temp_max")
+TELEMETRY_ENTRIES = ("sb_telemetry_attach", "sb_telemetry_detach", "sb_telemetry_get", "sb_telemetry_set",
+                     "sb_telemetry_zone_get", "sb_telemetry_zone_set", "sb_telemetry_actions")
+SB_TL_FIELDS = 13                        # include/sbsim_amd.h: doubles per building of the telemetry scores (sb_telemetry_score)
+SB_TL_ZONE_FIELDS = 4                    # ... and per zone of the per-zone tables
+TELEMETRY_SCORE_NAMES = (
+    "episode", "steps", "samples", "missing", "sum_err", "sum_abs_err", "sum_sq_err", "max_abs_err", "max_abs_row",
+    "max_abs_zone", "weighted_abs_err", "weighted_sq_err", "weight_sum")
+TELEMETRY_ZONE_SCORE_NAMES = ("samples", "sum_err", "sum_abs_err", "sum_sq_err")
 MATERIALS_ENTRIES = ("sb_create_materials", "sb_plan_info_materials", "sb_set_building_materials", "sb_get_building_coef")
 
 _lib = None
@@ -367,6 +382,12 @@ def load():
     L.sb_episode_metrics_detach.argtypes = [vp]
     L.sb_episode_metrics_get.argtypes = [vp, vp, vp, vp]
     L.sb_episode_metrics_set.argtypes = [vp, vp, vp, vp]
+  if all(hasattr(L, name) for name in TELEMETRY_ENTRIES):
+    L.sb_telemetry_attach.argtypes = [vp, C.POINTER(Telemetry)]
+    L.sb_telemetry_detach.argtypes = [vp]
+    for name in ("sb_telemetry_get", "sb_telemetry_set", "sb_telemetry_zone_get", "sb_telemetry_zone_set"):
+      getattr(L, name).argtypes = [vp, vp, vp, vp]
+    L.sb_telemetry_actions.argtypes = [vp, vp, vp]
   if all(hasattr(L, name) for name in PLAN_DIGEST_ENTRIES):
     L.sb_debug_plan_digest.argtypes = [C.POINTER(PlanDesc), C.c_int32, C.POINTER(C.c_uint64)]
   _lib = L
@@ -452,6 +473,11 @@ def episode_starts_entry(name: str):
 def episode_metrics_entry(name: str):
   """The episode-totals entry `name` (sb_episode_metrics_attach, sb_episode_metrics_detach, sb_episode_metrics_get,
   sb_episode_metrics_set): see entry()."""
+  return entry(name)
+
+
+def telemetry_entry(name: str):
+  """The telemetry entry `name` (one of TELEMETRY_ENTRIES): see entry()."""
   return entry(name)
 
 

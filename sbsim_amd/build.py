@@ -21,10 +21,11 @@ SOURCES = ["sbsim_hip.hip", "runtime.hip",                    # host: sb_create;
            "randomize.hip",                                  # per-building parameters and materials re-drawn at every episode start
            "episode_starts.hip",                             # a start time and weather per building drawn at every episode start
            "episode_metrics.hip",                            # per-building episode totals: a kernel behind k_post, a latch in front of a reset
+           "telemetry.hip",                                  # every building scored against recorded zone temperatures: a kernel behind k_post, the same latch
            "planner.cpp", "floorplan.cpp", "episode.cpp",    # host-only: the launch planner, floor-plan preprocessing, episode shards
            "spatial_plan.cpp"]                               # host-only: k_spatial's index tables
 HEADERS = [os.path.join(CSRC, "sb_device.h"), os.path.join(CSRC, "sb_host.h"), os.path.join(CSRC, "sweep_common.h"), os.path.join(CSRC, "step_two_impl.h"), os.path.join(CSRC, "step_two_cfg.h"), os.path.join(CSRC, "step_band_impl.h"), os.path.join(CSRC, "step_band_cfg.h"),
-           *(os.path.join(CSRC, h) for h in ("planner.h", "philox.h", "episode_draw.h", "episode_metrics.h", "spatial.h", "conv_seeded.h", "sb_error.h", "sb_layout.h", "step_roll_cfg.h", "step_reg_cfg.h", "step_stream_cfg.h", "step_stream_ms_cfg.h", "step_lds_cfg.h")),
+           *(os.path.join(CSRC, h) for h in ("planner.h", "philox.h", "episode_draw.h", "episode_metrics.h", "telemetry.h", "spatial.h", "conv_seeded.h", "sb_error.h", "sb_layout.h", "step_roll_cfg.h", "step_reg_cfg.h", "step_stream_cfg.h", "step_stream_ms_cfg.h", "step_lds_cfg.h")),
            os.path.join(ROOT, "include", "sbsim_amd.h")]
 # SBSIM_BUILD_EXPERIMENTAL=1: also the sweep kernels that are exact and tested but slower than what they were meant to replace
 # (step_stream_ms.hip: several sweeps per pass; step_stream.hip's k_sweep_stream_roll: overlapped sweeps) -- opt-in at run time

@@ -645,6 +645,7 @@ int sb_reset(sb_handle *h, double initial_temp, const double *temps_dev, void *s
   if (!h) return fail(SB_ERR_INVALID, "sb_reset: null handle");
   SB_ON_DEVICE(h->device);
   if (h->em_draws.attached) SB_CHECK(sb_episode_metrics_close(h, nullptr, (hipStream_t)stream)); // the episodes that end here: their totals latched
+  if (h->tl_draws.attached) SB_CHECK(sb_telemetry_close(h, nullptr, (hipStream_t)stream)); // ... and their scores against the recording
   if (h->rz_draws.attached) SB_CHECK(sb_randomization_redraw(h, nullptr, (hipStream_t)stream)); // the new episode's rows, before the reset reads them
   if (h->es_draws.attached) SB_CHECK(sb_episode_starts_redraw(h, nullptr, (hipStream_t)stream)); // ... its start and weather
   launch_reset(h, EpisodeArgs{nullptr, h->ep_start.p, nullptr, nullptr, 0}, initial_temp, temps_dev, (hipStream_t)stream);
@@ -710,6 +711,7 @@ int sb_reset_buildings(sb_handle *h, const uint8_t *mask_host, int32_t restart_p
   SB_CHECK(upload_mask(h, mask_host, "sb_reset_buildings", (hipStream_t)stream));
   if (!h->ep_start.p) SB_CHECK(alloc_zero(h->ep_start, (size_t)B));
   if (h->em_draws.attached) SB_CHECK(sb_episode_metrics_close(h, h->ep_mask.p, (hipStream_t)stream)); // the masked buildings' totals latched
+  if (h->tl_draws.attached) SB_CHECK(sb_telemetry_close(h, h->ep_mask.p, (hipStream_t)stream)); // ... and their scores against the recording
   if (h->rz_draws.attached) SB_CHECK(sb_randomization_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // the masked buildings' new rows
   if (h->es_draws.attached) SB_CHECK(sb_episode_starts_redraw(h, h->ep_mask.p, (hipStream_t)stream)); // ... their starts and weather
   launch_reset(h, EpisodeArgs{h->ep_mask.p, h->ep_start.p, clk ? h->clock_eff.p : nullptr, h->clock_offs.p, restart_pos},
@@ -828,6 +830,7 @@ int sb_step_phases(sb_handle *h, const float *actions_dev, const sb_step_in *in,
     ++h->steps_since_reset;
     SB_HIP(hipGetLastError());
     if (h->em_draws.attached) SB_CHECK(sb_episode_metrics_step(h, reward_dev, s.info, (hipStream_t)stream)); // a launch of its own: k_post is untouched
+    if (h->tl_draws.attached) SB_CHECK(sb_telemetry_step(h, (hipStream_t)stream)); // the zone means k_post left, against the recording
   }
   return SB_OK;
 }

@@ -263,6 +263,14 @@ struct sb_handle {
   DevBuf<double> em_running;        // [SB_EM_FIELDS][B] the episodes in progress
   DevBuf<double> em_completed;      // [SB_EM_FIELDS][B] every building's last closed episode
   DevBuf<float> em_info;            // [B][SB_INFO_STRIDE] k_post's info rows when sb_step is given none
+  // sb_telemetry_attach (telemetry.hip): the buildings scored against recorded zone temperatures
+  EpisodeDraws tl_draws;            // attached: sb_step launches k_telemetry, a reset k_telemetry_close (no draws: the flag alone)
+  DevBuf<double> tl_running, tl_completed;           // [SB_TL_FIELDS][B]
+  DevBuf<double> tl_zone_running, tl_zone_completed; // [SB_TL_ZONE_FIELDS][Z][B] with per_zone, else null
+  DevBuf<double> tl_traces, tl_weights;              // [n_traces][n_rows][Z] the recording; [Z] the zone weights
+  DevBuf<float> tl_actions;                          // [n_traces][n_rows][n_actions] the recorded setpoints, or null
+  DevBuf<int> tl_trace_of, tl_first_row;             // [B]
+  int tl_n_traces = 0, tl_n_rows = 0;
   // SB_KERNEL_JACOBI (sb_create_jacobi): the float32 grid and the class tables; jac.grid etc. point into them
   DevBuf<float> jgrid, jtab, jscratch; // (jscratch: k_sweep_jacobi_g's per-workgroup grids)
   DevBuf<double> jrden;
@@ -342,6 +350,11 @@ int draws_attached(const sb_handle *h, EpisodeDraws sb_handle::*draws, const cha
 // only.  Only called while em_draws.attached.
 int sb_episode_metrics_step(sb_handle *h, const float *reward_dev, const float *info_dev, hipStream_t stream);
 int sb_episode_metrics_close(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream);
+
+// telemetry.hip: k_telemetry behind k_post (and behind k_episode_metrics), and the latch at the top of a reset, next to
+// the one above.  Stream-ordered launches only.  Only called while tl_draws.attached.
+int sb_telemetry_step(sb_handle *h, hipStream_t stream);
+int sb_telemetry_close(sb_handle *h, const uint8_t *mask_dev, hipStream_t stream);
 
 // randomize.hip: the redraw at the top of a reset (sb_reset: mask_dev NULL, every building; sb_reset_buildings: its
 // device mask), stream-ordered launches only.  Only called while a randomisation is attached.

@@ -376,6 +376,7 @@ class BatchedSimulator:
     self._randomization = None   # randomization_attach: the host_inputs.EpisodeRandomization in force
     self._randomization_base = None   # ... and the rows in force when it was attached, by name
     self._episode_metrics = False   # episode_metrics_attach: episode totals are kept (not state: no fingerprint entry)
+    self._telemetry = None   # telemetry_attach: the host_inputs.Telemetry in force (not state either)
     self._fingerprint = None
     self.n_actions = len(config.action_names)
     H0, W0 = plan.shape
@@ -1182,6 +1183,100 @@ class BatchedSimulator:
       ptrs.append(C.c_void_p(t.data_ptr()) if t is not None else None)
     self._draws_call("sb_episode_metrics_set", ptrs[0], ptrs[1], self._stream())
 
+  # ---- every building scored against recorded zone temperatures (sb_telemetry_attach) ----
+  TELEMETRY_SCORE_NAMES = _ffi.TELEMETRY_SCORE_NAMES
+  TELEMETRY_ZONE_SCORE_NAMES = _ffi.TELEMETRY_ZONE_SCORE_NAMES
+
+  def telemetry_attach(self, tel: host_inputs.Telemetry) -> None:
+    """sb_telemetry_attach: from now on every step compares each building's post-update zone means with its row of the
+    recording ``tel`` and adds to its running row of scores (``TELEMETRY_SCORE_NAMES``, include/sbsim_amd.h states
+    each), and every reset of a building that has stepped closes its episode into its completed row.  One more launch
+    per step, on tables allocated here; the library copies the arrays; attaching again replaces the recording and
+    re-initialises the tables.  The call synchronises the device, not under stream capture.  Not part of a snapshot:
+    ``telemetry_scores`` / ``completed_telemetry_scores`` / ``telemetry_set`` are how a checkpoint keeps them."""
+    if not isinstance(tel, host_inputs.Telemetry):
+      raise ValueError("telemetry_attach needs a host_inputs.Telemetry (telemetry_detach clears it)")
+    tel.check(self.B, self.Z, self.n_actions)
+    d = _ffi.Telemetry()
+    traces = np.ascontiguousarray(tel.zone_temps, dtype=np.float64)
+    keep = [traces]
+    d.traces, d.n_traces, d.n_rows = traces.ctypes.data_as(_ffi._dp), tel.n_traces, tel.n_rows
+    for name, ptr_t, dtype in (("trace_of", _ffi._ip, np.int32), ("first_row", _ffi._ip, np.int32),
+                               ("zone_weights", _ffi._dp, np.float64), ("actions", C.POINTER(C.c_float), np.float32)):
+      a = getattr(tel, name)
+      if a is not None:
+        a = np.ascontiguousarray(a, dtype=dtype)
+        keep.append(a)
+        setattr(d, name, a.ctypes.data_as(ptr_t))
+    d.n_actions, d.per_zone = tel.n_actions, int(tel.per_zone)
+    self._draws_call("sb_telemetry_attach", C.byref(d))
+    self._telemetry = tel
+
+  def telemetry_detach(self) -> None:
+    """sb_telemetry_detach: the tables and the recording go; the simulator launches what it launched before the attach."""
+    self._draws_call("sb_telemetry_detach")
+    self._telemetry = None
+
+  @property
+  def telemetry(self) -> Optional[host_inputs.Telemetry]:
+    return self._telemetry
+
+  def _telemetry_get(self, running: bool, zone: bool) -> torch.Tensor:
+    shape = (self.B, self.Z, _ffi.SB_TL_ZONE_FIELDS) if zone else (self.B, _ffi.SB_TL_FIELDS)
+    out = torch.empty(shape, dtype=torch.float64, device=self.tdev)
+    ptr = C.c_void_p(out.data_ptr())
+    self._draws_call("sb_telemetry_zone_get" if zone else "sb_telemetry_get", ptr if running else None, None if running else ptr,
+                     self._stream())
+    return out
+
+  def telemetry_scores(self) -> torch.Tensor:
+    """sb_telemetry_get: the running rows, float64 [B, 13] on the device (columns: ``TELEMETRY_SCORE_NAMES``), a
+    stream-ordered copy -- the scores of every building's episode in progress.  ValueError without an attachment."""
+    return self._telemetry_get(True, False)
+
+  def completed_telemetry_scores(self) -> torch.Tensor:
+    """sb_telemetry_get: the completed rows, float64 [B, 13] -- the scores of every building's last closed episode
+    (``episode`` -1, no steps: none closed since the attach)."""
+    return self._telemetry_get(False, False)
+
+  def telemetry_zone_scores(self) -> torch.Tensor:
+    """sb_telemetry_zone_get: the running per-zone rows, float64 [B, Z, 4] (``TELEMETRY_ZONE_SCORE_NAMES``).  ValueError
+    without an attachment, or one without ``per_zone``."""
+    return self._telemetry_get(True, True)
+
+  def completed_telemetry_zone_scores(self) -> torch.Tensor:
+    """sb_telemetry_zone_get: the completed per-zone rows, float64 [B, Z, 4]."""
+    return self._telemetry_get(False, True)
+
+  def telemetry_set(self, running: Optional[torch.Tensor] = None, completed: Optional[torch.Tensor] = None,
+                    zone_running: Optional[torch.Tensor] = None, zone_completed: Optional[torch.Tensor] = None) -> None:
+    """sb_telemetry_set / sb_telemetry_zone_set: puts back what the four readers returned, bit for bit; any may be None,
+    not all."""
+    if all(t is None for t in (running, completed, zone_running, zone_completed)):
+      raise ValueError("telemetry_set needs at least one table")
+    for name, shape, pair in (("sb_telemetry_set", (self.B, _ffi.SB_TL_FIELDS), (running, completed)),
+                              ("sb_telemetry_zone_set", (self.B, self.Z, _ffi.SB_TL_ZONE_FIELDS), (zone_running, zone_completed))):
+      ptrs = []
+      for t in pair:
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self.tdev
+                              or tuple(t.shape) != shape or not t.is_contiguous()):
+          raise ValueError(f"telemetry tables must be contiguous float64 {list(shape)} tensors on {self.tdev}")
+        ptrs.append(C.c_void_p(t.data_ptr()) if t is not None else None)
+      if ptrs[0] is not None or ptrs[1] is not None:
+        self._draws_call(name, ptrs[0], ptrs[1], self._stream())
+
+  def telemetry_actions(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sb_telemetry_actions: the recorded setpoints of every building's next step, float32 [B, A] on the device -- row
+    ``first_row[b] + steps_b`` of the building's trace, the last row past the end of the recording.  ValueError without an
+    attachment or without recorded actions."""
+    if out is None:
+      out = torch.empty((self.B, self.n_actions), dtype=torch.float32, device=self.tdev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != self.tdev
+          or tuple(out.shape) != (self.B, self.n_actions) or not out.is_contiguous()):
+      raise ValueError(f"out must be a contiguous float32 [{self.B}, {self.n_actions}] tensor on {self.tdev}")
+    self._draws_call("sb_telemetry_actions", C.c_void_p(out.data_ptr()), self._stream())
+    return out
+
   # ---- state snapshots (sb_state_save / sb_state_load) ----
   def state_fingerprint(self) -> Tuple:
     """What a SimState of this simulator means: plan shape and zones, a hash of the compiled plan tables (in the
@@ -1472,8 +1567,14 @@ class BatchedEnvironment:
                initial_conditions: Optional[host_inputs.InitialConditions] = None,
                episode_randomization: Optional[host_inputs.EpisodeRandomization] = None,
                episode_starts: Optional[host_inputs.EpisodeStarts] = None, max_start_offset: Optional[int] = None,
-               episode_metrics: bool = False):
-    """``episode_metrics``: True -- every building's episode totals are kept on the device:
+               episode_metrics: bool = False, telemetry: Optional[host_inputs.Telemetry] = None):
+    """``telemetry``: a ``host_inputs.Telemetry`` -- every building is scored against recorded zone temperatures on the
+    device: ``telemetry_scores()`` the running rows, ``completed_telemetry_scores()`` each building's
+    last closed episode, float64 [B, 13] with the columns ``TELEMETRY_SCORE_NAMES``, the per-zone readers with
+    ``per_zone``, ``telemetry_actions()`` the recorded setpoints of every building's next step.  Works with and without
+    ``per_building_episodes`` and ``collect_info``; not together with ``episode_starts`` (the rows follow a building's
+    step count, not a drawn start).  None (the default): nothing of this is built or launched.
+    ``episode_metrics``: True -- every building's episode totals are kept on the device:
     ``episode_metrics()`` the running rows, ``completed_episodes()`` each building's last closed episode, float64
     [B, 20] with the columns ``EPISODE_METRIC_NAMES``; works with and without ``collect_info``.  False (the default):
     nothing of this is built or launched.
@@ -1575,6 +1676,12 @@ class BatchedEnvironment:
     if max_start_offset is not None and (isinstance(max_start_offset, bool) or not isinstance(max_start_offset, (int, np.integer))
                                          or not 0 <= max_start_offset <= (1 << 22)):
       raise ValueError(f"max_start_offset must be an integer >= 0 (and at most 2^22), got {max_start_offset!r}")
+    if telemetry is not None:   # (before anything is built)
+      if not isinstance(telemetry, host_inputs.Telemetry):
+        raise ValueError("telemetry must be a host_inputs.Telemetry (or None)")
+      if episode_starts is not None:
+        raise ValueError("telemetry together with episode_starts: the recording's rows follow a building's step count, not a "
+                         "drawn start time")
     if episode_starts is not None:   # (likewise)
       if not isinstance(episode_starts, host_inputs.EpisodeStarts):
         raise ValueError("episode_starts must be a host_inputs.EpisodeStarts (or None)")
@@ -1652,6 +1759,9 @@ class BatchedEnvironment:
     self.has_episode_metrics = bool(episode_metrics)
     if self.has_episode_metrics:
       self.sim.episode_metrics_attach()
+    self.has_telemetry = telemetry is not None
+    if self.has_telemetry:
+      self.sim.telemetry_attach(telemetry)
     self._action_spec = ArraySpec((self.sim.n_actions,), np.dtype(np.float32), "action", -1.0, 1.0)
     self._observation_spec = ArraySpec((self.sim.O,), np.dtype(np.float32), "observation")
     self.field_names = self.sim.field_names
@@ -1719,6 +1829,40 @@ class BatchedEnvironment:
     the reset that followed it: ``reset()``, the autoreset inside ``step()``, ``reset_buildings``)."""
     self._need_episode_metrics()
     return self.sim.completed_episodes()
+
+  # ---- every building scored against recorded zone temperatures (telemetry=...; INTEGRATION.md 4s) ----
+  TELEMETRY_SCORE_NAMES = _ffi.TELEMETRY_SCORE_NAMES
+  TELEMETRY_ZONE_SCORE_NAMES = _ffi.TELEMETRY_ZONE_SCORE_NAMES
+
+  def _need_telemetry(self) -> None:
+    if not self.has_telemetry:
+      raise ValueError("the environment was built without telemetry=...")
+
+  def telemetry_scores(self) -> torch.Tensor:
+    """The running rows: float64 [B, 13] on the device, the scores of every building's episode in progress."""
+    self._need_telemetry()
+    return self.sim.telemetry_scores()
+
+  def completed_telemetry_scores(self) -> torch.Tensor:
+    """The completed rows: float64 [B, 13] on the device, the scores of every building's last closed episode (closed by
+    the reset that followed it: ``reset()``, the autoreset inside ``step()``, ``reset_buildings``)."""
+    self._need_telemetry()
+    return self.sim.completed_telemetry_scores()
+
+  def telemetry_zone_scores(self) -> torch.Tensor:
+    """The running per-zone rows: float64 [B, Z, 4] (``Telemetry(per_zone=True)``)."""
+    self._need_telemetry()
+    return self.sim.telemetry_zone_scores()
+
+  def completed_telemetry_zone_scores(self) -> torch.Tensor:
+    """The completed per-zone rows: float64 [B, Z, 4]."""
+    self._need_telemetry()
+    return self.sim.completed_telemetry_zone_scores()
+
+  def telemetry_actions(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The recorded setpoints of every building's next step: float32 [B, A] on the device, ready for ``step``."""
+    self._need_telemetry()
+    return self.sim.telemetry_actions(out)
 
   def current_simulation_timestamps(self) -> List[dt.datetime]:
     """Every building's own instant: ``current_simulation_timestamp`` (the batch's base clock) moved by the building's
@@ -2304,7 +2448,9 @@ class MixedBatchedEnvironment:
                building_materials: Optional[Sequence[Optional[host_inputs.BuildingMaterials]]] = None,
                initial_conditions: Optional[Sequence[Optional[host_inputs.InitialConditions]]] = None,
                episode_randomization=None, **env_kwargs):
-    """``episode_randomization``: one ``host_inputs.EpisodeRandomization`` for every class, or a list / tuple with one or
+    """``telemetry`` (among ``env_kwargs``): a list / tuple with one ``host_inputs.Telemetry`` or None per class (a
+    recording has a floor plan's zones; its [B] arrays have one row per building of the class); one rank only.
+    ``episode_randomization``: one ``host_inputs.EpisodeRandomization`` for every class, or a list / tuple with one or
     None per class (material slots are a floor plan's own); ``first_building`` moves to the class's first GLOBAL building
     on this rank, as for ``initial_conditions``.
     ``initial_conditions``: a list / tuple with one ``host_inputs.InitialConditions`` or None per class (a grid
@@ -2327,6 +2473,13 @@ class MixedBatchedEnvironment:
                        "BatchedEnvironment, and the classes of a mixed batch are block-partitioned over classes and ranks")
     if env_kwargs.get("episode_starts") is not None:
       raise ValueError("episode_starts is not implemented for MixedBatchedEnvironment (its classes share one simulator clock)")
+    if env_kwargs.get("telemetry") is not None:
+      if not isinstance(env_kwargs["telemetry"], (list, tuple)) or len(env_kwargs["telemetry"]) != len(classes):
+        raise ValueError(f"telemetry: a list with one host_inputs.Telemetry or None per class ({len(classes)})")
+      if int(world) != 1:
+        raise ValueError("telemetry is not implemented for a MixedBatchedEnvironment over several ranks")
+    else:
+      env_kwargs.pop("telemetry", None)
     if isinstance(env_kwargs.get("convection_simulator"), host_inputs.SeededStochasticConvectionSimulator):
       raise ValueError("SeededStochasticConvectionSimulator is not implemented for MixedBatchedEnvironment (its seeds belong "
                        "to the buildings of one BatchedEnvironment); use host_inputs.StochasticConvectionSimulator")
@@ -2368,6 +2521,8 @@ class MixedBatchedEnvironment:
         if len(kw["solver"]) != len(classes):
           raise ValueError(f"solver: one per class ({len(classes)}), or one for all")
         kw["solver"] = kw["solver"][k]
+      if "telemetry" in kw:   # one Telemetry (or None) per class: a recording has a floor plan's zones
+        kw["telemetry"] = kw["telemetry"][k]
       if isinstance(kw.get("spatial"), (list, tuple)):   # one SpatialOutputs (or None) per class
         if len(kw["spatial"]) != len(classes):
           raise ValueError(f"spatial: one per class ({len(classes)}), or one for all")
@@ -2459,6 +2614,41 @@ class MixedBatchedEnvironment:
   def completed_episodes(self) -> torch.Tensor:
     """``BatchedEnvironment.completed_episodes`` of every class: float64 [B_total, 20], the rows in class order."""
     return self._cat_rows(lambda k, env: env.completed_episodes())
+
+  # ---- every building scored against recorded zone temperatures (telemetry=[one or None per class]) ----
+  TELEMETRY_SCORE_NAMES = _ffi.TELEMETRY_SCORE_NAMES
+  TELEMETRY_ZONE_SCORE_NAMES = _ffi.TELEMETRY_ZONE_SCORE_NAMES
+
+  @property
+  def has_telemetry(self) -> bool:
+    return all(e.has_telemetry for e in self.envs)
+
+  def telemetry_scores(self) -> torch.Tensor:
+    """``BatchedEnvironment.telemetry_scores`` of every class: float64 [B_total, 13], the rows in class order."""
+    return self._cat_rows(lambda k, env: env.telemetry_scores())
+
+  def completed_telemetry_scores(self) -> torch.Tensor:
+    """``BatchedEnvironment.completed_telemetry_scores`` of every class: float64 [B_total, 13], in class order."""
+    return self._cat_rows(lambda k, env: env.completed_telemetry_scores())
+
+  def telemetry_zone_scores(self) -> List[torch.Tensor]:
+    """Every class's running per-zone rows, a list of float64 [B_k, Z_k, 4] (Z differs between classes)."""
+    return self._list_rows(lambda k, env: env.telemetry_zone_scores())
+
+  def completed_telemetry_zone_scores(self) -> List[torch.Tensor]:
+    """Every class's completed per-zone rows, a list of float64 [B_k, Z_k, 4]."""
+    return self._list_rows(lambda k, env: env.completed_telemetry_zone_scores())
+
+  def telemetry_actions(self) -> torch.Tensor:
+    """``BatchedEnvironment.telemetry_actions`` of every class: float32 [B_total, A], the rows in class order."""
+    return self._cat_rows(lambda k, env: env.telemetry_actions())
+
+  def _list_rows(self, fn) -> List[torch.Tensor]:
+    cur = torch.cuda.current_stream(self.tdev)
+    parts = self._on_streams(fn)
+    for t in parts:   # allocated on a class stream, read on the caller's
+      t.record_stream(cur)
+    return parts
 
   def _cat_rows(self, fn) -> torch.Tensor:
     cur = torch.cuda.current_stream(self.tdev)

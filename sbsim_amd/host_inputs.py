@@ -2219,3 +2219,199 @@ class EpisodeMetricsTwin:
     fresh[:, 0] = self.running[closing, 0] + 1.0
     self.running[closing] = fresh
     return closing
+
+
+# ---- buildings scored against recorded zone temperatures (sb_telemetry_attach; include/sbsim_amd.h states the table) ----
+TELEMETRY_SCORE_NAMES = _ffi.TELEMETRY_SCORE_NAMES
+TELEMETRY_ZONE_SCORE_NAMES = _ffi.TELEMETRY_ZONE_SCORE_NAMES
+
+
+class Telemetry:
+  """Recorded zone temperatures to score every building of a batch against, on the device (sb_telemetry_attach).
+
+      tel = Telemetry(recorded, actions=recorded_setpoints)          # one recording [n_rows, Z] for every building
+      tel = Telemetry(recordings, trace_of=which, first_row=where)   # [n_traces, n_rows, Z]; a trace and a first row per building
+      env = BatchedEnvironment(plan, B, telemetry=tel)
+
+  ``zone_temps``: float32 or float64 [n_rows, Z] or [n_traces, n_rows, Z], kelvin, widened to float64; NaN is "no
+  sample", +-inf is refused.  ``trace_of``: int [B], building b's trace (None: 0).  ``first_row``: int [B] in
+  [0, n_rows), the row building b's first step after a reset is compared with (None: 0); row r goes with the building's
+  (r - first_row)-th step since its reset, rows at or beyond n_rows count as missing.  ``zone_weights``: float64 [Z],
+  finite and >= 0 (None: all 1).  ``actions``: float32 [n_rows, A] or [n_traces, n_rows, A], the normalised setpoints
+  recorded with the temperatures (``telemetry_actions()`` hands each building its next row; past the end, the last).
+  ``per_zone``: also keep samples, sum_err, sum_abs_err, sum_sq_err per zone.
+  ValueError, naming what is at fault: here whatever the arrays themselves show, in ``check`` what needs the batch."""
+
+  def __init__(self, zone_temps, trace_of=None, first_row=None, zone_weights=None, actions=None, per_zone: bool = False):
+    t = np.asarray(zone_temps)
+    if t.dtype not in (np.float32, np.float64):
+      raise ValueError(f"zone_temps must be float32 or float64, got {t.dtype}")
+    t = np.array(t, dtype=np.float64)
+    if t.ndim == 2:
+      t = t[None]
+    if t.ndim != 3 or 0 in t.shape:
+      raise ValueError(f"zone_temps must have shape [n_rows, Z] or [n_traces, n_rows, Z], got {np.shape(zone_temps)}")
+    bad = np.argwhere(np.isinf(t))
+    if bad.size:
+      raise ValueError(f"zone_temps: trace {int(bad[0][0])} row {int(bad[0][1])} zone {int(bad[0][2])} is infinite (NaN is \"no sample\")")
+    t.setflags(write=False)
+    self.zone_temps = t
+    self.trace_of = self._index("trace_of", trace_of, self.n_traces, "traces")
+    self.first_row = self._index("first_row", first_row, self.n_rows, "rows")
+    if self.trace_of is not None and self.first_row is not None and len(self.trace_of) != len(self.first_row):
+      raise ValueError(f"trace_of has {len(self.trace_of)} rows, first_row {len(self.first_row)}")
+    self.zone_weights = None
+    if zone_weights is not None:
+      w = np.array(zone_weights, dtype=np.float64)
+      if w.shape != (self.n_zones,):
+        raise ValueError(f"zone_weights must have shape [{self.n_zones}], got {w.shape}")
+      bad = np.nonzero(~np.isfinite(w) | (w < 0))[0]
+      if bad.size:
+        raise ValueError(f"zone_weights[{int(bad[0])}] = {w[bad[0]]} must be finite and >= 0")
+      w.setflags(write=False)
+      self.zone_weights = w
+    self.actions = None
+    if actions is not None:
+      a = np.array(actions, dtype=np.float32)
+      if a.ndim == 2:
+        a = a[None]
+      if a.ndim != 3 or a.shape[2] == 0:
+        raise ValueError(f"actions must have shape [n_rows, A] or [n_traces, n_rows, A], got {np.shape(actions)}")
+      if a.shape[:2] != t.shape[:2]:
+        raise ValueError(f"actions hold {a.shape[0]} traces of {a.shape[1]} rows, zone_temps {t.shape[0]} of {t.shape[1]}")
+      if not np.isfinite(a).all():
+        raise ValueError("actions must be finite")
+      a.setflags(write=False)
+      self.actions = a
+    self.per_zone = bool(per_zone)
+
+  @staticmethod
+  def _index(name, values, n, what):
+    if values is None:
+      return None
+    k = _per_building(name, values, np.int32)
+    bad = np.nonzero((k < 0) | (k >= n))[0]
+    if bad.size:
+      raise ValueError(f"building {int(bad[0])}: {name} {int(k[bad[0]])} is outside the {n} {what}")
+    k = k.astype(np.int32)
+    k.setflags(write=False)
+    return k
+
+  @property
+  def n_traces(self) -> int:
+    return int(self.zone_temps.shape[0])
+
+  @property
+  def n_rows(self) -> int:
+    return int(self.zone_temps.shape[1])
+
+  @property
+  def n_zones(self) -> int:
+    return int(self.zone_temps.shape[2])
+
+  @property
+  def n_actions(self) -> int:
+    return 0 if self.actions is None else int(self.actions.shape[2])
+
+  def check(self, n_buildings: int, n_zones: int, n_actions: Optional[int] = None) -> None:
+    """What needs the batch: Z zones, [B] arrays of the batch's length, actions of the simulator's A columns."""
+    if self.n_zones != n_zones:
+      raise ValueError(f"zone_temps hold {self.n_zones} zones, the floor plan {n_zones}")
+    for name, a in (("trace_of", self.trace_of), ("first_row", self.first_row)):
+      if a is not None and a.shape[0] != n_buildings:
+        raise ValueError(f"{name} has {a.shape[0]} rows, the batch {n_buildings} buildings")
+    if self.actions is not None and n_actions is not None and self.n_actions != n_actions:
+      raise ValueError(f"actions have {self.n_actions} columns, the simulator {n_actions}")
+
+  def per_building(self, n_buildings: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(trace_of, first_row) as int32 [B], the defaults filled in."""
+    zeros = np.zeros(n_buildings, dtype=np.int32)
+    return (zeros if self.trace_of is None else self.trace_of, zeros if self.first_row is None else self.first_row)
+
+
+class TelemetryTwin:
+  """csrc/telemetry.h restated in NumPy float64 with plain loops, for B buildings of Z zones: ``running`` and
+  ``completed``, float64 [B, 13] with the columns ``TELEMETRY_SCORE_NAMES``, and with ``tel.per_zone`` ``zone_running``
+  and ``zone_completed``, float64 [B, Z, 4] (``TELEMETRY_ZONE_SCORE_NAMES``).  ``step`` is what one sb_step adds,
+  ``close`` the latch in front of a reset.  Every operation is one IEEE double operation in the header's order, so the
+  device tables equal these bit for bit."""
+
+  def __init__(self, tel: Telemetry, n_buildings: int, n_zones: Optional[int] = None):
+    self.tel, self.B, self.Z = tel, int(n_buildings), tel.n_zones if n_zones is None else int(n_zones)
+    tel.check(self.B, self.Z)
+    self.trace_of, self.first_row = tel.per_building(self.B)
+    self.weights = np.ones(self.Z) if tel.zone_weights is None else tel.zone_weights
+    self.running = self._fresh(self.B, 0.0)
+    self.completed = self._fresh(self.B, -1.0)   # no episode closed yet
+    self.zone_running = np.zeros((self.B, self.Z, _ffi.SB_TL_ZONE_FIELDS)) if tel.per_zone else None
+    self.zone_completed = np.zeros((self.B, self.Z, _ffi.SB_TL_ZONE_FIELDS)) if tel.per_zone else None
+
+  @staticmethod
+  def _fresh(n: int, episode) -> np.ndarray:
+    rows = np.zeros((n, _ffi.SB_TL_FIELDS), dtype=np.float64)
+    rows[:, 0] = episode
+    rows[:, 7:10] = -1.0
+    return rows
+
+  def step(self, zone_means) -> None:
+    """zone_means: float64 [B, Z], the post-update zone means (``sim.zone_temps()``)."""
+    zm = np.asarray(zone_means, dtype=np.float64).reshape(self.B, self.Z)
+    traces, n_rows = self.tel.zone_temps, self.tel.n_rows
+    with np.errstate(all="ignore"):
+      for b in range(self.B):
+        R = self.running[b]
+        r = np.float64(self.first_row[b]) + R[1]
+        R[1] += 1.0
+        if not (r >= 0.0 and r < n_rows):
+          R[3] += np.float64(self.Z)
+          continue
+        row = traces[self.trace_of[b], int(r)]
+        for z in range(self.Z):
+          obs = row[z]
+          if np.isnan(obs):
+            R[3] += 1.0
+            continue
+          e = zm[b, z] - obs
+          a = np.abs(e)
+          q = e * e
+          w = self.weights[z]
+          R[2] += 1.0
+          R[4] += e
+          R[5] += a
+          R[6] += q
+          if a > R[7]:
+            R[7], R[8], R[9] = a, r, np.float64(z)
+          R[10] += w * a
+          R[11] += w * q
+          R[12] += w
+          if self.zone_running is not None:
+            zr = self.zone_running[b, z]
+            zr[0] += 1.0
+            zr[1] += e
+            zr[2] += a
+            zr[3] += q
+
+  def close(self, mask=None) -> np.ndarray:
+    """The latch: every building of ``mask`` (None: all) with steps > 0 has its running rows copied to its completed rows
+    and re-initialised with episode + 1; the others keep every row.  Returns which buildings closed."""
+    m = np.ones(self.B, dtype=bool) if mask is None else np.asarray(mask).astype(bool)
+    closing = m & (self.running[:, 1] > 0)
+    self.completed[closing] = self.running[closing]
+    fresh = self._fresh(int(closing.sum()), 0.0)
+    fresh[:, 0] = self.running[closing, 0] + 1.0
+    self.running[closing] = fresh
+    if self.zone_running is not None:
+      self.zone_completed[closing] = self.zone_running[closing]
+      self.zone_running[closing] = 0.0
+    return closing
+
+  def action_rows(self) -> np.ndarray:
+    """The row of the recording every building's next step is scored on, the last row past the end: int [B]."""
+    r = self.first_row.astype(np.float64) + self.running[:, 1]
+    return np.where(r < self.tel.n_rows, np.maximum(r, 0.0), self.tel.n_rows - 1).astype(np.int64)
+
+  def actions(self) -> np.ndarray:
+    """What ``telemetry_actions()`` returns: float32 [B, A]."""
+    if self.tel.actions is None:
+      raise ValueError("the telemetry holds no actions")
+    return self.tel.actions[self.trace_of, self.action_rows()]
